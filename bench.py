@@ -38,6 +38,8 @@ equivalent figure for a genome held as 24 parts.  `projected_speedup_8`: genome 
 all-reduce), the prediction the first real 8-GPU run is to be held against.  After the headline: the same step as ONE hipGraph replay
 (`graph_ms_per_step`), an RCCL self-test when there is a process group (`rccl_selftest`), the distribution variants of SURVEY.md
 8d (`dist_variants`).  A secondary measurement that hangs ends the run with exit code 3 AFTER the line has been printed.
+`--dump-outputs DIR`: what the last timed step handed its caller -- exp_freq and the float32 scores (all bins, or a fixed seeded
+sample of 48 MiB of them) -- as DIR/*.npy, so that two builds can be compared output for output on identical inputs.
 """
 import argparse
 import json
@@ -502,6 +504,39 @@ def rccl_selftest(torch, dist, dev, rank, world, N, S):
     return out
 
 
+DUMP_BYTES = 48 << 20     # --dump-outputs: the scores written in all, over every rank (the rest is a few bytes)
+DUMP_SEED = 20251015
+
+
+def dump_rows(R_global, S):
+    """Global bins whose scores --dump-outputs writes: all of them when they fit DUMP_BYTES, else a sorted sample drawn with a
+    fixed seed -- the same bins for the same --bins / --states, whatever the GPU count."""
+    n = DUMP_BYTES // (4 * S)
+    if R_global <= n:
+        return np.arange(R_global, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(R_global, size=n, replace=False)).astype(np.int64)
+
+
+def dump_outputs(torch, out_dir, scores, exp_freq, rank, world, bin0, R_global):
+    """What the timed path handed its caller in the last timed step, as <out_dir>/<name>.npy: exp_freq (float32 [S], rank 0) and
+    the float32 scores of the bins of dump_rows() this rank holds (scores.npy; scores_rank<r>.npy with more than one rank, which
+    concatenated in rank order are the one-rank file).  -> what was written, for the JSON line."""
+    R, S = scores.shape
+    rows = dump_rows(R_global, S)
+    mine = rows[(rows >= bin0) & (rows < bin0 + R)] - bin0
+    idx = torch.from_numpy(mine).to(scores.device)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    files = {("scores.npy" if world == 1 else "scores_rank%d.npy" % rank): scores.index_select(0, idx).cpu().numpy()}
+    if rank == 0:
+        files["exp_freq.npy"] = np.asarray(exp_freq, dtype=np.float32).reshape(-1)
+    for name, arr in files.items():
+        assert arr.dtype in (np.float32, np.float64)
+        np.save(out_dir / name, arr)
+    return {"dir": str(out_dir.resolve()), "files": {name: list(arr.shape) for name, arr in files.items()},
+            "score_rows": "all %d bins" % R_global if rows.size == R_global else
+                          "%d of %d bins: sorted sample, numpy default_rng(%d)" % (rows.size, R_global, DUMP_SEED)}
+
+
 def launch_command(gpus, argv, port):
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(gpus),
             "--master-addr", "127.0.0.1", "--master-port", str(port), str(Path(__file__).resolve())] + list(argv)
@@ -639,7 +674,12 @@ def main():
     ap.add_argument("--placement-experiment", type=int, default=1, help="0: skip the jobs with an unplaced histogram cache after the timed region")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to test the "
                                                       "multi-rank path on a box with one GPU, ranks then share cuda:0)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps: write what the last timed step computed (exp_freq, the float32 scores; a fixed, seeded "
+                         "sample of bins when the scores exceed %d MiB) as DIR/<name>.npy" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # a plain start with --gpus N: this process becomes the launcher (the reference's one command submits its own
@@ -827,7 +867,7 @@ def main():
     table_note = None
     if use_session:
         sess = last["sess"]
-        sess.finish(R_global, N)                # the job's host side: count check (sum == bins * biosamples), table verification
+        exp_freq = sess.finish(R_global, N)     # the job's host side: count check (sum == bins * biosamples), table verification
         patched = sess.tables_patched
         table_note = {"built_on": "device (k_s1_combine, in the launch that normalises)",
                       "float32_table_equals_numpy_reference_table": patched == 0}
@@ -837,7 +877,11 @@ def main():
         assert total == R_global * N, "state counts %d != bins*biosamples %d" % (total, R_global * N)
         assert int(counts.abs().sum().item()) == 0                         # every job left the accumulator zeroed
         res = out32
+        exp_freq = q.cpu().numpy()
     assert bool(torch.isfinite(res[:: max(R // 4096, 1)]).all())
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(torch, Path(args.dump_outputs), res, exp_freq, rank, world, bin0, R_global)
     del res
 
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
@@ -1043,6 +1087,8 @@ def main():
             "configs": configs,
             "cpu_baseline": cpu,
         }
+        if dumped is not None:
+            line["dump_outputs"] = dumped
     emitted = threading.Lock()
 
     def serialise(**more):
@@ -1092,8 +1138,8 @@ def main():
         checkpoint(name)
         if os.environ.get("EPG_BENCH_HANG_LEG") == name:               # tests: a secondary measurement that never returns
             time.sleep(10 ** 6)
-        if os.environ.get("EPG_BENCH_ABORT_LEG") == name and rank == 0:  # tests: rank 0 dies in a secondary measurement
-            os.abort()
+        if os.environ.get("EPG_BENCH_EXIT_LEG") == name and rank == 0:   # tests: rank 0 dies in a secondary measurement
+            os._exit(1)                                                # (at once: no flush, no handlers, the line unprinted)
 
     # ---- secondary: the same jobs with the histogram cache where a plain allocation puts it (add_device(place=False))
     placement["report"] = engine.placement_report(dev)

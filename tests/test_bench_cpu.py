@@ -155,3 +155,22 @@ elif how == "torn":
         res = subprocess.run([sys.executable, "-c", prog, how], capture_output=True, text=True, timeout=120, cwd=str(tmp_path))
         assert (res.returncode == 0) == (how == "final"), (how, res.returncode, res.stderr[-500:])
         assert res.stdout.strip().splitlines() == [want], (how, res.stdout, res.stderr[-500:])
+
+
+def test_dump_rows_fixed_sample_within_budget():
+    """--dump-outputs: every bin when the scores fit the budget, else the same sorted sample for the same --bins (any GPU count)."""
+    import bench
+    assert np.array_equal(bench.dump_rows(1000, 18), np.arange(1000))
+    rows = bench.dump_rows(15_000_000, 18)
+    assert rows.size * 18 * 4 <= bench.DUMP_BYTES <= 64 * 10 ** 6
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < 15_000_000
+    assert np.array_equal(rows, bench.dump_rows(15_000_000, 18))
+
+
+def test_bench_refuses_zero_steps():
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parents[1]
+    res = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert res.returncode == 2 and "--steps must be at least 1" in res.stderr
