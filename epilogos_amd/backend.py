@@ -267,7 +267,15 @@ class _HipSession:
             self.acc = self.torch.zeros(n, dtype=dtype or self.torch.int64, device=self.device)
         return self.acc
 
+    def _flush(self):
+        """Launch the count pass of the parts that wait for one (a session that counts every part at once has none)."""
+
+    def drop_part(self, pid):
+        self._flush()
+        self.parts[pid] = None
+
     def all_reduce(self, d):
+        self._flush()
         d.all_reduce_tensor(self.acc)                    # RCCL over xGMI: the tensor never leaves HBM
 
     def _score_s1(self, H, N):
@@ -314,6 +322,7 @@ class _HipSession:
         count check (the reference dies on a state outside the model, expected.py:113; here such a byte is counted nowhere, so
         the total comes out short) is DEFERRED to check(), which whoever takes results off the device calls -- finish(),
         scores(), results() do; S3's 899 MB array is summed at once."""
+        self._flush()
         self._pending_check = (self.acc, total_rows, N)
         if self.sal == 3:
             self.check()
@@ -348,10 +357,11 @@ class _HipSession:
         self._launched = True
         self._begin([p for p in pids if p is not None])
 
-    def _finish(self, total_rows, N, shape):
+    def finish(self, total_rows, N):
         """The host side of STEP 2: the count check (the reference dies on a state outside the model, expected.py:113), the
         device-built S1 tables against numpy's (a table that differs is replaced and the parts scored before are scored
         again: never seen, tools/s1_table_probe.py), exp_freq as the host array that is saved."""
+        self._ws3 = None                                 # (S3: the count pass's workspace goes; the score pass sizes its own)
         if not self._launched:
             self.finish_device(total_rows, N)
         self._launched = False
@@ -359,7 +369,8 @@ class _HipSession:
         if self.verify_tables() and self._early:
             self._begin(list(self._early))               # (the early results came from a table that was replaced)
         self._settle()
-        return self.q.cpu().numpy().reshape(shape)
+        S = self.S                                       # (a paired session has saliency 1 or 2)
+        return self.q.cpu().numpy().reshape({1: (S,), 2: (S, S), 3: (N, N, S, S)}[self.sal])
 
 
 _PENDING = object()                                      # a part whose count pass has not been launched yet (see _HipSingleSession._flush)
@@ -454,28 +465,11 @@ class _HipSingleSession(_HipSession):
         self.parts.append(tensors[0].to(self.device))
         return len(self.parts) - 1
 
-    def drop_part(self, pid):
-        self._flush()
-        self.parts[pid] = None
-
     def ensure_acc(self, N):
         self._flush()
         S = self.S                                       # a rank without bins still takes part in the all-reduce
         self.N = N
         self._acc({1: S, 2: S * S, 3: N * N * S * S}[self.sal], self.torch.int32 if self.sal == 3 else None)
-
-    def all_reduce(self, d):
-        self._flush()
-        super().all_reduce(d)
-
-    def finish_device(self, total_rows, N):
-        self._flush()
-        return super().finish_device(total_rows, N)
-
-    def finish(self, total_rows, N):
-        S = self.S
-        self._ws3 = None
-        return self._finish(total_rows, N, {1: (S,), 2: (S, S), 3: (N, N, S, S)}[self.sal])
 
     def scores_device(self, pid, keep=False):
         """float32 [R, S] scores of part `pid` from its resident data, as a device tensor."""
@@ -702,25 +696,9 @@ class _HipPairedSession(_HipSession):
             self._start_null([pid])
         return pid
 
-    def drop_part(self, pid):
-        self._flush()
-        self.parts[pid] = None
-
     def ensure_acc(self, N):
         self._flush()
         self._acc(self.S if self.sal == 1 else self.S * self.S)
-
-    def all_reduce(self, d):
-        self._flush()
-        super().all_reduce(d)
-
-    def finish_device(self, total_rows, N):
-        self._flush()
-        return super().finish_device(total_rows, N)
-
-    def finish(self, total_rows, N):
-        S = self.S
-        return self._finish(total_rows, N, (S,) if self.sal == 1 else (S, S))
 
     def results_device(self, pid, keep=False):
         """Scores of A, B and the two null groups, deltas, null distances, STEP 4's per-bin reduction and the quiescence mask

@@ -59,7 +59,6 @@ class _Timer:
     """EPILOGOS_TIMING=1 prints the wall time of the driver's phases on rank 0."""
 
     def __init__(self, rank):
-        import time
         self.on = rank == 0 and bool(os.environ.get("EPILOGOS_TIMING"))
         self.time = time.perf_counter
         self.t = self.time()
@@ -166,14 +165,6 @@ class _Dist:
 
     def recv_arrays(self, n, src):
         return [t.cpu().numpy() for t in self.recv_tensors(n, src)]
-
-
-def _open_single(be, S, saliency):
-    return be.open_single(S, saliency)
-
-
-def _open_paired(be, S, saliency, quiescentState, groupSize, seed):
-    return be.open_paired(S, saliency, quiescentState, groupSize, seed)
 
 
 # ---- input side
@@ -496,56 +487,128 @@ def finish_writes():
         tm.lap(label)
 
 
-def run_single_group(files, numStates, saliency, outputDir, fileTag, verbose=False, backend=None, device=None,
-                     keep_temp_scores=True, defer_writes=False):
-    """STEP 1-3 for a single group over `files` (one per chromosome).  Returns (exp_freq float32, results) where results
-    (rank 0 only, else None) maps file stem -> (chrName, float32 scores [R, S], _io.Locations) for an in-process STEP 4.
-    keep_temp_scores writes the reference's temp_scores_{tag}_{stem}.npz (scores.py:166-169) for a STEP 4 run
-    elsewhere; the command line skips them because its STEP 4 would delete them a moment later."""
+# ---- STEP 1-3, written once for both modes.  Every rank runs the same collectives (barrier, all-reduce, send / recv) in the
+# same order, so the sequence lives in _run_groups alone; a mode object supplies only what differs between the modes: its
+# inputs and session, how a parsed file becomes a session part, its per-part outputs and rank 0's per-file result.
+class _Single:
+    """One group: a part is one file's rows; scores_* text; rank 0's result per file is (chrName, scores, Locations)."""
+    kind, census, upload_note = "scores", "single", ""
+    n_payload = 1                                      # arrays of a part that travel to rank 0, besides its Locations
+
+    def __init__(self, files, numStates, saliency, keep_temps):
+        self.groups, self.S, self.sal, self.keep_temps = (files,), numStates, saliency, keep_temps
+
+    def open(self, be):
+        return be.open_single(self.S, self.sal)
+
+    def add(self, sess, t, arr, n, part):
+        """A parsed job (its index t, its states) into the session -> the part's session id (None while it is incomplete)."""
+        return sess.add_part(arr, n, t)
+
+    def part_out(self, sess, pid):
+        """-> (the array written as text, [the arrays rank 0 collects]) of a part."""
+        sc = sess.scores(pid)
+        return sc, [sc]
+
+    def result(self, temp, chrName, loc, arrays):
+        """Rank 0: a file's entry of the results from its parts' arrays (arrays[i] = array i of every part, in row order)."""
+        scoreArr = _cat(arrays[0], np.zeros((0, self.S), dtype=np.float32))
+        if self.keep_temps:
+            np.savez_compressed(temp("scores"), chrName=np.array([chrName]), scoreArr=scoreArr, locationArr=loc.to_object_array())
+        return chrName, scoreArr, loc
+
+
+class _Paired:
+    """Two groups: a part is the same rows of a file of each group; pairwiseDelta_* text; rank 0's result per file is a dict."""
+    kind, census, upload_note = "pairwiseDelta", "paired", " x 2 groups"
+    n_payload = 4
+
+    def __init__(self, files1, files2, numStates, saliency, quiescentState, groupSize, nullSeed, keep_temps):
+        self.groups, self.S, self.sal, self.keep_temps = (files1, files2), numStates, saliency, keep_temps
+        self.qstate, self.groupSize, self.seed = quiescentState, groupSize, nullSeed
+        self.halves = {}                               # part index -> its group that arrived first
+
+    def open(self, be):
+        return be.open_paired(self.S, self.sal, self.qstate, self.groupSize, self.seed)
+
+    def add(self, sess, t, x, n, part):
+        staged = (sess.stage(x, n, t), n, x.shape[0])
+        other = self.halves.pop(t // 2, None)          # part k's two groups are jobs 2k and 2k + 1, in HBM as soon as parsed
+        if other is None:
+            self.halves[t // 2] = staged
+            return None
+        (XA, nA, rA), (XB, nB, rB) = (other, staged) if t % 2 else (staged, other)
+        fi, lo, _hi = part
+        if rA != rB:
+            raise ValueError("paired inputs differ in length: {} vs {}".format(self.groups[0][fi], self.groups[1][fi]))
+        # the key of the part's first row in the null shuffle: (file, row in the file) -- known here in every mode, so the
+        # session draws the null groups right behind the count pass (on its second stream)
+        return sess.add_staged(XA, nA, XB, nB, shuffle_key(fi, lo))
+
+    def part_out(self, sess, pid):
+        res = sess.results(pid)
+        return res["delta"], [np.asarray(res["null"], dtype=np.float32), np.asarray(res["quies"], dtype=np.bool_),
+                              np.asarray(res["rdist"], dtype=np.float32), np.asarray(res["mdiff"], dtype=np.int32)]
+
+    def result(self, temp, chrName, loc, arrays):
+        null, quies, dist, mdiff = (_cat(a, np.zeros(0, dtype=t)).astype(t) for a, t in zip(arrays, (np.float32, bool, np.float32, np.int32)))
+        if self.keep_temps:
+            np.savez_compressed(temp("nullDistances"), chrName=np.array([chrName]), nullDistances=null)
+            np.savez_compressed(temp("quiescence"), chrName=np.array([chrName]), quiescenceArr=quies)
+            # side-car for this engine's STEP 4 (roiAndVisualPairwise.readInData): the per-bin reduction the reference redoes
+            # from the pairwiseDelta text, already computed on the GPU; removed with the other temps
+            starts, ends = loc.start_end()
+            np.savez_compressed(temp("pairMetrics"), chrName=np.array([chrName]), distances=dist, maxDiff=mdiff, starts=starts, ends=ends)
+        return {"chrName": chrName, "locations": loc, "nullDistances": null, "quiescenceArr": quies, "distances": dist, "maxDiff": mdiff}
+
+
+def _run_groups(mode, outputDir, fileTag, backend, defer_writes):
+    """STEP 1-3 of either mode over the bin-range partition -> (exp_freq, results of rank 0 by file stem, else None)."""
     be = backend if backend is not None else _backend.get()
-    _io.set_state_limit(numStates)                     # above 31 states the parser keeps values up to 127 (wide kernels)
+    _io.set_state_limit(mode.S)                        # above 31 states the parser keeps values up to 127 (wide kernels)
     d = _Dist()
-    files = [Path(f) for f in files]
+    files = mode.groups[0]
     outputDir = Path(outputDir)
     tm = _Timer(d.rank)
     if d.rank == 0:
-        _clean_parts(outputDir, "scores", fileTag)
+        _clean_parts(outputDir, mode.kind, fileTag)
     d.barrier()
-    mode, rows, my_parts, owner = _plan(files, d, tm)
-    sess = _open_single(be, numStates, saliency)
+    layout, rows, my_parts, owner = _plan(files, d, tm, *mode.groups[1:])
+    sess = mode.open(be)
 
     # STEP 1: every part of this rank is parsed, uploaded once and counted; what the score pass needs stays resident
-    pids, locs, N = [None] * len(my_parts), [None] * len(my_parts), None
-    with closing(_stream_parts([(files[fi], lo, hi) for fi, lo, hi in my_parts], sess, numStates)) as stream:
-        for t, arr, n, loc in stream:                  # in order of completion; t = index in my_parts
-            N = max(N or 0, n)                         # an empty file has no width: it must not be the one that is remembered
-            pids[t] = sess.add_part(arr, n, t)
-            locs[t] = loc
-    if mode == "whole":
+    pids, locs, widths = [None] * len(my_parts), [None] * len(my_parts), [0] * len(mode.groups)
+    # paired: part k's two groups are jobs 2k and 2k + 1, the second group follows the first one's row ranges
+    with closing(_stream_parts([(group[fi], lo, hi) for fi, lo, hi in my_parts for group in mode.groups], sess, mode.S)) as stream:
+        for t, arr, n, loc in stream:                  # in order of completion
+            k, g = divmod(t, len(mode.groups))
+            widths[g] = max(widths[g], n)              # an empty file has no width: it must not be the one that is remembered
+            if g == 0:
+                locs[k] = loc
+            pids[k] = mode.add(sess, t, arr, n, my_parts[k])
+    if layout == "whole":                              # single rank: the row counts come from the parse
         rows = [len(l) for l in locs]
         my_parts = [(fi, 0, rows[fi]) for fi in range(len(files))]
     if d.world > 1:
-        N = d.max_ints([N or 0])[0]                    # a rank without bins learns the width from the others
-    if mode == "assigned":
+        widths = d.max_ints(widths)                    # a rank without bins learns the widths from the others
+    if layout == "assigned":
         rows = _exchange_rows(d, my_parts, locs, len(files))
         tm.lap("parse + upload + expected counts (each file once, on one rank)")
         plans = plan_partition(rows, d.world)
         starts = np.concatenate([[0], np.cumsum(rows)])
-        mine = {fi: (pids[t], locs[t]) for t, (fi, _lo, _hi) in enumerate(my_parts)}
-        pids, locs = _redistribute(d, sess, plans, owner, mine, starts, N)
+        mine = {fi: (pids[k], locs[k]) for k, (fi, _lo, _hi) in enumerate(my_parts)}
+        session_widths = widths[0] if len(widths) == 1 else tuple(widths)          # N, or (NA, NB)
+        pids, locs = _redistribute(d, sess, plans, owner, mine, starts, session_widths)
         my_parts = plans[d.rank]
         tm.lap("hand border pieces to their owners")
     else:
         plans = plan_partition(rows, d.world) if d.world > 1 else [my_parts]
         tm.lap("parse + upload + expected counts")
-    if not N:
-        N = _columns_of(files[0])
-    if hasattr(sess, "pool") and os.environ.get("EPILOGOS_POOL_CLOSE") == "1":
-        # every part is uploaded: the staging buffers could be un-locked in the background now.  Measured (gpurun_out/r04ab):
-        # 8 GB less to give back at exit (0.6 -> 0.5 s) but STEP 4 and the writers, which fault pages meanwhile, lose more.  Off.
-        sess.pool.close()
+    if not widths[0]:
+        widths = [_columns_of(group[0]) for group in mode.groups]
+    N = sum(widths)                                    # paired: the background counts are over the concatenation [A|B]
     sess.ensure_acc(N)
-    sess.all_reduce(d)                                # the one exchange step; a rank without bins contributes zeros
+    sess.all_reduce(d)                                 # the one exchange step; a rank without bins contributes zeros
     # STEP 2 (identical normalisation on every rank) and STEP 3 of every part enqueued without a host synchronisation; then
     # the host side: count check, S1 table verification, exp_freq as a host array (bench.py times this very sequence)
     sess.launch(int(sum(rows)), N, pids)
@@ -554,19 +617,18 @@ def run_single_group(files, numStates, saliency, outputDir, fileTag, verbose=Fal
         np.save(outputDir / "exp_freq_{}.npy".format(fileTag), q, allow_pickle=False)
     tm.lap("all-reduce + check + normalise")
 
-    # STEP 3: scores from the resident data; text is formatted and compressed by writer threads while the next part scores
-    payloads = []
+    # STEP 3: results from the resident data; text is formatted and compressed by writer threads while the next part scores
+    payloads, jobs = [], []
     nwriters = min(2, _io.host_budget())               # two files are written at a time: half of this rank's cores each
     wthreads = max(1, _io.host_budget() // nwriters)
     writer = ThreadPoolExecutor(max_workers=nwriters)
-    jobs = []
     try:
         for k, (fi, lo, hi) in enumerate(my_parts):
-            sc = sess.scores(pids[k])
+            text, arrays = mode.part_out(sess, pids[k])
             whole = lo == 0 and hi == rows[fi]
-            name = "scores_{}_{}.txt.gz".format(fileTag, fileStem(files[fi])) if whole else _part_name("scores", fileTag, fi, lo)
-            jobs.append(writer.submit(writeScores, sc, outputDir / name, locs[k], None, wthreads))
-            payloads.append([sc, np.asarray(locs[k].blob), np.asarray(locs[k].offsets)])
+            name = "{}_{}_{}.txt.gz".format(mode.kind, fileTag, fileStem(files[fi])) if whole else _part_name(mode.kind, fileTag, fi, lo)
+            jobs.append(writer.submit(writeScores, text, outputDir / name, locs[k], None, wthreads))
+            payloads.append(arrays + [np.asarray(locs[k].blob), np.asarray(locs[k].offsets)])
         tm.lap("scores (kernels + download)")
     except BaseException:
         writer.shutdown(wait=True)
@@ -578,31 +640,38 @@ def run_single_group(files, numStates, saliency, outputDir, fileTag, verbose=Fal
     else:
         _wait_writes(writer, jobs)
         tm.lap("write text (overlapped tail)")
-    tm.note("H2D uploads: %d for %d part(s)" % (getattr(sess, "n_uploads", 0), len(my_parts)))
+    tm.note("H2D uploads: %d for %d part(s)" % (getattr(sess, "n_uploads", 0), len(my_parts)) + mode.upload_note)
     d.barrier()
-    got = _gather_parts(d, plans, payloads, 3)
-    results = None
+    got = _gather_parts(d, plans, payloads, mode.n_payload + 2)
+    results = {} if d.rank == 0 else None
     if d.rank == 0:
-        results = {}
         for fi, f in enumerate(files):
             stem = fileStem(f)
+            final = "{}_{}_{}.txt.gz".format(mode.kind, fileTag, stem)
             owners = sorted((lo, hi) for parts in plans for (pf, lo, hi) in parts if pf == fi)
-            _assemble_text(outputDir, "scores", "scores_{}_{}.txt.gz".format(fileTag, stem), fileTag, fi, owners, rows[fi])
+            _assemble_text(outputDir, mode.kind, final, fileTag, fi, owners, rows[fi])
             if not owners:                             # an empty input file still gets its (empty) output
-                writeScores(np.zeros((0, numStates), dtype=np.float32), outputDir / "scores_{}_{}.txt.gz".format(fileTag, stem),
+                writeScores(np.zeros((0, mode.S), dtype=np.float32), outputDir / final,
                             _io.Locations(np.zeros(0, dtype=np.uint8), np.zeros(1, dtype=np.int64)))
             parts = [got[(fi, lo)] for lo, _ in owners]
-            scoreArr = _cat([p[0] for p in parts], np.zeros((0, numStates), dtype=np.float32))
-            loc = _cat_locations([_io.Locations(p[1], p[2]) for p in parts])
+            loc = _cat_locations([_io.Locations(p[-2], p[-1]) for p in parts])
             chrName = loc.slice(0, 1).to_object_array()[0, 0] if len(loc) else ""
-            results[stem] = (chrName, scoreArr, loc)
-            if keep_temp_scores:
-                np.savez_compressed(outputDir / "temp_scores_{}_{}.npz".format(fileTag, stem), chrName=np.array([chrName]),
-                                    scoreArr=scoreArr, locationArr=loc.to_object_array())
-        tm.lap("assemble files" + (" + temp_scores npz" if keep_temp_scores else ""))
-    _io.log_thread_census("single s%d rank %d of %d" % (saliency, d.rank, d.world))
+            results[stem] = mode.result(lambda what: outputDir / "temp_{}_{}_{}.npz".format(what, fileTag, stem), chrName, loc,
+                                        [[p[i] for p in parts] for i in range(mode.n_payload)])
+        tm.lap("assemble files" + (" + temp npz" if mode.keep_temps else ""))
+    _io.log_thread_census("%s s%d rank %d of %d" % (mode.census, mode.sal, d.rank, d.world))
     d.barrier()
     return q, results
+
+
+def run_single_group(files, numStates, saliency, outputDir, fileTag, verbose=False, backend=None, device=None,
+                     keep_temp_scores=True, defer_writes=False):
+    """STEP 1-3 for a single group over `files` (one per chromosome).  Returns (exp_freq float32, results) where results
+    (rank 0 only, else None) maps file stem -> (chrName, float32 scores [R, S], _io.Locations) for an in-process STEP 4.
+    keep_temp_scores writes the reference's temp_scores_{tag}_{stem}.npz (scores.py:166-169) for a STEP 4 run
+    elsewhere; the command line skips them because its STEP 4 would delete them a moment later."""
+    mode = _Single([Path(f) for f in files], numStates, saliency, keep_temp_scores)
+    return _run_groups(mode, outputDir, fileTag, backend, defer_writes)
 
 
 def run_paired_groups(files1, files2, numStates, saliency, outputDir, fileTag, quiescentState, groupSize, nullSeed,
@@ -615,129 +684,6 @@ def run_paired_groups(files1, files2, numStates, saliency, outputDir, fileTag, q
     dict(chrName, locations, nullDistances, quiescenceArr, distances, maxDiff) for an in-process STEP 4; keep_temps
     also writes temp_nullDistances / temp_quiescence (the reference's, scores.py:246-255) and temp_pairMetrics (the
     side-car of this engine's STEP 4)."""
-    be = backend if backend is not None else _backend.get()
-    _io.set_state_limit(numStates)
-    d = _Dist()
-    files1, files2 = [Path(f) for f in files1], [Path(f) for f in files2]
-    outputDir = Path(outputDir)
-    tm = _Timer(d.rank)
-    if d.rank == 0:
-        _clean_parts(outputDir, "pairwiseDelta", fileTag)
-    d.barrier()
-    mode, rows, my_parts, owner = _plan(files1, d, tm, files2)
-    sess = _open_paired(be, numStates, saliency, quiescentState, groupSize, nullSeed)
-
-    # group 1 and group 2 of a part are jobs 2k and 2k + 1; the second group follows the first one's row ranges
-    jobs = []
-    for fi, lo, hi in my_parts:
-        jobs += [(files1[fi], lo, hi), (files2[fi], lo, hi)]
-    locs, pids, NA, NB = [None] * len(my_parts), [None] * len(my_parts), None, None
-    halves = {}                                        # part index -> its group that arrived first, already in HBM
-    with closing(_stream_parts(jobs, sess, numStates)) as stream:
-        for t, x, n, loc in stream:                    # in order of completion; jobs 2k and 2k + 1 are part k
-            k, second = t // 2, t % 2
-            if second:
-                NB = max(NB or 0, n)                   # (an empty file has no width)
-            else:
-                NA, locs[k] = max(NA or 0, n), loc
-            staged = (sess.stage(x, n, t), n, x.shape[0])
-            if k not in halves:
-                halves[k] = (second, staged)
-                continue
-            other_second, other = halves.pop(k)
-            (XA, nA, rA), (XB, nB, rB) = (other, staged) if second else (staged, other)
-            fi, lo, hi = my_parts[k]
-            if rA != rB:
-                raise ValueError("paired inputs differ in length: {} vs {}".format(files1[fi], files2[fi]))
-            # the key of the part's first row in the null shuffle: (file, row in the file) -- known here in every mode, so the
-            # session draws the null groups right behind the count pass (on its second stream)
-            pids[k] = sess.add_staged(XA, nA, XB, nB, shuffle_key(fi, lo))
-    if mode == "whole":                                # single rank: the row counts come from the parse
-        rows = [len(l) for l in locs]
-        my_parts = [(fi, 0, rows[fi]) for fi in range(len(files1))]
-    if d.world > 1:
-        NA, NB = d.max_ints([NA or 0, NB or 0])
-    if mode == "assigned":
-        rows = _exchange_rows(d, my_parts, locs, len(files1))
-        tm.lap("parse + upload + expected counts (each file once, on one rank)")
-        plans = plan_partition(rows, d.world)
-        starts = np.concatenate([[0], np.cumsum(rows)])
-        mine = {fi: (pids[k], locs[k]) for k, (fi, _lo, _hi) in enumerate(my_parts)}
-        pids, locs = _redistribute(d, sess, plans, owner, mine, starts, (NA, NB))
-        my_parts = plans[d.rank]
-        tm.lap("hand border pieces to their owners")
-    else:
-        plans = plan_partition(rows, d.world) if d.world > 1 else [my_parts]
-        tm.lap("parse + upload + expected counts")
-    if not NA:
-        NA, NB = _columns_of(files1[0]), _columns_of(files2[0])
-    if hasattr(sess, "pool") and os.environ.get("EPILOGOS_POOL_CLOSE") == "1":
-        sess.pool.close()
-    sess.ensure_acc(NA + NB)
-    sess.all_reduce(d)
-    sess.launch(int(sum(rows)), NA + NB, pids)        # STEP 2 + the one-launch score pass of all parts, no host sync
-    q = sess.finish(int(sum(rows)), NA + NB)
-    if d.rank == 0:
-        np.save(outputDir / "exp_freq_{}.npy".format(fileTag), q, allow_pickle=False)
-    tm.lap("all-reduce + check + normalise")
-
-    payloads = []
-    nwriters = min(2, _io.host_budget())
-    wthreads = max(1, _io.host_budget() // nwriters)
-    writer = ThreadPoolExecutor(max_workers=nwriters)
-    wjobs = []
-    try:
-        for k, (fi, lo, hi) in enumerate(my_parts):
-            res = sess.results(pids[k])
-            whole = lo == 0 and hi == rows[fi]
-            name = ("pairwiseDelta_{}_{}.txt.gz".format(fileTag, fileStem(files1[fi])) if whole
-                    else _part_name("pairwiseDelta", fileTag, fi, lo))
-            wjobs.append(writer.submit(writeScores, res["delta"], outputDir / name, locs[k], None, wthreads))
-            payloads.append([np.asarray(res["null"], dtype=np.float32), np.asarray(res["quies"], dtype=np.bool_),
-                             np.asarray(res["rdist"], dtype=np.float32), np.asarray(res["mdiff"], dtype=np.int32),
-                             np.asarray(locs[k].blob), np.asarray(locs[k].offsets)])
-    except BaseException:
-        writer.shutdown(wait=True)
-        raise
-    if defer_writes and d.world == 1:
-        tm.lap("scores, nulls, deltas (kernels + download)")
-        _deferred.append((writer, wjobs, tm, "write text (under STEP 4)"))
-    else:
-        _wait_writes(writer, wjobs)
-        tm.lap("scores, nulls, deltas + write text")
-    tm.note("H2D uploads: %d for %d part(s) x 2 groups" % (getattr(sess, "n_uploads", 0), len(my_parts)))
-    d.barrier()
-    got = _gather_parts(d, plans, payloads, 6)
-    results = None
-    if d.rank == 0:
-        results = {}
-        for fi, f in enumerate(files1):
-            stem = fileStem(f)
-            owners = sorted((lo, hi) for parts in plans for (pf, lo, hi) in parts if pf == fi)
-            _assemble_text(outputDir, "pairwiseDelta", "pairwiseDelta_{}_{}.txt.gz".format(fileTag, stem), fileTag, fi, owners, rows[fi])
-            if not owners:
-                writeScores(np.zeros((0, numStates), dtype=np.float32), outputDir / "pairwiseDelta_{}_{}.txt.gz".format(fileTag, stem),
-                            _io.Locations(np.zeros(0, dtype=np.uint8), np.zeros(1, dtype=np.int64)))
-            parts = [got[(fi, lo)] for lo, _ in owners]
-            loc = _cat_locations([_io.Locations(p[4], p[5]) for p in parts])
-            chrName = loc.slice(0, 1).to_object_array()[0, 0] if len(loc) else ""
-            res = {"chrName": chrName, "locations": loc,
-                   "nullDistances": _cat([p[0] for p in parts], np.zeros(0, dtype=np.float32)).astype(np.float32),
-                   "quiescenceArr": _cat([p[1] for p in parts], np.zeros(0, dtype=bool)).astype(bool),
-                   "distances": _cat([p[2] for p in parts], np.zeros(0, dtype=np.float32)).astype(np.float32),
-                   "maxDiff": _cat([p[3] for p in parts], np.zeros(0, dtype=np.int32)).astype(np.int32)}
-            results[stem] = res
-            if keep_temps:
-                np.savez_compressed(outputDir / "temp_nullDistances_{}_{}.npz".format(fileTag, stem), chrName=np.array([chrName]),
-                                    nullDistances=res["nullDistances"])
-                np.savez_compressed(outputDir / "temp_quiescence_{}_{}.npz".format(fileTag, stem), chrName=np.array([chrName]),
-                                    quiescenceArr=res["quiescenceArr"])
-                # side-car for this engine's STEP 4 (roiAndVisualPairwise.readInData): the per-bin reduction the
-                # reference redoes from the pairwiseDelta text, already computed on the GPU; removed with the other temps
-                starts, ends = loc.start_end()
-                np.savez_compressed(outputDir / "temp_pairMetrics_{}_{}.npz".format(fileTag, stem), chrName=np.array([chrName]),
-                                    distances=res["distances"], maxDiff=res["maxDiff"], starts=starts, ends=ends)
-        tm.lap("assemble files" + (" + temp npz" if keep_temps else ""))
-    _io.log_thread_census("paired s%d rank %d of %d" % (saliency, d.rank, d.world))
-    d.barrier()
-    return q, results
+    mode = _Paired([Path(f) for f in files1], [Path(f) for f in files2], numStates, saliency, quiescentState, groupSize, nullSeed,
+                   keep_temps)
+    return _run_groups(mode, outputDir, fileTag, backend, defer_writes)

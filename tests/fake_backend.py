@@ -74,13 +74,21 @@ class _HostSession:
     def _add_counts(self, c):
         self.counts = c if self.counts is None else self.counts + c
 
+    def drop_part(self, pid):
+        self.parts[pid] = None
+
+    def ensure_acc(self, N):
+        if self.counts is None:                        # a rank without bins still takes part in the all-reduce
+            S = self.S
+            self.counts = np.zeros({1: (S,), 2: (S, S), 3: (N, N, S, S)}[self.sal], dtype=np.int32 if self.sal == 3 else np.int64)
+
     def all_reduce(self, d):
         self.counts = d.all_reduce_counts(self.counts)
 
     def launch(self, total_rows, N, pids):
         pass                                           # (the host stand-in has nothing to enqueue ahead of its checks)
 
-    def _finish(self, total_rows, N, shape):
+    def finish(self, total_rows, N):
         self.be.check_counts(self.counts, total_rows, N, self.sal)
         self.q = self.be.normalise(self.counts)
         return self.q
@@ -105,18 +113,6 @@ class _HostSingleSession(_HostSession):
     def import_rows(self, tensors, N, row0=None):
         self.parts.append(tensors[0].cpu().numpy())
         return len(self.parts) - 1
-
-    def drop_part(self, pid):
-        self.parts[pid] = None
-
-    def ensure_acc(self, N):
-        if self.counts is None:                        # a rank without bins still takes part in the all-reduce
-            S = self.S
-            self.counts = np.zeros({1: (S,), 2: (S, S), 3: (N, N, S, S)}[self.sal], dtype=np.int32 if self.sal == 3 else np.int64)
-
-    def finish(self, total_rows, N):
-        S = self.S
-        return self._finish(total_rows, N, {1: (S,), 2: (S, S), 3: (N, N, S, S)}[self.sal])
 
     def scores(self, pid):
         x, self.parts[pid] = self.parts[pid], None
@@ -157,16 +153,6 @@ class _HostPairedSession(_HostSession):
     def import_rows(self, tensors, widths, row0=None):
         self.parts.append((tensors[0].cpu().numpy(), tensors[1].cpu().numpy(), row0))
         return len(self.parts) - 1
-
-    def drop_part(self, pid):
-        self.parts[pid] = None
-
-    def ensure_acc(self, N):
-        if self.counts is None:
-            self.counts = np.zeros((self.S,) if self.sal == 1 else (self.S, self.S), dtype=np.int64)
-
-    def finish(self, total_rows, N):
-        return self._finish(total_rows, N, (self.S,) if self.sal == 1 else (self.S, self.S))
 
     def results(self, pid):
         be, S, sal, q = self.be, self.S, self.sal, self.q
