@@ -55,6 +55,8 @@ PROTOTYPES = {
     "epg_null_hist_from_binhist": (C.c_int, [_p, _p, _i64, _i32, _i32, _i32, _i32, _u64, _i64, _p, _p, _p]),
     "epg_null_hist_from_binhist_parts": (C.c_int, [_i32, _p, _p, _p, _i32, _i32, _i32, _i32, _u64, _p, _p, _p, _p]),
     "epg_pair_count_null_parts": (C.c_int, [_i32, _p, _p, _p, _i32, _i32, _p, _p, _i32, _p, _p, _p, _u64, _p, _p, _p, _p]),
+    "epg_simsearch_ws_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "epg_simsearch": (C.c_int, [_p, _i64, _i32, _i32, _p, _i32, _p, _i32, _u64, _p, _i64, _p, _p, _p, _p]),
     "epg_test_force": (C.c_int, [_i32, _i32]),
 }
 

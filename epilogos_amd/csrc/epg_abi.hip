@@ -67,6 +67,10 @@ int pair_count_null_parts_impl(int32_t, const int8_t* const*, const int8_t* cons
 
 int bin_hist_s2_impl(const int8_t*, int64_t, int32_t, int64_t, int32_t, uint16_t*, int64_t*, int64_t*, hipStream_t);
 
+int64_t simsearch_ws_bytes_impl(int64_t, int32_t, int32_t, int32_t);
+int simsearch_impl(const int32_t*, int64_t, int32_t, int32_t, const int32_t*, int32_t, const int32_t*, int32_t, uint64_t, void*, int64_t,
+                   int32_t*, uint64_t*, uint64_t*, hipStream_t);
+
 int g_force[FORCE_COUNT] = {0};
 
 }  // namespace epg
@@ -240,6 +244,13 @@ int epg_null_hist_from_binhist(const uint16_t* HA, const uint16_t* HB, int64_t R
 int epg_quiescent_from_binhist(const uint16_t* HA, const uint16_t* HB, int64_t R, int32_t S, int32_t NA, int32_t NB, int32_t qstate,
                                uint8_t* mask, void* stream) {
     return quiescent_from_binhist_impl(HA, HB, R, S, NA, NB, qstate, mask, (hipStream_t)stream);
+}
+
+int64_t epg_simsearch_ws_bytes(int64_t Pg, int32_t S, int32_t W, int32_t B) { return simsearch_ws_bytes_impl(Pg, S, W, B); }
+
+int epg_simsearch(const int32_t* G, int64_t Pg, int32_t S, int32_t W, const int32_t* Q, int32_t B, const int32_t* self_start, int32_t n,
+                  uint64_t key_bound, void* ws, int64_t ws_bytes, int32_t* idx, uint64_t* mode, uint64_t* dist, void* stream) {
+    return simsearch_impl(G, Pg, S, W, Q, B, self_start, n, key_bound, ws, ws_bytes, idx, mode, dist, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,0 +1,145 @@
+"""`python -m epilogos_amd.similaritySearch_run` -- similarity search, the option surface of the reference's
+epilogos/similaritySearch_run.py (click options :72-111, main :112-140, buildSimSearch :143-219, querySimSearch :237-285, block
+sizes :288-345).  -b runs the three stages in this process (STEP 2 on the GPU) instead of submitting SLURM jobs: -j, -p, -t,
+--mm-mem, --calc-mem and --write-mem are accepted and ignored, as the `epilogos` command does with its SLURM options; -c caps
+the host thread pools (torch's; the process is not pinned).  -q writes one similarity_search_region_*_recs.bed per query region
+found in a built simsearch.bed.gz."""
+import os
+import re
+from pathlib import Path
+from time import time
+
+import click
+import numpy as np
+import pandas as pd
+
+BLOCK_SIZES_200 = {5000: 1, 10000: 2, 25000: 5, 50000: 10, 75000: 15, 100000: 20}
+BLOCK_SIZES_20 = {500: 1, 1000: 2, 2500: 5, 5000: 10, 7500: 15, 10000: 20}
+
+
+def determineBlockSize200(windowBP):
+    if windowBP not in BLOCK_SIZES_200:
+        raise ValueError("Error: window size must be either 5000, 10000, 25000, 50000, 75000, or 100000 (in bp)")
+    return BLOCK_SIZES_200[windowBP]
+
+
+def determineBlockSize20(windowBP):
+    if windowBP not in BLOCK_SIZES_20:
+        raise ValueError("Error: window size must be either 500, 1000, 2500, 5000, 7500, or 10000 (in bp)")
+    return BLOCK_SIZES_20[windowBP]
+
+
+def determineBinSize(scoresPath):
+    row1 = pd.read_table(scoresPath, sep="\t", header=None, usecols=[0, 1, 2], nrows=1)
+    return int(row1.iloc[0, 2] - row1.iloc[0, 1])
+
+
+def windowParameters(scoresPath, windowBP):
+    """(windowBP, windowBins, blockSize) for the scores file's bin size (reference :173-184)."""
+    binSize = determineBinSize(scoresPath)
+    if binSize == 200:
+        windowBP = 25000 if windowBP == -1 else windowBP
+        return windowBP, int(windowBP / 200), determineBlockSize200(windowBP)
+    if binSize == 20:
+        windowBP = 2500 if windowBP == -1 else windowBP
+        return windowBP, int(windowBP / 20), determineBlockSize20(windowBP)
+    raise ValueError("Similarity Search is only compatible with bins of size 200bp or 20bp")
+
+
+def generateRegionArr(query):
+    """Query regions as an object array [n, 3] (reference helpers.py:197-221)."""
+    if re.fullmatch("chr[a-zA-z\\d]+:[\\d]+-[\\d]+", query):
+        chrom, rng = query.split(":")
+        start, end = rng.split("-")
+        return np.array([[chrom, int(start), int(end)]], dtype=object)
+    elif Path(query).is_file():
+        return pd.read_table(Path(query), sep="\t", header=None, usecols=[0, 1, 2]).to_numpy(dtype=object)
+    raise ValueError("Please input valid query (region formatted as chr:start-end"
+                     + "or path to bed file containing query regions)")
+
+
+def buildSimSearch(scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatches, filterState, filterScore):
+    from . import similaritySearch_calc, similaritySearch_max_mean, similaritySearch_write
+    print("\n\n\n        Building Similarity Search Results...", flush=True)
+    windowBP, windowBins, blockSize = windowParameters(scoresPath, windowBP)
+    if nCores > 0:                               # the host thread pools (the reference's -c sized its worker pool); no pinning
+        import torch
+        torch.set_num_threads(nCores)
+    print("\n        STEP 1: Salient Region Selection", flush=True)
+    similaritySearch_max_mean.main(outputDir, scoresPath, windowBins, blockSize, windowBP, filterState, filterScore)
+    print("\n        STEP 2: Similarity Search Calculation", flush=True)
+    similaritySearch_calc.main(outputDir, windowBins, blockSize, nCores, nDesiredMatches, 1, 0)
+    print("\n        STEP 3: Writing results", flush=True)
+    similaritySearch_write.main(outputDir, windowBins, blockSize, 1, nDesiredMatches)
+
+
+def querySimSearch(query, simSearchPath, outputDir):
+    print("\n\n\n        Reading in data...", flush=True); readTime = time()
+    queryArr = generateRegionArr(query)
+    matchesDF = pd.read_table(Path(simSearchPath), sep="\t", header=None)
+    print("            Time:", format(time() - readTime, '.0f'), "seconds\n", flush=True)
+    print("        Querying regions...", flush=True)
+    for chrom, start, end in queryArr:
+        index = np.where((matchesDF.iloc[:, 0] == chrom) & (matchesDF.iloc[:, 1] >= start) & (matchesDF.iloc[:, 2] <= end))[0]
+        if index.size > 0:
+            index = index[0]
+            regionChr, regionStart, regionEnd = matchesDF.iloc[index, :3]
+            outfile = Path(outputDir) / "similarity_search_region_{}_{}_{}_recs.bed".format(regionChr, regionStart, regionEnd)
+            recs = matchesDF.iloc[index, 3][2:-2].split('", "')[1:]
+            with open(outfile, "w+") as f:
+                f.write("".join("{0[0]}\t{0[1]}\t{0[2]}\n".format(r.split(":")) for r in recs))
+            print("            Found region {}:{}-{} within user query {}:{}-{}".format(regionChr, regionStart, regionEnd, chrom,
+                                                                                        start, end))
+            print("                See {} for matches\n".format(outfile), flush=True)
+        else:
+            print("            ValueError: Could not find region in given query range: {}:{}-{}\n".format(chrom, start, end))
+
+
+@click.command(context_settings=dict(help_option_names=['-h', '--help']))
+@click.option("-b", "--build", "buildBool", is_flag=True,
+              help="If true builds the similarity search files needed to query regions")
+@click.option("-s", "--scores", "scoresPath", type=str, help="Path to scores file to be used in similarity search")
+@click.option("-o", "--output-directory", "outputDir", required=True, type=str,
+              help="Path to desired similarity search output directory")
+@click.option("-w", "--window-bp", "windowBP", type=int, default=-1, show_default=True,
+              help="Window size (in BP) on which to perform similarity search [default: 25000]")
+@click.option("-j", "--num-jobs", "nJobs", type=int, default=10, show_default=True,
+              help="Accepted for compatibility (number of SLURM jobs); the build runs in this process")
+@click.option("-c", "--num-cores", "nCores", type=int, default=1, show_default=True,
+              help="Host threads for the build's thread pools (the process is not pinned). If set to 0, no cap.")
+@click.option("-n", "--num-matches", "nDesiredMatches", type=int, default=100, show_default=True,
+              help="Number of matches to be found by simsearch for each query region [default: 100]")
+@click.option("-f", "--filter-state", "filterState", type=int, default=-1,
+              help="If the max signal within a region is from the filter state, the region is removed from the region "
+                   + "list. If set to 0, filtering is not done. [default: last state]")
+@click.option("--filter-score", "filterScore", type=float, default=-1,
+              help="If the max signal within a region is less than the filter score, the region is removed from the "
+                   + "region list. [default: -1 == no filtering]")
+@click.option("-p", "--partition", "partition", type=str, help="Accepted for compatibility (SLURM partition); ignored")
+@click.option("-t", "--tag", "jobTag", type=str, default="", help="Accepted for compatibility (SLURM job tag); ignored")
+@click.option("--mm-mem", "mmMem", type=str, default=10000, help="Accepted for compatibility (SLURM memory); ignored")
+@click.option("--calc-mem", "calcMem", type=int, default=50000, help="Accepted for compatibility (SLURM memory); ignored")
+@click.option("--write-mem", "writeMem", type=int, default=5000, help="Accepted for compatibility (SLURM memory); ignored")
+@click.option("-q", "--query", "query", type=str, default="",
+              help="Query region formatted as chr:start-end or path to tab-separated bed file containing query regions")
+@click.option("-m", "--matches-file", "simSearchPath", type=str,
+              help="Path to previously built simsearch.bed.gz file to be queried for matches")
+def main(buildBool, scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatches, filterState, filterScore,
+         partition, jobTag, mmMem, calcMem, writeMem, query, simSearchPath):
+    if not buildBool and query == "":
+        raise ValueError("Either -b or -q flag must be used to run simsearch")
+    elif buildBool and query != "":
+        raise ValueError("Both -b and -q flags cannot be used at the same time")
+    outputDir = Path(outputDir)
+    if not outputDir.exists():
+        outputDir.mkdir(parents=True)
+    if not outputDir.is_dir():
+        raise NotADirectoryError("Given path is not a directory: {}".format(str(outputDir)))
+    if buildBool:
+        buildSimSearch(scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatches, filterState, filterScore)
+    else:
+        querySimSearch(query, simSearchPath, outputDir)
+
+
+if __name__ == "__main__":
+    main()

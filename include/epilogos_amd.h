@@ -225,6 +225,24 @@ int epg_pair_count_null_parts(int32_t nparts, const int8_t* const* XA, const int
                               uint16_t* const* HB, int64_t* counts, uint64_t seed, const int64_t* row0, uint16_t* const* OA,
                               uint16_t* const* OB, void* stream);
 
+/* ---- similarity search (simsearch -b, STEP 2) -----------------------------------------------------------------
+ * G: int32 [Pg, S], the block-reduced genome (reduced_genome.npy) as "%.5f" values scaled by 1e5; Q: int32 [B, W, S], B regions of
+ * interest (ROIs, rows of simsearch_cube.npz) on the same scale; self_start: int32 [B], the reduced position of each ROI's own
+ * window.  For every window position p < P = Pg - W + 1
+ *     D[r][p] = sum_{k<W} sum_s (G[p+k][s] - Q[r][k][s])^2      (exact, in units of 1e-10; dist[B, P] receives it when not NULL)
+ * mode[r] = the most frequent D[r][.], the smallest on ties (scipy.stats.mode); then, over the positions in ascending (D, p) order,
+ * a position whose window overlaps the ROI's own or an already picked one is skipped, the first other one with 2*D > mode
+ * ends the row (its remaining slots become -1), every other one is picked; up to n picks, idx int32 [B, n]; slots left when the
+ * positions run out are 0.  -- similaritySearch_calc.py:67-123 runEuclideanDistance.
+ * key_bound >= every D of the call (the caller's bound from per-state ranges: W * sum_s range_s^2); the distances are fp64 sums
+ * of integer-valued doubles, exact below 2^53: EPG_ERR_UNSUPPORTED above.  The sort runs over the bit length of key_bound.
+ * Workspace: epg_simsearch_ws_bytes(Pg, S, W, B) bytes (device memory, caller-allocated; about 20 * B * P bytes).
+ * Limits: 1 <= W <= 64, 1 <= n <= 1024, (64 + W - 1) * S <= 16000 (S <= 181 at W = 25). */
+int64_t epg_simsearch_ws_bytes(int64_t Pg, int32_t S, int32_t W, int32_t B);
+int epg_simsearch(const int32_t* G, int64_t Pg, int32_t S, int32_t W, const int32_t* Q, int32_t B, const int32_t* self_start,
+                  int32_t n, uint64_t key_bound, void* ws, int64_t ws_bytes, int32_t* idx, uint64_t* mode, uint64_t* dist,
+                  void* stream);
+
 /* ---- test hook (tests/ only; nothing in the package calls it) ----------------------------------------------
  * Several entry points have a fallback kernel that other shapes take; epg_test_force(which, value) makes the next calls take it
  * on any shape so that the tests can compare it with the default on theirs.  which: 0 = the column-by-column null sampler
