@@ -43,30 +43,6 @@ class HipBackend:
             return eng.hist_s3(X, N, S).cpu().numpy().reshape(N, N, S, S)
         raise ValueError("Please ensure that saliency metric is either 1, 2, or 3")
 
-    # device-resident accumulation for the genome-wide driver: the S3 count array is 899 MB at N = 833, so it stays in
-    # HBM from the first chunk to the all-reduce and the normalisation instead of crossing PCIe once per chunk
-    def counts_begin(self, S, saliency, N):
-        n = {1: S, 2: S * S, 3: N * N * S * S}[saliency]
-        return self.torch.zeros(n, dtype=self.torch.int32 if saliency == 3 else self.torch.int64, device=self.device)
-
-    def counts_add(self, acc, x, S, saliency):
-        eng = self.engine
-        N = x.shape[1]
-        X = self.to_device(x)
-        if saliency == 1:
-            eng.bin_hist(X, N, S, want_hist=False, counts=acc)
-        elif saliency == 2:
-            eng.bin_hist_s2(X, N, S, counts2=acc)
-        elif saliency == 3:
-            eng.hist_s3(X, N, S, counts=acc)
-        else:
-            raise ValueError("Please ensure that saliency metric is either 1, 2, or 3")
-
-    def counts_finish(self, acc, shape):
-        """(exp_freq on the device for the score pass, exp_freq as the host array that is saved)."""
-        qd = self.engine.normalise(acc)
-        return qd, qd.cpu().numpy().reshape(shape)
-
     def check_counts(self, counts, R, N, saliency):
         """Every state byte must have been counted: a byte outside [0, S) is silently skipped by the kernels.  `counts` is
         the count array or its already computed total."""
@@ -126,7 +102,7 @@ class HipBackend:
         """Scores of the two shuffled null halves (reference helpers.py:183-194 + scores.py:321-322,418-421)."""
         eng = self.engine
         NA, NB = xa.shape[1], xb.shape[1]
-        ga, gb = (NA, NB) if groupSize == -1 else (groupSize, groupSize)
+        ga, gb = _null_widths(NA, NB, groupSize)
         if S > 31:                                       # the wide models: the matrix-scanning kernel decodes five bits
             hA, _ = eng.bin_hist(self.to_device(xa), NA, S, want_counts=False)
             hB, _ = eng.bin_hist(self.to_device(xb), NB, S, want_counts=False)
@@ -154,6 +130,28 @@ class HipBackend:
         return _HipPairedSession(self, S, saliency, quiescentState, groupSize, seed)
 
 
+def _null_widths(NA, NB, groupSize):
+    """Widths of the two null groups: the real groups' by default, `groupSize` each with -g."""
+    return (NA, NB) if groupSize == -1 else (groupSize, groupSize)
+
+
+def _count_shape(saliency, S, N):
+    """Shape of the count array (and of exp_freq) of a saliency level."""
+    return {1: (S,), 2: (S, S), 3: (N, N, S, S)}[saliency]
+
+
+def _unless_unsupported(fn, *args, **kw):
+    """fn(*args, **kw), or None when the kernel does not take these shapes (EPG_ERR_UNSUPPORTED); the caller then takes the
+    separate launches that give the same results."""
+    from ._abi import EpilogosHipError
+    try:
+        return fn(*args, **kw)
+    except EpilogosHipError as e:
+        if e.code != -2:
+            raise
+        return None
+
+
 def _aligned_rows(T, lo, hi):
     """Rows [lo, hi) of a resident part as the kernels want them: the score entry points take 16-byte aligned bases
     (epg_s1.hip check_score_from_hist_args, epg_null.hip, epg_s2.hip), and a row slice of an [R, S] uint16 array starts at
@@ -168,7 +166,12 @@ def _aligned_rows(T, lo, hi):
 
 
 class _HipSession:
-    """Shared plumbing: pinned staging, one asynchronous upload per matrix, the count accumulator."""
+    """Shared plumbing: pinned staging, one asynchronous upload per matrix, the count accumulator, the queue of parts that wait
+    for their count pass and the early results of the score pass."""
+
+    # parts are COUNTED IN BATCHES: one launch per BATCH_ROWS rows or BATCH_PARTS parts, or when anything needs their histograms
+    # (_flush).  A subclass says how a batch is counted (_count) and which parts join the queue.
+    BATCH_ROWS, BATCH_PARTS = 8_000_000, 32
 
     def __init__(self, be, S, saliency):
         self.be, self.S, self.sal = be, S, saliency
@@ -186,9 +189,9 @@ class _HipSession:
         self._t1_verified = set()
         self.tables_patched = 0
         self._pending_check = None
-        self._ws3 = None                                 # S3 expected pass: ONE workspace for all parts of the session
+        self._pending, self._pending_rows = [], 0        # queued parts (what _count needs of each) and their rows
         self._launched = False                           # launch() ran: STEP 2 is on the device, STEP 3 of `_early` parts enqueued
-        self._early = {}                                 # part id -> its results, computed before the host-side checks
+        self._early = {}                                 # part id -> its device results, computed before the host-side checks
 
     @property
     def pool(self):
@@ -262,17 +265,35 @@ class _HipSession:
             self._releaser.start()
         self._release_q.put((ev, buf))
 
-    def _acc(self, n, dtype=None):
+    def _acc(self, N=None):
+        """The count accumulator (flat): int64 for S1 / S2, int32 for S3."""
         if self.acc is None:
-            self.acc = self.torch.zeros(n, dtype=dtype or self.torch.int64, device=self.device)
+            t = self.torch
+            self.acc = t.zeros(int(np.prod(_count_shape(self.sal, self.S, N))), dtype=t.int32 if self.sal == 3 else t.int64,
+                               device=self.device)
         return self.acc
 
+    def _queue(self, item, rows):
+        """A part joins the queue of the next count launch; the batch is counted once it is full."""
+        self._pending.append(item)
+        self._pending_rows += rows
+        if self._pending_rows >= self.BATCH_ROWS or len(self._pending) >= self.BATCH_PARTS:
+            self._flush()
+
     def _flush(self):
-        """Launch the count pass of the parts that wait for one (a session that counts every part at once has none)."""
+        """Count the queued parts.  They leave the queue only once their count launch has been issued: a launch that raises
+        leaves the queue as it was."""
+        if self._pending:
+            self._count(self._pending)
+            self._pending, self._pending_rows = [], 0
 
     def drop_part(self, pid):
         self._flush()
         self.parts[pid] = None
+
+    def ensure_acc(self, N):
+        self._flush()                                    # a rank without bins still takes part in the all-reduce
+        self._acc(N)
 
     def all_reduce(self, d):
         self._flush()
@@ -282,9 +303,6 @@ class _HipSession:
         """S1 score pass: gathers from the [N + 1, S] float32 table of this group width (see _s1_table)."""
         o32, _ = self.eng.score_s1_from_binhist_table(H, N, self.S, T32=self._s1_table(N))
         return o32
-
-    def _s1_widths(self):
-        return []
 
     def _s1_table(self, N):
         """The S1 score table of group width N.  finish_device builds the tables of the session's widths ON THE DEVICE in the
@@ -300,7 +318,7 @@ class _HipSession:
 
     def verify_tables(self):
         """-> number of device-built S1 tables that had to be replaced by the host's (0 = the device's float32 tables ARE the
-        reference's).  Synchronises; called by finish() and, after its timed region, by bench.py."""
+        reference's).  Synchronises; called by finish()."""
         if self.sal != 1 or self.q is None:
             return 0
         from .scores import s1ScoreTable
@@ -357,11 +375,14 @@ class _HipSession:
         self._launched = True
         self._begin([p for p in pids if p is not None])
 
+    def _settle(self):
+        for pid in self._early:                          # verified: the resident data of the scored parts can go
+            self.parts[pid] = None
+
     def finish(self, total_rows, N):
         """The host side of STEP 2: the count check (the reference dies on a state outside the model, expected.py:113), the
         device-built S1 tables against numpy's (a table that differs is replaced and the parts scored before are scored
         again: never seen, tools/s1_table_probe.py), exp_freq as the host array that is saved."""
-        self._ws3 = None                                 # (S3: the count pass's workspace goes; the score pass sizes its own)
         if not self._launched:
             self.finish_device(total_rows, N)
         self._launched = False
@@ -369,29 +390,43 @@ class _HipSession:
         if self.verify_tables() and self._early:
             self._begin(list(self._early))               # (the early results came from a table that was replaced)
         self._settle()
-        S = self.S                                       # (a paired session has saliency 1 or 2)
-        return self.q.cpu().numpy().reshape({1: (S,), 2: (S, S), 3: (N, N, S, S)}[self.sal])
+        return self.q.cpu().numpy().reshape(_count_shape(self.sal, self.S, N))
 
 
-_PENDING = object()                                      # a part whose count pass has not been launched yet (see _HipSingleSession._flush)
+class _Batch:
+    """S1 parts of one group width counted in one launch: their histograms are rows of `flat` (part i from starts[i], rows[i]
+    rows), so the batch can be scored in one launch too."""
+    __slots__ = ("pids", "flat", "starts", "rows", "N")
+
+    def __init__(self, pids, flat, starts, rows, N):
+        self.pids, self.flat, self.starts, self.rows, self.N = pids, flat, starts, rows, N
+
+
+class _Part:
+    """A single-mode part.  D: what its score pass reads -- histograms (S1, S2) or state rows (S3) -- or None while the part waits
+    in the count queue.  batch: the _Batch whose flat buffer D is a view of (None: D is an allocation of its own)."""
+    __slots__ = ("D", "batch")
+
+    def __init__(self, D=None, batch=None):
+        self.D, self.batch = D, batch
 
 
 class _HipSingleSession(_HipSession):
     def __init__(self, be, S, saliency):
+        if saliency not in (1, 2, 3):
+            raise ValueError("Please ensure that saliency metric is either 1, 2, or 3")
         super().__init__(be, S, saliency)
-        self._pending, self._pending_rows = [], 0        # S1: (pid, X, N) of part-sized matrices waiting for their ONE count launch
-        self._batches = []                               # S1: {"pids", "flat", "starts", "rows", "N"} of the batches counted so far
+        self.N = 0                                       # the widest part's width (an empty file has none)
+        self._ws3 = None                                 # S3: ONE workspace for all parts of the session
 
     def add_part(self, arr, N, ticket):
         return self.add_device(self._upload(arr, N, ticket), N)
 
-    # S1 parts of less than a GiB -- the chromosome files of a genome -- are COUNTED IN BATCHES: one epg_bin_hist_parts launch per
-    # 8 M rows or 32 parts (or when anything needs their histograms), histograms in one flat allocation, and later ONE score
-    # launch over that allocation.  Per part this was 24 count launches and 24 score launches of 0.1-0.25 ms with their ramps and
-    # tails: 3.42 ms per 15 M-bin genome against 2.6 ms as one matrix (bench.py s1_paths, round 6); in batches the same job
-    # is two count launches and two score launches.  Same integers, same float32 scores.
-    BATCH_ROWS, BATCH_PARTS = 8_000_000, 32
-
+    # S1 parts of less than a GiB -- the chromosome files of a genome -- are counted in batches (the queue of _HipSession): one
+    # epg_bin_hist_parts launch per 8 M rows or 32 parts, histograms in one flat allocation, and later ONE score launch over that
+    # allocation.  Per part this was 24 count launches and 24 score launches of 0.1-0.25 ms with their ramps and tails: 3.42 ms
+    # per 15 M-bin genome against 2.6 ms as one matrix (bench.py s1_paths, round 6); in batches the same job is two count
+    # launches and two score launches.  Same integers, same float32 scores.
     def add_device(self, X, N, place=None):
         """Count pass over a RESIDENT part -- the ONE entry of the command line (add_part, after its upload), of bench.py and of
         library callers.  place=None (everybody's default): engine.alloc_hist decides -- the histogram cache of a matrix of a GiB
@@ -400,52 +435,46 @@ class _HipSingleSession(_HipSession):
         (engine.placement_enabled: EPILOGOS_PLACEMENT=0, ranks sharing a GPU).  The command line's parts are one chromosome file
         each -- under a GiB up to ~880 columns -- so a whole-genome run of the reference's shape counts with plain allocations
         (bench.py reports that figure as placement.unplaced; its count passes hide under the parse anyway) while a caller that holds
-        the genome as one matrix gets the placed cache.  place=False forces a plain allocation (bench.py's comparison)."""
+        the genome as one matrix gets the placed cache.  place=False forces a plain allocation and a count launch of the part's
+        own (bench.py's comparison)."""
         eng, S = self.eng, self.S
-        self.N = max(getattr(self, "N", 0) or 0, N or 0)  # (an empty file has no width)
+        self.N = max(self.N, N or 0)
+        pid = len(self.parts)
         if X.shape[0] == 0 or not N:                     # an empty part: nothing to count, and the ABI rejects a zero width
-            self.parts.append(self.torch.empty((0, S), dtype=self.torch.int16, device=self.device) if self.sal < 3 else X)
-            return len(self.parts) - 1
-        if self.sal == 1 and place is None and X.numel() < eng.PLACE_MIN_BYTES and os.environ.get("EPILOGOS_SINGLE_BATCH", "1") != "0":
-            self.parts.append(_PENDING)
-            self._pending.append((len(self.parts) - 1, X, N))
-            self._pending_rows += X.shape[0]
-            if self._pending_rows >= self.BATCH_ROWS or len(self._pending) >= self.BATCH_PARTS:
-                self._flush()
-            return len(self.parts) - 1
-        if self.sal == 1:
-            H, _ = eng.bin_hist(X, N, S, counts=self._acc(S), H=eng.alloc_hist(X, N, S) if place is not False else None)
-            self.parts.append(H)
-        elif self.sal == 2:                              # the count pass with the pair counts folded in: one launch
-            H, _ = eng.bin_hist_s2(X, N, S, counts2=self._acc(S * S), H=eng.alloc_hist(X, N, S) if place is not False else None)
-            self.parts.append(H)
+            self.parts.append(_Part(self.torch.empty((0, S), dtype=self.torch.int16, device=self.device) if self.sal < 3 else X))
+        elif self.sal == 1 and place is None and X.numel() < eng.PLACE_MIN_BYTES:
+            self.parts.append(_Part())
+            self._queue((pid, X, N), X.shape[0])
         elif self.sal == 3:
-            # the ~8 GB workspace of the matrix-core contraction is allocated once per session and grows to the largest
-            # part (round 2 allocated and freed one per part: freed device memory is scrubbed at every HBM kernel's expense)
-            need = eng.hist_s3_ws_bytes(X.shape[0], N, S)
-            if self._ws3 is None or self._ws3.numel() < need:
-                self._ws3 = None
-                self._ws3 = self.torch.empty(need, dtype=self.torch.uint8, device=self.device)
-            eng.hist_s3(X, N, S, counts=self._acc(N * N * S * S, self.torch.int32), ws=self._ws3)
-            self.parts.append(X)
-        else:
-            raise ValueError("Please ensure that saliency metric is either 1, 2, or 3")
-        return len(self.parts) - 1
+            eng.hist_s3(X, N, S, counts=self._acc(N), ws=self._s3_workspace(X.shape[0], N))
+            self.parts.append(_Part(X))
+        else:                                            # (S2: the count pass with the pair counts folded in, one launch)
+            H = eng.alloc_hist(X, N, S) if place is not False else None
+            H, _ = eng.bin_hist(X, N, S, counts=self._acc(), H=H) if self.sal == 1 else eng.bin_hist_s2(X, N, S, counts2=self._acc(), H=H)
+            self.parts.append(_Part(H))
+        return pid
 
-    def _flush(self):
-        """The count pass of the pending S1 parts: one launch (per schedule class of their widths), histograms from one allocation."""
-        if not self._pending:
-            return
+    def _s3_workspace(self, R, N):
+        """The ~8 GB workspace of the S3 matrix-core contraction (count pass) and of the S3 score pass (table, transposed matrix,
+        cells), grown to the largest part (round 2 allocated and freed one per part: freed device memory is scrubbed at every
+        HBM kernel's expense)."""
+        need = self.eng.hist_s3_ws_bytes(R, N, self.S)
+        if self._ws3 is None or self._ws3.numel() < need:
+            self._ws3 = None
+            self._ws3 = self.torch.empty(need, dtype=self.torch.uint8, device=self.device)
+        return self._ws3
+
+    def _count(self, batch):
+        """The count pass of queued S1 parts: one launch (per schedule class of their widths), histograms from one allocation."""
         eng, S = self.eng, self.S
-        batch, self._pending, self._pending_rows = self._pending, [], 0
-        rows = [X.shape[0] for _pid, X, _n in batch]
+        rows = [X.shape[0] for _pid, X, _N in batch]
         flat, starts = eng.hist_rows_flat(rows, S, self.device)
         Hs = [flat[a:a + r] for a, r in zip(starts, rows)]
-        eng.bin_hist_parts([X for _pid, X, _n in batch], [n for _pid, _X, n in batch], S, counts=self._acc(S), Hs=Hs)
-        for (pid, _X, _n), H in zip(batch, Hs):
-            self.parts[pid] = H
-        if len({n for _pid, _X, n in batch}) == 1:       # (one group width: the batch can be scored in one launch too)
-            self._batches.append({"pids": [pid for pid, _X, _n in batch], "flat": flat, "starts": starts, "rows": rows, "N": batch[0][2]})
+        eng.bin_hist_parts([X for _pid, X, _N in batch], [N for _pid, _X, N in batch], S, counts=self._acc(), Hs=Hs)
+        widths = {N for _pid, _X, N in batch}
+        b = _Batch([pid for pid, _X, _N in batch], flat, starts, rows, widths.pop()) if len(widths) == 1 else None
+        for (pid, _X, _N), H in zip(batch, Hs):
+            self.parts[pid] = _Part(H, b)
 
     # ---- multi-rank hand-over (driver._redistribute): a part is what the score pass reads -- per-bin histograms (S1, S2)
     # or state rows (S3)
@@ -453,70 +482,60 @@ class _HipSingleSession(_HipSession):
 
     def slice_part(self, pid, lo, hi, row0=None):
         self._flush()
-        self.parts.append(_aligned_rows(self.parts[pid], lo, hi))
+        self.parts.append(_Part(_aligned_rows(self.parts[pid].D, lo, hi)))
         return len(self.parts) - 1
 
     def export_rows(self, pid, lo, hi):
         self._flush()
-        return [self.parts[pid][lo:hi]]
+        return [self.parts[pid].D[lo:hi]]
 
     def import_rows(self, tensors, N, row0=None):
         self.N = N
-        self.parts.append(tensors[0].to(self.device))
+        self.parts.append(_Part(tensors[0].to(self.device)))
         return len(self.parts) - 1
 
     def ensure_acc(self, N):
-        self._flush()
-        S = self.S                                       # a rank without bins still takes part in the all-reduce
         self.N = N
-        self._acc({1: S, 2: S * S, 3: N * N * S * S}[self.sal], self.torch.int32 if self.sal == 3 else None)
+        super().ensure_acc(N)
+
+    def finish(self, total_rows, N):
+        self._ws3 = None                                 # (S3: the count pass's workspace goes; the score pass sizes its own)
+        return super().finish(total_rows, N)
 
     def scores_device(self, pid, keep=False):
         """float32 [R, S] scores of part `pid` from its resident data, as a device tensor."""
         self._flush()
         eng, S, N = self.eng, self.S, self.N
-        D = self.parts[pid]
+        D = self.parts[pid].D
         if not keep:
             self.parts[pid] = None                       # the part's device data is released with its scores
         if D.shape[0] == 0:
             return self.torch.empty((0, S), dtype=self.torch.float32, device=self.device)
         if self.sal == 1:
-            o32 = self._score_s1(D, N)
-        elif self.sal == 2:
-            o32, _ = eng.score_s2_from_binhist(D, N, S, self.q)
-        else:                                            # one score workspace (table, transposed matrix, cells) for all parts
-            need = eng.hist_s3_ws_bytes(D.shape[0], N, S)
-            if self._ws3 is None or self._ws3.numel() < need:
-                self._ws3 = None
-                self._ws3 = self.torch.empty(need, dtype=self.torch.uint8, device=self.device)
-            o32, _ = eng.score_s3(D, N, S, self.q, ws=self._ws3)
-        return o32
+            return self._score_s1(D, N)
+        if self.sal == 2:
+            return eng.score_s2_from_binhist(D, N, S, self.q)[0]
+        return eng.score_s3(D, N, S, self.q, ws=self._s3_workspace(D.shape[0], N))[0]
 
     def _s1_widths(self):
-        return [getattr(self, "N", None)]
+        return [self.N]
 
     def _begin(self, pids):
         self._flush()
         want = [pid for pid in pids if self.parts[pid] is not None]
-        self._early = {}
         asked = set(want)
-        for b in self._batches:
-            # a batch whose parts are all asked for and still hold the rows the count pass left: ONE score launch over its flat
-            # histogram buffer, the parts' scores are views of one flat result
-            if self.sal == 1 and b["N"] == self.N and all(pid in asked and self.parts[pid] is not None and self.parts[pid].shape[0] == r
-                                                          and self.parts[pid].data_ptr() == b["flat"][a:].data_ptr()
-                                                          for pid, a, r in zip(b["pids"], b["starts"], b["rows"])):
-                o32 = self._score_s1(b["flat"], self.N)
-                for pid, a, r in zip(b["pids"], b["starts"], b["rows"]):
+        self._early = {}
+        # a batch whose parts are all asked for and still hold the rows its count pass left: ONE score launch over its flat
+        # histogram buffer, the parts' scores are views of one flat result (the <= 7 rows between two parts are scored too)
+        batches = {self.parts[pid].batch for pid in want} - {None}
+        for b in sorted(batches, key=lambda b: b.pids[0]):                # (in the order they were counted)
+            if b.N == self.N and all(pid in asked and self.parts[pid].batch is b for pid in b.pids):
+                o32 = self._score_s1(b.flat, self.N)
+                for pid, a, r in zip(b.pids, b.starts, b.rows):
                     self._early[pid] = o32[a:a + r]
         for pid in want:
             if pid not in self._early:
                 self._early[pid] = self.scores_device(pid, keep=True)
-
-    def _settle(self):
-        for pid in self._early:                          # verified: the resident data of the scored parts can go
-            self.parts[pid] = None
-        self._batches = [b for b in self._batches if any(self.parts[pid] is not None for pid in b["pids"])]
 
     def early_scores(self, pid):
         """Device tensor of a part scored by launch() (bench.py: the scores stay in HBM)."""
@@ -530,14 +549,29 @@ class _HipSingleSession(_HipSession):
         return self.scores_device(pid).cpu().numpy()
 
 
+class _Pair:
+    """A paired-mode part: the two groups' state rows (XA, XB; None for rows taken over from another part or rank), their
+    histograms (HA, HB; None while the part waits in the count queue), the shuffle key of its first row (row0), its null
+    groups' histograms (HnA, HnB; None until drawn) and the event that says they are (null_done; None: drawn on the main
+    stream)."""
+    __slots__ = ("XA", "XB", "HA", "HB", "row0", "HnA", "HnB", "null_done")
+
+    def __init__(self, XA, XB, HA, HB, row0, HnA=None, HnB=None):
+        self.XA, self.XB, self.HA, self.HB, self.row0 = XA, XB, HA, HB, row0
+        self.HnA, self.HnB, self.null_done = HnA, HnB, None
+
+
 class _HipPairedSession(_HipSession):
     def __init__(self, be, S, saliency, quiescentState, groupSize, seed):
         if saliency not in (1, 2):
             raise ValueError("Please ensure that saliency metric is either 1 or 2 for Pairwise Epilogos")
         super().__init__(be, S, saliency)
         self.qstate, self.groupSize, self.seed = quiescentState, groupSize, seed
-        self._ready = None                               # results of all parts, computed at the first results() call
-        self._pending, self._pending_rows = [], 0        # parts whose count pass has not been launched yet (see add_staged)
+        self.NA = self.NB = 0                            # the widest part's widths (an empty file pair has none)
+        # rows per batch: the default group sizes take the fused kernel (nothing to overlap: two launches per genome, 4.62 ms per
+        # 15 M bins against 4.71 with seven); the two-kernel path overlaps batch k's sampler with batch k + 1's count pass
+        # (1 / 2 / 3 / 4 M rows: 5.04 / 5.05 / 5.12 / 5.10 ms before the score pass prefetched, one batch 6.1)
+        self.BATCH_ROWS = 8_000_000 if groupSize == -1 else 2_000_000
         if getattr(be, "_null_stream", None) is None:    # one second stream per backend, not per session (used by the two-kernel path)
             be._null_stream = self.torch.cuda.Stream(device=self.device)
         self.null_stream = be._null_stream
@@ -547,13 +581,6 @@ class _HipPairedSession(_HipSession):
         part must not sit on two of the few buffers while its other half is still being inflated)."""
         return self._upload(arr, N, ticket)
 
-    def set_row0(self, pid, row0):
-        self._flush()
-        XA, XB, HA, HB, _, null = self.parts[pid]
-        self.parts[pid] = (XA, XB, HA, HB, row0, null)
-        if null is None and HA.shape[0]:
-            self._start_null([pid])
-
     def add_part(self, arrA, NA, ticketA, arrB, NB, ticketB, row0):
         return self.add_staged(self._upload(arrA, NA, ticketA), NA, self._upload(arrB, NB, ticketB), NB, row0)
 
@@ -561,245 +588,159 @@ class _HipPairedSession(_HipSession):
     # groups are drawn in ONE launch on the second stream, under the count pass of the next batch (the sampler is VALU-bound,
     # the count pass HBM-bound: tools/overlap_probe.py).  Round 4 launched per part: 2 x 24 count passes of ~80 us and 24 samplers
     # for a genome, each with its ramp and tail -- the count phase of BASELINE config 5 ran at 0.36 of its bytes.
-    # rows per batch: the default group sizes take the fused kernel (nothing to overlap: two launches per genome, 4.62 ms per
-    # 15 M bins against 4.71 with seven); the two-kernel path overlaps batch k's sampler with batch k + 1's count pass
-    # (1 / 2 / 3 / 4 M rows: 5.04 / 5.05 / 5.12 / 5.10 ms before the score pass prefetched, one batch 6.1)
-    BATCH_ROWS = os.environ.get("EPILOGOS_PAIR_BATCH_ROWS")
-
     def add_staged(self, XA, NA, XB, NB, row0):
         """One part's two groups, resident.  row0 keys the null shuffle of the part's first row: the driver passes
         (file ordinal << 40) + row in the file -- known the moment a file is parsed, whatever the partition.  The part joins
-        the pending batch; the batch is launched when it holds BATCH_ROWS rows (half a genome with the fused kernel, an eighth
+        the count queue; the batch is launched when it holds BATCH_ROWS rows (half a genome with the fused kernel, an eighth
         with the two-kernel path: a streaming run still counts while it parses) or 32 parts, or when anything needs its
         histograms."""
-        S = self.S
-        # widths of the widest part seen: an empty file pair (no columns) must not be the one that is remembered
-        self.NA, self.NB = max(getattr(self, "NA", 0) or 0, NA or 0), max(getattr(self, "NB", 0) or 0, NB or 0)
+        self.NA, self.NB = max(self.NA, NA or 0), max(self.NB, NB or 0)
+        pid = len(self.parts)
         if XA.shape[0] == 0 or not NA or not NB:         # nothing to count (and the ABI rejects a zero width)
-            self.parts.append((XA, XB, self.torch.empty((0, S), dtype=self.torch.int16, device=self.device),
-                               self.torch.empty((0, S), dtype=self.torch.int16, device=self.device), row0, None))
-            return len(self.parts) - 1
-        self.parts.append((XA, XB, None, None, row0, None))
-        pid = len(self.parts) - 1
-        self._pending.append((pid, NA, NB))
-        self._pending_rows += XA.shape[0]
-        limit = int(self.BATCH_ROWS) if self.BATCH_ROWS else (8_000_000 if self.groupSize == -1 else 2_000_000)
-        if self._pending_rows >= limit or len(self._pending) >= 32:
-            self._flush()
+            t = self.torch
+            self.parts.append(_Pair(XA, XB, t.empty((0, self.S), dtype=t.int16, device=self.device),
+                                    t.empty((0, self.S), dtype=t.int16, device=self.device), row0))
+            return pid
+        self.parts.append(_Pair(XA, XB, None, None, row0))
+        self._queue((pid, NA, NB), XA.shape[0])
         return pid
 
-    def _flush(self):
-        """Count pass of the pending batch and its null groups.  The default group sizes, a state model and widths the fused
-        kernel takes: ONE launch does both (epg_pair_count_null_parts: a wave counts a tile of both groups, then draws its null
-        groups -- the memory pipe and the VALU of a CU are busy at the same time without a second kernel).  Otherwise one launch
-        for the count pass (epg_bin_hist_parts), then one for the null groups on the second stream (_start_null)."""
-        if not self._pending:
-            return
+    def _count(self, batch):
+        """Count pass of a batch and its null groups.  The default group sizes, a state model and widths the fused kernel takes:
+        ONE launch does both (epg_pair_count_null_parts: a wave counts a tile of both groups, then draws its null groups -- the
+        memory pipe and the VALU of a CU are busy at the same time without a second kernel).  Otherwise one launch for the
+        count pass (epg_bin_hist_parts), then one for the null groups on the second stream (_start_null)."""
         eng, S = self.eng, self.S
-        batch, self._pending, self._pending_rows = self._pending, [], 0
-        XAs = [self.parts[pid][0] for pid, _na, _nb in batch]
-        XBs = [self.parts[pid][1] for pid, _na, _nb in batch]
-        k = len(batch)
-        counts = self._acc(S) if self.sal == 1 else None  # counts over [A|B] = counts of A + counts of B (helpers.py:173)
+        parts = [self.parts[pid] for pid, _na, _nb in batch]
+        counts = self._acc() if self.sal == 1 else None  # counts over [A|B] = counts of A + counts of B (helpers.py:173)
         fused = None
-        uniform = all(na == self.NA and nb == self.NB for _p, na, nb in batch)
-        if (self.groupSize == -1 and uniform and all(self.parts[pid][4] is not None for pid, _na, _nb in batch)
-                and os.environ.get("EPILOGOS_PAIR_FUSED", "1") != "0"):
-            try:
-                fused = eng.pair_count_null_parts(XAs, XBs, self.NA, self.NB, S, self.seed, [self.parts[pid][4] for pid, _na, _nb in batch],
-                                                  counts=counts)
-            except eng.EpilogosHipError as e:
-                if e.code != -2:
-                    raise
+        if self.groupSize == -1 and all(na == self.NA and nb == self.NB for _pid, na, nb in batch):
+            fused = _unless_unsupported(eng.pair_count_null_parts, [p.XA for p in parts], [p.XB for p in parts], self.NA, self.NB, S,
+                                        self.seed, [p.row0 for p in parts], counts=counts)
         if fused is not None:
-            HAs, HBs, OAs, OBs = fused
-            for i, (pid, _na, _nb) in enumerate(batch):
-                XA, XB, _ha, _hb, row0, _null = self.parts[pid]
-                self.parts[pid] = (XA, XB, HAs[i], HBs[i], row0, (OAs[i], OBs[i], None))
+            for p, HA, HB, HnA, HnB in zip(parts, *fused):
+                p.HA, p.HB, p.HnA, p.HnB = HA, HB, HnA, HnB
         else:
-            widths = [na for _p, na, _nb in batch] + [nb for _p, _na, nb in batch]
-            Hs, _ = eng.bin_hist_parts(XAs + XBs, widths, S, counts=counts)
-            HAs, HBs = Hs[:k], Hs[k:]
-            for i, (pid, _na, _nb) in enumerate(batch):
-                XA, XB, _ha, _hb, row0, null = self.parts[pid]
-                self.parts[pid] = (XA, XB, HAs[i], HBs[i], row0, null)
-        if self.sal != 1:
-            for i in range(k):
-                eng.hist_s2_from_binhist_pair(HAs[i], HBs[i], S, counts=self._acc(S * S))
+            Hs, _ = eng.bin_hist_parts([p.XA for p in parts] + [p.XB for p in parts],
+                                       [na for _pid, na, _nb in batch] + [nb for _pid, _na, nb in batch], S, counts=counts)
+            for p, HA, HB in zip(parts, Hs, Hs[len(parts):]):
+                p.HA, p.HB = HA, HB
+        if self.sal == 2:
+            for p in parts:
+                eng.hist_s2_from_binhist_pair(p.HA, p.HB, S, counts=self._acc())
         if fused is None:
-            self._start_null([pid for pid, _na, _nb in batch if self.parts[pid][4] is not None])
+            self._start_null(parts)
 
-    def _start_null(self, pids):
-        """The null groups' histograms of the parts `pids` (multivariate hypergeometric, from the real groups' histograms; they
-        do not depend on exp_freq): one launch on the session's second stream, behind the launch that produced HA / HB."""
-        if not pids:
-            return
-        t, eng = self.torch, self.eng
-        NA, NB = self.NA, self.NB
-        ga, gb = (NA, NB) if self.groupSize == -1 else (self.groupSize, self.groupSize)
-        HAs, HBs = [self.parts[p][2] for p in pids], [self.parts[p][3] for p in pids]
-        row0s = [self.parts[p][4] for p in pids]
-        overlap = self.null_stream is not None and os.environ.get("EPILOGOS_NULL_OVERLAP", "1") != "0"
-        done = None
-        if overlap:
-            # outputs from the main stream's pool (a second stream has a pool of its own in torch's allocator: every new session
-            # would start with device mallocs), launch on the second stream between two events, no stream switch on the host
-            main = t.cuda.current_stream()
-            ready = t.cuda.Event()
-            ready.record(main)
-            self.null_stream.wait_event(ready)
-            HnAs, HnBs = eng.null_hist_from_binhist_parts(HAs, HBs, NA + NB, self.S, ga, gb, self.seed, row0s, stream=self.null_stream)
-            done = t.cuda.Event()
-            done.record(self.null_stream)
-            for x in (HAs[0], HBs[0], HnAs[0], HnBs[0]):
-                x.record_stream(self.null_stream)        # used there: their memory must not be reused before it is through
-        else:
-            HnAs, HnBs = eng.null_hist_from_binhist_parts(HAs, HBs, NA + NB, self.S, ga, gb, self.seed, row0s)
-        for i, p in enumerate(pids):
-            XA, XB, HA, HB, row0, _ = self.parts[p]
-            self.parts[p] = (XA, XB, HA, HB, row0, (HnAs[i], HnBs[i], done))
+    def _start_null(self, parts):
+        """The null groups' histograms of `parts` (multivariate hypergeometric, from the real groups' histograms; they do not
+        depend on exp_freq): one launch on the session's second stream, behind the launch that produced HA / HB.  Its outputs
+        come from the main stream's pool (a second stream has a pool of its own in torch's allocator: every new session would
+        start with device mallocs); the launch sits between two events, no stream switch on the host."""
+        t = self.torch
+        ga, gb = _null_widths(self.NA, self.NB, self.groupSize)
+        ready = t.cuda.Event()
+        ready.record(t.cuda.current_stream())
+        self.null_stream.wait_event(ready)
+        HnAs, HnBs = self.eng.null_hist_from_binhist_parts([p.HA for p in parts], [p.HB for p in parts], self.NA + self.NB, self.S,
+                                                           ga, gb, self.seed, [p.row0 for p in parts], stream=self.null_stream)
+        done = t.cuda.Event()
+        done.record(self.null_stream)
+        for x in (parts[0].HA, parts[0].HB, HnAs[0], HnBs[0]):
+            x.record_stream(self.null_stream)            # used there: their memory must not be reused before it is through
+        for p, HnA, HnB in zip(parts, HnAs, HnBs):
+            p.HnA, p.HnB, p.null_done = HnA, HnB, done
 
     def _null_of(self, pid):
         """(HnA, HnB) of part `pid`, ready for the current stream."""
         self._flush()
-        if self.parts[pid][5] is None:
-            self._start_null([pid])
-        HnA, HnB, done = self.parts[pid][5]
-        if done is not None:
-            self.torch.cuda.current_stream().wait_event(done)
-        return HnA, HnB
+        p = self.parts[pid]
+        if p.null_done is not None:
+            self.torch.cuda.current_stream().wait_event(p.null_done)
+        return p.HnA, p.HnB
 
     # ---- multi-rank hand-over: the score pass of paired mode reads the two groups' histograms only
     n_export = 2
 
-    def slice_part(self, pid, lo, hi, row0=None):
+    def slice_part(self, pid, lo, hi, row0):
         self._flush()
-        _XA, _XB, HA, HB, _, null = self.parts[pid]
-        self.parts.append((None, None, _aligned_rows(HA, lo, hi), _aligned_rows(HB, lo, hi), row0, None))
-        new = len(self.parts) - 1
-        if null is not None:
+        src = self.parts[pid]
+        new = _Pair(None, None, _aligned_rows(src.HA, lo, hi), _aligned_rows(src.HB, lo, hi), row0)
+        if src.HnA is not None:
             # the shuffle is keyed by (file, row in file): the rows' null groups are the ones drawn for the whole file
             HnA, HnB = self._null_of(pid)
-            self.parts[new] = self.parts[new][:5] + ((_aligned_rows(HnA, lo, hi), _aligned_rows(HnB, lo, hi), None),)
-        return new
+            new.HnA, new.HnB = _aligned_rows(HnA, lo, hi), _aligned_rows(HnB, lo, hi)
+        self.parts.append(new)
+        return len(self.parts) - 1
 
     def export_rows(self, pid, lo, hi):
         self._flush()
-        _XA, _XB, HA, HB, _, _null = self.parts[pid]
-        return [HA[lo:hi], HB[lo:hi]]
+        p = self.parts[pid]
+        return [p.HA[lo:hi], p.HB[lo:hi]]
 
-    def import_rows(self, tensors, widths, row0=None):
+    def import_rows(self, tensors, widths, row0):
         self.NA, self.NB = widths
-        self.parts.append((None, None, tensors[0].to(self.device), tensors[1].to(self.device), row0, None))
-        pid = len(self.parts) - 1
-        if row0 is not None and self.parts[pid][2].shape[0]:
-            self._start_null([pid])
-        return pid
+        p = _Pair(None, None, tensors[0].to(self.device), tensors[1].to(self.device), row0)
+        self.parts.append(p)
+        if p.HA.shape[0]:
+            self._start_null([p])
+        return len(self.parts) - 1
 
-    def ensure_acc(self, N):
+    def _results(self, pids):
+        """{pid: device results} of the held parts among `pids`.  Paired S1 (the tables fit a CU's LDS): ONE launch of the fused
+        pass over all the parts' histograms, quiescence masks included (epg_pair_scores_s1_parts) -- a launch per chromosome file
+        paid the copy of the tables into LDS, the ramp and the tail 24 times (1.5 against 1.0 ms per 15 M bins).  Otherwise the
+        separate passes, part by part (_separate)."""
         self._flush()
-        self._acc(self.S if self.sal == 1 else self.S * self.S)
+        pids = [pid for pid in pids if self.parts[pid] is not None]
+        live = [pid for pid in pids if self.parts[pid].HA.shape[0]]
+        out = {}
+        if self.sal == 1 and live:
+            NA, NB = self.NA, self.NB
+            ga, gb = _null_widths(NA, NB, self.groupSize)
+            tabs = [self._s1_table(n) for n in (NA, NB, ga, gb)]
+            quads = [(self.parts[pid].HA, self.parts[pid].HB) + self._null_of(pid) for pid in live]
+            out = dict(zip(live, _unless_unsupported(self.eng.pair_scores_s1_parts, quads, self.S, NA, NB, ga, gb, *tabs,
+                                                     qstate=self.qstate) or []))
+        return {pid: out[pid] if pid in out else self._separate(pid) for pid in pids}
 
-    def results_device(self, pid, keep=False):
+    def _separate(self, pid):
         """Scores of A, B and the two null groups, deltas, null distances, STEP 4's per-bin reduction and the quiescence mask
-        of part `pid` from its resident histograms, as device tensors."""
-        self._flush()
+        of part `pid` from its resident histograms, one launch after another."""
         eng, S, NA, NB, q = self.eng, self.S, self.NA, self.NB, self.q
-        XA, XB, HA, HB, row0, _null = self.parts[pid]
-        if HA.shape[0] and row0 is None:
-            raise ValueError("paired part %d has no shuffle key (row0)" % pid)
-        HnA, HnB = self._null_of(pid) if HA.shape[0] else (None, None)
-        if not keep:
-            self.parts[pid] = None
+        HA, HB = self.parts[pid].HA, self.parts[pid].HB
         if HA.shape[0] == 0:
             t, dv = self.torch, self.device
             return {"delta": t.empty((0, S), dtype=t.float32, device=dv), "null": t.empty(0, dtype=t.float32, device=dv),
                     "quies": t.empty(0, dtype=t.uint8, device=dv), "rdist": t.empty(0, dtype=t.float32, device=dv),
                     "mdiff": t.empty(0, dtype=t.int32, device=dv)}
-        ga, gb = (NA, NB) if self.groupSize == -1 else (self.groupSize, self.groupSize)
-        # (the null groups' histograms were drawn straight from the real groups' when the part was counted: _start_null)
+        HnA, HnB = self._null_of(pid)                    # (drawn straight from the real groups' when the part was counted)
+        ga, gb = _null_widths(NA, NB, self.groupSize)
         if self.sal == 1:
-            # one pass over the four histograms: table gathers, deltas, null distances and STEP 4's reduction (round 3); groups
-            # too wide for the tables to sit in LDS take the separate passes below
-            tabs = [self._s1_table(n) for n in (NA, NB, ga, gb)]
-            try:
-                delta, null, rdist, mdiff = eng.pair_scores_s1_from_binhist(HA, HB, HnA, HnB, S, NA, NB, ga, gb, *tabs)
-                quies = eng.quiescent_from_binhist(HA, NA, HB, NB, S, self.qstate)
-                return {"delta": delta, "null": null, "quies": quies, "rdist": rdist, "mdiff": mdiff}
-            except self.eng.EpilogosHipError as e:
-                if e.code != -2:
-                    raise
-            sA, sB = self._score_s1(HA, NA), self._score_s1(HB, NB)
-            nA, nB = self._score_s1(HnA, ga), self._score_s1(HnB, gb)
+            sA, sB, nA, nB = (self._score_s1(H, n) for H, n in ((HA, NA), (HB, NB), (HnA, ga), (HnB, gb)))
         else:                                            # quirk Q9: null halves keep the original groups' permutation counts
-            sA, _ = eng.score_s2_from_binhist(HA, NA, S, q, perms=NA * (NA - 1))
-            sB, _ = eng.score_s2_from_binhist(HB, NB, S, q, perms=NB * (NB - 1))
-            nA, _ = eng.score_s2_from_binhist(HnA, max(ga, NA), S, q, perms=NA * (NA - 1))
-            nB, _ = eng.score_s2_from_binhist(HnB, max(gb, NB), S, q, perms=NB * (NB - 1))
+            sA, sB, nA, nB = (eng.score_s2_from_binhist(H, n, S, q, perms=p)[0] for H, n, p in
+                              ((HA, NA, NA * (NA - 1)), (HB, NB, NB * (NB - 1)), (HnA, max(ga, NA), NA * (NA - 1)),
+                               (HnB, max(gb, NB), NB * (NB - 1))))
         delta, _ = eng.pair_finish(sA, sB, want_dist=False)
         _, null = eng.pair_finish(nA, nB)
         rdist, mdiff = eng.pair_metrics(delta, roundtrip=True)     # what STEP 4 would recompute from the text
         quies = eng.quiescent_from_binhist(HA, NA, HB, NB, S, self.qstate)
         return {"delta": delta, "null": null, "quies": quies, "rdist": rdist, "mdiff": mdiff}
 
-    def results_device_all(self, pids, keep=False):
-        """results_device of several parts at once.  Paired S1 (the tables fit a CU's LDS): ONE launch of the fused pass over all the
-        parts' histograms, quiescence masks included (epg_pair_scores_s1_parts) -- a launch per chromosome file paid the copy of
-        the tables into LDS, the ramp and the tail 24 times (1.5 against 1.0 ms per 15 M bins).  Otherwise part by part."""
-        self._flush()
-        eng, S, NA, NB = self.eng, self.S, getattr(self, "NA", None), getattr(self, "NB", None)
-        out = {}
-        live = [pid for pid in pids if self.parts[pid] is not None and self.parts[pid][2].shape[0]]
-        if self.sal == 1 and live and NA and NB:
-            ga, gb = (NA, NB) if self.groupSize == -1 else (self.groupSize, self.groupSize)
-            tabs = [self._s1_table(n) for n in (NA, NB, ga, gb)]
-            quads = []
-            for pid in live:
-                if self.parts[pid][4] is None:
-                    raise ValueError("paired part %d has no shuffle key (row0)" % pid)
-                HnA, HnB = self._null_of(pid)
-                quads.append((self.parts[pid][2], self.parts[pid][3], HnA, HnB))
-            try:
-                res = eng.pair_scores_s1_parts(quads, S, NA, NB, ga, gb, *tabs, qstate=self.qstate)
-                for pid, r in zip(live, res):
-                    out[pid] = r
-                    if not keep:
-                        self.parts[pid] = None
-            except eng.EpilogosHipError as e:
-                if e.code != -2:
-                    raise
-        for pid in pids:
-            if pid not in out:
-                out[pid] = self.results_device(pid, keep=keep)
-        return [out[pid] for pid in pids]
-
-    def _todo(self):
-        self._flush()
-        return [k for k, part in enumerate(self.parts) if part is not None and len(part) == 6 and (part[4] is not None or not part[2].shape[0])]
-
     def _begin(self, pids):
-        todo = [pid for pid in pids if pid in set(self._todo())]
-        self._early = dict(zip(todo, self.results_device_all(todo, keep=True)))
-
-    def _settle(self):
-        for pid in self._early:
-            self.parts[pid] = None
-        if self._early:
-            self._ready = dict(self._early) if self._ready is None else dict(self._ready, **self._early)
-        self._early = {}
+        self._early = self._results(pids)
 
     def _s1_widths(self):
-        NA, NB = getattr(self, "NA", None), getattr(self, "NB", None)
-        return [NA, NB] + ([self.groupSize] if self.groupSize != -1 else [])
+        return [self.NA, self.NB] + ([self.groupSize] if self.groupSize != -1 else [])
 
     def results(self, pid):
-        """Host arrays of part `pid`.  The first call computes the results of EVERY part still held (one launch, see
-        results_device_all); the parts are then downloaded one by one as the driver asks for them."""
+        """Host arrays of part `pid`.  A part launch() did not score is scored with EVERY part still held (see _results); the
+        parts are then downloaded one by one as the driver asks for them."""
         self.check()
-        if self._ready is None:
-            todo = self._todo()
-            self._ready = dict(zip(todo, self.results_device_all(todo)))
-        r = self._ready.pop(pid) if pid in self._ready else self.results_device(pid)
+        if pid not in self._early:
+            self._early.update(self._results([p for p, part in enumerate(self.parts) if part is not None]))
+            self._settle()
+        r = self._early.pop(pid)
         return {"delta": r["delta"].cpu().numpy(), "null": r["null"].cpu().numpy(), "quies": r["quies"].cpu().numpy().astype(bool),
                 "rdist": r["rdist"].cpu().numpy(), "mdiff": r["mdiff"].cpu().numpy()}
 

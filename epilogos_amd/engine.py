@@ -391,8 +391,9 @@ def _ptr_array(ts):
 
 def hist_rows_flat(rows, S, device, dtype=torch.int16):
     """One allocation for the [R_p, S] rows of several parts: -> (flat [R_total_padded, S], starts).  Every part starts 16-byte
-    aligned (its first row at a multiple of 8 rows: 8 rows of any S are a multiple of 16 bytes); the <= 7 rows between two parts
-    are never written by the count pass (the score pass looks nothing up for them: k_score_s1_from_hist)."""
+    aligned (its first row at a multiple of 8 rows: 8 rows of any S are a multiple of 16 bytes).  The <= 7 rows between two parts
+    are never written by the count pass, and a score launch over the whole buffer scores them from whatever they hold: the lookup
+    stays in bounds (k_score_s1_from_hist scores a count outside 1 .. N as 0) and their scores are never handed out."""
     starts, at = [], 0
     for r in rows:
         starts.append(at)
@@ -628,7 +629,7 @@ def pair_scores_s1_from_binhist(HA, HB, HnA, HnB, S, NA, NB, ga, gb, TA, TB, TnA
 def pair_scores_s1_parts(parts, S, NA, NB, ga, gb, TA, TB, TnA, TnB, qstate=None):
     """epg_pair_scores_s1_parts: `parts` is a list of (HA, HB, HnA, HnB) of the parts' histograms; one launch (per 24 parts) gives
     every part's delta [R, S], null distance [R], STEP 4's distance [R] and largest-difference state [R] and -- with qstate not
-    None -- its quiescence mask uint8 [R] (qstate < 0: all zero).  Returns a list of dicts like _HipPairedSession.results_device."""
+    None -- its quiescence mask uint8 [R] (qstate < 0: all zero).  Returns a list of dicts like _HipPairedSession._separate."""
     n = len(parts)
     if n == 0:
         return []

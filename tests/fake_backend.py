@@ -57,7 +57,7 @@ class OracleBackend:
 
 
 # ---- sessions over the host-array stand-in: same protocol as the device-resident sessions of backend.HipBackend
-# (alloc / skip / add_part / stage / add_staged / set_row0 / ensure_acc / all_reduce / finish / scores / results),
+# (alloc / skip / add_part / stage / add_staged / ensure_acc / all_reduce / finish / scores / results),
 # arithmetic through the stand-in's array methods
 class _HostSession:
     def __init__(self, be, S, saliency):
@@ -127,10 +127,6 @@ class _HostPairedSession(_HostSession):
     def stage(self, arr, N, ticket):
         return arr[:, :N]
 
-    def set_row0(self, pid, row0):
-        xa, xb, _ = self.parts[pid]
-        self.parts[pid] = (xa, xb, row0)
-
     def add_part(self, arrA, NA, ticketA, arrB, NB, ticketB, row0):
         return self.add_staged(arrA[:, :NA], NA, arrB[:, :NB], NB, row0)
 
@@ -141,7 +137,7 @@ class _HostPairedSession(_HostSession):
 
     n_export = 2
 
-    def slice_part(self, pid, lo, hi, row0=None):
+    def slice_part(self, pid, lo, hi, row0):
         xa, xb, _ = self.parts[pid]
         self.parts.append((xa[lo:hi], xb[lo:hi], row0))
         return len(self.parts) - 1
@@ -150,7 +146,7 @@ class _HostPairedSession(_HostSession):
         xa, xb, _ = self.parts[pid]
         return [np.ascontiguousarray(xa[lo:hi]), np.ascontiguousarray(xb[lo:hi])]
 
-    def import_rows(self, tensors, widths, row0=None):
+    def import_rows(self, tensors, widths, row0):
         self.parts.append((tensors[0].cpu().numpy(), tensors[1].cpu().numpy(), row0))
         return len(self.parts) - 1
 

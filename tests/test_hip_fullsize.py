@@ -148,10 +148,10 @@ def test_placed_histogram_cache(world, monkeypatch):
     be = backend.HipBackend()
     sess = be.open_single(S, 1)
     pid = sess.add_device(X, N)
-    assert sess.parts[pid].data_ptr() == home and torch.equal(sess.parts[pid], H)
+    assert sess.parts[pid].D.data_ptr() == home and torch.equal(sess.parts[pid].D, H)
     sess2 = be.open_single(S, 2)                                      # (S2 sessions place too; this one finds the home taken)
     pid2 = sess2.add_device(X, N)
-    assert sess2.parts[pid2].data_ptr() != home and torch.equal(sess2.parts[pid2], H)
+    assert sess2.parts[pid2].D.data_ptr() != home and torch.equal(sess2.parts[pid2].D, H)
     del sess, sess2
     Y = X[: R // 4].clone()                                           # another matrix: one probe of the home, kept or replaced
     Hy = eng.alloc_hist(Y, N, S)
@@ -174,7 +174,7 @@ def test_placed_histogram_cache(world, monkeypatch):
     torch.cuda.empty_cache()                                          # (the walked blocks back to the driver: the tests behind this one want the memory)
 
 
-def test_paired_job_full_size_properties(world):
+def test_paired_session_full_size_properties(world):
     """BASELINE config 5 at full size (15 M bins x (379 + 342) columns of the same synthetic matrix) through the command line's
     session, fed in 24 chromosome-sized parts like bench.py does: size-independent properties.  Every null draw is a
     permutation's bookkeeping (per bin: the two null groups add up to the two real ones and have the groups' sizes); a group
@@ -197,8 +197,9 @@ def test_paired_job_full_size_properties(world):
         sess.ensure_acc(NA + NB)
         sess.finish_device(sum(b - a for _f, _r0, a, b in part_list), NA + (NB if groups[1] is XB else NA))
         nulls = [sess._null_of(p) for p in pids]
-        hists = [(sess.parts[p][2], sess.parts[p][3]) for p in pids]
-        res = sess.results_device_all(pids)
+        hists = [(sess.parts[p].HA, sess.parts[p].HB) for p in pids]
+        sess.launch_scores(pids)
+        res = [sess._early[p] for p in pids]
         sess.check()
         return res, nulls, hists
 

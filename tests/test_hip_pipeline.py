@@ -89,10 +89,10 @@ def test_cli_single_s1_on_input_only_pandas_reads(tmp_path, golden_real, capsys)
     assert (out / "regionsOfInterest_in10_s1.txt").read_text() == (out2 / "regionsOfInterest_in10_s1.txt").read_text()
 
 
-def test_single_session_counts_and_scores_parts_in_batches(monkeypatch):
+def test_single_session_batches_equal_per_part_launches():
     """S1 parts of less than a GiB are counted in ONE launch per batch (epg_bin_hist_parts, histograms in one flat allocation with
     unwritten rows between the parts) and scored in ONE launch per batch: the same counts, exp_freq and float32 scores, bit for bit,
-    as a launch per part (EPILOGOS_SINGLE_BATCH=0) and as the oracle -- with row counts that are no multiple of eight, an empty
+    as a launch per part (add_device(place=False)) and as the oracle -- with row counts that are no multiple of eight, an empty
     part, a one-row part, parts asked for out of order, a part sliced and one dropped before the batch was counted, and a batch
     that is only partly scored early."""
     from epilogos_amd import backend
@@ -107,13 +107,13 @@ def test_single_session_counts_and_scores_parts_in_batches(monkeypatch):
     be = backend.HipBackend()
 
     def job(batch, early):
-        monkeypatch.setenv("EPILOGOS_SINGLE_BATCH", "1" if batch else "0")
         sess = be.open_single(S, 1)
-        pids = [sess.add_device(be.to_device(x) if len(x) else torch.empty((0, 80), dtype=torch.int8, device="cuda"), N if len(x) else 0) for x in xs]
+        pids = [sess.add_device(be.to_device(x) if len(x) else torch.empty((0, 80), dtype=torch.int8, device="cuda"), N if len(x) else 0,
+                                place=None if batch else False) for x in xs]
         if batch:
-            assert sum(p is backend._PENDING for p in sess.parts) == 5 and sess._pending_rows == sum(rows)
+            assert sum(p.D is None for p in sess.parts) == 5 and sess._pending_rows == sum(rows)
         extra = sess.slice_part(pids[3], 100, 1100)                       # (forces the count pass of the pending batch)
-        assert not sess._pending and all(p is not backend._PENDING for p in sess.parts)
+        assert not sess._pending and all(p.D is not None for p in sess.parts)
         sess.ensure_acc(N)
         total = sum(rows)
         sess.launch(total, N, [pids[k] for k in early] + [extra])
@@ -809,3 +809,67 @@ def test_launch_then_finish_rescores_when_a_device_table_differs(mode):
         assert np.array_equal(q0, onp.normalise(onp.expected_s1(both, S_)))
         ref = onp.score_s1(xa, q0, S_).astype(np.float32) - onp.score_s1(xb, q0, S_).astype(np.float32)
         np.testing.assert_allclose(clean, ref, rtol=1e-6, atol=1e-7)
+
+
+def _paired_session_against_composed_calls(sal, NA, NB, g, R):
+    """A paired session over two files, the first of them cut to a row slice (odd start) and its whole-file part dropped: the
+    deltas and quiescence masks are the oracle's; the null distances, STEP 4's distances and largest-difference states -- and the
+    deltas -- are, bit for bit, what the engine's own calls give when composed by hand: bin_hist_parts, null_hist_from_binhist
+    with the part's shuffle key, the four score passes, pair_finish twice and pair_metrics."""
+    from epilogos_amd import backend
+    from epilogos_amd.driver import shuffle_key
+    from epilogos_amd.scores import s1ScoreTable
+    from oracle import oracle_np as onp
+    from tests.conftest import synth_states
+    be = backend.HipBackend()
+    eng = be.engine
+    seed, qs = 77, S - 1
+    xa, xb = synth_states(R, NA, seed=NA), synth_states(R, NB, seed=NB + 1)
+    xa[5:9], xb[5:8] = qs, qs                                      # three quiescent bins, in the slice
+    cut, lo = R * 2 // 5, 3
+    hi = cut - 7
+    sess = be.open_paired(S, sal, qs, g, seed)
+    pids = [sess.add_staged(be.to_device(xa[a:b]), NA, be.to_device(xb[a:b]), NB, shuffle_key(f, 0))
+            for f, (a, b) in enumerate(((0, cut), (cut, R)))]
+    sl = sess.slice_part(pids[0], lo, hi, shuffle_key(0, lo))
+    sess.drop_part(pids[0])
+    sess.ensure_acc(NA + NB)
+    sess.launch(R, NA + NB, [sl, pids[1]])
+    q = sess.finish(R, NA + NB)
+    assert np.array_equal(q, onp.normalise((onp.expected_s1 if sal == 1 else onp.expected_s2)(np.concatenate([xa, xb], axis=1), S)))
+    got = {pid: sess.results(pid) for pid in (pids[1], sl)}
+    qd = torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32).reshape(-1)).cuda()
+    ga, gb = (NA, NB) if g == -1 else (g, g)
+    for pid, a, b, key in ((sl, xa[lo:hi], xb[lo:hi], shuffle_key(0, lo)), (pids[1], xa[cut:], xb[cut:], shuffle_key(1, 0))):
+        (HA, HB), _ = eng.bin_hist_parts([be.to_device(a), be.to_device(b)], [NA, NB], S)
+        HnA, HnB = eng.null_hist_from_binhist(HA, HB, NA + NB, S, ga, gb, seed, key)
+        if sal == 1:
+            tab = {n: torch.from_numpy(s1ScoreTable(q, n)[1]).cuda() for n in (NA, NB, ga, gb)}
+            sA, sB, nA, nB = (eng.score_s1_from_binhist_table(H, n, S, T32=tab[n])[0] for H, n in ((HA, NA), (HB, NB), (HnA, ga), (HnB, gb)))
+            ra, rb = onp.score_s1(a, q, S), onp.score_s1(b, q, S)
+        else:                                                      # (quirk Q9: the null halves keep the real groups' permutation counts)
+            sA, sB, nA, nB = (eng.score_s2_from_binhist(H, n, S, qd, perms=p)[0] for H, n, p in
+                              ((HA, NA, NA * (NA - 1)), (HB, NB, NB * (NB - 1)), (HnA, max(ga, NA), NA * (NA - 1)), (HnB, max(gb, NB), NB * (NB - 1))))
+            ra, rb = onp.score_s2(a, q, S, perms=NA * (NA - 1)), onp.score_s2(b, q, S, perms=NB * (NB - 1))
+        delta, _ = eng.pair_finish(sA, sB, want_dist=False)
+        _, null = eng.pair_finish(nA, nB)
+        rdist, mdiff = eng.pair_metrics(delta, roundtrip=True)
+        r = got[pid]
+        for k, v in (("delta", delta), ("null", null), ("rdist", rdist), ("mdiff", mdiff)):
+            assert np.array_equal(r[k], v.cpu().numpy()), (pid, k)
+        want, _ = onp.pair_finish(ra.astype(np.float32), rb.astype(np.float32))
+        np.testing.assert_allclose(r["delta"], want, atol=1.01e-5)
+        assert np.array_equal(r["quies"], onp.quiescent_mask(a, b, qs))
+    assert got[sl]["quies"].sum() == 3
+
+
+@pytest.mark.parametrize("sal", [1, 2])
+def test_paired_session_with_a_group_size(sal):
+    """-g: the count pass and the null draw as two kernels (the draw on the session's second stream), then separate score passes."""
+    _paired_session_against_composed_calls(sal, 61, 47, 20, 600)
+
+
+def test_paired_session_with_groups_too_wide_for_the_fused_score_pass():
+    """Paired S1 with 900 + 900 columns: the S1 tables do not fit a CU's LDS next to the fused pass's staging areas, so every part
+    takes the separate score passes."""
+    _paired_session_against_composed_calls(1, 900, 900, -1, 300)
