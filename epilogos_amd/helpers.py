@@ -43,6 +43,35 @@ def splitRows(totalRows, numProcesses):
     return [(i * totalRows // numProcesses, (i + 1) * totalRows // numProcesses) for i in range(numProcesses)]
 
 
+def splitGpusOption(argv):
+    """`--gpus N` / `--gpus=N`, anywhere in an argument list -> (N as written, the last one given; None when there is none;
+    "" for a trailing `--gpus` without a value) and the list without them.  Shared by the `epilogos` and simsearch command
+    lines."""
+    value, out, skip = None, [], False
+    for a in argv:
+        if skip:
+            value, skip = a, False
+        elif a == "--gpus":
+            value, skip = "", True
+        elif a.startswith("--gpus="):
+            value = a[len("--gpus="):]
+        else:
+            out.append(a)
+    return value, out
+
+
+def gpusCount(value):
+    """The number of a `--gpus` value as written: an integer >= 0 (0 = every visible GPU), else click.UsageError."""
+    import click
+    try:
+        n = int(value)
+    except (TypeError, ValueError):
+        raise click.UsageError("--gpus takes a whole number of GPUs (0 means use all visible GPUs), not %r" % value)
+    if n < 0:
+        raise click.UsageError("Number of GPUs must be positive or zero (0 means use all visible GPUs)")
+    return n
+
+
 def _cache_paths(path):
     """Binary cache of a parsed matrix file: EPILOGOS_CACHE_DIR/<key>.{states,locblob,locoff}.npy, keyed
     by the file's absolute path, size and modification time so that a changed input is parsed again."""

@@ -321,15 +321,8 @@ def _visible_gpus():
 
 def _strip_gpus(argv):
     """The argument list without --gpus (the children learn their number from WORLD_SIZE)."""
-    out, skip = [], False
-    for a in argv:
-        if skip:
-            skip = False
-        elif a == "--gpus":
-            skip = True
-        elif not a.startswith("--gpus="):
-            out.append(a)
-    return out
+    from .helpers import splitGpusOption
+    return splitGpusOption(argv)[1]
 
 
 def _launch_command(gpus, argv, port):

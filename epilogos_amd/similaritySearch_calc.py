@@ -6,6 +6,7 @@ For every region of interest (ROI) the distance to every window of the reduced g
 greedy pick of non-overlapping windows closer than half the mode run in epg_simsearch (csrc/epg_simsearch.hip) on exact
 integers, ROI batches sized from a workspace cap."""
 import ctypes as C
+import os
 import sys
 from pathlib import Path
 from time import time
@@ -133,5 +134,10 @@ def main(outputDir, windowBins, blockSize, nCores, nDesiredMatches, nJobs, proce
 
 
 if __name__ == "__main__":
+    if "LOCAL_RANK" in os.environ:              # a child of `similaritySearch_run --gpus N`: its own GPU (shared under
+        import torch                             # EPILOGOS_DIST_BACKEND=gloo, as the `epilogos` command's ranks share it)
+        if torch.cuda.is_available():            # (without one, simsearch's require_gpu says so)
+            local = int(os.environ["LOCAL_RANK"])
+            torch.cuda.set_device(local % torch.cuda.device_count() if os.environ.get("EPILOGOS_DIST_BACKEND") else local)
     main(Path(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5]), int(sys.argv[6]),
          int(sys.argv[7]))

@@ -2,16 +2,25 @@
 epilogos/similaritySearch_run.py (click options :72-111, main :112-140, buildSimSearch :143-219, querySimSearch :237-285, block
 sizes :288-345).  -b runs the three stages in this process (STEP 2 on the GPU) instead of submitting SLURM jobs: -j, -p, -t,
 --mm-mem, --calc-mem and --write-mem are accepted and ignored, as the `epilogos` command does with its SLURM options; -c caps
-the host thread pools (torch's; the process is not pinned).  -q writes one similarity_search_region_*_recs.bed per query region
-found in a built simsearch.bed.gz."""
+the host thread pools (torch's; the process is not pinned).  `--gpus N` (cli(), not an option of main: main's options are the
+reference's) splits STEP 2 over N GPUs of the node instead: one child process per GPU, each running the module's argv interface
+(the reference's SLURM job) on its contiguous share of the ROIs, while this process stays GPU-free and runs STEP 1 and 3.
+-q writes one similarity_search_region_*_recs.bed per query region found in a built simsearch.bed.gz."""
 import os
 import re
+import signal
+import subprocess
+import sys
+import tempfile
+import threading
 from pathlib import Path
-from time import time
+from time import sleep, time
 
 import click
 import numpy as np
 import pandas as pd
+
+from .helpers import splitGpusOption
 
 BLOCK_SIZES_200 = {5000: 1, 10000: 2, 25000: 5, 50000: 10, 75000: 15, 100000: 20}
 BLOCK_SIZES_20 = {500: 1, 1000: 2, 2500: 5, 5000: 10, 7500: 15, 10000: 20}
@@ -58,19 +67,127 @@ def generateRegionArr(query):
                      + "or path to bed file containing query regions)")
 
 
-def buildSimSearch(scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatches, filterState, filterScore):
+def buildSimSearch(scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatches, filterState, filterScore, gpus=1):
+    """STEP 1-3.  gpus > 1: STEP 2 as that many child processes, one per GPU (runChildren); nJobs (-j) is ignored either way."""
     from . import similaritySearch_calc, similaritySearch_max_mean, similaritySearch_write
     print("\n\n\n        Building Similarity Search Results...", flush=True)
     windowBP, windowBins, blockSize = windowParameters(scoresPath, windowBP)
-    if nCores > 0:                               # the host thread pools (the reference's -c sized its worker pool); no pinning
+    if gpus > 1:
+        checkDevices(gpus)                       # before STEP 1, which takes minutes on a whole genome
+    elif nCores > 0:                             # the host thread pools (the reference's -c sized its worker pool); no pinning
         import torch
         torch.set_num_threads(nCores)
     print("\n        STEP 1: Salient Region Selection", flush=True)
     similaritySearch_max_mean.main(outputDir, scoresPath, windowBins, blockSize, windowBP, filterState, filterScore)
     print("\n        STEP 2: Similarity Search Calculation", flush=True)
-    similaritySearch_calc.main(outputDir, windowBins, blockSize, nCores, nDesiredMatches, 1, 0)
+    if gpus > 1:
+        for stale in Path(outputDir).glob("simsearch_indices_*.npy"):     # an earlier build's: STEP 3 would merge them in
+            os.remove(stale)
+        print("Splitting the regions over %d GPU processes..." % gpus, flush=True)
+        try:
+            runChildren(childJobs(outputDir, windowBins, blockSize, nCores, nDesiredMatches, gpus))
+        except BaseException:                    # the children that finished wrote theirs: a later build must not merge them
+            for part in Path(outputDir).glob("simsearch_indices_*.npy"):
+                os.remove(part)
+            raise
+    else:
+        similaritySearch_calc.main(outputDir, windowBins, blockSize, nCores, nDesiredMatches, 1, 0)
     print("\n        STEP 3: Writing results", flush=True)
-    similaritySearch_write.main(outputDir, windowBins, blockSize, 1, nDesiredMatches)
+    similaritySearch_write.main(outputDir, windowBins, blockSize, gpus, nDesiredMatches)
+
+
+def checkDevices(gpus):
+    """Refuse more children than visible GPUs (counted without torch: this process stays GPU-free), in the words of the
+    `epilogos` command; EPILOGOS_DIST_BACKEND=gloo lets them share the GPUs (child i on device i % count)."""
+    from . import run
+    count = run._visible_gpus()
+    if gpus > count and not os.environ.get("EPILOGOS_DIST_BACKEND", ""):
+        raise SystemExit("ERROR: rank %d of this node has no GPU: %d rank(s) were started for %d usable device(s) "
+                         "(--gpus / *_VISIBLE_DEVICES)" % (count, gpus, count))
+
+
+def childJobs(outputDir, windowBins, blockSize, nCores, nDesiredMatches, gpus):
+    """[(argv, env)] of the STEP 2 children: child i runs `python -m epilogos_amd.similaritySearch_calc` (the reference's SLURM
+    job interface) for processTag i of nJobs = gpus, on GPU LOCAL_RANK = i, with an equal share of the host thread budget
+    (the node's cores, capped by -c as the `epilogos` command's host budget is) as OMP_NUM_THREADS and nCores."""
+    from ._io import node_cores
+    budget = min(nCores, node_cores()) if nCores > 0 else node_cores()
+    share = max(1, budget // gpus)
+    root = str(Path(__file__).resolve().parents[1])
+    jobs = []
+    for i in range(gpus):
+        env = dict(os.environ)
+        env["LOCAL_RANK"] = str(i)
+        env["OMP_NUM_THREADS"] = str(share)
+        env["PYTHONPATH"] = root + (os.pathsep + env["PYTHONPATH"] if env.get("PYTHONPATH") else "")
+        argv = [sys.executable, "-m", "epilogos_amd.similaritySearch_calc", str(Path(outputDir).resolve()), str(windowBins),
+                str(blockSize), str(share), str(nDesiredMatches), str(gpus), str(i)]
+        jobs.append((argv, env))
+    return jobs
+
+
+def _stop(procs, grace=10.0):
+    """SIGTERM, up to `grace` seconds for all of them together, then SIGKILL."""
+    for p in procs:
+        if p.poll() is None:
+            p.terminate()
+    end = time() + grace
+    for p in procs:
+        try:
+            p.wait(timeout=max(0.0, end - time()))
+        except subprocess.TimeoutExpired:
+            p.kill()
+            p.wait()
+
+
+def _status(rc):
+    if rc < 0:
+        try:
+            return "was killed by signal %s (%d)" % (signal.Signals(-rc).name, -rc)
+        except ValueError:
+            return "was killed by signal %d" % -rc
+    return "exited with status %d" % rc
+
+
+def runChildren(jobs, poll=0.05, tail=20):
+    """Start every (argv, env) job, wait for all of them, and pass their stderr on.  The first that fails ends the build:
+    the others are stopped (_stop) and SystemExit names the child, its status and the last lines of its stderr.  A failed
+    child is never started again.  A SIGTERM to this process ends the build the same way (the children are stopped)."""
+    procs, errs = [], []
+
+    def terminated(signum, _frame):
+        raise SystemExit("ERROR: similarity search stopped by %s" % signal.Signals(signum).name)
+    main_thread = threading.current_thread() is threading.main_thread()
+    previous = signal.signal(signal.SIGTERM, terminated) if main_thread else None
+    try:
+        for argv, env in jobs:
+            errs.append(tempfile.TemporaryFile())
+            procs.append(subprocess.Popen(argv, env=env, stderr=errs[-1]))
+        running = set(range(len(procs)))
+        while running:
+            for i in sorted(running):
+                rc = procs[i].poll()
+                if rc is None:
+                    continue
+                running.discard(i)
+                errs[i].seek(0)
+                err = errs[i].read().decode(errors="replace")
+                if rc != 0:
+                    _stop([procs[j] for j in running])
+                    last = "\n".join(err.splitlines()[-tail:])
+                    raise SystemExit("ERROR: similarity search STEP 2 child %d of %d %s; STEP 3 is skipped: no simsearch.bed.gz "
+                                     "was written.%s" % (i, len(procs), _status(rc),
+                                                         "\nLast lines of its stderr:\n" + last if last else ""))
+                if err:
+                    sys.stderr.write(err)
+            if running:
+                sleep(poll)
+    finally:
+        _stop(procs)                             # nothing outlives the build (an error or an interrupt in this process)
+        for f in errs:
+            f.close()
+        if main_thread:
+            signal.signal(signal.SIGTERM, signal.SIG_DFL if previous is None else previous)
 
 
 def querySimSearch(query, simSearchPath, outputDir):
@@ -130,16 +247,41 @@ def main(buildBool, scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatc
         raise ValueError("Either -b or -q flag must be used to run simsearch")
     elif buildBool and query != "":
         raise ValueError("Both -b and -q flags cannot be used at the same time")
+    gpus = (click.get_current_context().obj or {}).get("gpus")        # cli()'s --gpus: None when not given
+    if gpus is not None and query != "":
+        raise click.UsageError("--gpus applies to -b only: query mode does not use a GPU")
     outputDir = Path(outputDir)
     if not outputDir.exists():
         outputDir.mkdir(parents=True)
     if not outputDir.is_dir():
         raise NotADirectoryError("Given path is not a directory: {}".format(str(outputDir)))
     if buildBool:
-        buildSimSearch(scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatches, filterState, filterScore)
+        buildSimSearch(scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatches, filterState, filterScore,
+                       gpus=1 if gpus is None else gpus)
     else:
         querySimSearch(query, simSearchPath, outputDir)
 
 
+def resolveGpus(value):
+    """A --gpus value as written -> the number of GPU processes (0: every visible GPU, counted without torch)."""
+    from . import run
+    from .helpers import gpusCount
+    n = gpusCount(value)
+    return run._visible_gpus() if n == 0 else n
+
+
+def cli(argv=None):
+    """`python -m epilogos_amd.similaritySearch_run`: main with `--gpus N` / `--gpus=N` taken out of the arguments first (main's
+    click options stay the reference's); the value reaches main through click's ctx.obj."""
+    argv = sys.argv[1:] if argv is None else list(argv)
+    value, rest = splitGpusOption(argv)
+    try:
+        gpus = None if value is None else resolveGpus(value)
+    except click.UsageError as e:
+        e.show()
+        sys.exit(e.exit_code)
+    main.main(args=rest, prog_name="python -m epilogos_amd.similaritySearch_run", obj={"gpus": gpus})
+
+
 if __name__ == "__main__":
-    main()
+    cli()

@@ -9,11 +9,20 @@ genome.  Timed: the bare epg_simsearch calls over all ROIs in batches (`ms_per_r
 similaritySearch_calc.simsearch (host bounds, uploads, downloads: what `similaritySearch_run -b` runs as STEP 2,
 `simsearch_path_ms_per_roi`).  The split into distance, sort and select (`stages_ms_per_roi`) comes from a child run of this tool
 under `rocprofv3 --kernel-trace --stats` (kernel device time: k_simsearch_dist, the rocPRIM sort kernels with their buffer fills,
-k_simsearch_select); --no-stages skips it.  Prints one JSON line, with the path's time extrapolated to 20 000 and 120 000 ROIs."""
+k_simsearch_select); --no-stages skips it.  Prints one JSON line, with the path's time extrapolated to 20 000 and 120 000 ROIs.
+
+    python tools/simsearch_bench.py --gpus N [--bins 1000000]
+
+times the whole command instead, `python -m epilogos_amd.similaritySearch_run -b --gpus N`, on a synthetic 200-bp scores file of
+--bins bins drawn the same way (default window: 25 kb, block size 5).  The JSON line has the wall time of the command and of its
+STEP 1, STEP 2 and STEP 3 (from the moment each STEP line reaches this tool's pipe; `startup_s` is the time before STEP 1).  This
+process never touches the GPU.  With more processes than GPUs, set EPILOGOS_DIST_BACKEND=gloo to let them share one: STEP 2's
+GPU work is then the same as with --gpus 1 and the difference is the cost of the extra processes."""
 import argparse
 import csv
 import ctypes as C
 import json
+import os
 import shutil
 import subprocess
 import sys
@@ -34,7 +43,12 @@ def main():
     ap.add_argument("--batch", type=int, default=0, help="ROIs per call (0: from the 2 GiB workspace cap)")
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--no-stages", action="store_true", help="skip the profiled child run that splits the stages")
+    ap.add_argument("--gpus", type=int, default=None, help="time the -b command with --gpus N end to end instead")
+    ap.add_argument("--bins", type=int, default=1_000_000, help="bins of the synthetic scores file (with --gpus)")
     a = ap.parse_args()
+    if a.gpus is not None:
+        build_bench(a)
+        return
     import torch
     from epilogos_amd import _abi, engine
     from epilogos_amd import similaritySearch_calc as calc
@@ -97,6 +111,53 @@ def main():
     res["simsearch_path_ms_per_roi"] = round(path_ms, 4)
     res["extrapolated_s"] = {"20000": round(path_ms * 20000 / 1e3, 1), "120000": round(path_ms * 120000 / 1e3, 1)}
     res["stages_ms_per_roi"] = stages(a, B)
+    print(json.dumps(res), flush=True)
+
+
+def synthetic_scores(path, bins, S):
+    """A 200-bp scores file (chr1) of 40 row classes, the first on 90 % of the bins, values on the 1e-5 grid in [0, 1)."""
+    from epilogos_amd import _io
+    rng = np.random.default_rng(0)
+    base = rng.integers(0, 100000, size=(40, S))
+    x = base[np.where(rng.random(bins) < 0.9, 0, rng.integers(0, 40, size=bins))] + rng.integers(0, 50, size=(bins, S))
+    lines = ["chr1\t%d\t%d\n" % (200 * i, 200 * i + 200) for i in range(bins)]
+    blob = "".join(lines).encode()
+    off = np.zeros(bins + 1, dtype=np.int64)
+    np.cumsum([len(line) for line in lines], out=off[1:])
+    _io.write_scores(path, _io.Locations(np.frombuffer(blob, dtype=np.uint8).copy(), off), (x / 1e5).astype(np.float32))
+
+
+def build_bench(a):
+    """`similaritySearch_run -b --gpus N` end to end: total and per-STEP wall times, as the command's STEP lines arrive."""
+    root = Path(__file__).resolve().parents[1]
+    with tempfile.TemporaryDirectory() as d:
+        sp = Path(d) / "scores.txt.gz"
+        synthetic_scores(sp, a.bins, a.states)
+        out = Path(d) / "out"
+        cmd = [sys.executable, "-m", "epilogos_amd.similaritySearch_run", "-b", "-s", str(sp), "-o", str(out),
+               "--gpus", str(a.gpus)]
+        env = dict(os.environ)
+        env["PYTHONPATH"] = str(root) + (os.pathsep + env["PYTHONPATH"] if env.get("PYTHONPATH") else "")
+        marks = {}
+        with tempfile.TemporaryFile() as err:
+            t0 = time.perf_counter()
+            p = subprocess.Popen(cmd, cwd=root, env=env, stdout=subprocess.PIPE, stderr=err, text=True)
+            for line in p.stdout:
+                for k in ("STEP 1:", "STEP 2:", "STEP 3:"):
+                    if line.strip().startswith(k):
+                        marks[k[:6]] = time.perf_counter() - t0
+            rc = p.wait()
+            total = time.perf_counter() - t0
+            if rc != 0:
+                err.seek(0)
+                sys.exit("the build failed (%d):\n%s" % (rc, err.read().decode(errors="replace")[-3000:]))
+        rois = len(np.load(out / "simsearch_indices.npy"))
+        positions = len(np.load(out / "reduced_genome.npy"))
+    s1, s2, s3 = marks["STEP 1"], marks["STEP 2"], marks["STEP 3"]
+    res = {"tool": "simsearch_bench", "mode": "build", "gpus": a.gpus, "bins": a.bins, "states": a.states, "rois": rois,
+           "positions": positions, "total_s": round(total, 2), "startup_s": round(s1, 2), "step1_s": round(s2 - s1, 2),
+           "step2_s": round(s3 - s2, 2), "step3_s": round(total - s3, 2),
+           "shared_gpu": bool(os.environ.get("EPILOGOS_DIST_BACKEND"))}
     print(json.dumps(res), flush=True)
 
 
