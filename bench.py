@@ -18,10 +18,15 @@ Synthetic states are i.i.d. with the empirical chr1 state frequencies (SURVEY.md
 global chunk seed, so the matrix does not depend on the GPU count.
 
 Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` for the dominant kernel
-(k_bin_hist, HBM-bound, 833 algorithmic bytes per bin) and `cpu_baseline` (the per-bin numpy loop of
-oracle/rowloop_baseline.py on the host cores, N = 1 only).
+(k_bin_hist, HBM-bound, 833 algorithmic bytes per bin) from the events of the timed steps.
 
-The same line carries `configs`: BASELINE.json's configurations 3, 4 and 5 measured in the same run, device-resident,
+A plain run does only what that line's headline needs: it sets up, warms up, times the steps, writes --dump-outputs and prints
+the line.  Everything below that takes runs of its own -- `cpu_baseline`, `s1_paths`, `allreduce_probe`, `placement.unplaced`,
+`configs`, `dist_variants`, `rccl_selftest`, `graph_ms_per_step`, `projected_speedup_8`, and the kernel probe of --graph -- is
+measured with `--full` only; their own options (--configs, --shard-bins, ...) choose among them there.
+
+`--full`: `cpu_baseline` (the per-bin numpy loop of oracle/rowloop_baseline.py on the host cores, N = 1 only), and
+`configs`: BASELINE.json's configurations 3, 4 and 5 measured in the same run, device-resident,
 through the sessions the command line uses (backend.HipBackend.open_single / open_paired -- the product's own sequence
 of launches), each with its own roofline figure:
     "s2"     whole S2 job on the S1 matrix (K1, pair counts from the histograms, all-reduce, normalise, score pass),
@@ -649,29 +654,33 @@ def main():
                     help="default strong: ONE --bins genome split over the GPUs")
     ap.add_argument("--biosamples", type=int, default=833)
     ap.add_argument("--states", type=int, default=18)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also every measurement that takes runs of its own: the CPU baseline, s1_paths, the "
+                         "all-reduce probe, the unplaced jobs, --configs, the distribution variants, the RCCL self-test, the graph "
+                         "leg, projected_speedup_8 and the kernel probe of --graph; without it a run measures the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--packed", action="store_true", help="row pitch = biosamples (unaligned rows) instead of 16-byte padded")
     ap.add_argument("--dist", choices=["chr1", "uniform", "correlated"], default="chr1", help="synthetic state distribution")
-    ap.add_argument("--configs", default="s2,s3,s3_small,paired", help="BASELINE configs 3-5 measured next to the headline: any of s2,s3,s3_small,paired; none")
+    ap.add_argument("--configs", default="s2,s3,s3_small,paired", help="--full: BASELINE configs 3-5 measured next to the headline: any of s2,s3,s3_small,paired; none")
     ap.add_argument("--s3-bins", type=int, default=0, help="bins of the S3 measurement (whole job, all ranks); 0 = the genome (--bins), one repetition")
     ap.add_argument("--s3-small-bins", type=int, default=2_000_000, help="bins of the s3_small measurement (--config-reps repetitions)")
-    ap.add_argument("--dist-variants", type=int, default=1, help="one GPU: K1 / job time on the uniform and the row-correlated matrix (SURVEY 8d); 0 = skip")
-    ap.add_argument("--graph-leg", type=int, default=1, help="after the headline: the step as one hipGraph replay (graph_ms_per_step); 0 = skip")
+    ap.add_argument("--dist-variants", type=int, default=1, help="--full, one GPU: K1 / job time on the uniform and the row-correlated matrix (SURVEY 8d); 0 = skip")
+    ap.add_argument("--graph-leg", type=int, default=1, help="--full: after the headline, the step as one hipGraph replay (graph_ms_per_step); 0 = skip")
     ap.add_argument("--config-reps", type=int, default=3)
     ap.add_argument("--extras-deadline", type=int, default=300,
                     help="seconds the measurements after the timed region (--configs, the unplaced jobs, the self-test, the graph leg) may take before rank 0 "
                          "prints the line without the rest and every rank exits; 0 = no limit")
     ap.add_argument("--graph", action="store_true", help="capture the step (K1, all-reduce, combine, score) in a hipGraph and replay it "
-                                                         "(kernels_ms then comes from an un-captured probe after the timed region)")
+                                                         "(kernels_ms then comes from an un-captured probe after the timed region, with --full)")
     ap.add_argument("--path", choices=["session", "engine"], default="session",
                     help="what a headline step runs: session = backend._HipSingleSession, the command line's own sequence of calls "
                          "(add_device -> all_reduce -> finish_device -> scores_device; per-step allocations like the product's); "
                          "engine = the bare ABI calls on preallocated buffers (always used by --graph)")
-    ap.add_argument("--shard-bins", type=int, default=1_875_000, help="one GPU: both paths are also timed on a shard of this "
+    ap.add_argument("--shard-bins", type=int, default=1_875_000, help="--full, one GPU: both paths are also timed on a shard of this "
                                                                         "many bins (an eighth of the genome: the 8-GPU share); 0 = skip")
-    ap.add_argument("--allreduce-leg", type=int, default=1, help="one GPU without --pg: join a one-rank RCCL group AFTER the timed region to time the count vector's all-reduce (for projected_speedup_8); 0 = skip")
+    ap.add_argument("--allreduce-leg", type=int, default=1, help="--full, one GPU without --pg: join a one-rank RCCL group AFTER the timed region to time the count vector's all-reduce (for projected_speedup_8); 0 = skip")
     ap.add_argument("--pg", action="store_true", help="one GPU: still join a one-rank RCCL process group, so that the step contains the all-reduce")
-    ap.add_argument("--placement-experiment", type=int, default=1, help="0: skip the jobs with an unplaced histogram cache after the timed region")
+    ap.add_argument("--placement-experiment", type=int, default=1, help="--full: 0 skips the jobs with an unplaced histogram cache after the timed region")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to test the "
                                                       "multi-rank path on a box with one GPU, ranks then share cuda:0)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -710,7 +719,7 @@ def main():
         except OSError:
             keeper = None                                            # no child to be had: rank 0 prints the line itself
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(N, S)      # before any GPU initialisation: it forks
         except Exception as e:            # a host without fork / enough memory must not take the GPU measurement down
@@ -888,14 +897,16 @@ def main():
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
-    if not ev:                                                             # graph replay / no events: per-kernel times from a probe
+    if not ev and args.full:                                               # graph replay / no events: per-kernel times from a probe
         _, ev, _, _ = timed_steps(X, H, out32, min(args.steps, 10), 1, session=use_session)
     if os.environ.get("EPG_BENCH_TRACE") and rank == 0:      # per-step k_bin_hist times (clock ramps, box variance)
         print("k_bin_hist ms per step:", " ".join("%.3f" % e[0].elapsed_time(e[1]) for e in ev), file=sys.stderr, flush=True)
         print("host enqueue done at ms:", " ".join("%.1f" % (t * 1e3) for t in host_t), file=sys.stderr, flush=True)
-    hist_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
-    ar_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev]))
-    rest_ms = float(np.mean([e[2].elapsed_time(e[3]) for e in ev]))
+    hist_ms = ar_ms = rest_ms = None                                       # (no events and no probe: no per-kernel figures)
+    if ev:
+        hist_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
+        ar_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in ev]))
+        rest_ms = float(np.mean([e[2].elapsed_time(e[3]) for e in ev]))
 
     # ---- several ranks: what every rank saw (K1 per launch, its own time for the K steps), gathered on rank 0
     per_rank = None
@@ -909,25 +920,27 @@ def main():
     else:
         whos = [who]
     if world > 1:
-        mine = torch.tensor([hist_ms, own_dt * 1e3 / args.steps, ar_ms, rest_ms], dtype=torch.float64, device=dev)
+        # (every rank has events or none: same arguments, same environment)
+        mine = torch.tensor([own_dt * 1e3 / args.steps] + ([hist_ms, ar_ms, rest_ms] if ev else []), dtype=torch.float64, device=dev)
         allv = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allv, mine)
         allv = np.array([v.cpu().numpy() for v in allv])
-        per_rank = {"k_bin_hist_ms": [round(float(v), 4) for v in allv[:, 0]],
-                    "k_bin_hist_ms_min_max": [round(float(allv[:, 0].min()), 4), round(float(allv[:, 0].max()), 4)],
-                    "own_ms_per_step": [round(float(v), 4) for v in allv[:, 1]],
-                    "skew_ms_per_step": round(float(allv[:, 1].max() - allv[:, 1].min()), 4),
-                    "allreduce_ms": [round(float(v), 4) for v in allv[:, 2]],
-                    "combine+score_ms": [round(float(v), 4) for v in allv[:, 3]],
+        per_rank = {"own_ms_per_step": [round(float(v), 4) for v in allv[:, 0]],
+                    "skew_ms_per_step": round(float(allv[:, 0].max() - allv[:, 0].min()), 4),
                     "ranks": whos,
                     "what": "own_ms_per_step = a rank's wall time from the common start until ITS last step had drained, over the "
                             "steps (the closing barrier excluded); skew = slowest - fastest rank"}
+        if ev:
+            per_rank.update({"k_bin_hist_ms": [round(float(v), 4) for v in allv[:, 1]],
+                             "k_bin_hist_ms_min_max": [round(float(allv[:, 1].min()), 4), round(float(allv[:, 1].max()), 4)],
+                             "allreduce_ms": [round(float(v), 4) for v in allv[:, 2]],
+                             "combine+score_ms": [round(float(v), 4) for v in allv[:, 3]]})
     elif use_pg or os.environ.get("EPG_BENCH_WHO"):
         per_rank = {"ranks": whos}
 
     # ---- one GPU: the other path on the same genome, and both paths on an eighth of it (the share of one of 8 GPUs)
     s1_paths = None
-    if world == 1 and not args.graph:
+    if args.full and world == 1 and not args.graph:
         k = min(args.steps, 10)
 
         def both(Xs, k):
@@ -1005,7 +1018,7 @@ def main():
 
     # ---- the all-reduce by itself (device time between events, host time of the call), when there is a process group
     allreduce_probe = None
-    if use_pg:
+    if args.full and use_pg:
         t = torch.zeros(S, dtype=torch.int64, device=dev)
         for _ in range(20):
             dist.all_reduce(t)
@@ -1035,7 +1048,7 @@ def main():
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
         value = R_global * args.steps / dt / 1e6
-        achieved = R * N / (hist_ms * 1e-3) / 1e9
+        achieved = R * N / (hist_ms * 1e-3) / 1e9 if ev else None
         # HBM bytes per launch from the PMC passes of tools/profile_bench.sh (rocprofv3 cannot run inside this process):
         # reported only when they were taken on this very kernel source and this shape
         traffic, traffic_note = None, "no PMC record for this shape"
@@ -1076,9 +1089,9 @@ def main():
                          "algorithmic_bytes_per_bin": N, "avg_launch_ms": round(hist_ms, 4),
                          # the whole step against the bytes it has to move: X read once, H written and read, float32 scores written
                          "step_bytes_per_bin": N + 2 * 2 * S + 4 * S,
-                         "step_GBps": round(R * (N + 2 * 2 * S + 4 * S) / (ms_per_step * 1e-3) / 1e9, 1)},
+                         "step_GBps": round(R * (N + 2 * 2 * S + 4 * S) / (ms_per_step * 1e-3) / 1e9, 1)} if ev else None,
             "kernels_ms": {"k_bin_hist": round(hist_ms, 4), "allreduce": round(ar_ms, 4),
-                           "combine(normalise,table)+score_from_hist": round(rest_ms, 4)},
+                           "combine(normalise,table)+score_from_hist": round(rest_ms, 4)} if ev else None,
             "allreduce_probe": allreduce_probe,
             "per_rank": per_rank,
             "s1_paths": s1_paths,
@@ -1146,7 +1159,7 @@ def main():
     if placement["report"]:
         placement["search_ms"] = placement["report"].get("search_ms")
         placement["left_in_torch_cache_GiB"] = placement["report"].get("left_in_torch_cache_GiB")
-    if args.placement_experiment and world == 1 and R * X.stride(0) >= (1 << 30) and not args.packed and use_session:
+    if args.full and args.placement_experiment and world == 1 and R * X.stride(0) >= (1 << 30) and not args.packed and use_session:
         hang_hook("unplaced")
         try:
             kk = min(args.steps, 10)
@@ -1161,7 +1174,7 @@ def main():
             placement["unplaced"] = {"failed": repr(e)[:200]}
 
     # ---- BASELINE configs 3-5 through the product's sessions
-    want = [] if args.configs in ("none", "") else [c.strip() for c in args.configs.split(",") if c.strip()]
+    want = [] if not args.full or args.configs in ("none", "") else [c.strip() for c in args.configs.split(",") if c.strip()]
     if want:
         for name in want:
             hang_hook(name)
@@ -1182,7 +1195,7 @@ def main():
 
     # ---- SURVEY 8d's distribution variants: the same job on a uniform matrix (the contention-free control) and on the
     # row-correlated stress shape, generated into the SAME buffer (the headline's matrix is not needed any more)
-    if args.dist_variants and world == 1 and use_session and args.dist == "chr1" and line is not None:
+    if args.full and args.dist_variants and world == 1 and use_session and args.dist == "chr1" and line is not None:
         hang_hook("dist_variants")
         try:
             dv = {"chr1 (headline)": {"k_bin_hist_ms": round(hist_ms, 4), "frac": round(R * N / (hist_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
@@ -1205,7 +1218,7 @@ def main():
             line["dist_variants"] = {"error": repr(e)[:300]}
 
     # ---- RCCL self-test: every collective of the multi-rank command line against numbers (reported, never fatal)
-    if use_pg:
+    if args.full and use_pg:
         hang_hook("rccl_selftest")
         st = rccl_selftest(torch, dist, dev, rank, world, N, S)
         oks = torch.tensor([1 if st["ok"] else 0], dtype=torch.int32, device=dev)
@@ -1221,10 +1234,10 @@ def main():
     # ---- LAST (a captured collective is the one leg no box of this pool could try with more than one rank): the same step as ONE
     # hipGraph replay (K1, all-reduce, combine, score captured together): what is left of the step when
     # the host side of three launches and a collective is taken out -- on an eighth of the genome that is 10 % of the step
-    if args.graph_leg and not args.graph and use_pg and args.backend != "nccl":
+    if args.full and args.graph_leg and not args.graph and use_pg and args.backend != "nccl":
         if line is not None:                                             # (a host-side backend syncs inside the collective)
             line["graph_ms_per_step"], line["graph_error"] = None, "not captured: the %s backend's all-reduce cannot be part of a hipGraph" % args.backend
-    elif args.graph_leg and not args.graph:
+    elif args.full and args.graph_leg and not args.graph:
         hang_hook("graph")
         try:
             Hg = engine.alloc_hist(X, N, S)

@@ -417,7 +417,8 @@ def test_bench_one_rank_group_and_graph_replay(tmp_path):
     env = dict(os.environ, PYTHONPATH=str(root))
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    base = [sys.executable, str(root / "bench.py"), "--steps", "5", "--warmup", "2", "--bins", "400000", "--no-cpu-baseline", "--configs", "none"]
+    base = [sys.executable, str(root / "bench.py"), "--steps", "5", "--warmup", "2", "--bins", "400000", "--full", "--no-cpu-baseline",
+            "--configs", "none"]
     lines = {}
     for tag, extra in (("plain", []), ("pg", ["--pg"]), ("graph", ["--pg", "--graph"])):
         res = subprocess.run(base + extra, env=env, capture_output=True, text=True, timeout=900, cwd=str(root))
@@ -430,6 +431,37 @@ def test_bench_one_rank_group_and_graph_replay(tmp_path):
     assert lines["graph"]["config"]["step_launch"] == "hipGraph replay"
     for l in lines.values():
         assert l["kernels_ms"]["k_bin_hist"] > 0 and l["value"] > 0
+
+
+def test_bench_without_full_measures_the_headline_only(tmp_path):
+    """bench.py without --full: set-up, warm-up, the timed steps and the line -- nothing that takes runs of its own.  The kernel
+    figures of the default path come from the timed steps' own events; under --graph (no events) there are none."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from pathlib import Path
+    root = Path(__file__).resolve().parents[1]
+    env = dict(os.environ, PYTHONPATH=str(root))
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(k, None)
+    base = [sys.executable, str(root / "bench.py"), "--steps", "3", "--warmup", "1", "--bins", "400000", "--shard-bins", "50000"]
+    lines = {}
+    for tag, extra in (("plain", []), ("graph", ["--graph"])):
+        res = subprocess.run(base + extra, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+        assert res.returncode == 0, res.stdout + res.stderr
+        out = [l for l in res.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1
+        lines[tag] = json.loads(out[0])
+    for l in lines.values():
+        assert l["value"] > 0 and l["ms_per_step"] > 0 and l["steps"] == 3 and l["warmup"] == 1
+        assert l["unit"] == "Mbins/s" and l["higher_is_better"] is True and l["dtype"] == "u8"
+        assert l["cpu_baseline"] is None and l["s1_paths"] is None and l["allreduce_probe"] is None and l["configs"] == {}
+        assert "unplaced" not in l["placement"]
+        assert not {"dist_variants", "rccl_selftest", "graph_ms_per_step", "projected_speedup_8"} & set(l)
+    assert lines["plain"]["kernels_ms"]["k_bin_hist"] > 0 and lines["plain"]["roofline"]["frac"] > 0
+    assert lines["graph"]["config"]["step_launch"] == "hipGraph replay"
+    assert lines["graph"]["kernels_ms"] is None and lines["graph"]["roofline"] is None
 
 
 def test_bench_dump_outputs_are_the_last_steps_results(tmp_path):
@@ -551,7 +583,7 @@ def test_bench_gpus_flag_from_a_plain_start(tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     cmd = [sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--bins", "300001", "--backend", "gloo",
-           "--configs", "none"]
+           "--full", "--configs", "none"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert res.returncode == 0, res.stdout + res.stderr
     out = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -566,7 +598,7 @@ def test_bench_gpus_flag_from_a_plain_start(tmp_path):
     assert line["config"]["step_path"].startswith("backend._HipSingleSession: add_device(X, N) -> all_reduce -> launch") and line["s1_table"]["built_on"].startswith("device")
     # one GPU: unchanged contract, plus both S1 paths on the genome and on the shard
     one = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "3", "--warmup", "1", "--bins", "400000", "--shard-bins", "50000",
-                          "--no-cpu-baseline", "--configs", "none", "--placement-experiment", "0"], env=env, capture_output=True, text=True,
+                          "--full", "--no-cpu-baseline", "--configs", "none", "--placement-experiment", "0"], env=env, capture_output=True, text=True,
                          timeout=900, cwd=str(tmp_path))
     assert one.returncode == 0, one.stdout + one.stderr
     l1 = json.loads([l for l in one.stdout.splitlines() if l.startswith("{")][-1])
@@ -673,7 +705,7 @@ def test_bench_four_ranks_on_one_gpu(tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     cmd = [sys.executable, str(root / "bench.py"), "--gpus", "4", "--backend", "gloo", "--bins", "800008", "--s3-bins", "80000",
-           "--s3-small-bins", "40000", "--steps", "3", "--warmup", "1", "--config-reps", "1"]
+           "--s3-small-bins", "40000", "--steps", "3", "--warmup", "1", "--config-reps", "1", "--full"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert res.returncode == 0, res.stdout + res.stderr[-3000:]
     line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
@@ -709,7 +741,7 @@ def test_bench_extras_timeout_exits_nonzero_after_the_line(tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     cmd = [sys.executable, str(root / "bench.py"), "--gpus", "2", "--backend", "gloo", "--bins", "200000", "--steps", "2",
-           "--warmup", "1", "--config-reps", "1", "--extras-deadline", "25", "--graph-leg", "0"]
+           "--warmup", "1", "--config-reps", "1", "--extras-deadline", "25", "--graph-leg", "0", "--full"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     assert res.returncode != 0, res.stdout[-2000:]
     line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
@@ -718,7 +750,7 @@ def test_bench_extras_timeout_exits_nonzero_after_the_line(tmp_path):
     assert "s2" not in line["configs"]
     # one process, no launcher: the exit code is bench.py's own
     env1 = dict(env, EPG_BENCH_HANG_LEG="unplaced")
-    res1 = subprocess.run([sys.executable, str(root / "bench.py"), "--bins", "1500000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    res1 = subprocess.run([sys.executable, str(root / "bench.py"), "--bins", "1500000", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                            "--extras-deadline", "20", "--graph-leg", "0", "--shard-bins", "0"], env=env1, capture_output=True, text=True,
                           timeout=600, cwd=str(tmp_path))
     assert res1.returncode == 3, res1.stdout[-2000:] + res1.stderr[-2000:]
@@ -741,7 +773,7 @@ def test_bench_line_survives_rank0_dying_in_a_secondary_measurement(tmp_path):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     cmd = [sys.executable, str(root / "bench.py"), "--gpus", "2", "--backend", "gloo", "--bins", "200000", "--steps", "2",
-           "--warmup", "1", "--config-reps", "1", "--configs", "s2,paired", "--extras-deadline", "120", "--graph-leg", "0"]
+           "--warmup", "1", "--config-reps", "1", "--configs", "s2,paired", "--extras-deadline", "120", "--graph-leg", "0", "--full"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     assert res.returncode != 0, res.stdout[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]

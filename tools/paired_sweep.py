@@ -14,7 +14,7 @@ for spec in sys.argv[1:] or ["-"]:
         for kv in spec.split(","):
             k, v = kv.split("=", 1)
             env[k] = v
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--no-cpu-baseline", "--configs", "paired", "--dist-variants", "0", "--graph-leg", "0",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--full", "--no-cpu-baseline", "--configs", "paired", "--dist-variants", "0", "--graph-leg", "0",
                         "--placement-experiment", "0", "--shard-bins", "0", "--steps", "3", "--warmup", "1", "--config-reps", "5"], env=env, capture_output=True, text=True)
     try:
         p = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])["configs"]["paired"]

@@ -12,7 +12,7 @@ groups[sq]="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE
 groups[mem]="SQ_ACTIVE_INST_ANY SQ_INST_LEVEL_VMEM SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VMEM SQ_INSTS_SALU SQ_ACTIVE_INST_SCA"
 cd /tmp
 for g in ${PMC_GROUPS:-sq mem}; do
-  timeout 300 rocprofv3 --pmc ${groups[$g]} --kernel-trace --output-format csv -d $out/$g -o p -- python3 $R/bench.py --no-cpu-baseline --configs paired \
+  timeout 300 rocprofv3 --pmc ${groups[$g]} --kernel-trace --output-format csv -d $out/$g -o p -- python3 $R/bench.py --full --no-cpu-baseline --configs paired \
      --dist-variants 0 --graph-leg 0 --placement-experiment 0 --shard-bins 0 --steps 2 --warmup 1 --config-reps 2 "${@:2}" > $out/$g.log 2>&1 || echo "pass $g failed"
 done
 cd $R

@@ -12,7 +12,7 @@ for spec in sys.argv[1:] * 2:
                 env["EPILOGOS_HIP_LIB"] = R + "/tools/_ab_libs/" + v
             else:
                 env[k] = v
-    r = subprocess.run([sys.executable, R + "/bench.py", "--no-cpu-baseline", "--configs", "none", "--dist-variants", "0", "--graph-leg", "0", "--placement-experiment", "0"],
+    r = subprocess.run([sys.executable, R + "/bench.py", "--full", "--no-cpu-baseline", "--configs", "none", "--dist-variants", "0", "--graph-leg", "0", "--placement-experiment", "0"],
                        env=env, capture_output=True, text=True)
     try:
         d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -12,7 +12,7 @@ for spec in sys.argv[1:]:
                 env["EPILOGOS_HIP_LIB"] = R + "/tools/_ab_libs/" + v
             else:
                 env[k] = v
-    r = subprocess.run([sys.executable, R + "/bench.py", "--no-cpu-baseline", "--configs", "s3_small", "--dist-variants", "0", "--graph-leg", "0", "--placement-experiment", "0",
+    r = subprocess.run([sys.executable, R + "/bench.py", "--full", "--no-cpu-baseline", "--configs", "s3_small", "--dist-variants", "0", "--graph-leg", "0", "--placement-experiment", "0",
                         "--shard-bins", "0", "--steps", "2", "--warmup", "1", "--config-reps", "3", "--s3-small-bins", os.environ.get("S3_AB_BINS", "2000000")], env=env, capture_output=True, text=True)
     try:
         p = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])["configs"]["s3_small"]
