@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "epilogos_amd.h"
 
 typedef unsigned int u32;
@@ -47,6 +49,44 @@ extern int g_force[FORCE_COUNT];
     } while (0)
 
 static inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+
+// f(std::integral_constant<int, V>{}) for the first V of VS that equals v, f(std::integral_constant<int, DEFAULT>{}) when none
+// does: how a run-time value (a model size, 128-byte groups per row ...) picks one of a kernel's compile-time instantiations.
+// with_constant<0, 1, 2>(ng, f) instantiates f for 1, 2 and 0, and nothing else.
+template <int DEFAULT, typename F>
+static inline auto with_constant(int, F&& f) {
+    return f(std::integral_constant<int, DEFAULT>{});
+}
+template <int DEFAULT, int V, int... VS, typename F>
+static inline auto with_constant(int v, F&& f) {
+    if (v == V) return f(std::integral_constant<int, V>{});
+    return with_constant<DEFAULT, VS...>(v, f);
+}
+
+// The library-internal functions that one source file defines and another calls (the extern "C" entry points are declared in
+// epilogos_amd.h).
+int64_t s1_ws_bytes(int64_t R, int N, int S);                                        // epg_s1.hip
+int64_t s2_table_bytes(int maxc, int S);                                              // epg_s2.hip
+int64_t s3_ws_bytes(int64_t R, int N, int S);                                         // epg_s3.hip
+// epg_s3_transpose.hip: XT[sample][bin] of a call of R bins, see the definition
+int64_t s3_xt_bytes(int64_t R, int N);
+int transpose_states(const char* X, int64_t R, int32_t N, int64_t ldx, int32_t S, char* XT, int64_t Rp, int shift, int bad, int* dirty,
+                     hipStream_t st);
+// epg_s3_gemm.hip: the matrix-core S3 count pass
+int64_t s3_gemm_ws_bytes(int64_t R, int N, int S);
+int64_t s3_gemm_ws_min_bytes(int64_t R, int N, int S);
+int hist_s3_gemm(const char* X, int64_t R, int32_t N, int64_t ldx, int32_t S, int32_t* counts, void* ws, int64_t ws_bytes, hipStream_t st);
+// epg_s3_lanes.hip: the biosample-lane S3 score pass
+bool s3_lanes_ok(int N, int S);
+int64_t s3_lanes_ws_bytes(int64_t R, int N, int S);
+int score_s3_lanes(const int8_t* X8, int64_t R, int32_t N, int64_t ldx, int32_t S, const float* q, double* out64, float* out32, void* ws,
+                   int64_t ws_bytes, hipStream_t st);
+// epg_wide.hip: the models of 32 .. 127 states
+int wide_hist_s2_from_binhist(const uint16_t* H, const uint16_t* H2, int64_t R, int32_t S, int64_t* counts, hipStream_t st);
+int wide_score_s2_from_hist(const uint16_t* H, int64_t R, int32_t S, int64_t perms, const float* q, double* out64, float* out32, hipStream_t st);
+int wide_hist_s3(const int8_t* X, int64_t R, int32_t N, int64_t ldx, int32_t S, int32_t* counts, hipStream_t st);
+int wide_score_s3(const int8_t* X, int64_t R, int32_t N, int64_t ldx, int32_t S, const float* q, double* out64, float* out32, void* ws,
+                  int64_t ws_bytes, hipStream_t st);
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) of a kernel that wants more than 64 KB of dynamic LDS: once per kernel AND
 // device, safe when two host threads meet at a kernel's first launch (round 5 kept a plain `static bool` per call site: a second

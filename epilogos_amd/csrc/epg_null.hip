@@ -600,8 +600,10 @@ __global__ __launch_bounds__(256) void k_null_hist_h2(const NhParts pt, int S, i
     }
 }
 
-int null_hist_parts_impl(int32_t nparts, const uint16_t* const* HA, const uint16_t* const* HB, const int64_t* R, int32_t S, int32_t n_cols,
-                         int32_t ga, int32_t gb, uint64_t seed, const int64_t* row0, uint16_t* const* OA, uint16_t* const* OB, hipStream_t st) {
+extern "C" int epg_null_hist_from_binhist_parts(int32_t nparts, const uint16_t* const* HA, const uint16_t* const* HB, const int64_t* R, int32_t S,
+                                                int32_t n_cols, int32_t ga, int32_t gb, uint64_t seed, const int64_t* row0, uint16_t* const* OA,
+                                                uint16_t* const* OB, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (nparts < 0 || S < 1 || S > 127 || n_cols < 1 || n_cols > 65535) return fail(EPG_ERR_INVALID_ARG, "null_hist_from_binhist: bad shape");
     if (ga < 0 || gb < 0 || (long)ga + gb > n_cols)
         return fail(EPG_ERR_INVALID_ARG, "null_hist_from_binhist: group sizes %d + %d exceed the %d columns", ga, gb, n_cols);
@@ -660,10 +662,10 @@ int null_hist_parts_impl(int32_t nparts, const uint16_t* const* HA, const uint16
     return EPG_OK;
 }
 
-int null_hist_from_binhist_impl(const uint16_t* HA, const uint16_t* HB, int64_t R, int32_t S, int32_t n_cols, int32_t ga, int32_t gb,
-                                uint64_t seed, int64_t row0, uint16_t* OA, uint16_t* OB, hipStream_t st) {
+extern "C" int epg_null_hist_from_binhist(const uint16_t* HA, const uint16_t* HB, int64_t R, int32_t S, int32_t n_cols, int32_t ga, int32_t gb,
+                                          uint64_t seed, int64_t row0, uint16_t* OA, uint16_t* OB, void* stream) {
     if (R > 0 && (!HA || !HB || !OA || !OB)) return fail(EPG_ERR_INVALID_ARG, "null_hist_from_binhist: NULL argument");
-    return null_hist_parts_impl(1, &HA, &HB, &R, S, n_cols, ga, gb, seed, &row0, &OA, &OB, st);
+    return epg_null_hist_from_binhist_parts(1, &HA, &HB, &R, S, n_cols, ga, gb, seed, &row0, &OA, &OB, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -850,21 +852,13 @@ static int launch_pair_count_null(const PcParts& pt, int NA, int NB, u64* counts
     return EPG_OK;
 }
 
-template <int S>
-static int dispatch_pair_count_null(int ng, const PcParts& pt, int NA, int NB, u64* counts, u64 seed, hipStream_t st) {
-    switch (ng) {
-        case 1: return launch_pair_count_null<S, 1>(pt, NA, NB, counts, seed, st);
-        case 2: return launch_pair_count_null<S, 2>(pt, NA, NB, counts, seed, st);
-        case 3: return launch_pair_count_null<S, 3>(pt, NA, NB, counts, seed, st);
-        default: return launch_pair_count_null<S, 4>(pt, NA, NB, counts, seed, st);
-    }
-}
-
 // -> EPG_ERR_UNSUPPORTED when the shape is not the fused kernel's (the caller then takes epg_bin_hist_parts +
 // epg_null_hist_from_binhist_parts: the same results)
-int pair_count_null_parts_impl(int32_t nparts, const int8_t* const* XA, const int8_t* const* XB, const int64_t* R, int32_t NA, int32_t NB,
-                               const int64_t* ldxa, const int64_t* ldxb, int32_t S, uint16_t* const* HA, uint16_t* const* HB, int64_t* counts,
-                               uint64_t seed, const int64_t* row0, uint16_t* const* OA, uint16_t* const* OB, hipStream_t st) {
+extern "C" int epg_pair_count_null_parts(int32_t nparts, const int8_t* const* XA, const int8_t* const* XB, const int64_t* R, int32_t NA,
+                                         int32_t NB, const int64_t* ldxa, const int64_t* ldxb, int32_t S, uint16_t* const* HA, uint16_t* const* HB,
+                                         int64_t* counts, uint64_t seed, const int64_t* row0, uint16_t* const* OA, uint16_t* const* OB,
+                                         void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (nparts < 0 || NA < 1 || NB < 1 || S < 1) return fail(EPG_ERR_INVALID_ARG, "pair_count_null: bad shape");
     if (nparts && (!XA || !XB || !R || !ldxa || !ldxb || !HA || !HB || !row0 || !OA || !OB)) return fail(EPG_ERR_INVALID_ARG, "pair_count_null: NULL argument array");
     const int ng = (NA + 127) / 128;
@@ -898,10 +892,11 @@ int pair_count_null_parts_impl(int32_t nparts, const int8_t* const* XA, const in
         pt.t0[pt.n] = tiles;
         p0 = p;
         if (pt.n == 0) break;
-        int rc;
-        if (S == 18) rc = dispatch_pair_count_null<18>(ng, pt, NA, NB, cnt, (u64)seed, st);
-        else if (S == 15) rc = dispatch_pair_count_null<15>(ng, pt, NA, NB, cnt, (u64)seed, st);
-        else rc = dispatch_pair_count_null<25>(ng, pt, NA, NB, cnt, (u64)seed, st);
+        const int rc = with_constant<25, 18, 15>(S, [&](auto SC) {
+            return with_constant<4, 1, 2, 3>(ng, [&](auto NG) {
+                return launch_pair_count_null<decltype(SC)::value, NG>(pt, NA, NB, cnt, (u64)seed, st);
+            });
+        });
         if (rc) return rc;
     }
     return EPG_OK;
@@ -916,8 +911,9 @@ __global__ __launch_bounds__(256) void k_quiescent_h(const u16* __restrict__ HA,
     mask[row] = (uint8_t)(HA[row * S + qstate] == (u16)NA && HB[row * S + qstate] == (u16)NB);
 }
 
-int quiescent_from_binhist_impl(const uint16_t* HA, const uint16_t* HB, int64_t R, int32_t S, int32_t NA, int32_t NB, int32_t qstate,
-                                uint8_t* mask, hipStream_t st) {
+extern "C" int epg_quiescent_from_binhist(const uint16_t* HA, const uint16_t* HB, int64_t R, int32_t S, int32_t NA, int32_t NB, int32_t qstate,
+                                          uint8_t* mask, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (R < 0 || S < 1 || NA < 1 || NB < 1 || NA > 65535 || NB > 65535 || qstate >= S)
         return fail(EPG_ERR_INVALID_ARG, "quiescent_from_binhist: bad shape");
     if (R == 0) return EPG_OK;
@@ -931,9 +927,9 @@ int quiescent_from_binhist_impl(const uint16_t* HA, const uint16_t* HB, int64_t 
     return EPG_OK;
 }
 
-
-int null_hist_impl(const int8_t* XA, int32_t NA, int64_t ldxa, const int8_t* XB, int32_t NB, int64_t ldxb, int64_t R, int32_t S,
-                   int32_t ga, int32_t gb, uint64_t seed, int64_t row0, uint16_t* HA, uint16_t* HB, hipStream_t st) {
+extern "C" int epg_null_hist(const int8_t* XA, int32_t NA, int64_t ldxa, const int8_t* XB, int32_t NB, int64_t ldxb, int64_t R, int32_t S,
+                             int32_t ga, int32_t gb, uint64_t seed, int64_t row0, uint16_t* HA, uint16_t* HB, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (R < 0 || NA < 1 || NB < 1 || ldxa < NA || ldxb < NB || S < 1)
         return fail(EPG_ERR_INVALID_ARG, "null_hist: bad shape");
     if (S > 31) return fail(EPG_ERR_UNSUPPORTED, "null_hist: the matrix-scanning kernel decodes five bits; for S=%d count the groups with "

@@ -416,34 +416,19 @@ static int grid_for_tiles(long R) {
     return (int)blocks;
 }
 
-template <int S, int NG>
-static void launch_bin_hist(const char* X, long R, int N, long ldx, int Sout, u16* H, u64* counts, hipStream_t st) {
-    // odd S stores uint16 by uint16 either way; with the row width as a run-time value that path measured 2.30 ms
-    // against 2.64 ms for the compile-time one (15 M x 833, S = 15), so only even S takes the compile-time width
-    constexpr bool FULL = (S & 1) == 0;
-    hipLaunchKernelGGL((k_bin_hist<S, NG, FULL>), dim3(grid_for_tiles(R)), dim3(256), 0, st, X, R, N, ldx, Sout, H, counts);
-}
-
-// a state model of another size: the counting core of the next instantiated size, any-N load loop, only Sout columns stored
-template <int SC>
-static void launch_bin_hist_any(const char* X, long R, int N, long ldx, int Sout, u16* H, u64* counts, hipStream_t st) {
-    hipLaunchKernelGGL((k_bin_hist<SC, 0, false>), dim3(grid_for_tiles(R)), dim3(256), 0, st, X, R, N, ldx, Sout, H, counts);
-}
-
-template <int S>
-static void dispatch_bin_hist_ng(const char* X, long R, int N, long ldx, int Sout, u16* H, u64* counts, hipStream_t st) {
-    const int ng = (N + 127) / 128;
-    switch (ng) {
-        case 1: launch_bin_hist<S, 1>(X, R, N, ldx, Sout, H, counts, st); break;
-        case 2: launch_bin_hist<S, 2>(X, R, N, ldx, Sout, H, counts, st); break;
-        case 3: launch_bin_hist<S, 3>(X, R, N, ldx, Sout, H, counts, st); break;
-        case 4: launch_bin_hist<S, 4>(X, R, N, ldx, Sout, H, counts, st); break;
-        case 5: launch_bin_hist<S, 5>(X, R, N, ldx, Sout, H, counts, st); break;
-        case 6: launch_bin_hist<S, 6>(X, R, N, ldx, Sout, H, counts, st); break;
-        case 7: launch_bin_hist<S, 7>(X, R, N, ldx, Sout, H, counts, st); break;
-        case 8: launch_bin_hist<S, 8>(X, R, N, ldx, Sout, H, counts, st); break;
-        default: launch_bin_hist<S, 0>(X, R, N, ldx, Sout, H, counts, st); break;
-    }
+// The count kernels' instantiations: f(SC, NG, MODEL) with the counting core SC, the 128-byte groups per row NG and MODEL = Sout
+// == SC at compile time.  The reference's 15-, 18- and 25-state models have their own core and a load schedule per row width (1..8
+// groups, 0 = the any-width loop); a model of another size runs on the next larger core, any-width load loop, only its Sout
+// columns stored.
+template <typename F>
+static void with_count_core(int S, int ng, F&& f) {
+    if (S == 15 || S == 18 || S == 25)
+        with_constant<25, 15, 18>(S, [&](auto sc) {
+            with_constant<0, 1, 2, 3, 4, 5, 6, 7, 8>(ng, [&](auto NG) { f(sc, NG, std::true_type{}); });
+        });
+    else
+        with_constant<31, 15, 18, 25>(S < 15 ? 15 : S < 18 ? 18 : S < 25 ? 25 : 31,
+                                      [&](auto sc) { f(sc, std::integral_constant<int, 0>{}, std::false_type{}); });
 }
 
 // rows the fast kernel may touch: all of them unless its 16-byte last chunk could run past the allocation
@@ -455,8 +440,8 @@ static long fast_rows(long R, int N, long ldx) {
     return R > unsafe ? R - unsafe : 0;
 }
 
-int bin_hist_impl(const int8_t* X8, int64_t R, int32_t N, int64_t ldx, int32_t S, uint16_t* H, int64_t* counts,
-                  hipStream_t st) {
+extern "C" int epg_bin_hist(const int8_t* X8, int64_t R, int32_t N, int64_t ldx, int32_t S, uint16_t* H, int64_t* counts, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (R < 0 || N < 1 || ldx < N || S < 1) return fail(EPG_ERR_INVALID_ARG, "bin_hist: bad shape R=%lld N=%d ldx=%lld S=%d", (long long)R, N, (long long)ldx, S);
     if (S > 127) return fail(EPG_ERR_UNSUPPORTED, "bin_hist: S=%d > 127 (states are int8)", S);
     if (N > 65535) return fail(EPG_ERR_UNSUPPORTED, "bin_hist: N=%d > 65535 (uint16 per-bin counts)", N);
@@ -473,14 +458,11 @@ int bin_hist_impl(const int8_t* X8, int64_t R, int32_t N, int64_t ldx, int32_t S
     }
     const long Rf = fast_rows(R, N, ldx);
     if (Rf > 0) {
-        // the reference's models have their own instantiation; any other size runs on the next larger counting core
-        if (S == 15) dispatch_bin_hist_ng<15>(X, Rf, N, ldx, S, H, cnt, st);
-        else if (S == 18) dispatch_bin_hist_ng<18>(X, Rf, N, ldx, S, H, cnt, st);
-        else if (S == 25) dispatch_bin_hist_ng<25>(X, Rf, N, ldx, S, H, cnt, st);
-        else if (S < 15) launch_bin_hist_any<15>(X, Rf, N, ldx, S, H, cnt, st);
-        else if (S < 18) launch_bin_hist_any<18>(X, Rf, N, ldx, S, H, cnt, st);
-        else if (S < 25) launch_bin_hist_any<25>(X, Rf, N, ldx, S, H, cnt, st);
-        else launch_bin_hist_any<31>(X, Rf, N, ldx, S, H, cnt, st);
+        with_count_core(S, (N + 127) / 128, [&](auto SC, auto NG, auto MODEL) {
+            // odd S stores uint16 by uint16 either way; with the row width as a run-time value that path measured 2.30 ms
+            // against 2.64 ms for the compile-time one (15 M x 833, S = 15), so only even S takes the compile-time width
+            hipLaunchKernelGGL((k_bin_hist<SC, NG, MODEL && (SC & 1) == 0>), dim3(grid_for_tiles(Rf)), dim3(256), 0, st, X, Rf, N, ldx, S, H, cnt);
+        });
         EPG_LAUNCH_CHECK("k_bin_hist");
     }
     if (Rf < R) {
@@ -490,77 +472,41 @@ int bin_hist_impl(const int8_t* X8, int64_t R, int32_t N, int64_t ldx, int32_t S
     return EPG_OK;
 }
 
-// ---- K1 with the S2 pair counts folded in (epg_bin_hist_s2)
-int hist_s2_from_binhist_impl(const uint16_t*, const uint16_t*, int64_t, int32_t, int64_t*, hipStream_t);
-
-template <int S>
-static void dispatch_bin_hist_s2(const char* X, long R, int N, long ldx, u16* H, u64* counts, u64* counts2, hipStream_t st) {
-#define EPG_K1S2(NGV) hipLaunchKernelGGL((k_bin_hist_s2<S, NGV>), dim3(grid_for_tiles(R)), dim3(256), 0, st, X, R, N, ldx, H, counts, counts2)
-    switch ((N + 127) / 128) {
-        case 1: EPG_K1S2(1); break;
-        case 2: EPG_K1S2(2); break;
-        case 3: EPG_K1S2(3); break;
-        case 4: EPG_K1S2(4); break;
-        case 5: EPG_K1S2(5); break;
-        case 6: EPG_K1S2(6); break;
-        case 7: EPG_K1S2(7); break;
-        default: EPG_K1S2(8); break;
-    }
-#undef EPG_K1S2
-}
-
+// ---- K1 with the S2 pair counts folded in
 // H = per-bin histograms of X, counts2[S * S] += the S2 pair counts of its bins (and counts[S] += the state counts when given): ONE
 // launch for the reference's 15-, 18- and 25-state models on rows of up to 1024 columns; anything else: the count pass, then
 // the pair-count pass over H (the same integers).
-int bin_hist_s2_impl(const int8_t* X8, int64_t R, int32_t N, int64_t ldx, int32_t S, uint16_t* H, int64_t* counts, int64_t* counts2,
-                     hipStream_t st) {
+extern "C" int epg_bin_hist_s2(const int8_t* X8, int64_t R, int32_t N, int64_t ldx, int32_t S, uint16_t* H, int64_t* counts, int64_t* counts2,
+                               void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (!H || !counts2) return fail(EPG_ERR_INVALID_ARG, "bin_hist_s2: H and counts2 are required");
     const bool fused = (S == 15 || S == 18 || S == 25) && R > 0 && N >= 1 && N <= 1024 && ldx >= N && X8 &&
                        !(reinterpret_cast<uintptr_t>(H) & 15) && fast_rows(R, N, ldx) == R;
     if (!fused) {
-        int rc = bin_hist_impl(X8, R, N, ldx, S, H, counts, st);
+        int rc = epg_bin_hist(X8, R, N, ldx, S, H, counts, stream);
         if (rc) return rc;
-        return hist_s2_from_binhist_impl(H, nullptr, R, S, counts2, st);
+        return epg_hist_s2_from_binhist(H, R, S, counts2, stream);
     }
     const char* X = reinterpret_cast<const char*>(X8);
     u64* c1 = reinterpret_cast<u64*>(counts);
     u64* c2 = reinterpret_cast<u64*>(counts2);
-    if (S == 18) dispatch_bin_hist_s2<18>(X, R, N, ldx, H, c1, c2, st);
-    else if (S == 15) dispatch_bin_hist_s2<15>(X, R, N, ldx, H, c1, c2, st);
-    else dispatch_bin_hist_s2<25>(X, R, N, ldx, H, c1, c2, st);
+    with_constant<25, 18, 15>(S, [&](auto SC) {
+        with_constant<8, 1, 2, 3, 4, 5, 6, 7>((N + 127) / 128, [&](auto NG) {
+            hipLaunchKernelGGL((k_bin_hist_s2<decltype(SC)::value, NG>), dim3(grid_for_tiles(R)), dim3(256), 0, st, X, R, N, ldx, H, c1, c2);
+        });
+    });
     EPG_LAUNCH_CHECK("k_bin_hist_s2");
     return EPG_OK;
 }
 
 // ---- several matrices, one launch
-template <int S, int NG>
-static void launch_bin_hist_parts(const KhParts& pt, int Sout, u64* counts, int nmax, hipStream_t st) {
-    constexpr bool FULL = NG > 0 && (S & 1) == 0;          // (the any-width instantiation stores column by column, like launch_bin_hist_any)
-    const long nsuper = pt.st0[pt.n];
-    hipLaunchKernelGGL((k_bin_hist_parts<S, NG, FULL>), dim3(grid_for_tiles(nsuper * 32)), dim3(256), 0, st, pt, Sout, counts, nmax);
-}
-
-template <int S>
-static void dispatch_bin_hist_parts(int ng, const KhParts& pt, int Sout, u64* counts, int nmax, hipStream_t st) {
-    switch (ng) {
-        case 1: launch_bin_hist_parts<S, 1>(pt, Sout, counts, nmax, st); break;
-        case 2: launch_bin_hist_parts<S, 2>(pt, Sout, counts, nmax, st); break;
-        case 3: launch_bin_hist_parts<S, 3>(pt, Sout, counts, nmax, st); break;
-        case 4: launch_bin_hist_parts<S, 4>(pt, Sout, counts, nmax, st); break;
-        case 5: launch_bin_hist_parts<S, 5>(pt, Sout, counts, nmax, st); break;
-        case 6: launch_bin_hist_parts<S, 6>(pt, Sout, counts, nmax, st); break;
-        case 7: launch_bin_hist_parts<S, 7>(pt, Sout, counts, nmax, st); break;
-        case 8: launch_bin_hist_parts<S, 8>(pt, Sout, counts, nmax, st); break;
-        default: launch_bin_hist_parts<S, 0>(pt, Sout, counts, nmax, st); break;
-    }
-}
-
 // epg_bin_hist over `nparts` matrices in as few launches as their widths allow: parts whose widths share a load schedule
 // (the same number of 128-byte groups per row; more than eight: the any-width loop) go into one launch, KH_MAXP at a time.  The
-// same integers as nparts calls of bin_hist_impl (tests/test_hip_parity.py); restates the per-file loop of run.py:236-257 +
+// same integers as nparts calls of epg_bin_hist (tests/test_hip_parity.py); restates the per-file loop of run.py:236-257 +
 // expected.py:111-113 for resident files.
-int bin_hist_parts_impl(int32_t nparts, const int8_t* const* X, const int64_t* R, const int32_t* N, const int64_t* ldx, int32_t S,
-                        uint16_t* const* H, int64_t* counts, hipStream_t st) {
+extern "C" int epg_bin_hist_parts(int32_t nparts, const int8_t* const* X, const int64_t* R, const int32_t* N, const int64_t* ldx, int32_t S,
+                                  uint16_t* const* H, int64_t* counts, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (nparts < 0 || (nparts && (!X || !R || !N || !ldx))) return fail(EPG_ERR_INVALID_ARG, "bin_hist_parts: NULL argument array");
     if (S < 1 || S > 127) return fail(EPG_ERR_UNSUPPORTED, "bin_hist_parts: S=%d outside 1..127", S);
     for (int p = 0; p < nparts; ++p) {
@@ -571,7 +517,7 @@ int bin_hist_parts_impl(int32_t nparts, const int8_t* const* X, const int64_t* R
     }
     if (S > 31) {                                  // the wide models: part by part
         for (int p = 0; p < nparts; ++p) {
-            const int rc = bin_hist_impl(X[p], R[p], N[p], ldx[p], S, H ? H[p] : nullptr, counts, st);
+            const int rc = epg_bin_hist(X[p], R[p], N[p], ldx[p], S, H ? H[p] : nullptr, counts, stream);
             if (rc) return rc;
         }
         return EPG_OK;
@@ -582,7 +528,6 @@ int bin_hist_parts_impl(int32_t nparts, const int8_t* const* X, const int64_t* R
     bool seen[9] = {false, false, false, false, false, false, false, false, false};
     for (int p = 0; p < nparts; ++p)
         if (R[p]) seen[cls(N[p])] = true;
-    const bool generic = !(S == 15 || S == 18 || S == 25);      // another model size: the any-width loop of the next larger core
     for (int c = 0; c <= 8; ++c) {
         if (!seen[c]) continue;
         for (int p0 = 0; p0 < nparts;) {
@@ -612,41 +557,15 @@ int bin_hist_parts_impl(int32_t nparts, const int8_t* const* X, const int64_t* R
             pt.st0[pt.n] = supers;
             p0 = p;
             if (pt.n == 0) break;
-            const int ng = generic ? 0 : c;
-            if (S == 15) dispatch_bin_hist_parts<15>(ng, pt, S, cnt, nmax, st);
-            else if (S == 18) dispatch_bin_hist_parts<18>(ng, pt, S, cnt, nmax, st);
-            else if (S == 25) dispatch_bin_hist_parts<25>(ng, pt, S, cnt, nmax, st);
-            else if (S < 15) launch_bin_hist_parts<15, 0>(pt, S, cnt, nmax, st);
-            else if (S < 18) launch_bin_hist_parts<18, 0>(pt, S, cnt, nmax, st);
-            else if (S < 25) launch_bin_hist_parts<25, 0>(pt, S, cnt, nmax, st);
-            else launch_bin_hist_parts<31, 0>(pt, S, cnt, nmax, st);
+            with_count_core(S, c, [&](auto SC, auto NG, auto) {
+                // (the any-width instantiation stores column by column, like the one-matrix kernel of another model size)
+                hipLaunchKernelGGL((k_bin_hist_parts<SC, NG, (NG > 0 && (SC & 1) == 0)>), dim3(grid_for_tiles(supers * 32)), dim3(256), 0, st, pt, S,
+                                   cnt, nmax);
+            });
             EPG_LAUNCH_CHECK("k_bin_hist_parts");
         }
     }
     return EPG_OK;
-}
-
-template <int S, int NG, typename OT>
-static void launch_score_s1(const char* X, long R, int N, long ldx, const OT* T, OT* out, hipStream_t st) {
-    hipLaunchKernelGGL((k_score_s1<S, NG, OT>), dim3(grid_for_tiles(R)), dim3(256), 0, st, X, R, N, ldx, T, out);
-}
-
-template <typename OT>
-static bool dispatch_score_s1(const char* X, long R, int N, long ldx, int S, const OT* T, OT* out, hipStream_t st) {
-    if (S != 18) return false;
-    const int ng = (N + 127) / 128;
-    switch (ng) {
-        case 1: launch_score_s1<18, 1, OT>(X, R, N, ldx, T, out, st); break;
-        case 2: launch_score_s1<18, 2, OT>(X, R, N, ldx, T, out, st); break;
-        case 3: launch_score_s1<18, 3, OT>(X, R, N, ldx, T, out, st); break;
-        case 4: launch_score_s1<18, 4, OT>(X, R, N, ldx, T, out, st); break;
-        case 5: launch_score_s1<18, 5, OT>(X, R, N, ldx, T, out, st); break;
-        case 6: launch_score_s1<18, 6, OT>(X, R, N, ldx, T, out, st); break;
-        case 7: launch_score_s1<18, 7, OT>(X, R, N, ldx, T, out, st); break;
-        case 8: launch_score_s1<18, 8, OT>(X, R, N, ldx, T, out, st); break;
-        default: launch_score_s1<18, 0, OT>(X, R, N, ldx, T, out, st); break;
-    }
-    return true;
 }
 
 static int64_t s1_table_bytes(int N, int S) { return align_up((int64_t)(N + 1) * S * 8, 256) + align_up((int64_t)(N + 1) * S * 4, 256); }
@@ -664,7 +583,6 @@ static int build_s1_table(const float* q, int N, int S, void* ws, double** T64, 
     EPG_LAUNCH_CHECK("k_s1_table");
     return EPG_OK;
 }
-
 static int check_score_from_hist_args(const uint16_t* H, const double* out64, const float* out32) {
     if ((reinterpret_cast<uintptr_t>(H) & 7) != 0) return fail(EPG_ERR_INVALID_ARG, "score_s1_from_binhist: H must be 8-byte aligned");
     if ((out32 && (reinterpret_cast<uintptr_t>(out32) & 15)) || (out64 && (reinterpret_cast<uintptr_t>(out64) & 15)))
@@ -705,8 +623,10 @@ static int launch_score_s1_from_hist(const uint16_t* H, int64_t R, int32_t N, in
     return rc;
 }
 
-int score_s1_from_hist_impl(const uint16_t* H, int64_t R, int32_t N, int32_t S, const float* q, double* out64,
-                            float* out32, void* ws, int64_t ws_bytes, hipStream_t st) {
+
+extern "C" int epg_score_s1_from_binhist(const uint16_t* H, int64_t R, int32_t N, int32_t S, const float* q, double* out64, float* out32,
+                                         void* ws, int64_t ws_bytes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (R < 0 || N < 1 || S < 1) return fail(EPG_ERR_INVALID_ARG, "score_s1: bad shape");
     if (R == 0) return EPG_OK;
     if (!H || !q || !ws) return fail(EPG_ERR_INVALID_ARG, "score_s1_from_binhist: NULL argument");
@@ -723,8 +643,8 @@ int score_s1_from_hist_impl(const uint16_t* H, int64_t R, int32_t N, int32_t S, 
 // together with its output): the command line builds T[c, s] = kl(c / N, q[s]) on the host with numpy's log2 -- the
 // reference's own arithmetic (scores.py:343,550) -- so that scores_*.txt.gz equals the reference's byte for byte; the device
 // table above differs from it in the last bit of a few float64 logarithms, which moves ~0.1 % of the float32 stores.
-int score_s1_from_hist_table_impl(const uint16_t* H, int64_t R, int32_t N, int32_t S, const double* T64, const float* T32,
-                                  double* out64, float* out32, hipStream_t st) {
+extern "C" int epg_score_s1_from_binhist_table(const uint16_t* H, int64_t R, int32_t N, int32_t S, const double* T64, const float* T32,
+                                               double* out64, float* out32, void* stream) {
     if (R < 0 || N < 1 || S < 1) return fail(EPG_ERR_INVALID_ARG, "score_s1: bad shape");
     if (R == 0) return EPG_OK;
     if (!H || (out64 && !T64) || (out32 && !T32)) return fail(EPG_ERR_INVALID_ARG, "score_s1_from_binhist_table: NULL argument");
@@ -732,7 +652,7 @@ int score_s1_from_hist_table_impl(const uint16_t* H, int64_t R, int32_t N, int32
         return fail(EPG_ERR_INVALID_ARG, "score_s1_from_binhist_table: misaligned table");
     int rc = check_score_from_hist_args(H, out64, out32);
     if (rc) return rc;
-    return launch_score_s1_from_hist(H, R, N, S, T64, T32, out64, out32, st);
+    return launch_score_s1_from_hist(H, R, N, S, T64, T32, out64, out32, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -767,11 +687,9 @@ __global__ __launch_bounds__(256) void k_s1_combine(const u64* __restrict__ coun
     }
 }
 
-template <typename IT>
-static int normalise_impl(const IT* C, int64_t n, float* q, void* ws, int64_t ws_bytes, hipStream_t st);
-
-int combine_score_s1_impl(int64_t* counts, int32_t rezero, const uint16_t* H, int64_t R, int32_t N, int32_t S, float* q,
-                          double* out64, float* out32, void* ws, int64_t ws_bytes, hipStream_t st) {
+extern "C" int epg_combine_score_s1(int64_t* counts, int32_t rezero, const uint16_t* H, int64_t R, int32_t N, int32_t S, float* q,
+                                    double* out64, float* out32, void* ws, int64_t ws_bytes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (R < 0 || N < 1 || S < 1) return fail(EPG_ERR_INVALID_ARG, "combine_score_s1: bad shape R=%lld N=%d S=%d", (long long)R, N, S);
     if (S > 127) return fail(EPG_ERR_UNSUPPORTED, "combine_score_s1: S=%d > 127 (states are int8)", S);
     if (!counts || !q || !ws || (R > 0 && !H)) return fail(EPG_ERR_INVALID_ARG, "combine_score_s1: NULL argument");
@@ -790,8 +708,14 @@ int combine_score_s1_impl(int64_t* counts, int32_t rezero, const uint16_t* H, in
     return launch_score_s1_from_hist(H, R, N, S, T64, T32, out64, out32, st, rezero ? reinterpret_cast<u64*>(counts) : nullptr);
 }
 
-int score_s1_impl(const int8_t* X8, int64_t R, int32_t N, int64_t ldx, int32_t S, const float* q, double* out64,
-                  float* out32, void* ws, int64_t ws_bytes, hipStream_t st) {
+extern "C" int epg_hist_s1(const int8_t* X, int64_t R, int32_t N, int64_t ldx, int32_t S, int64_t* counts, void* stream) {
+    if (!counts) return fail(EPG_ERR_INVALID_ARG, "hist_s1: counts is NULL");
+    return epg_bin_hist(X, R, N, ldx, S, nullptr, counts, stream);
+}
+
+extern "C" int epg_score_s1(const int8_t* X8, int64_t R, int32_t N, int64_t ldx, int32_t S, const float* q, double* out64, float* out32,
+                            void* ws, int64_t ws_bytes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (R < 0 || N < 1 || ldx < N || S < 1) return fail(EPG_ERR_INVALID_ARG, "score_s1: bad shape");
     if (S > 127) return fail(EPG_ERR_UNSUPPORTED, "score_s1: S=%d > 127 (states are int8)", S);
     if (R == 0) return EPG_OK;
@@ -804,17 +728,20 @@ int score_s1_impl(const int8_t* X8, int64_t R, int32_t N, int64_t ldx, int32_t S
         // histogram into the workspace, then score from it
         if (ws_bytes < s1_ws_bytes(R, N, S)) return fail(EPG_ERR_WORKSPACE, "score_s1: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)s1_ws_bytes(R, N, S));
         u16* H = reinterpret_cast<u16*>(reinterpret_cast<char*>(ws) + s1_table_bytes(N, S));
-        int rc = bin_hist_impl(X8, R, N, ldx, S, H, nullptr, st);
+        int rc = epg_bin_hist(X8, R, N, ldx, S, H, nullptr, stream);
         if (rc) return rc;
-        return score_s1_from_hist_impl(H, R, N, S, q, out64, out32, ws, s1_table_bytes(N, S), st);
+        return epg_score_s1_from_binhist(H, R, N, S, q, out64, out32, ws, s1_table_bytes(N, S), stream);
     }
     if (ws_bytes < s1_table_bytes(N, S)) return fail(EPG_ERR_WORKSPACE, "score_s1: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)s1_table_bytes(N, S));
     double* T64; float* T32;
     int rc = build_s1_table(q, N, S, ws, &T64, &T32, st);
     if (rc) return rc;
     const char* X = reinterpret_cast<const char*>(X8);
-    if (out32) dispatch_score_s1<float>(X, R, N, ldx, S, T32, out32, st);
-    if (out64) dispatch_score_s1<double>(X, R, N, ldx, S, T64, out64, st);
+    // the fused kernel is instantiated for the 18-state model only, per row width (1..8 groups of 128 bytes, 0 = any width)
+    with_constant<0, 1, 2, 3, 4, 5, 6, 7, 8>((N + 127) / 128, [&](auto NG) {
+        if (out32) hipLaunchKernelGGL((k_score_s1<18, NG, float>), dim3(grid_for_tiles(R)), dim3(256), 0, st, X, R, N, ldx, T32, out32);
+        if (out64) hipLaunchKernelGGL((k_score_s1<18, NG, double>), dim3(grid_for_tiles(R)), dim3(256), 0, st, X, R, N, ldx, T64, out64);
+    });
     EPG_LAUNCH_CHECK("k_score_s1");
     return EPG_OK;
 }
@@ -838,11 +765,11 @@ static int normalise_impl(const IT* C, int64_t n, float* q, void* ws, int64_t ws
     return EPG_OK;
 }
 
-int normalise_i64_impl(const int64_t* C, int64_t n, float* q, void* ws, int64_t ws_bytes, hipStream_t st) {
-    return normalise_impl<long long>(reinterpret_cast<const long long*>(C), n, q, ws, ws_bytes, st);
+extern "C" int epg_normalise_i64(const int64_t* C, int64_t n, float* q, void* ws, int64_t ws_bytes, void* stream) {
+    return normalise_impl<long long>(reinterpret_cast<const long long*>(C), n, q, ws, ws_bytes, (hipStream_t)stream);
 }
-int normalise_i32_impl(const int32_t* C, int64_t n, float* q, void* ws, int64_t ws_bytes, hipStream_t st) {
-    return normalise_impl<int>(C, n, q, ws, ws_bytes, st);
+extern "C" int epg_normalise_i32(const int32_t* C, int64_t n, float* q, void* ws, int64_t ws_bytes, void* stream) {
+    return normalise_impl<int>(C, n, q, ws, ws_bytes, (hipStream_t)stream);
 }
 
 }  // namespace epg

@@ -749,10 +749,12 @@ __global__ __launch_bounds__(64 * PF_WAVES_MAX) __attribute__((amdgpu_waves_per_
     }
 }
 
-int pair_scores_s1_parts_impl(int32_t nparts, const uint16_t* const* HA, const uint16_t* const* HB, const uint16_t* const* HnA,
-                              const uint16_t* const* HnB, const int64_t* R, int32_t S, int32_t NA, int32_t NB, int32_t ga, int32_t gb,
-                              const float* TA, const float* TB, const float* TnA, const float* TnB, float* const* delta, float* const* ndist,
-                              float* const* rdist, int32_t* const* maxdiff, uint8_t* const* mask, int32_t qstate, hipStream_t st) {
+extern "C" int epg_pair_scores_s1_parts(int32_t nparts, const uint16_t* const* HA, const uint16_t* const* HB, const uint16_t* const* HnA,
+                                        const uint16_t* const* HnB, const int64_t* R, int32_t S, int32_t NA, int32_t NB, int32_t ga, int32_t gb,
+                                        const float* TA, const float* TB, const float* TnA, const float* TnB, float* const* delta,
+                                        float* const* ndist, float* const* rdist, int32_t* const* maxdiff, uint8_t* const* mask, int32_t qstate,
+                                        void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (nparts < 0 || S < 1 || S > 127 || NA < 1 || NB < 1 || ga < 1 || gb < 1 || qstate >= S) return fail(EPG_ERR_INVALID_ARG, "pair_scores_s1: bad shape");
     if (nparts == 0) return EPG_OK;
     if (!HA || !HB || !HnA || !HnB || !R || !TA || !TB || !TnA || !TnB || !delta || !ndist || !rdist || !maxdiff)
@@ -783,13 +785,6 @@ int pair_scores_s1_parts_impl(int32_t nparts, const uint16_t* const* HA, const u
         if (e && atoi(e) >= 1 && atoi(e) < waves) waves = atoi(e);
     }
     const size_t shmem = tab + (size_t)waves * per_wave;
-#define PF_LAUNCH(SC)                                                                                                            \
-    do {                                                                                                                         \
-        static DynLds lds_attr;                                                                                                  \
-        EPG_HIP(ensure_dyn_lds(lds_attr, reinterpret_cast<const void*>(k_pair_fused_s1<SC>), 160 * 1024));                       \
-        hipLaunchKernelGGL(k_pair_fused_s1<SC>, dim3((unsigned)blocks), dim3(64 * waves), shmem, st, pt, S, TA, entA, TB, entB, TnA, entnA, \
-                           TnB, entnB, NA, NB, qstate);                                                                          \
-    } while (0)
     for (int p0 = 0; p0 < nparts;) {                                                  // PF_MAXP parts with rows per launch
         PfParts pt;
         memset(&pt, 0, sizeof(pt));
@@ -810,31 +805,35 @@ int pair_scores_s1_parts_impl(int32_t nparts, const uint16_t* const* HA, const u
         if (pt.n == 0) break;
         long blocks = (tiles + waves - 1) / waves;
         if (blocks > num_cus()) blocks = num_cus();
-        if (S == 18) PF_LAUNCH(18);
-        else if (S == 15) PF_LAUNCH(15);
-        else if (S == 25) PF_LAUNCH(25);
-        else PF_LAUNCH(0);
+        // S at compile time for the reference's models, 0 = any S
+        const int rc = with_constant<0, 18, 15, 25>(S, [&](auto SC) {
+            static DynLds lds_attr;                                                       // (one per instantiation)
+            EPG_HIP(ensure_dyn_lds(lds_attr, reinterpret_cast<const void*>(k_pair_fused_s1<SC>), 160 * 1024));
+            hipLaunchKernelGGL(k_pair_fused_s1<SC>, dim3((unsigned)blocks), dim3(64 * waves), shmem, st, pt, S, TA, entA, TB, entB, TnA, entnA,
+                               TnB, entnB, NA, NB, qstate);
+            return EPG_OK;
+        });
+        if (rc) return rc;
         EPG_LAUNCH_CHECK("k_pair_fused_s1");
     }
-#undef PF_LAUNCH
     return EPG_OK;
 }
 
-int pair_scores_s1_impl(const uint16_t* HA, const uint16_t* HB, const uint16_t* HnA, const uint16_t* HnB, int64_t R, int32_t S, int32_t NA,
-                        int32_t NB, int32_t ga, int32_t gb, const float* TA, const float* TB, const float* TnA, const float* TnB, float* delta,
-                        float* ndist, float* rdist, int32_t* maxdiff, hipStream_t st) {
+extern "C" int epg_pair_scores_s1_from_binhist(const uint16_t* HA, const uint16_t* HB, const uint16_t* HnA, const uint16_t* HnB, int64_t R,
+                                               int32_t S, int32_t NA, int32_t NB, int32_t ga, int32_t gb, const float* TA, const float* TB,
+                                               const float* TnA, const float* TnB, float* delta, float* ndist, float* rdist, int32_t* maxdiff,
+                                               void* stream) {
     if (R < 0) return fail(EPG_ERR_INVALID_ARG, "pair_scores_s1: bad shape");
     if (R > 0 && (!HA || !HB || !HnA || !HnB || !delta || !ndist || !rdist || !maxdiff)) return fail(EPG_ERR_INVALID_ARG, "pair_scores_s1: NULL argument");
-    return pair_scores_s1_parts_impl(1, &HA, &HB, &HnA, &HnB, &R, S, NA, NB, ga, gb, TA, TB, TnA, TnB, &delta, &ndist, &rdist, &maxdiff, nullptr, -1, st);
+    return epg_pair_scores_s1_parts(1, &HA, &HB, &HnA, &HnB, &R, S, NA, NB, ga, gb, TA, TB, TnA, TnB, &delta, &ndist, &rdist, &maxdiff, nullptr, -1,
+                                    stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
 // host-side dispatch
 // ---------------------------------------------------------------------------------------------------------------
-int wide_hist_s2_from_binhist(const uint16_t* H, const uint16_t* H2, int64_t R, int32_t S, int64_t* counts, hipStream_t st);
-int wide_score_s2_from_hist(const uint16_t* H, int64_t R, int32_t S, int64_t perms, const float* q, double* out64, float* out32, hipStream_t st);
-
-int hist_s2_from_binhist_impl(const uint16_t* H, const uint16_t* H2, int64_t R, int32_t S, int64_t* counts, hipStream_t st) {
+// S2 pair counts of the per-bin histograms H, or of H + H2 bin by bin when H2 is not NULL
+static int hist_s2_from_binhist(const uint16_t* H, const uint16_t* H2, int64_t R, int32_t S, int64_t* counts, hipStream_t st) {
     if (R < 0 || S < 1 || S > 127) return fail(EPG_ERR_INVALID_ARG, "hist_s2: bad shape R=%lld S=%d", (long long)R, S);
     if (R == 0) return EPG_OK;
     if (!H || !counts) return fail(EPG_ERR_INVALID_ARG, "hist_s2: NULL argument");
@@ -852,10 +851,29 @@ int hist_s2_from_binhist_impl(const uint16_t* H, const uint16_t* H2, int64_t R, 
     return EPG_OK;
 }
 
+extern "C" int epg_hist_s2_from_binhist(const uint16_t* H, int64_t R, int32_t S, int64_t* counts, void* stream) {
+    return hist_s2_from_binhist(H, nullptr, R, S, counts, (hipStream_t)stream);
+}
+
+extern "C" int epg_hist_s2_from_binhist_pair(const uint16_t* HA, const uint16_t* HB, int64_t R, int32_t S, int64_t* counts, void* stream) {
+    if (R > 0 && !HB) return fail(EPG_ERR_INVALID_ARG, "hist_s2_pair: HB is NULL");
+    return hist_s2_from_binhist(HA, HB, R, S, counts, (hipStream_t)stream);
+}
+
+extern "C" int epg_hist_s2(const int8_t* X, int64_t R, int32_t N, int64_t ldx, int32_t S, int64_t* counts, void* ws, int64_t ws_bytes,
+                           void* stream) {
+    if (R > 0 && (!ws || ws_bytes < R * S * 2)) return fail(EPG_ERR_WORKSPACE, "hist_s2: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)(R * S * 2));
+    uint16_t* H = reinterpret_cast<uint16_t*>(ws);
+    int rc = epg_bin_hist(X, R, N, ldx, S, H, nullptr, stream);
+    if (rc) return rc;
+    return epg_hist_s2_from_binhist(H, R, S, counts, stream);
+}
+
 int64_t s2_table_bytes(int maxc, int S) { return align_up((int64_t)(maxc + 1) * 8, 256) + align_up((int64_t)(2 * S * S + 1) * 8, 256); }
 
-int score_s2_from_hist_impl(const uint16_t* H, int64_t R, int32_t N, int32_t S, int64_t perms, const float* q,
-                            double* out64, float* out32, void* ws, int64_t ws_bytes, hipStream_t st) {
+extern "C" int epg_score_s2_from_binhist(const uint16_t* H, int64_t R, int32_t N, int32_t S, int64_t perms, const float* q, double* out64,
+                                         float* out32, void* ws, int64_t ws_bytes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (R < 0 || N < 1 || S < 1 || S > 127 || perms < 1) return fail(EPG_ERR_INVALID_ARG, "score_s2: bad shape R=%lld N=%d S=%d perms=%lld", (long long)R, N, S, (long long)perms);
     if (R == 0) return EPG_OK;
     if (!H || !q || !ws) return fail(EPG_ERR_INVALID_ARG, "score_s2: NULL argument");
@@ -885,17 +903,25 @@ int score_s2_from_hist_impl(const uint16_t* H, int64_t R, int32_t N, int32_t S, 
     // k_score_s2_bin holds a static staging area of 4 waves x 64 rows x S outputs next to the log table: the table goes to LDS
     // only while both fit the 64 KB a workgroup gets without asking (S = 25 with float64 outputs: N <= 1791)
     const bool lds32 = lds_lh && (size_t)256 * S * 4 + lh_bytes <= 65536, lds64 = lds_lh && (size_t)256 * S * 8 + lh_bytes <= 65536;
-#define EPG_S2_FAST(SV)                                                                                                         \
-    if (S == SV) {                                                                                                              \
-        if (out32 && lds32) hipLaunchKernelGGL((k_score_s2_bin<SV, float, true>), dim3((int)bblocks), dim3(256), lh_bytes, st, H, (long)R, inv, N, LH, LPQ, out32);   \
-        if (out32 && !lds32) hipLaunchKernelGGL((k_score_s2_bin<SV, float, false>), dim3((int)bblocks), dim3(256), 0, st, H, (long)R, inv, N, LH, LPQ, out32);         \
-        if (out64 && lds64) hipLaunchKernelGGL((k_score_s2_bin<SV, double, true>), dim3((int)bblocks), dim3(256), lh_bytes, st, H, (long)R, inv, N, LH, LPQ, out64);  \
-        if (out64 && !lds64) hipLaunchKernelGGL((k_score_s2_bin<SV, double, false>), dim3((int)bblocks), dim3(256), 0, st, H, (long)R, inv, N, LH, LPQ, out64);        \
-    }
-    EPG_S2_FAST(15) EPG_S2_FAST(18) EPG_S2_FAST(25)
-#undef EPG_S2_FAST
+    if (fast)
+        with_constant<25, 15, 18>(S, [&](auto SV) {
+            if (out32 && lds32) hipLaunchKernelGGL((k_score_s2_bin<SV, float, true>), dim3((int)bblocks), dim3(256), lh_bytes, st, H, (long)R, inv, N, LH, LPQ, out32);
+            if (out32 && !lds32) hipLaunchKernelGGL((k_score_s2_bin<SV, float, false>), dim3((int)bblocks), dim3(256), 0, st, H, (long)R, inv, N, LH, LPQ, out32);
+            if (out64 && lds64) hipLaunchKernelGGL((k_score_s2_bin<SV, double, true>), dim3((int)bblocks), dim3(256), lh_bytes, st, H, (long)R, inv, N, LH, LPQ, out64);
+            if (out64 && !lds64) hipLaunchKernelGGL((k_score_s2_bin<SV, double, false>), dim3((int)bblocks), dim3(256), 0, st, H, (long)R, inv, N, LH, LPQ, out64);
+        });
     EPG_LAUNCH_CHECK("k_score_s2_bin");
     return EPG_OK;
+}
+
+extern "C" int epg_score_s2(const int8_t* X, int64_t R, int32_t N, int64_t ldx, int32_t S, int64_t perms, const float* q, double* out64,
+                            float* out32, void* ws, int64_t ws_bytes, void* stream) {
+    const int64_t tb = s2_table_bytes(N, S);
+    if (R > 0 && (!ws || ws_bytes < tb + R * S * 2)) return fail(EPG_ERR_WORKSPACE, "score_s2: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)(tb + R * S * 2));
+    uint16_t* H = reinterpret_cast<uint16_t*>(reinterpret_cast<char*>(ws) + tb);
+    int rc = epg_bin_hist(X, R, N, ldx, S, H, nullptr, stream);
+    if (rc) return rc;
+    return epg_score_s2_from_binhist(H, R, N, S, perms, q, out64, out32, ws, tb, stream);
 }
 
 // "%.5f" then strtod then float32: v * 1e5 is exact in double (24-bit x 17-bit significands), rint is half-even on that
@@ -942,7 +968,8 @@ __global__ __launch_bounds__(256) void k_pair_metrics(const float* __restrict__ 
     }
 }
 
-int pair_metrics_impl(const float* delta, int64_t R, int32_t S, int32_t roundtrip, float* dist, int32_t* maxdiff, hipStream_t st) {
+extern "C" int epg_pair_metrics(const float* delta, int64_t R, int32_t S, int32_t roundtrip, float* dist, int32_t* maxdiff, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (R < 0 || S < 1) return fail(EPG_ERR_INVALID_ARG, "pair_metrics: bad shape");
     if (R == 0) return EPG_OK;
     if (!delta || !dist || !maxdiff) return fail(EPG_ERR_INVALID_ARG, "pair_metrics: NULL argument");
@@ -955,7 +982,8 @@ int pair_metrics_impl(const float* delta, int64_t R, int32_t S, int32_t roundtri
     return EPG_OK;
 }
 
-int pair_finish_impl(const float* a, const float* b, int64_t R, int32_t S, float* delta, float* dist, hipStream_t st) {
+extern "C" int epg_pair_finish(const float* a, const float* b, int64_t R, int32_t S, float* delta, float* dist, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (R < 0 || S < 1 || S > 127) return fail(EPG_ERR_INVALID_ARG, "pair_finish: bad shape");   // numpy's pairwise sum recurses above 128
     if (R == 0) return EPG_OK;
     if (!a || !b || !delta) return fail(EPG_ERR_INVALID_ARG, "pair_finish: NULL argument");
@@ -969,8 +997,9 @@ int pair_finish_impl(const float* a, const float* b, int64_t R, int32_t S, float
     return EPG_OK;
 }
 
-int quiescent_impl(const int8_t* XA, int32_t NA, int64_t ldxa, const int8_t* XB, int32_t NB, int64_t ldxb, int64_t R,
-                   int32_t qstate, uint8_t* mask, hipStream_t st) {
+extern "C" int epg_quiescent(const int8_t* XA, int32_t NA, int64_t ldxa, const int8_t* XB, int32_t NB, int64_t ldxb, int64_t R,
+                             int32_t qstate, uint8_t* mask, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (R < 0 || NA < 1 || NB < 1 || ldxa < NA || ldxb < NB) return fail(EPG_ERR_INVALID_ARG, "quiescent: bad shape");
     if (R == 0) return EPG_OK;
     if (!XA || !XB || !mask) return fail(EPG_ERR_INVALID_ARG, "quiescent: NULL argument");

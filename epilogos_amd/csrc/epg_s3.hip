@@ -280,23 +280,8 @@ static int s3_ta(int S) {
     return ta;
 }
 
-int64_t s3_xt_bytes(int64_t R, int N);
-int transpose_states(const char* X, int64_t R, int32_t N, int64_t ldx, int32_t S, char* XT, int64_t Rp, int shift, hipStream_t st);
-int64_t s3_gemm_ws_bytes(int64_t R, int N, int S);
-int64_t s3_gemm_ws_min_bytes(int64_t R, int N, int S);
-int hist_s3_gemm(const char* X, int64_t R, int32_t N, int64_t ldx, int32_t S, int32_t* counts, void* ws, int64_t ws_bytes, hipStream_t st);
-bool s3_lanes_ok(int N, int S);
-int64_t s3_lanes_ws_bytes(int64_t R, int N, int S);
-int score_s3_lanes(const int8_t* X8, int64_t R, int32_t N, int64_t ldx, int32_t S, const float* q, double* out64, float* out32, void* ws,
-                   int64_t ws_bytes, hipStream_t st);
-
-
-int wide_hist_s3(const int8_t* X, int64_t R, int32_t N, int64_t ldx, int32_t S, int32_t* counts, hipStream_t st);
-int wide_score_s3(const int8_t* X, int64_t R, int32_t N, int64_t ldx, int32_t S, const float* q, double* out64, float* out32, void* ws,
-                  int64_t ws_bytes, hipStream_t st);
-
 static int s3_nceil(int N) { return (N + S3S_ACH - 1) / S3S_ACH * S3S_ACH; }
-int64_t s3_table_bytes(int N, int S) { return align_up((int64_t)s3_nceil(N) * N * S * S * 4, 256); }
+static int64_t s3_table_bytes(int N, int S) { return align_up((int64_t)s3_nceil(N) * N * S * S * 4, 256); }
 int64_t s3_ws_bytes(int64_t R, int N, int S) {
     if (S > 31) return align_up(R * S * 8, 256) + 256;       // the wide models (epg_wide.hip): the fixed-point cells, nothing else
     // score: table + transposed state matrix + float64 accumulator; expected: transposed state matrix (+ a chunk of the
@@ -307,8 +292,9 @@ int64_t s3_ws_bytes(int64_t R, int N, int S) {
     return score > expected ? score : expected;
 }
 
-int hist_s3_impl(const int8_t* X8, int64_t R, int32_t N, int64_t ldx, int32_t S, int32_t* counts, void* ws, int64_t ws_bytes,
-                 hipStream_t st) {
+extern "C" int epg_hist_s3(const int8_t* X8, int64_t R, int32_t N, int64_t ldx, int32_t S, int32_t* counts, void* ws, int64_t ws_bytes,
+                           void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (R < 0 || N < 2 || ldx < N || S < 1) return fail(EPG_ERR_INVALID_ARG, "hist_s3: bad shape R=%lld N=%d ldx=%lld S=%d", (long long)R, N, (long long)ldx, S);
     if (S > 127) return fail(EPG_ERR_UNSUPPORTED, "hist_s3: S=%d > 127 (states are int8)", S);
     if (R == 0) return EPG_OK;
@@ -334,8 +320,9 @@ int hist_s3_impl(const int8_t* X8, int64_t R, int32_t N, int64_t ldx, int32_t S,
     return EPG_OK;
 }
 
-int score_s3_impl(const int8_t* X8, int64_t R, int32_t N, int64_t ldx, int32_t S, const float* q, double* out64, float* out32,
-                  void* ws, int64_t ws_bytes, hipStream_t st) {
+extern "C" int epg_score_s3(const int8_t* X8, int64_t R, int32_t N, int64_t ldx, int32_t S, const float* q, double* out64, float* out32,
+                            void* ws, int64_t ws_bytes, void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     if (R < 0 || N < 2 || ldx < N || S < 1) return fail(EPG_ERR_INVALID_ARG, "score_s3: bad shape");
     if (S > 127) return fail(EPG_ERR_UNSUPPORTED, "score_s3: S=%d > 127 (states are int8)", S);
     if (R == 0) return EPG_OK;
@@ -360,7 +347,7 @@ int score_s3_impl(const int8_t* X8, int64_t R, int32_t N, int64_t ldx, int32_t S
     hipLaunchKernelGGL(k_s3_table, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, q, N, Nceil, S, T);
     EPG_LAUNCH_CHECK("k_s3_table");
     const long Rp = align_up(R, 32);
-    int rc = transpose_states(reinterpret_cast<const char*>(X8), R, N, ldx, S, XT, Rp, 2, st);   // bytes = 4 * state
+    int rc = transpose_states(reinterpret_cast<const char*>(X8), R, N, ldx, S, XT, Rp, 2, 31, nullptr, st);   // bytes = 4 * state
     if (rc) return rc;
     EPG_HIP(hipMemsetAsync(acc, 0, (size_t)R * S * 8, st));
     const long nslices = (R + S3S_SLICE - 1) / S3S_SLICE;

@@ -342,8 +342,6 @@ __global__ __launch_bounds__(64 * G_NW, 2) void k_s3_syrk_fp4(const char* __rest
 // cycle trace of its segments, a one-wave-per-SIMD shape with 4 x 4 tiles -- each bit-identical and within +-3 % of this kernel
 // (profiles/r03p_*, r03s_*).  They were deleted in round 5: the library holds one schedule.)
 
-int transpose_states(const char* X, int64_t R, int32_t N, int64_t ldx, int32_t S, char* XT, int64_t Rp, int shift, hipStream_t st);
-
 static long g_chunk_bins(long Rp) { return Rp < G_KC_MAX ? Rp : G_KC_MAX; }
 static int64_t g_reduced_bytes(int N, int S);
 
@@ -366,9 +364,6 @@ int64_t s3_gemm_ws_bytes(int64_t R, int N, int S) {
     const int NSP = g_rows_padded(N * S), NT = NSP / 32, NQ = NSP / G_BN;
     return g_fixed_bytes(Rp, N, NQ) + (int64_t)NT * 1024 * (g_chunk_bins(Rp) / 64) + (S >= 3 ? g_reduced_bytes(N, S) : 0);
 }
-
-int transpose_states_flag(const char* X, int64_t R, int32_t N, int64_t ldx, int32_t S, char* XT, int64_t Rp, int shift, int bad, int* dirty,
-                          hipStream_t st);
 
 // ---------------------------------------------------------------------------------------------------------------
 // The REDUCED contraction.  In a bin every biosample is in exactly one state, so the one-hot column of ONE state per biosample
@@ -505,7 +500,7 @@ int hist_s3_gemm(const char* X, int64_t R, int32_t N, int64_t ldx, int32_t S, in
     if (!reduced) {
         const long KC = chunk_bins(ws_bytes - fixed);
         if (KC < 512) return fail(EPG_ERR_WORKSPACE, "hist_s3: workspace too small for the precomputed-operand kernel");
-        int rc = transpose_states(X, R, N, ldx, S, XT, Rp, 0, st);
+        int rc = transpose_states(X, R, N, ldx, S, XT, Rp, 0, 31, nullptr, st);
         if (rc) return rc;
         hipLaunchKernelGGL(k_s3_tasks, dim3(1), dim3(1), 0, st, NQ, tasks);
         EPG_LAUNCH_CHECK("k_s3_tasks");
@@ -518,7 +513,7 @@ int hist_s3_gemm(const char* X, int64_t R, int32_t N, int64_t ldx, int32_t S, in
     const long KC = chunk_bins(tail - E4);
     if (KC < 512) return fail(EPG_ERR_WORKSPACE, "hist_s3: workspace too small for the precomputed-operand kernel");
     EPG_HIP(hipMemsetAsync(tail, 0, (size_t)red - 1024 + 64, st));        // reduced counts, marginals, flag
-    int rc = transpose_states_flag(X, R, N, ldx, S, XT, Rp, 0, 31, dirty, st);
+    int rc = transpose_states(X, R, N, ldx, S, XT, Rp, 0, 31, dirty, st);
     if (rc) return rc;
     // clean call: the contraction without state S - 1 (same XT: a byte S - 1 matches none of the N (S - 1) rows), then the rest
     const int NQ1 = g_rows_padded(N * (S - 1)) / G_BN;

@@ -41,8 +41,6 @@
 
 namespace epg {
 
-int transpose_states_bad(const char* X, int64_t R, int32_t N, int64_t ldx, int32_t S, char* XT, int64_t Rp, int shift, int bad, hipStream_t st);
-
 constexpr int BL_GW = 15;                          // gather waves; wave BL_GW of the workgroup is the loader
 constexpr int BL_THREADS = 64 * (BL_GW + 1);
 constexpr int BL_BW = 48;                          // bins of a half wave
@@ -397,7 +395,7 @@ int score_s3_lanes(const int8_t* X8, int64_t R, int32_t N, int64_t ldx, int32_t 
         EPG_LAUNCH_CHECK("k_s3_tq_build");
     }
     const long Rp = align_up(R, BL_SLICE);
-    int rc = transpose_states_bad(reinterpret_cast<const char*>(X8), R, N, ldx, S, XT, Rp, 2, S, st);   // bytes = 4 * state, 4 * S = "not a state"
+    int rc = transpose_states(reinterpret_cast<const char*>(X8), R, N, ldx, S, XT, Rp, 2, S, nullptr, st);   // bytes = 4 * state, 4 * S = "not a state"
     if (rc) return rc;
     EPG_HIP(hipMemsetAsync(acc, 0, (size_t)R * S * 8, st));
     const long nslices = Rp / BL_SLICE;

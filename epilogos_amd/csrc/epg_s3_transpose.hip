@@ -87,22 +87,16 @@ int64_t s3_xt_bytes(int64_t R, int N) { return align_up((int64_t)N * align_up(R,
 // `bad` is the code stored for "not a state" (31 for the kernels of this file and k_s3_score; S for k_s3_score_bl, whose
 // table rows have exactly one zero column after the S states)
 // `dirty` (optional, device int, caller-zeroed): set to 1 when a byte of the first N columns of a row < R is not a state
-int transpose_states_flag(const char* X, int64_t R, int32_t N, int64_t ldx, int32_t S, char* XT, int64_t Rp, int shift, int bad, int* dirty,
-                          hipStream_t st) {
+int transpose_states(const char* X, int64_t R, int32_t N, int64_t ldx, int32_t S, char* XT, int64_t Rp, int shift, int bad, int* dirty,
+                     hipStream_t st) {
     // 16-byte stores need XT rows that start 16-byte aligned (Rp a multiple of 16, an aligned base): so for every workspace this
-    // library lays out (hist_s3_impl / score_s3_impl refuse a misaligned one)
+    // library lays out (epg_hist_s3 / epg_score_s3 refuse a misaligned one)
     if (Rp % 16 != 0 || (reinterpret_cast<uintptr_t>(XT) & 15) != 0)
         return fail(EPG_ERR_INVALID_ARG, "transpose_states: the transposed matrix must be 16-byte aligned with a pitch that is a multiple of 16");
     hipLaunchKernelGGL(k_transpose_states16, dim3((unsigned)(((Rp + 63) / 64) * ((N + 63) / 64))), dim3(256), 0, st, X, (long)R, N,
                        (long)ldx, S, XT, (long)Rp, shift, bad, dirty);
     EPG_LAUNCH_CHECK("k_transpose_states");
     return EPG_OK;
-}
-int transpose_states_bad(const char* X, int64_t R, int32_t N, int64_t ldx, int32_t S, char* XT, int64_t Rp, int shift, int bad, hipStream_t st) {
-    return transpose_states_flag(X, R, N, ldx, S, XT, Rp, shift, bad, nullptr, st);
-}
-int transpose_states(const char* X, int64_t R, int32_t N, int64_t ldx, int32_t S, char* XT, int64_t Rp, int shift, hipStream_t st) {
-    return transpose_states_bad(X, R, N, ldx, S, XT, Rp, shift, 31, st);
 }
 
 }  // namespace epg

@@ -208,7 +208,7 @@ static int simsearch_check(int64_t Pg, int32_t S, int32_t W, int32_t B, int32_t 
     return EPG_OK;
 }
 
-int64_t simsearch_ws_bytes_impl(int64_t Pg, int32_t S, int32_t W, int32_t B) {
+extern "C" int64_t epg_simsearch_ws_bytes(int64_t Pg, int32_t S, int32_t W, int32_t B) {
     int rc = simsearch_check(Pg, S, W, B, 1);
     if (rc) return rc;
     SimsearchLayout L;
@@ -216,9 +216,10 @@ int64_t simsearch_ws_bytes_impl(int64_t Pg, int32_t S, int32_t W, int32_t B) {
     return rc ? rc : L.total;
 }
 
-int simsearch_impl(const int32_t* G, int64_t Pg, int32_t S, int32_t W, const int32_t* Q, int32_t B, const int32_t* self_start,
-                   int32_t n, uint64_t key_bound, void* ws, int64_t ws_bytes, int32_t* idx, uint64_t* mode, uint64_t* dist,
-                   hipStream_t st) {
+extern "C" int epg_simsearch(const int32_t* G, int64_t Pg, int32_t S, int32_t W, const int32_t* Q, int32_t B, const int32_t* self_start,
+                             int32_t n, uint64_t key_bound, void* ws, int64_t ws_bytes, int32_t* idx, uint64_t* mode, uint64_t* dist,
+                             void* stream) {
+    hipStream_t st = (hipStream_t)stream;
     int rc = simsearch_check(Pg, S, W, B, n);
     if (rc) return rc;
     if (key_bound >= (1ull << 53))

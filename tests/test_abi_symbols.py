@@ -1,6 +1,7 @@
 """CPU-side checks of the drop-in boundary: the library builds, loads, and exports exactly what the header
 declares.  No compute calls (no GPU here)."""
 import ctypes
+import re
 import shutil
 import subprocess
 
@@ -18,10 +19,40 @@ def lib():
     return _abi.load()
 
 
+def _header_prototypes():
+    """name -> (return type, [parameter declarations]) of every prototype in include/epilogos_amd.h."""
+    txt = re.sub(r"/\*.*?\*/", "", _abi.HEADER.read_text(), flags=re.S)
+    txt = re.sub(r'^\s*(#.*|extern "C" \{|\})\s*$', "", txt, flags=re.M)
+    protos = {}
+    for stmt in txt.split(";"):
+        m = re.match(r"\s*(.*?)\b(epg_[a-z0-9_]+)\s*\((.*)\)\s*$", stmt, flags=re.S)
+        if m:
+            args = " ".join(m.group(3).split())
+            protos[m.group(2)] = (" ".join(m.group(1).split()), [] if args in ("", "void") else [a.strip() for a in args.split(",")])
+    return protos
+
+
+def _ctypes_of(decl):
+    """The ctypes types that bind a header type (a parameter declaration, with or without its name)."""
+    if "*" in decl:
+        return {ctypes.c_void_p, ctypes.c_char_p}
+    base = decl.replace("const ", "").split()[0]
+    return {"int64_t": {ctypes.c_int64}, "int32_t": {ctypes.c_int32, ctypes.c_int}, "int": {ctypes.c_int32, ctypes.c_int},
+            "uint64_t": {ctypes.c_uint64}}[base]
+
+
 def test_header_and_binding_agree():
     hdr = _abi.header_symbols()
     assert hdr, "no prototypes parsed from include/epilogos_amd.h"
     assert sorted(_abi.PROTOTYPES) == hdr
+    protos = _header_prototypes()
+    assert sorted(protos) == hdr
+    for name, (res, args) in _abi.PROTOTYPES.items():
+        ret, params = protos[name]
+        assert res in _ctypes_of(ret), "%s returns %s in the header, %s in _abi.PROTOTYPES" % (name, ret, res.__name__)
+        assert len(args) == len(params), "%s: %d parameters in the header, %d in _abi.PROTOTYPES" % (name, len(params), len(args))
+        for i, (a, p) in enumerate(zip(args, params)):
+            assert a in _ctypes_of(p), "%s: parameter %d is `%s` in the header, %s in _abi.PROTOTYPES" % (name, i, p, a.__name__)
 
 
 def test_library_exports_every_header_symbol(lib):
