@@ -9,8 +9,6 @@
 
 #include <string.h>
 
-#include <stdlib.h>
-
 namespace epg {
 
 __device__ __forceinline__ void philox4x32_10(u32 (&c)[4], u32 k0, u32 k1) {
@@ -124,168 +122,156 @@ __global__ __launch_bounds__(256) void k_null_hist(const char* __restrict__ XA, 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// The same law from the two REAL groups' per-bin histograms (round 2).  Only the per-state counts of the shuffled groups are
-// needed, and they depend on the row only through its combined histogram h = hA + hB: the counts of the first ga and the next
-// gb columns of a uniform permutation of a row with h[s] columns of state s are MULTIVARIATE HYPERGEOMETRIC.  Sampled exactly,
-// category by category, by the same selection sampling as above (a column joins A with probability need_A / remaining, B with
-// need_B / remaining), except that the LAST category needs no draws at all: whatever is still needed comes from it.  The
-// row's most frequent state goes last, so a row costs n - max_s h[s] uniform numbers instead of n (71 % of real cells are
-// one state; i.i.d. synthetic rows at the chr1 frequencies: 209 of 721), and the kernel reads 72 bytes per bin instead of 721:
-// no state matrix, no LDS hand-over of rows.  Columns that hold no state (n - sum h) are one more category that is drawn
-// but not reported.  Philox4x32-10, counter = (global row, block of four draws, tag): a pure function of (seed, global row,
-// the row's histograms) -- not of the launch geometry or of the GPU count.  A lane owns a row; rows are handed over through
-// LDS both ways so that loads and stores cover whole lines.
+// The same law from the two REAL groups' per-bin histograms.  Only the per-state counts of the shuffled groups are needed, and
+// they depend on the row only through its combined histogram h = hA + hB: the counts of the first ga and the next gb columns of
+// a uniform permutation of a row with h[s] columns of state s are MULTIVARIATE HYPERGEOMETRIC.  Sampled exactly by the same
+// selection sampling as above: the column at position d of n joins A with probability need_A / (n - d) and B with
+// need_B / (n - d), whatever it holds.
+//
+// Column layout.  A row's columns are taken in the order [non-modal states, ascending | columns without a state | modal state].
+// The modal state (the most frequent one, the first of equals) needs no draws at all: whatever is still needed after the first
+// m = n - max_s h[s] positions comes from it.  A row costs m uniform numbers instead of n (71 % of real cells are one state;
+// i.i.d. synthetic rows at the chr1 frequencies: 209 +- 12 of 721), and the kernels read 72 bytes per bin instead of 721: no state
+// matrix.  The columns without a state (n - sum h) are drawn -- they take places in the groups -- but not reported.
+//
+// A draw takes SIXTEEN BITS v of Philox output, eight draws per call: with u in [v, v + 1) / 65536 and rem = n - d the column
+// joins A if (v + 1) rem <= need_A << 16, B if v rem >= need_A << 16 and (v + 1) rem <= (need_A + need_B) << 16, neither if
+// v rem >= (need_A + need_B) << 16.  In the remaining ~2 of 65536 cases the interval straddles a threshold and 32 more bits from
+// a second stream decide: the outcome is that of a 48-bit uniform number (NhRng::tie_pick).  With byte-sized draws a wave walked
+// the tie path whenever ONE of its 64 lanes tied: at 22 % of the draws.
+//
+// Philox4x32-10 keyed by the seed; counter = (row key low, row key high, call number, tag), one tag per stream, where the row key
+// is row0 of the part + the row's index in it.  The draws are a pure function of (seed, row key, the row's two histograms): not
+// of the launch geometry, the GPU count, the batch of parts or the kernel that a shape selects.  All three samplers below give
+// the SAME groups (tests/test_hip_s3_null.py compares them, tests/test_hip_null_draws.py pins the groups themselves).
+//
+// Two samplers:
+//  * nh_sample_row_seq walks the columns with the category bookkeeping in the loop (an LDS store + load and a divergent inner
+//    loop whenever ANY lane of the wave crosses into its next state, i.e. at nearly every draw).  It takes any row of up to
+//    65535 columns: the fallback.
+//  * nh_sample_row takes the categories OUT of the loop: the loop over the first m positions is the same for every row and
+//    appends ONE BIT of outcome per group to a per-lane bit string in LDS ([word][lane], flushed every 32 draws by all lanes at
+//    once); the per-state counts are then range popcounts of the string between the prefix sums of the row's histogram.  The
+//    eight draws of a Philox call run SPECULATIVELY, six instructions each with one string -- x = (need_A << 16) - 1 - v rem by
+//    one v_mad_i32_i24 (rem is scalar: every lane of a wave is at the same d), a = x >= rem - 1 (signed), the outcome bit into
+//    the string by v_lshl_or, need_A by another v_mad_i32_i24 -- and ONE test per call, umin over the eight (u32)x < rem, catches
+//    every possible tie (a tie is 0 <= x < rem - 1; the test is conservative).  If any lane of the wave fails it (0.8 % of the
+//    calls) the wave repeats the call's eight draws from the saved state with the careful `draw`, which resolves ties.  Measured
+//    per 15 M bins of 379 + 342 columns: 3.15 ms with byte-sized draws and no speculation (~14 instructions per draw, Philox 4 of
+//    them -- the 32 x 32 multiplies are full rate on gfx950, tools/ubench/rng_rate.hip), 2.1 ms now.
+//    TWO = false: ga + gb == n (the command line without -g), a column that does not join A joins B, one threshold and one bit
+//    string.  TWO = true (-g: ga + gb < n): a column joins A, B or neither, two thresholds ((need_A << 16) - 1 and
+//    ((need_A + need_B) << 16) - 1), two strings, 13 instructions per speculative draw; a tie at either threshold sends the call
+//    through the careful path.  This shape with byte-sized draws was 5 % slower than the column-by-column sampler; with 16-bit
+//    draws: 4.7 -> 3.2 ms per 15 M bins (-g 100).
+//    Limits: the arithmetic is signed 32-bit, hence rows of at most 32767 columns; a wave's bit strings get 24 KB of LDS, hence
+//    3072 columns with one string, 1536 with two (the two entry points below check).
 // ---------------------------------------------------------------------------------------------------------------
-// Several parts (the chromosome files of a genome) in ONE launch: pointers, row counts and shuffle keys travel in the kernel
-// argument, tiles are numbered through the parts in order and never straddle two parts; a wave's tile index ascends, so its
-// part only moves forward (the pattern of k_pair_fused_s1 and k_bin_hist_parts).  A row's draws depend on (seed, key + row in
-// the part, the row's histograms) only -- the same numbers as a launch per part.
-constexpr int NH_MAXP = 48;
-struct NhParts {
-    const u16* ha[NH_MAXP];
-    const u16* hb[NH_MAXP];
-    u16* oa[NH_MAXP];
-    u16* ob[NH_MAXP];
-    long rows[NH_MAXP];
-    long key[NH_MAXP];                     // row0 of the part: the shuffle key of its first row
-    long t0[NH_MAXP + 1];                  // first tile (TR rows) of every part, and their total
-    int n;
+constexpr u32 NH_TAG_DRAWS = 0x6e756c6cu;  // "null": the main stream, eight 16-bit draws per call
+constexpr u32 NH_TAG_TIES = 0x74696573u;   // "ties": the second stream, one 32-bit word per tie
+
+// The two Philox streams of one row.
+struct NhRng {
+    u64 seed, grow;                        // grow: the row's shuffle key
+    u32 calls = 0;                         // main stream: calls made
+    u32 a0w = 0, a1w = 0, a2w = 0, a3w = 0, ahave = 0, acalls = 0;   // tie stream: the words of its last call that are still unused
+    __device__ __forceinline__ NhRng(u64 seed_, u64 grow_) : seed(seed_), grow(grow_) {}
+    __device__ __forceinline__ void call(u32 (&c)[4], u32 n, u32 tag) {
+        c[0] = (u32)grow; c[1] = (u32)(grow >> 32); c[2] = n; c[3] = tag;
+        philox4x32_10(c, (u32)seed, (u32)(seed >> 32));
+    }
+    // the next 128 bits of the main stream
+    __device__ __forceinline__ void block(u32 (&c)[4]) { call(c, calls++, NH_TAG_DRAWS); }
+    // the draw whose 16 bits v did not decide: uniform in [0, rem) from the 48 bits (v, the tie stream's next word)
+    __device__ __forceinline__ u32 tie_pick(u32 v, u32 rem) {
+        if (ahave == 0) {
+            u32 c[4];
+            call(c, acalls++, NH_TAG_TIES);
+            a0w = c[0]; a1w = c[1]; a2w = c[2]; a3w = c[3];
+            ahave = 4;
+        }
+        const u64 u48 = ((u64)v << 32) | a0w;
+        a0w = a1w; a1w = a2w; a2w = a3w;
+        --ahave;
+        return (u32)((u48 * rem) >> 48);
+    }
 };
 
-#define NH_PART_STATE                                                                                                   \
-    const long ntiles = pt.t0[pt.n];                                                                                    \
-    int part = -1;                                                                                                      \
-    long next = 0, base = 0, R = 0, row0 = 0;                                                                           \
-    const u16* __restrict__ HA = nullptr;                                                                               \
-    const u16* __restrict__ HB = nullptr;                                                                               \
-    u16* __restrict__ OA = nullptr;                                                                                     \
-    u16* __restrict__ OB = nullptr;
-#define NH_PART_ENTER                                                                                                   \
-    if (tile >= next) {                                                                                                 \
-        do { ++part; next = pt.t0[part + 1]; } while (tile >= next);                                                    \
-        HA = pt.ha[part]; HB = pt.hb[part]; OA = pt.oa[part]; OB = pt.ob[part];                                         \
-        R = pt.rows[part]; row0 = pt.key[part]; base = pt.t0[part];                                                     \
-    }                                                                                                                   \
-    const long r0 = (tile - base) * TR;
-
-__device__ __forceinline__ void nh_stage_in(char* lds, const char* src, int nbytes, int lane) {
-    const int nchunks = nbytes >> 4;
-    for (int c = lane; c < nchunks; c += 64) *reinterpret_cast<uint4*>(lds + 16 * c) = *reinterpret_cast<const uint4*>(src + 16 * c);
-    for (int o = (nchunks << 4) + 2 * lane; o + 2 <= nbytes; o += 128) *reinterpret_cast<u16*>(lds + o) = *reinterpret_cast<const u16*>(src + o);
-}
-
-__global__ __launch_bounds__(256) void k_null_hist_h_seq(const NhParts pt, int S, int n_cols, int ga, int gb, u64 seed, int TR) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int rowb = 2 * S;
-    char* sa = smem + (size_t)wave * 2 * TR * rowb;               // the wave's TR (64) rows of hA, later of the A group's counts
-    char* sb = sa + TR * rowb;
-    __builtin_amdgcn_s_setprio(3);                                // (see k_null_hist_h)
-    NH_PART_STATE
-    for (long tile = (long)blockIdx.x * 4 + wave; tile < ntiles; tile += (long)gridDim.x * 4) {
-        NH_PART_ENTER
-        const int rows = (int)(R - r0 < TR ? R - r0 : TR);
-        nh_stage_in(sa, reinterpret_cast<const char*>(HA + r0 * S), rows * rowb, lane);
-        nh_stage_in(sb, reinterpret_cast<const char*>(HB + r0 * S), rows * rowb, lane);
-        __builtin_amdgcn_wave_barrier();
-        if (lane < rows) {
-            u16* pa = reinterpret_cast<u16*>(sa + lane * rowb);
-            u16* pb = reinterpret_cast<u16*>(sb + lane * rowb);
-            // combined counts into pa (pb becomes the zeroed output row), the most frequent state (first of equals) and the
-            // number of columns that hold a state
-            u32 tot = 0, best = 0;
-            int modal = 0;
-            for (int s = 0; s < S; ++s) {
-                const u32 h = (u32)pa[s] + pb[s];
-                pa[s] = (u16)h;
-                pb[s] = 0;
-                tot += h;
-                if (h > best) { best = h; modal = s; }
-            }
-            // ONE flat loop over the columns that are drawn -- every state but the modal one, then the columns without a state
-            // -- so that the 64 rows of a wave run n - max h steps each (209 +- 12 on chr1-like rows) instead of the sum over
-            // the categories of the wave's largest count.  A draw takes SIXTEEN BITS of Philox output (round 4; a byte before):
-            // with u in [v, v + 1) / 65536 the column joins A if (v + 1) rem <= 65536 needA, B if v rem >= 65536 needA and
-            // (v + 1) rem <= 65536 (needA + needB), neither if v rem >= 65536 (needA + needB); in the remaining ~2 of 65536 cases
-            // 32 more bits from a second stream decide -- the outcome is that of a 48-bit uniform number, 8 draws per Philox call.
-            u32 A256 = (u32)ga << 16, AB256 = (u32)(ga + gb) << 16, rem = (u32)n_cols;
-            const u32 ndraw = (u32)n_cols - best;
-            const u64 grow = (u64)(row0 + r0 + lane);
-            u32 r0w = 0, r1w = 0, r2w = 0, r3w = 0, cur = 0, nb = 0, calls = 0;          // main stream: 16 bytes per call
-            u32 a0w = 0, a1w = 0, a2w = 0, a3w = 0, ahave = 0, acalls = 0;               // second stream for the rare ties
-            int s = -1;
-            u32 left = 0, inA = 0, inB = 0;
-            for (u32 d = 0; d < ndraw; ++d) {
-                if (AB256 == 0) break;                                                    // both groups are full: the rest joins neither
-                while (left == 0) {                                                       // next non-empty category
-                    if (s >= 0 && s < S) { pa[s] = (u16)inA; pb[s] = (u16)inB; }
-                    ++s;
-                    if (s == modal) ++s;
-                    left = s < S ? (u32)pa[s] : (u32)n_cols - tot;
-                    inA = 0; inB = 0;
-                }
-                if ((nb & 1u) == 0) {
-                    if (nb == 0) {
-                        u32 c[4] = {(u32)grow, (u32)(grow >> 32), calls++, 0x6e756c6cu};
-                        philox4x32_10(c, (u32)seed, (u32)(seed >> 32));
-                        r0w = c[0]; r1w = c[1]; r2w = c[2]; r3w = c[3];
-                        nb = 8;
-                    }
-                    cur = r0w; r0w = r1w; r1w = r2w; r2w = r3w;
-                }
-                const u32 byte = cur & 0xffffu;                                           // (sixteen bits)
-                cur >>= 16;
-                --nb;
-                const u32 t = byte * rem, hi = t + rem;
-                bool a = hi <= A256;
-                bool b = t >= A256 && hi <= AB256;
-                if (!(a || b || t >= AB256)) {                                            // the byte's interval straddles a boundary
-                    if (ahave == 0) {
-                        u32 c[4] = {(u32)grow, (u32)(grow >> 32), acalls++, 0x74696573u};
-                        philox4x32_10(c, (u32)seed, (u32)(seed >> 32));
-                        a0w = c[0]; a1w = c[1]; a2w = c[2]; a3w = c[3];
-                        ahave = 4;
-                    }
-                    const u64 u48 = ((u64)byte << 32) | a0w;
-                    a0w = a1w; a1w = a2w; a2w = a3w;
-                    --ahave;
-                    const u32 pick = (u32)((u48 * rem) >> 48);                            // uniform in [0, rem)
-                    a = pick < (A256 >> 16);
-                    b = !a && pick < (AB256 >> 16);
-                }
-                inA += a; inB += b;
-                A256 -= a ? 65536u : 0u;
-                AB256 -= (a || b) ? 65536u : 0u;
-                --rem;
-                --left;
-            }
-            // the category the loop stopped in, the ones it never reached (nothing joins A or B any more), and the modal
-            // state, which takes what is still missing
-            if (s >= 0 && s < S) { pa[s] = (u16)inA; pb[s] = (u16)inB; }
-            for (int z = s + 1; z < S; ++z)
-                if (z != modal) pa[z] = 0;
-            pa[modal] = (u16)(A256 >> 16);
-            pb[modal] = (u16)((AB256 - A256) >> 16);
-        }
-        __builtin_amdgcn_wave_barrier();
-        store_staged(sa, reinterpret_cast<char*>(OA + r0 * S), rows * rowb, lane);
-        store_staged(sb, reinterpret_cast<char*>(OB + r0 * S), rows * rowb, lane);
-        __builtin_amdgcn_wave_barrier();
+// One row, column by column: pa / pb = the row's histograms of the two real groups in LDS on entry, of the two null groups on
+// return.  (rng by value: the compiler's draw loop is then 1 % faster than with a reference, 4.73 against 4.79 ms per 15 M bins.)
+__device__ __forceinline__ void nh_sample_row_seq(u16* pa, u16* pb, int S, int n_cols, int ga, int gb, NhRng rng) {
+    // combined counts into pa (pb becomes the zeroed output row), the modal state and the number of columns that hold a state
+    u32 tot = 0, best = 0;
+    int modal = 0;
+    for (int s = 0; s < S; ++s) {
+        const u32 h = (u32)pa[s] + pb[s];
+        pa[s] = (u16)h;
+        pb[s] = 0;
+        tot += h;
+        if (h > best) { best = h; modal = s; }
     }
+    // ONE flat loop over the columns that are drawn, so that the 64 rows of a wave run n - max h steps each instead of the sum
+    // over the categories of the wave's largest count
+    u32 A256 = (u32)ga << 16, AB256 = (u32)(ga + gb) << 16, rem = (u32)n_cols;
+    const u32 ndraw = (u32)n_cols - best;
+    u32 r0w = 0, r1w = 0, r2w = 0, r3w = 0, cur = 0, nb = 0;                      // main stream: the unused 16-bit pieces of a call
+    int s = -1;
+    u32 left = 0, inA = 0, inB = 0;
+    for (u32 d = 0; d < ndraw; ++d) {
+        if (AB256 == 0) break;                                                    // both groups are full: the rest joins neither
+        while (left == 0) {                                                       // next non-empty category
+            if (s >= 0 && s < S) { pa[s] = (u16)inA; pb[s] = (u16)inB; }
+            ++s;
+            if (s == modal) ++s;
+            left = s < S ? (u32)pa[s] : (u32)n_cols - tot;
+            inA = 0; inB = 0;
+        }
+        if ((nb & 1u) == 0) {
+            if (nb == 0) {
+                u32 c[4];
+                rng.block(c);
+                r0w = c[0]; r1w = c[1]; r2w = c[2]; r3w = c[3];
+                nb = 8;
+            }
+            cur = r0w; r0w = r1w; r1w = r2w; r2w = r3w;
+        }
+        const u32 v = cur & 0xffffu;
+        cur >>= 16;
+        --nb;
+        const u32 t = v * rem, hi = t + rem;
+        bool a = hi <= A256;
+        bool b = t >= A256 && hi <= AB256;
+        if (!(a || b || t >= AB256)) {                                            // the interval straddles a threshold
+            // NhRng::tie_pick written out: as a call the compiler lays its refill out as an if / else inside this divergent loop
+            // and the kernel takes 4.74 instead of 4.62 ms per 15 M bins
+            if (rng.ahave == 0) {
+                u32 c[4];
+                rng.call(c, rng.acalls++, NH_TAG_TIES);
+                rng.a0w = c[0]; rng.a1w = c[1]; rng.a2w = c[2]; rng.a3w = c[3];
+                rng.ahave = 4;
+            }
+            const u64 u48 = ((u64)v << 32) | rng.a0w;
+            rng.a0w = rng.a1w; rng.a1w = rng.a2w; rng.a2w = rng.a3w;
+            --rng.ahave;
+            const u32 pick = (u32)((u48 * rem) >> 48);
+            a = pick < (A256 >> 16);
+            b = !a && pick < (AB256 >> 16);
+        }
+        inA += a; inB += b;
+        A256 -= a ? 65536u : 0u;
+        AB256 -= (a || b) ? 65536u : 0u;
+        --rem;
+        --left;
+    }
+    // the category the loop stopped in, the ones it never reached (nothing joins A or B any more), and the modal state, which
+    // takes what is still missing
+    if (s >= 0 && s < S) { pa[s] = (u16)inA; pb[s] = (u16)inB; }
+    for (int z = s + 1; z < S; ++z)
+        if (z != modal) pa[z] = 0;
+    pa[modal] = (u16)(A256 >> 16);
+    pb[modal] = (u16)((AB256 - A256) >> 16);
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// Round 3: the same sampler with the categories taken OUT of the draw loop.  Selection sampling does not look at what a
-// column holds -- the column at position d joins A with probability need_A / remaining whatever its state -- so with the
-// columns of a row laid out [non-modal states in order | columns without a state | modal state] the loop over the first
-// m = n - max h positions is the same for every row: one byte of Philox output, a multiply-add, two compares, and ONE BIT of
-// outcome per group appended to a per-lane bit string in LDS ([word][lane], flushed every 32 draws by all lanes at once).
-// The per-state counts are then range popcounts of that string between the prefix sums of the row's histogram.  The category
-// bookkeeping of k_null_hist_h_seq (an LDS store + load and a divergent inner loop whenever ANY lane of the wave crosses into
-// its next state, i.e. at nearly every draw) is gone from the loop; the law, the Philox counters (global row, call number,
-// tag) and the tie rule are the same, which draw lands in which state is not: same seed, different -- equally distributed --
-// null groups.  FULL (ga + gb == n, the command line without -g): a column that does not join A joins B, one bit string.
-// ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ u32 nh_range_pop(const u32* __restrict__ bits, u32 o, u32 h) {    // ones in positions [o, o + h)
     u32 cnt = 0, p = o;
     const u32 e = o + h;
@@ -298,11 +284,13 @@ __device__ __forceinline__ u32 nh_range_pop(const u32* __restrict__ bits, u32 o,
     return cnt;
 }
 
-// One row of the bit-string sampler (ga + gb == n_cols): pa / pb = the row's histograms of the two real groups in LDS on entry,
-// the two null groups' on return; bitsA = the lane's outcome-bit words [word * 64]; grow = the row's shuffle key.  Shared by
-// k_null_hist_h and the fused count + sample kernel of paired mode (k_pair_count_null).
-__device__ __forceinline__ void nh_sample_row_full(u16* __restrict__ pa, u16* __restrict__ pb, u32* __restrict__ bitsA, int S, int n_cols,
-                                                   int ga, u64 seed, u64 grow) {
+// One row of the bit-string sampler: pa / pb as above; bitsA / bitsB = the lane's outcome-bit words [word * 64] of the two groups
+// (TWO = false: ga + gb == n_cols, gb and bitsB are not used).  pa / pb carry no __restrict__: with it the compiler packs the
+// u16 accesses of the first loop into 16-byte LDS operations on rows that are not 16-byte aligned (-g 100: 3.21 against 3.19 ms
+// per 15 M bins).
+template <bool TWO>
+__device__ __forceinline__ void nh_sample_row(u16* pa, u16* pb, u32* __restrict__ bitsA, u32* __restrict__ bitsB, int S,
+                                              int n_cols, int ga, int gb, NhRng& rng) {
     u32 best = 0;
     int modal = 0;
     for (int s = 0; s < S; ++s) {
@@ -311,119 +299,210 @@ __device__ __forceinline__ void nh_sample_row_full(u16* __restrict__ pa, u16* __
         if (h > best) { best = h; modal = s; }
     }
     int Am1 = (int)(((u32)ga << 16) - 1u);                                        // (need_A << 16) - 1
+    [[maybe_unused]] int ABm1 = (int)(((u32)(ga + gb) << 16) - 1u);               // ((need_A + need_B) << 16) - 1
     const u32 m = (u32)n_cols - best;
-    
-    u32 calls = 0;
-    u32 a0w = 0, a1w = 0, a2w = 0, a3w = 0, ahave = 0, acalls = 0;
     u32 wA = 0;
-    // the careful draw at position d: certain unless the 16-bit interval straddles need_A / rem, then 32 more bits decide
+    [[maybe_unused]] u32 wB = 0;
+    // the careful draw at position d: certain unless the 16-bit interval straddles a threshold, then 32 more bits decide
     auto draw = [&](u32 v, u32 d) {
         const int rem = n_cols - (int)d;
-        const int x = Am1 - (int)__umul24(v, (u32)rem);                           // (need_A << 16) - 1 - v rem
-        bool a = x >= rem - 1;                                                    // (v + 1) rem <= need_A << 16
-        if (!a && x >= 0) {                                                       // v rem < need_A << 16 < (v + 1) rem
-            if (ahave == 0) {
-                u32 c[4] = {(u32)grow, (u32)(grow >> 32), acalls++, 0x74696573u};
-                philox4x32_10(c, (u32)seed, (u32)(seed >> 32));
-                a0w = c[0]; a1w = c[1]; a2w = c[2]; a3w = c[3];
-                ahave = 4;
-            }
-            const u64 u48 = ((u64)v << 32) | a0w;
-            a0w = a1w; a1w = a2w; a2w = a3w;
-            --ahave;
-            const u32 pick = (u32)((u48 * (u32)rem) >> 48);                       // uniform in [0, rem)
+        const int t = (int)__umul24(v, (u32)rem);
+        const int xA = Am1 - t;                                                   // (need_A << 16) - 1 - v rem
+        const int xAB = ABm1 - t;
+        bool a = xA >= rem - 1;                                                   // (v + 1) rem <= need_A << 16: certainly A
+        bool b = TWO && xA < 0 && xAB >= rem - 1;                                 // certainly not A, certainly A or B
+        // v rem < need_A << 16 < (v + 1) rem, or the same at the other threshold: the interval straddles it
+        if ((!a && xA >= 0) || (TWO && xAB < rem - 1 && xAB >= 0)) {
+            const u32 pick = rng.tie_pick(v, (u32)rem);
             a = pick < (((u32)Am1 + 1u) >> 16);
+            b = TWO && !a && pick < (((u32)ABm1 + 1u) >> 16);
         }
-        wA |= a ? 1u << (d & 31u) : 0u;
+        const u32 bit = 1u << (d & 31u);
+        wA |= a ? bit : 0u;
         Am1 -= a ? 65536 : 0;
+        if constexpr (TWO) {
+            wB |= b ? bit : 0u;
+            ABm1 -= (a || b) ? 65536 : 0;
+        }
     };
+    auto half = [](const u32 (&c)[4], int k) { return (k & 1) ? c[k >> 1] >> 16 : c[k >> 1] & 0xffffu; };   // draw k of a call
     u32 d = 0;
     for (; d + 8 <= m; d += 8) {
-        u32 c[4] = {(u32)grow, (u32)(grow >> 32), calls++, 0x6e756c6cu};
-        philox4x32_10(c, (u32)seed, (u32)(seed >> 32));
+        u32 c[4];
+        rng.block(c);
         const int Am1_0 = Am1;
         const u32 wA_0 = wA;
+        [[maybe_unused]] const int ABm1_0 = ABm1;
+        [[maybe_unused]] const u32 wB_0 = wB;
         const int rem0 = __builtin_amdgcn_readfirstlane(n_cols - (int)d);         // every lane of the wave is at the same d
         const int bit0 = __builtin_amdgcn_readfirstlane((int)(d & 31u));
         u32 low = 0xffffffffu;
-        // two draws per word of Philox output, 13 instructions: v_and / v_lshrrev (the two halves), then per draw
-        // v_mad_i32_i24 (x), v_cmp_le_i32 (a), v_cndmask (a as 0 / 1), v_lshl_or (the outcome bit), v_mad_i32_i24 (need_A),
-        // and one v_min3_u32 for the tie test
+        if constexpr (!TWO) {
+            // two draws per word of Philox output, 13 instructions: v_and / v_lshrrev (the two halves), then per draw
+            // v_mad_i32_i24 (x), v_cmp_le_i32 (a), v_cndmask (a as 0 / 1), v_lshl_or (the outcome bit), v_mad_i32_i24 (need_A),
+            // and one v_min3_u32 for the tie test
 #define NH_PAIR(W, K)                                                                                                             \
-        {                                                                                                                 \
-            u32 v0_, v1_, x0_, x1_, a_;                                                                                   \
-            asm volatile(                                                                                                 \
-                "v_and_b32_e32 %[v0], 0xffff, %[w]\n\t"                                                                   \
-                "v_lshrrev_b32_e32 %[v1], 16, %[w]\n\t"                                                                   \
-                "v_mad_i32_i24 %[x0], %[v0], %[nr0], %[am]\n\t"                                                           \
-                "v_cmp_le_i32_e32 vcc, %[rm0], %[x0]\n\t"                                                                 \
-                "v_cndmask_b32_e64 %[a], 0, 1, vcc\n\t"                                                                   \
-                "v_lshl_or_b32 %[wa], %[a], %[b0], %[wa]\n\t"                                                             \
-                "v_mad_i32_i24 %[am], %[a], %[m64k], %[am]\n\t"                                                           \
-                "v_mad_i32_i24 %[x1], %[v1], %[nr1], %[am]\n\t"                                                           \
-                "v_cmp_le_i32_e32 vcc, %[rm1], %[x1]\n\t"                                                                 \
-                "v_cndmask_b32_e64 %[a], 0, 1, vcc\n\t"                                                                   \
-                "v_lshl_or_b32 %[wa], %[a], %[b1], %[wa]\n\t"                                                             \
-                "v_mad_i32_i24 %[am], %[a], %[m64k], %[am]\n\t"                                                           \
-                "v_min3_u32 %[lo], %[x0], %[x1], %[lo]"                                                                   \
-                : [v0] "=&v"(v0_), [v1] "=&v"(v1_), [x0] "=&v"(x0_), [x1] "=&v"(x1_), [a] "=&v"(a_), [wa] "+v"(wA),       \
-                  [am] "+v"(Am1), [lo] "+v"(low)                                                                          \
-                : [w] "v"(W), [nr0] "s"((K) - rem0), [nr1] "s"((K) + 1 - rem0), [rm0] "s"(rem0 - (K) - 1),                \
-                  [rm1] "s"(rem0 - (K) - 2), [b0] "s"(bit0 + (K)), [b1] "s"(bit0 + (K) + 1), [m64k] "s"(-65536)           \
-                : "vcc");                                                                                                 \
-        }
-        NH_PAIR(c[0], 0)
-        NH_PAIR(c[1], 2)
-        NH_PAIR(c[2], 4)
-        NH_PAIR(c[3], 6)
+            {                                                                                                                     \
+                u32 v0_, v1_, x0_, x1_, a_;                                                                                       \
+                asm volatile(                                                                                                     \
+                    "v_and_b32_e32 %[v0], 0xffff, %[w]\n\t"                                                                       \
+                    "v_lshrrev_b32_e32 %[v1], 16, %[w]\n\t"                                                                       \
+                    "v_mad_i32_i24 %[x0], %[v0], %[nr0], %[am]\n\t"                                                               \
+                    "v_cmp_le_i32_e32 vcc, %[rm0], %[x0]\n\t"                                                                     \
+                    "v_cndmask_b32_e64 %[a], 0, 1, vcc\n\t"                                                                       \
+                    "v_lshl_or_b32 %[wa], %[a], %[b0], %[wa]\n\t"                                                                 \
+                    "v_mad_i32_i24 %[am], %[a], %[m64k], %[am]\n\t"                                                               \
+                    "v_mad_i32_i24 %[x1], %[v1], %[nr1], %[am]\n\t"                                                               \
+                    "v_cmp_le_i32_e32 vcc, %[rm1], %[x1]\n\t"                                                                     \
+                    "v_cndmask_b32_e64 %[a], 0, 1, vcc\n\t"                                                                       \
+                    "v_lshl_or_b32 %[wa], %[a], %[b1], %[wa]\n\t"                                                                 \
+                    "v_mad_i32_i24 %[am], %[a], %[m64k], %[am]\n\t"                                                               \
+                    "v_min3_u32 %[lo], %[x0], %[x1], %[lo]"                                                                       \
+                    : [v0] "=&v"(v0_), [v1] "=&v"(v1_), [x0] "=&v"(x0_), [x1] "=&v"(x1_), [a] "=&v"(a_), [wa] "+v"(wA),           \
+                      [am] "+v"(Am1), [lo] "+v"(low)                                                                              \
+                    : [w] "v"(W), [nr0] "s"((K) - rem0), [nr1] "s"((K) + 1 - rem0), [rm0] "s"(rem0 - (K) - 1),                    \
+                      [rm1] "s"(rem0 - (K) - 2), [b0] "s"(bit0 + (K)), [b1] "s"(bit0 + (K) + 1), [m64k] "s"(-65536)               \
+                    : "vcc");                                                                                                     \
+            }
+            NH_PAIR(c[0], 0)
+            NH_PAIR(c[1], 2)
+            NH_PAIR(c[2], 4)
+            NH_PAIR(c[3], 6)
 #undef NH_PAIR
+        } else {
+            // per draw 12 instructions and the compiler's v_and / v_lshrrev: twice v_mad_i32_i24 (x), v_cmp_le_i32, v_cndmask,
+            // v_mad_i32_i24 (need); one v_sub for "B = joined but not A"; two v_lshl_or; one v_min3_u32 for the tie test
+#define NH_DRAW2(V, K)                                                                                                            \
+            {                                                                                                                     \
+                u32 x0_, x1_, a_, ab_;                                                                                            \
+                asm volatile(                                                                                                     \
+                    "v_mad_i32_i24 %[x0], %[v], %[nr], %[am]\n\t"                                                                 \
+                    "v_mad_i32_i24 %[x1], %[v], %[nr], %[abm]\n\t"                                                                \
+                    "v_cmp_le_i32_e32 vcc, %[rm], %[x0]\n\t"                                                                      \
+                    "v_cndmask_b32_e64 %[a], 0, 1, vcc\n\t"                                                                       \
+                    "v_cmp_le_i32_e32 vcc, %[rm], %[x1]\n\t"                                                                      \
+                    "v_cndmask_b32_e64 %[ab], 0, 1, vcc\n\t"                                                                      \
+                    "v_lshl_or_b32 %[wa], %[a], %[b], %[wa]\n\t"                                                                  \
+                    "v_mad_i32_i24 %[am], %[a], %[m64k], %[am]\n\t"                                                               \
+                    "v_mad_i32_i24 %[abm], %[ab], %[m64k], %[abm]\n\t"                                                            \
+                    "v_sub_u32_e32 %[ab], %[ab], %[a]\n\t"                                                                        \
+                    "v_lshl_or_b32 %[wb], %[ab], %[b], %[wb]\n\t"                                                                 \
+                    "v_min3_u32 %[lo], %[x0], %[x1], %[lo]"                                                                       \
+                    : [x0] "=&v"(x0_), [x1] "=&v"(x1_), [a] "=&v"(a_), [ab] "=&v"(ab_), [wa] "+v"(wA), [wb] "+v"(wB),             \
+                      [am] "+v"(Am1), [abm] "+v"(ABm1), [lo] "+v"(low)                                                            \
+                    : [v] "v"(V), [nr] "s"((K) - rem0), [rm] "s"(rem0 - (K) - 1), [b] "s"(bit0 + (K)), [m64k] "s"(-65536)         \
+                    : "vcc");                                                                                                     \
+            }
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const u32 v = half(c, k);
+                NH_DRAW2(v, k)
+            }
+#undef NH_DRAW2
+        }
         if (low < (u32)rem0) {                                                    // a tie is possible in this call: repeat it carefully
             Am1 = Am1_0;
             wA = wA_0;
+            if constexpr (TWO) { ABm1 = ABm1_0; wB = wB_0; }
 #pragma unroll
-            for (int k = 0; k < 8; ++k) draw((k & 1) ? c[k >> 1] >> 16 : c[k >> 1] & 0xffffu, d + k);
+            for (int k = 0; k < 8; ++k) draw(half(c, k), d + k);
         }
         if ((d & 31u) == 24u) {
             bitsA[(d >> 5) * 64] = wA;
             wA = 0;
+            if constexpr (TWO) { bitsB[(d >> 5) * 64] = wB; wB = 0; }
         }
     }
     if (d < m) {                                                                  // the last one to seven draws
-        u32 c[4] = {(u32)grow, (u32)(grow >> 32), calls++, 0x6e756c6cu};
-        philox4x32_10(c, (u32)seed, (u32)(seed >> 32));
+        u32 c[4];
+        rng.block(c);
 #pragma unroll
         for (int k = 0; k < 7; ++k)
-            if (d + k < m) draw((k & 1) ? c[k >> 1] >> 16 : c[k >> 1] & 0xffffu, d + k);
+            if (d + k < m) draw(half(c, k), d + k);
     }
-    if (m & 31u) bitsA[(m >> 5) * 64] = wA;
-    // counts per state: range popcounts between the prefix sums of the histogram; the modal state takes what is missing
+    if (m & 31u) {
+        bitsA[(m >> 5) * 64] = wA;
+        if constexpr (TWO) bitsB[(m >> 5) * 64] = wB;
+    }
+    // counts per state: range popcounts between the prefix sums of the histogram; positions o .. m - 1 after the loop are the
+    // columns without a state; the modal state takes what is missing
     u32 o = 0;
     for (int s = 0; s < S; ++s) {
         const u32 h = s == modal ? 0u : (u32)pa[s];
         const u32 ca = nh_range_pop(bitsA, o, h);
         pa[s] = (u16)ca;
-        pb[s] = (u16)(h - ca);
+        pb[s] = (u16)(TWO ? nh_range_pop(bitsB, o, h) : h - ca);
         o += h;
     }
-    // positions o .. m - 1 are the columns without a state: drawn (they take places in the groups), not reported
     const u32 needA = ((u32)Am1 + 1u) >> 16;                                      // = ga - (A members among the m drawn)
     pa[modal] = (u16)needA;
-    pb[modal] = (u16)(best - needA);
+    pb[modal] = (u16)(TWO ? (((u32)ABm1 + 1u) >> 16) - needA : best - needA);
 }
 
-// Round 4: the draw loop again.  Where round 3's 3.15 ms went: ~14 instructions per draw on the main path, Philox 4 (64 per
-// call -- the 32 x 32 multiplies are full rate on gfx950, tools/ubench/rng_rate.hip --, 16 byte-sized draws per call) and ~7 for
-// the tie path, which a wave walked whenever ONE of its 64 lanes' bytes straddled need_A / remaining: 22 % of the draws.  Now
-//  * a draw takes 16 bits (8 per Philox call: +4 instructions per draw), so a lane ties once in ~65536 draws instead of 256;
-//  * the eight draws of a call run SPECULATIVELY with six instructions each -- x = (need_A << 16) - 1 - v * rem by one
-//    v_mad_i32_i24 (rem = n - d is scalar), a = x >= rem - 1 (signed), the outcome bit into the string by v_lshl_or, need_A by
-//    another v_mad_i32_i24 -- and ONE test per call, umin over the eight (u32)x < rem, catches every possible tie (a tie is
-//    0 <= x < rem - 1; the test is conservative); if any lane of the wave fails it (0.8 % of the calls) the wave repeats the
-//    call's eight draws from the saved state on the careful path, which resolves ties with 32 more bits like k_null_hist_h_seq.
-// Same law, same Philox counters and tie rule as k_null_hist_h_seq (identical outputs, tests/test_hip_s3_null.py); the
-// arithmetic is signed 32-bit, hence rows of at most 32767 columns here (the bit strings limit the kernel to 3072 anyway).
-// Only the case the command line has without -g: ga + gb == n (a column that does not join A joins B, one bit string).
-__global__ __launch_bounds__(256) void k_null_hist_h(const NhParts pt, int S, int n_cols, int ga, int gb, u64 seed, int TR, int NW) {
+// ---------------------------------------------------------------------------------------------------------------
+// Several parts (the chromosome files of a genome) in ONE launch: pointers, row counts and shuffle keys travel in the kernel
+// argument, tiles of TR rows are numbered through the parts in order and never straddle two parts (the pattern of k_pair_fused_s1
+// and k_bin_hist_parts).  A row's draws are the same numbers as in a launch per part.
+// ---------------------------------------------------------------------------------------------------------------
+// Where a wave is among the parts.  A wave's tile index only ascends, so its part only moves forward.
+struct PartCursor {
+    int part = 0;
+    // `tile` (at or after the last one asked for) -> its first row in its part, `part`; t0 = first tile of every part, and the total
+    __device__ __forceinline__ long advance(const long* t0, long tile, int tile_rows) {
+        while (tile >= t0[part + 1]) ++part;
+        return (tile - t0[part]) * tile_rows;
+    }
+};
+
+// Host side: fills `pt` (an NhParts or a PcParts) with the parts p0, p0 + 1 ... that have rows, as many as it holds; fill(k, p)
+// copies part p's pointers and key into slot k.  -> the first part not taken.
+template <typename Parts, typename Fill>
+static int pack_parts(Parts& pt, int p0, int nparts, const int64_t* R, int tile_rows, Fill&& fill) {
+    constexpr int MAXP = (int)(sizeof(pt.rows) / sizeof(pt.rows[0]));
+    memset(&pt, 0, sizeof(pt));
+    long tiles = 0;
+    int p = p0;
+    for (; p < nparts && pt.n < MAXP; ++p) {
+        if (R[p] == 0) continue;
+        const int k = pt.n++;
+        fill(k, p);
+        pt.rows[k] = R[p];
+        pt.t0[k] = tiles;
+        tiles += (R[p] + tile_rows - 1) / tile_rows;
+    }
+    pt.t0[pt.n] = tiles;
+    return p;
+}
+
+constexpr int NH_MAXP = 48;
+struct NhParts {
+    const u16* ha[NH_MAXP];
+    const u16* hb[NH_MAXP];
+    u16* oa[NH_MAXP];
+    u16* ob[NH_MAXP];
+    long rows[NH_MAXP];
+    long key[NH_MAXP];                     // row0 of the part: the shuffle key of its first row
+    long t0[NH_MAXP + 1];                  // first tile (TR rows) of every part, and their total
+    int n;
+};
+
+__device__ __forceinline__ void nh_stage_in(char* lds, const char* src, int nbytes, int lane) {
+    const int nchunks = nbytes >> 4;
+    for (int c = lane; c < nchunks; c += 64) *reinterpret_cast<uint4*>(lds + 16 * c) = *reinterpret_cast<const uint4*>(src + 16 * c);
+    for (int o = (nchunks << 4) + 2 * lane; o + 2 <= nbytes; o += 128) *reinterpret_cast<u16*>(lds + o) = *reinterpret_cast<const u16*>(src + o);
+}
+
+// The sampler of a launch = the number of bit strings per row.
+constexpr int NH_SEQ = 0, NH_ONE = 1, NH_TWO = 2;
+static_assert(NH_SEQ == 0 && NH_ONE == 1 && NH_TWO == 2, "nh_lds_bytes and k_null_hist_rows multiply by the mode");
+
+// dynamic LDS of a block of four waves: a wave's TR rows of both histograms and its 64 lanes' bit strings of NW words
+static size_t nh_lds_bytes(int mode, int TR, int S, int NW) { return 4 * ((size_t)2 * TR * 2 * S + (size_t)mode * NW * 256); }
+
+// A lane owns a row, a wave a tile of TR rows.  The rows are handed over through LDS both ways, so that loads and stores cover
+// whole lines.
+template <int MODE>
+__global__ __launch_bounds__(256) void k_null_hist_rows(const NhParts pt, int S, int n_cols, int ga, int gb, u64 seed, int TR, int NW) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // The sampler is drawn on a second stream UNDER the count pass of the next batch of parts (backend._HipPairedSession): the two
     // share every SIMD, the sampler needs ~80 % of the VALU slots and the count pass ~25 %.  At equal priority the count pass's
@@ -433,171 +512,50 @@ __global__ __launch_bounds__(256) void k_null_hist_h(const NhParts pt, int S, in
     __builtin_amdgcn_s_setprio(3);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int rowb = 2 * S;
-    const size_t per_wave = (size_t)2 * TR * rowb + (size_t)NW * 256;
+    const size_t per_wave = (size_t)2 * TR * rowb + (size_t)MODE * NW * 256;
     char* sa = smem + (size_t)wave * per_wave;                    // the wave's TR rows of hA, later of the A group's counts
     char* sb = sa + TR * rowb;
-    u32* bitsA = reinterpret_cast<u32*>(sb + TR * rowb) + lane;   // [word][lane]
-    NH_PART_STATE
+    [[maybe_unused]] u32* bitsA = nullptr;                        // [word][lane]
+    [[maybe_unused]] u32* bitsB = nullptr;
+    if constexpr (MODE != NH_SEQ) {
+        bitsA = reinterpret_cast<u32*>(sb + TR * rowb) + lane;
+        bitsB = bitsA + NW * 64;
+    }
+    const long ntiles = pt.t0[pt.n];
+    PartCursor at;
     for (long tile = (long)blockIdx.x * 4 + wave; tile < ntiles; tile += (long)gridDim.x * 4) {
-        NH_PART_ENTER
+        const long r0 = at.advance(pt.t0, tile, TR);
+        const long R = pt.rows[at.part];
         const int rows = (int)(R - r0 < TR ? R - r0 : TR);
-        nh_stage_in(sa, reinterpret_cast<const char*>(HA + r0 * S), rows * rowb, lane);
-        nh_stage_in(sb, reinterpret_cast<const char*>(HB + r0 * S), rows * rowb, lane);
+        nh_stage_in(sa, reinterpret_cast<const char*>(pt.ha[at.part] + r0 * S), rows * rowb, lane);
+        nh_stage_in(sb, reinterpret_cast<const char*>(pt.hb[at.part] + r0 * S), rows * rowb, lane);
         __builtin_amdgcn_wave_barrier();
         if (lane < rows) {
             u16* pa = reinterpret_cast<u16*>(sa + lane * rowb);
             u16* pb = reinterpret_cast<u16*>(sb + lane * rowb);
-            nh_sample_row_full(pa, pb, bitsA, S, n_cols, ga, seed, (u64)(row0 + r0 + lane));
+            NhRng rng(seed, (u64)(pt.key[at.part] + r0 + lane));
+            if constexpr (MODE == NH_SEQ) nh_sample_row_seq(pa, pb, S, n_cols, ga, gb, rng);
+            else nh_sample_row<MODE == NH_TWO>(pa, pb, bitsA, bitsB, S, n_cols, ga, gb, rng);
         }
         __builtin_amdgcn_wave_barrier();
-        store_staged(sa, reinterpret_cast<char*>(OA + r0 * S), rows * rowb, lane);
-        store_staged(sb, reinterpret_cast<char*>(OB + r0 * S), rows * rowb, lane);
+        store_staged(sa, reinterpret_cast<char*>(pt.oa[at.part] + r0 * S), rows * rowb, lane);
+        store_staged(sb, reinterpret_cast<char*>(pt.ob[at.part] + r0 * S), rows * rowb, lane);
         __builtin_amdgcn_wave_barrier();
     }
 }
 
-// The same kernel for group sizes that do NOT fill the row (-g: ga + gb < n): a column joins A, B or neither, so there are two
-// thresholds ((need_A << 16) - 1 and ((need_A + need_B) << 16) - 1), two outcome bits per position and two bit strings; a draw is
-// 13 instructions on the speculative path (twice `v_mad_i32_i24` x, `v_cmp_le_i32`, `v_cndmask`, `v_mad_i32_i24` need; one `v_sub`
-// for "B = joined but not A"; two `v_lshl_or`; a share of `v_min3_u32`), a tie at either threshold sends the lane's call through
-// the careful path.  Same draws and tie rule as k_null_hist_h_seq: identical outputs.  Round 3 had tried this shape with byte-sized
-// draws and found it 5 % slower than the column-by-column kernel; with 16-bit draws: 4.7 -> 3.2 ms per 15 M bins (-g 100).
-__global__ __launch_bounds__(256) void k_null_hist_h2(const NhParts pt, int S, int n_cols, int ga, int gb, u64 seed, int TR, int NW) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int rowb = 2 * S;
-    const size_t per_wave = (size_t)2 * TR * rowb + (size_t)2 * NW * 256;
-    char* sa = smem + (size_t)wave * per_wave;
-    char* sb = sa + TR * rowb;
-    u32* bitsA = reinterpret_cast<u32*>(sb + TR * rowb) + lane;   // [word][lane]
-    u32* bitsB = bitsA + NW * 64;
-    __builtin_amdgcn_s_setprio(3);                                // (see k_null_hist_h)
-    NH_PART_STATE
-    for (long tile = (long)blockIdx.x * 4 + wave; tile < ntiles; tile += (long)gridDim.x * 4) {
-        NH_PART_ENTER
-        const int rows = (int)(R - r0 < TR ? R - r0 : TR);
-        nh_stage_in(sa, reinterpret_cast<const char*>(HA + r0 * S), rows * rowb, lane);
-        nh_stage_in(sb, reinterpret_cast<const char*>(HB + r0 * S), rows * rowb, lane);
-        __builtin_amdgcn_wave_barrier();
-        if (lane < rows) {
-            u16* pa = reinterpret_cast<u16*>(sa + lane * rowb);
-            u16* pb = reinterpret_cast<u16*>(sb + lane * rowb);
-            u32 best = 0;
-            int modal = 0;
-            for (int s = 0; s < S; ++s) {
-                const u32 h = (u32)pa[s] + pb[s];
-                pa[s] = (u16)h;
-                if (h > best) { best = h; modal = s; }
-            }
-            int Am1 = (int)(((u32)ga << 16) - 1u), ABm1 = (int)(((u32)(ga + gb) << 16) - 1u);
-            const u32 m = (u32)n_cols - best;
-            const u64 grow = (u64)(row0 + r0 + lane);
-            u32 calls = 0;
-            u32 a0w = 0, a1w = 0, a2w = 0, a3w = 0, ahave = 0, acalls = 0;
-            u32 wA = 0, wB = 0;
-            auto draw = [&](u32 v, u32 d) {                                               // the careful draw at position d
-                const int rem = n_cols - (int)d;
-                const int t = (int)__umul24(v, (u32)rem);
-                const int xA = Am1 - t, xAB = ABm1 - t;
-                bool a = xA >= rem - 1;                                                   // certainly A
-                bool b = xA < 0 && xAB >= rem - 1;                                        // certainly not A, certainly A or B
-                if ((!a && xA >= 0) || (xAB < rem - 1 && xAB >= 0)) {                     // the interval straddles a threshold
-                    if (ahave == 0) {
-                        u32 c[4] = {(u32)grow, (u32)(grow >> 32), acalls++, 0x74696573u};
-                        philox4x32_10(c, (u32)seed, (u32)(seed >> 32));
-                        a0w = c[0]; a1w = c[1]; a2w = c[2]; a3w = c[3];
-                        ahave = 4;
-                    }
-                    const u64 u48 = ((u64)v << 32) | a0w;
-                    a0w = a1w; a1w = a2w; a2w = a3w;
-                    --ahave;
-                    const u32 pick = (u32)((u48 * (u32)rem) >> 48);                       // uniform in [0, rem)
-                    a = pick < (((u32)Am1 + 1u) >> 16);
-                    b = !a && pick < (((u32)ABm1 + 1u) >> 16);
-                }
-                const u32 bit = 1u << (d & 31u);
-                wA |= a ? bit : 0u;
-                wB |= b ? bit : 0u;
-                Am1 -= a ? 65536 : 0;
-                ABm1 -= (a || b) ? 65536 : 0;
-            };
-            u32 d = 0;
-            for (; d + 8 <= m; d += 8) {
-                u32 c[4] = {(u32)grow, (u32)(grow >> 32), calls++, 0x6e756c6cu};
-                philox4x32_10(c, (u32)seed, (u32)(seed >> 32));
-                const int Am1_0 = Am1, ABm1_0 = ABm1;
-                const u32 wA_0 = wA, wB_0 = wB;
-                const int rem0 = __builtin_amdgcn_readfirstlane(n_cols - (int)d);
-                const int bit0 = __builtin_amdgcn_readfirstlane((int)(d & 31u));
-                u32 low = 0xffffffffu;
-#define NH_DRAW2(V, K)                                                                                                            \
-                {                                                                                                                 \
-                    u32 x0_, x1_, a_, ab_;                                                                                        \
-                    asm volatile(                                                                                                 \
-                        "v_mad_i32_i24 %[x0], %[v], %[nr], %[am]\n\t"                                                             \
-                        "v_mad_i32_i24 %[x1], %[v], %[nr], %[abm]\n\t"                                                            \
-                        "v_cmp_le_i32_e32 vcc, %[rm], %[x0]\n\t"                                                                  \
-                        "v_cndmask_b32_e64 %[a], 0, 1, vcc\n\t"                                                                   \
-                        "v_cmp_le_i32_e32 vcc, %[rm], %[x1]\n\t"                                                                  \
-                        "v_cndmask_b32_e64 %[ab], 0, 1, vcc\n\t"                                                                  \
-                        "v_lshl_or_b32 %[wa], %[a], %[b], %[wa]\n\t"                                                              \
-                        "v_mad_i32_i24 %[am], %[a], %[m64k], %[am]\n\t"                                                           \
-                        "v_mad_i32_i24 %[abm], %[ab], %[m64k], %[abm]\n\t"                                                        \
-                        "v_sub_u32_e32 %[ab], %[ab], %[a]\n\t"                                                                    \
-                        "v_lshl_or_b32 %[wb], %[ab], %[b], %[wb]\n\t"                                                             \
-                        "v_min3_u32 %[lo], %[x0], %[x1], %[lo]"                                                                   \
-                        : [x0] "=&v"(x0_), [x1] "=&v"(x1_), [a] "=&v"(a_), [ab] "=&v"(ab_), [wa] "+v"(wA), [wb] "+v"(wB),         \
-                          [am] "+v"(Am1), [abm] "+v"(ABm1), [lo] "+v"(low)                                                        \
-                        : [v] "v"(V), [nr] "s"((K) - rem0), [rm] "s"(rem0 - (K) - 1), [b] "s"(bit0 + (K)), [m64k] "s"(-65536)     \
-                        : "vcc");                                                                                                 \
-                }
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const u32 v = (k & 1) ? c[k >> 1] >> 16 : c[k >> 1] & 0xffffu;
-                    NH_DRAW2(v, k)
-                }
-#undef NH_DRAW2
-                if (low < (u32)rem0) {                                                    // a tie is possible in this call: repeat it carefully
-                    Am1 = Am1_0; ABm1 = ABm1_0;
-                    wA = wA_0; wB = wB_0;
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) draw((k & 1) ? c[k >> 1] >> 16 : c[k >> 1] & 0xffffu, d + k);
-                }
-                if ((d & 31u) == 24u) {
-                    bitsA[(d >> 5) * 64] = wA;
-                    bitsB[(d >> 5) * 64] = wB;
-                    wA = 0;
-                    wB = 0;
-                }
-            }
-            if (d < m) {                                                                  // the last one to seven draws
-                u32 c[4] = {(u32)grow, (u32)(grow >> 32), calls++, 0x6e756c6cu};
-                philox4x32_10(c, (u32)seed, (u32)(seed >> 32));
-#pragma unroll
-                for (int k = 0; k < 7; ++k)
-                    if (d + k < m) draw((k & 1) ? c[k >> 1] >> 16 : c[k >> 1] & 0xffffu, d + k);
-            }
-            if (m & 31u) {
-                bitsA[(m >> 5) * 64] = wA;
-                bitsB[(m >> 5) * 64] = wB;
-            }
-            u32 o = 0;
-            for (int s = 0; s < S; ++s) {
-                const u32 h = s == modal ? 0u : (u32)pa[s];
-                pa[s] = (u16)nh_range_pop(bitsA, o, h);
-                pb[s] = (u16)nh_range_pop(bitsB, o, h);
-                o += h;
-            }
-            // positions o .. m - 1 are the columns without a state: drawn (they take places in the groups), not reported
-            const u32 needA = ((u32)Am1 + 1u) >> 16, needAB = ((u32)ABm1 + 1u) >> 16;
-            pa[modal] = (u16)needA;
-            pb[modal] = (u16)(needAB - needA);
-        }
-        __builtin_amdgcn_wave_barrier();
-        store_staged(sa, reinterpret_cast<char*>(OA + r0 * S), rows * rowb, lane);
-        store_staged(sb, reinterpret_cast<char*>(OB + r0 * S), rows * rowb, lane);
-        __builtin_amdgcn_wave_barrier();
+template <int MODE>
+static int launch_null_hist_rows(const NhParts& pt, int S, int n_cols, int ga, int gb, u64 seed, int TR, int NW, hipStream_t st) {
+    long blocks = (pt.t0[pt.n] + 3) / 4;
+    if (blocks > num_cus() * 8L) blocks = num_cus() * 8L;
+    if constexpr (MODE != NH_SEQ) {                          // (the bit strings: more than 64 KB)
+        static DynLds lds_attr;                              // (one per instantiation)
+        EPG_HIP(ensure_dyn_lds(lds_attr, reinterpret_cast<const void*>(k_null_hist_rows<MODE>), 160 * 1024));
     }
+    hipLaunchKernelGGL(k_null_hist_rows<MODE>, dim3((unsigned)blocks), dim3(256), nh_lds_bytes(MODE, TR, S, NW), st, pt, S, n_cols, ga, gb, seed,
+                       TR, NW);
+    EPG_LAUNCH_CHECK("k_null_hist_rows");
+    return EPG_OK;
 }
 
 extern "C" int epg_null_hist_from_binhist_parts(int32_t nparts, const uint16_t* const* HA, const uint16_t* const* HB, const int64_t* R, int32_t S,
@@ -616,48 +574,22 @@ extern "C" int epg_null_hist_from_binhist_parts(int32_t nparts, const uint16_t* 
             return fail(EPG_ERR_INVALID_ARG, "null_hist_from_binhist: histogram arrays must be 16-byte aligned");
     }
     const int TR = tile_rows(2 * 2 * S);
-    // the bit-string kernel while a lane's string fits the wave's share of LDS and the two groups fill the row (the command line
-    // without -g); two bit strings with -g; otherwise the column-by-column kernel -- same draws, same outputs
-    const bool full = ga + gb == n_cols;
+    // one bit string when the two groups fill the row (the command line without -g), two with -g, while a wave's strings fit its
+    // 24 KB of LDS; otherwise -- or when a test asks for it on a shape that fits -- column by column: same draws, same outputs
     const int NW = (n_cols + 31) / 32;
-    const size_t bits_bytes = (size_t)NW * 256;
+    const int strings = ga + gb == n_cols ? 1 : 2;
+    const int mode = !g_force[FORCE_NULL_SEQ] && (size_t)strings * NW * 256 <= 24 * 1024 ? strings : NH_SEQ;
     for (int p0 = 0; p0 < nparts;) {
         NhParts pt;
-        memset(&pt, 0, sizeof(pt));
-        long tiles = 0;
-        int p = p0;
-        for (; p < nparts && pt.n < NH_MAXP; ++p) {
-            if (R[p] == 0) continue;
-            const int k = pt.n++;
+        p0 = pack_parts(pt, p0, nparts, R, TR, [&](int k, int p) {
             pt.ha[k] = HA[p]; pt.hb[k] = HB[p]; pt.oa[k] = OA[p]; pt.ob[k] = OB[p];
-            pt.rows[k] = R[p];
             pt.key[k] = row0[p];
-            pt.t0[k] = tiles;
-            tiles += (R[p] + TR - 1) / TR;
-        }
-        pt.t0[pt.n] = tiles;
-        p0 = p;
+        });
         if (pt.n == 0) break;
-        long blocks = (tiles + 3) / 4;
-        if (blocks > num_cus() * 8L) blocks = num_cus() * 8L;
-        const bool seq = g_force[FORCE_NULL_SEQ] != 0;          // (tests: the column-by-column kernel on shapes that fit the bit strings)
-        if (!seq && !full && 2 * bits_bytes <= 24 * 1024) {     // -g: two thresholds, two bit strings
-            const size_t shmem = 4 * ((size_t)2 * TR * 2 * S + 2 * bits_bytes);
-            static DynLds lds_attr2;
-            EPG_HIP(ensure_dyn_lds(lds_attr2, reinterpret_cast<const void*>(k_null_hist_h2), 160 * 1024));
-            hipLaunchKernelGGL(k_null_hist_h2, dim3((unsigned)blocks), dim3(256), shmem, st, pt, S, n_cols, ga, gb, (u64)seed, TR, NW);
-            EPG_LAUNCH_CHECK("k_null_hist_h2");
-        } else if (!seq && full && bits_bytes <= 24 * 1024) {
-            const size_t shmem = 4 * ((size_t)2 * TR * 2 * S + bits_bytes);
-            static DynLds lds_attr;
-            EPG_HIP(ensure_dyn_lds(lds_attr, reinterpret_cast<const void*>(k_null_hist_h), 160 * 1024));
-            hipLaunchKernelGGL(k_null_hist_h, dim3((unsigned)blocks), dim3(256), shmem, st, pt, S, n_cols, ga, gb, (u64)seed, TR, NW);
-            EPG_LAUNCH_CHECK("k_null_hist_h");
-        } else {
-            const size_t shmem = (size_t)4 * 2 * TR * 2 * S;
-            hipLaunchKernelGGL(k_null_hist_h_seq, dim3((unsigned)blocks), dim3(256), shmem, st, pt, S, n_cols, ga, gb, (u64)seed, TR);
-            EPG_LAUNCH_CHECK("k_null_hist_h_seq");
-        }
+        const int rc = with_constant<NH_SEQ, NH_ONE, NH_TWO>(mode, [&](auto MODE) {
+            return launch_null_hist_rows<decltype(MODE)::value>(pt, S, n_cols, ga, gb, (u64)seed, TR, NW, st);
+        });
+        if (rc) return rc;
     }
     return EPG_OK;
 }
@@ -669,15 +601,15 @@ extern "C" int epg_null_hist_from_binhist(const uint16_t* HA, const uint16_t* HB
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Paired mode, count pass AND null draw in one kernel (round 5).  Two kernels on two streams share every SIMD and lose ~30 % of
+// Paired mode, count pass AND null draw in one kernel.  Two kernels on two streams share every SIMD and lose ~30 % of
 // the issue slots to each other (count pass 2.44 ms + sampler 2.06 ms alone, 3.3-3.4 ms together: profiles/r05g_*).  Here a
 // wave owns tiles of 64 bins of a part: it counts the tile's rows of group A and of group B with k_bin_hist's core (four
-// 16-row sub-tiles, quad per row), leaves the two real groups'
-// histograms in its LDS slot, writes them out, then every lane draws its row's null groups from them (nh_sample_row_full) and the
-// wave writes those out too.  The waves of a CU are in different phases, so its memory pipe and its VALU are busy at the same
-// time without a second kernel.  Same integers and the same draws as epg_bin_hist_parts + epg_null_hist_from_binhist_parts
-// (tests/test_hip_abi_calls.py).  Compile-time S (15 / 18 / 25) and groups of 128 bytes per row (both widths the same number, <= 4);
-// the default group sizes only (ga = NA, gb = NB: one bit string); everything else takes the two kernels.
+// 16-row sub-tiles, quad per row), leaves the two real groups' histograms in its LDS slot, writes them out, then every lane draws
+// its row's null groups from them (nh_sample_row<false>) and the wave writes those out too.  The waves of a CU are in different
+// phases, so its memory pipe and its VALU are busy at the same time without a second kernel.  Same integers and the same draws
+// as epg_bin_hist_parts + epg_null_hist_from_binhist_parts (tests/test_hip_abi_calls.py).  Compile-time S (15 / 18 / 25) and
+// groups of 128 bytes per row (both widths the same number, <= 4); the default group sizes only (ga = NA, gb = NB: one bit
+// string); everything else takes the two kernels.
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int PC_MAXP = 32;
 struct PcParts {
@@ -753,12 +685,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     const long tstride = (long)gridDim.x * 4;
     // a tile's descriptor; `nx` is the tile after this one (its first sub-tile is loaded before this tile's draws start)
     struct Tile { const char* xa; const char* xb; u16* ha; u16* hb; u16* oa; u16* ob; long R, ldxa, ldxb, key, r0; };
-    int part = 0;
+    PartCursor at;
     auto describe = [&](long tile, Tile& t) {
-        while (tile >= pt.t0[part + 1]) ++part;                   // (a wave's tiles ascend: the part only moves forward)
+        t.r0 = at.advance(pt.t0, tile, 64);
+        const int part = at.part;
         t.xa = pt.xa[part]; t.xb = pt.xb[part]; t.ha = pt.ha[part]; t.hb = pt.hb[part]; t.oa = pt.oa[part]; t.ob = pt.ob[part];
         t.R = pt.rows[part]; t.ldxa = pt.ldxa[part]; t.ldxb = pt.ldxb[part]; t.key = pt.key[part];
-        t.r0 = (tile - pt.t0[part]) * 64;
     };
     // the loads of ONE 16-row sub-tile of one group (2 NG dwordx4 per lane), kept in flight while the previous sub-tile is counted
     u32 wa[NG][8], wb[NG][8];
@@ -821,9 +753,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         store_staged(sb, reinterpret_cast<char*>(cur.hb + cur.r0 * S), rows * ROWB, lane);
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_s_setprio(3);
-        if (lane < rows)
-            nh_sample_row_full(reinterpret_cast<u16*>(sa + lane * ROWB), reinterpret_cast<u16*>(sb + lane * ROWB), bitsA, S, n_cols, NA, seed,
-                               (u64)(cur.key + cur.r0 + lane));
+        if (lane < rows) {
+            NhRng rng(seed, (u64)(cur.key + cur.r0 + lane));
+            nh_sample_row<false>(reinterpret_cast<u16*>(sa + lane * ROWB), reinterpret_cast<u16*>(sb + lane * ROWB), bitsA, nullptr, S, n_cols, NA, NB,
+                                 rng);
+        }
         __builtin_amdgcn_wave_barrier();
         store_staged(sa, reinterpret_cast<char*>(cur.oa + cur.r0 * S), rows * ROWB, lane);
         store_staged(sb, reinterpret_cast<char*>(cur.ob + cur.r0 * S), rows * ROWB, lane);
@@ -840,7 +774,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 template <int S, int NG>
 static int launch_pair_count_null(const PcParts& pt, int NA, int NB, u64* counts, u64 seed, hipStream_t st) {
     const int NW = (NA + NB + 31) / 32;
-    const size_t shmem = 4 * ((size_t)2 * 64 * 2 * S + (size_t)NW * 256);
+    const size_t shmem = nh_lds_bytes(NH_ONE, 64, S, NW);
     static DynLds lds_attr;                                  // (one per <S, NG> instantiation)
     EPG_HIP(ensure_dyn_lds(lds_attr, reinterpret_cast<const void*>(k_pair_count_null<S, NG>), 160 * 1024 - 1024));   // (the kernel also holds a small static array)
     long blocks = (pt.t0[pt.n] + 3) / 4;
@@ -877,20 +811,11 @@ extern "C" int epg_pair_count_null_parts(int32_t nparts, const int8_t* const* XA
     u64* cnt = reinterpret_cast<u64*>(counts);
     for (int p0 = 0; p0 < nparts;) {
         PcParts pt;
-        memset(&pt, 0, sizeof(pt));
-        long tiles = 0;
-        int p = p0;
-        for (; p < nparts && pt.n < PC_MAXP; ++p) {
-            if (R[p] == 0) continue;
-            const int k = pt.n++;
+        p0 = pack_parts(pt, p0, nparts, R, 64, [&](int k, int p) {
             pt.xa[k] = reinterpret_cast<const char*>(XA[p]); pt.xb[k] = reinterpret_cast<const char*>(XB[p]);
             pt.ha[k] = HA[p]; pt.hb[k] = HB[p]; pt.oa[k] = OA[p]; pt.ob[k] = OB[p];
-            pt.rows[k] = R[p]; pt.ldxa[k] = ldxa[p]; pt.ldxb[k] = ldxb[p]; pt.key[k] = row0[p];
-            pt.t0[k] = tiles;
-            tiles += (R[p] + 63) / 64;
-        }
-        pt.t0[pt.n] = tiles;
-        p0 = p;
+            pt.ldxa[k] = ldxa[p]; pt.ldxb[k] = ldxb[p]; pt.key[k] = row0[p];
+        });
         if (pt.n == 0) break;
         const int rc = with_constant<25, 18, 15>(S, [&](auto SC) {
             return with_constant<4, 1, 2, 3>(ng, [&](auto NG) {

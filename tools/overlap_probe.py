@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Do the HBM-bound count pass (k_bin_hist) and the VALU-bound null sampler (k_null_hist_h) overlap when they run on two streams?
+"""Do the HBM-bound count pass (k_bin_hist) and the VALU-bound null sampler (k_null_hist_rows) overlap when they run on two streams?
 Times each alone and both together (the sampler on histograms of other bins than the count pass reads), for the paired shapes
 (379 + 342 columns) and for the count pass on the 833-column matrix.  usage: overlap_probe.py [--bins 7500000]"""
 import argparse
