@@ -57,6 +57,8 @@ PROTOTYPES = {
     "epg_pair_count_null_parts": (C.c_int, [_i32, _p, _p, _p, _i32, _i32, _p, _p, _i32, _p, _p, _p, _u64, _p, _p, _p, _p]),
     "epg_simsearch_ws_bytes": (_i64, [_i64, _i32, _i32, _i32]),
     "epg_simsearch": (C.c_int, [_p, _i64, _i32, _i32, _p, _i32, _p, _i32, _u64, _p, _i64, _p, _p, _p, _p]),
+    "epg_simsearch_reduce": (C.c_int, [_p, _i64, _i32, _i32, _p, _p, _p]),
+    "epg_simsearch_slices": (C.c_int, [_p, _i64, _i32, _i32, _i32, _p, _i32, _p, _p]),
     "epg_test_force": (C.c_int, [_i32, _i32]),
 }
 

@@ -27,14 +27,17 @@ def state_ranges(X):
     return X.min(axis=0), X.max(axis=0)
 
 
+def bound_from_ranges(g_range, q_range, W):
+    """W * sum_s range_s^2, range_s the spread of state s over the genome's and the ROIs' (min, max).  A Python int."""
+    lo = np.minimum(g_range[0], q_range[0]).astype(object)
+    hi = np.maximum(g_range[1], q_range[1]).astype(object)
+    return int(W) * int(sum((h - l) ** 2 for h, l in zip(hi, lo)))
+
+
 def key_bound(G, Q, W, g_range=None):
     """An upper bound of every distance between a W-row window of G [Pg, S] and a ROI of Q [B, W, S] (int64): W * sum_s range_s^2,
     range_s the spread of state s over both.  g_range: G's state_ranges, when the caller has them.  A Python int."""
-    gmin, gmax = g_range if g_range is not None else state_ranges(G)
-    qmin, qmax = state_ranges(Q)
-    lo = np.minimum(gmin, qmin).astype(object)
-    hi = np.maximum(gmax, qmax).astype(object)
-    return int(W) * int(sum((h - l) ** 2 for h, l in zip(hi, lo)))
+    return bound_from_ranges(g_range if g_range is not None else state_ranges(G), state_ranges(Q), W)
 
 
 def check_exact(bound, S, W):
@@ -52,6 +55,50 @@ def batch_rows(Pg, S, W, R, ws_cap=WS_CAP_BYTES):
     return int(max(1, min(R, (ws_cap - fixed) // (20 * P))))
 
 
+def tensor_ranges(x):
+    """state_ranges of a device tensor [..., S]."""
+    x = x.reshape(-1, x.shape[-1])
+    return x.amin(dim=0).cpu().numpy().astype(np.int64), x.amax(dim=0).cpu().numpy().astype(np.int64)
+
+
+def search_on_device(g, g_range, R, W, nDesiredMatches, batch_of, ws_cap=WS_CAP_BYTES, batch=None, want_dist=False):
+    """The search on tensors that are on the device already: g int32 [Pg, S] (the reduced genome, row-major), g_range its
+    state_ranges; batch_of(r0, r1) -> (q int32 [r1 - r0, W, S], self starts int32 [r1 - r0]) of ROIs r0 .. r1, device tensors.
+    ROI batches under the workspace cap, each with its own key_bound (check_exact refuses it beyond 2^53) -> (indices int32
+    [R, n], mode int64 [R] and, with want_dist, the distances int64 [R, Pg - W + 1]), numpy arrays."""
+    import torch
+    from . import engine
+    Pg, S = g.shape
+    n = int(nDesiredMatches)
+    if Pg < W:
+        raise ValueError("similarity search: a reduced genome of %d positions is shorter than the %d-position window" % (Pg, W))
+    P = Pg - W + 1
+    idx = np.zeros((R, n), dtype=np.int32)
+    mode = np.zeros(R, dtype=np.int64)
+    dist = np.zeros((R, P), dtype=np.int64) if want_dist else None
+    B = int(batch) if batch else batch_rows(Pg, S, W, R, ws_cap)
+    lib = _abi.load()
+    wsb = lib.epg_simsearch_ws_bytes(Pg, S, W, min(B, R))
+    _abi.check(wsb)
+    ws = torch.empty(int(wsb), dtype=torch.uint8, device=g.device)
+    for r0 in range(0, R, B):
+        r1 = min(R, r0 + B)
+        b = r1 - r0
+        q, ss = batch_of(r0, r1)
+        bound = bound_from_ranges(g_range, tensor_ranges(q), W)
+        check_exact(bound, S, W)
+        o_idx = torch.empty((b, n), dtype=torch.int32, device=g.device)
+        o_mode = torch.empty(b, dtype=torch.int64, device=g.device)
+        o_dist = torch.empty((b, P), dtype=torch.int64, device=g.device) if want_dist else None
+        _abi.call("epg_simsearch", engine._ptr(g), Pg, S, W, engine._ptr(q), b, engine._ptr(ss), n, C.c_uint64(bound),
+                  engine._ptr(ws), int(wsb), engine._ptr(o_idx), engine._ptr(o_mode), engine._ptr(o_dist), engine._stream())
+        idx[r0:r1] = o_idx.cpu().numpy()
+        mode[r0:r1] = o_mode.cpu().numpy()
+        if want_dist:
+            dist[r0:r1] = o_dist.cpu().numpy()
+    return (idx, mode, dist) if want_dist else (idx, mode)
+
+
 def simsearch(G, Q, selfStart, nDesiredMatches, ws_cap=WS_CAP_BYTES, batch=None, want_dist=False):
     """G int64 [Pg, S], Q int64 [R, W, S] (scaled scores), selfStart int [R] -> (indices int32 [R, n], mode int64 [R]
     (units of 1e-10) and, with want_dist, the distances int64 [R, Pg - W + 1])."""
@@ -63,39 +110,21 @@ def simsearch(G, Q, selfStart, nDesiredMatches, ws_cap=WS_CAP_BYTES, batch=None,
     Pg, S = G.shape
     R, W = Q.shape[0], Q.shape[1]
     n = int(nDesiredMatches)
-    idx = np.zeros((R, n), dtype=np.int32)
-    mode = np.zeros(R, dtype=np.int64)
     if R == 0:
+        idx, mode = np.zeros((0, n), dtype=np.int32), np.zeros(0, dtype=np.int64)
         return (idx, mode, np.zeros((0, max(Pg - W + 1, 0)), dtype=np.int64)) if want_dist else (idx, mode)
     if Pg < W:
         raise ValueError("similarity search: a reduced genome of %d positions is shorter than the %d-position window" % (Pg, W))
     g_range = state_ranges(G)                    # once: each batch's bound combines it with the batch's own ROIs
     check_exact(key_bound(G, Q, W, g_range), S, W)
-    P = Pg - W + 1
-    B = int(batch) if batch else batch_rows(Pg, S, W, R, ws_cap)
     dev = torch.device("cuda", torch.cuda.current_device())
     g = torch.from_numpy(np.ascontiguousarray(G, dtype=np.int32)).to(dev)   # row-major (reduced_genome.npy may be F-ordered)
-    lib = _abi.load()
-    wsb = lib.epg_simsearch_ws_bytes(Pg, S, W, min(B, R))
-    _abi.check(wsb)
-    ws = torch.empty(int(wsb), dtype=torch.uint8, device=dev)
-    dist = np.zeros((R, P), dtype=np.int64) if want_dist else None
-    for r0 in range(0, R, B):
-        r1 = min(R, r0 + B)
-        b = r1 - r0
-        q = torch.from_numpy(np.ascontiguousarray(Q[r0:r1], dtype=np.int32)).to(dev)
-        ss = torch.from_numpy(np.ascontiguousarray(selfStart[r0:r1], dtype=np.int32)).to(dev)
-        o_idx = torch.empty((b, n), dtype=torch.int32, device=dev)
-        o_mode = torch.empty(b, dtype=torch.int64, device=dev)
-        o_dist = torch.empty((b, P), dtype=torch.int64, device=dev) if want_dist else None
-        bound = key_bound(G, Q[r0:r1], W, g_range)
-        _abi.call("epg_simsearch", engine._ptr(g), Pg, S, W, engine._ptr(q), b, engine._ptr(ss), n, C.c_uint64(bound),
-                  engine._ptr(ws), int(wsb), engine._ptr(o_idx), engine._ptr(o_mode), engine._ptr(o_dist), engine._stream())
-        idx[r0:r1] = o_idx.cpu().numpy()
-        mode[r0:r1] = o_mode.cpu().numpy()
-        if want_dist:
-            dist[r0:r1] = o_dist.cpu().numpy()
-    return (idx, mode, dist) if want_dist else (idx, mode)
+    selfStart = np.asarray(selfStart)
+
+    def upload(r0, r1):
+        return (torch.from_numpy(np.ascontiguousarray(Q[r0:r1], dtype=np.int32)).to(dev),
+                torch.from_numpy(np.ascontiguousarray(selfStart[r0:r1], dtype=np.int32)).to(dev))
+    return search_on_device(g, g_range, R, W, n, upload, ws_cap, batch, want_dist)
 
 
 def selfStarts(genomeCoords, roiCoords, blockSize):

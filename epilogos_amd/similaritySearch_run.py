@@ -5,7 +5,9 @@ sizes :288-345).  -b runs the three stages in this process (STEP 2 on the GPU) i
 the host thread pools (torch's; the process is not pinned).  `--gpus N` (cli(), not an option of main: main's options are the
 reference's) splits STEP 2 over N GPUs of the node instead: one child process per GPU, each running the module's argv interface
 (the reference's SLURM job) on its contiguous share of the ROIs, while this process stays GPU-free and runs STEP 1 and 3.
--q writes one similarity_search_region_*_recs.bed per query region found in a built simsearch.bed.gz."""
+-q writes one similarity_search_region_*_recs.bed per query region: with -m, for the regions found in a built simsearch.bed.gz (the
+reference's lookup); with -s and no -m, for ANY region, searched live on the GPU against the scores file
+(similaritySearch_query.py)."""
 import os
 import re
 import signal
@@ -240,7 +242,8 @@ def querySimSearch(query, simSearchPath, outputDir):
 @click.option("-q", "--query", "query", type=str, default="",
               help="Query region formatted as chr:start-end or path to tab-separated bed file containing query regions")
 @click.option("-m", "--matches-file", "simSearchPath", type=str,
-              help="Path to previously built simsearch.bed.gz file to be queried for matches")
+              help="Path to previously built simsearch.bed.gz file to be queried for matches (without it, -q searches the "
+                   + "region live against the -s scores file)")
 def main(buildBool, scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatches, filterState, filterScore,
          partition, jobTag, mmMem, calcMem, writeMem, query, simSearchPath):
     if not buildBool and query == "":
@@ -250,6 +253,9 @@ def main(buildBool, scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatc
     gpus = (click.get_current_context().obj or {}).get("gpus")        # cli()'s --gpus: None when not given
     if gpus is not None and query != "":
         raise click.UsageError("--gpus applies to -b only: query mode does not use a GPU")
+    if query != "" and simSearchPath is None and scoresPath is None:
+        raise click.UsageError("-q needs either -m simsearch.bed.gz (look the region up in a built index) or -s scores.txt.gz "
+                               "(search the region live on the GPU)")
     outputDir = Path(outputDir)
     if not outputDir.exists():
         outputDir.mkdir(parents=True)
@@ -258,8 +264,11 @@ def main(buildBool, scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatc
     if buildBool:
         buildSimSearch(scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatches, filterState, filterScore,
                        gpus=1 if gpus is None else gpus)
-    else:
+    elif simSearchPath is not None:
         querySimSearch(query, simSearchPath, outputDir)
+    else:
+        from . import similaritySearch_query
+        similaritySearch_query.liveQuery(query, scoresPath, outputDir, windowBP, nDesiredMatches)
 
 
 def resolveGpus(value):

@@ -50,7 +50,9 @@ extern "C" {
  * reads the number from this header and refuses a library that reports another (a stale build behind EPILOGOS_HIP_LIB).
  *   1  rounds 1-5 (entry points were added without a bump: fixed in 2)
  *   2  round 6: epg_test_force switch 4 replaces the undeclared epg_debug_set_variant; epg_ws_bytes(3, ...) quotes operand chunks
- *      of 2 M bins (1 M before); S3 score tables are correctly rounded float32 (the device's log2f before) */
+ *      of 2 M bins (1 M before); S3 score tables are correctly rounded float32 (the device's log2f before)
+ *      (still 2: epg_simsearch_reduce and epg_simsearch_slices were ADDED for the live query; nothing a caller of version 2 relies on
+ *      changed, and a library without them fails to load by its missing symbols) */
 #define EPG_ABI_VERSION 2
 
 int epg_version(void);
@@ -242,6 +244,25 @@ int64_t epg_simsearch_ws_bytes(int64_t Pg, int32_t S, int32_t W, int32_t B);
 int epg_simsearch(const int32_t* G, int64_t Pg, int32_t S, int32_t W, const int32_t* Q, int32_t B, const int32_t* self_start,
                   int32_t n, uint64_t key_bound, void* ws, int64_t ws_bytes, int32_t* idx, uint64_t* mode, uint64_t* dist,
                   void* stream);
+
+/* ---- similarity search, the front of a live query (simsearch -q -s) -----------------------------------------------
+ * X: int32 [R, S], the whole gridded genome (every bin of the scores file, "%.5f" values scaled by 1e5), rows in file order.  A
+ * block is blockSize consecutive rows; its best row is the one with the largest exact (int64) row sum, the lowest row on ties.
+ *
+ * epg_simsearch_reduce: G_out int32 [ceil(R / blockSize), S], G_out[b] = the best row of block b (a partial last block included) --
+ * the G of epg_simsearch; kept (int64 [ceil(R / blockSize)], may be NULL) receives the row index of each.  Replaces
+ * similaritySearch_max_mean.py:139-160 reduceGenome.
+ *
+ * epg_simsearch_slices: Q int32 [B, nblk, S], Q[i][b] = the best row of rows first[i] + b * blockSize ... + blockSize -- the
+ * block-reduced slice of the window of nblk * blockSize rows that starts at row first[i], the Q of epg_simsearch.  first is a HOST
+ * array of B row indices (they travel as kernel arguments); first[i] < 0 or first[i] + nblk * blockSize > R is EPG_ERR_INVALID_ARG.
+ * Replaces similaritySearch_max_mean.py:80-102 makeSlice.
+ *
+ * Both are one streaming pass over the rows they read and need no workspace.  Limits: S >= 1, 1 <= blockSize <= 512,
+ * 1 <= nblk <= 64, B >= 1.  Every argument is validated before the first HIP call. */
+int epg_simsearch_reduce(const int32_t* X, int64_t R, int32_t S, int32_t blockSize, int32_t* G_out, int64_t* kept, void* stream);
+int epg_simsearch_slices(const int32_t* X, int64_t R, int32_t S, int32_t blockSize, int32_t nblk, const int64_t* first, int32_t B,
+                         int32_t* Q, void* stream);
 
 /* ---- test hook (tests/ only; nothing in the package calls it) ----------------------------------------------
  * Several entry points have a fallback kernel that other shapes take; epg_test_force(which, value) makes the next calls take it

@@ -17,7 +17,16 @@ times the whole command instead, `python -m epilogos_amd.similaritySearch_run -b
 --bins bins drawn the same way (default window: 25 kb, block size 5).  The JSON line has the wall time of the command and of its
 STEP 1, STEP 2 and STEP 3 (from the moment each STEP line reaches this tool's pipe; `startup_s` is the time before STEP 1).  This
 process never touches the GPU.  With more processes than GPUs, set EPILOGOS_DIST_BACKEND=gloo to let them share one: STEP 2's
-GPU work is then the same as with --gpus 1 and the difference is the cost of the extra processes."""
+GPU work is then the same as with --gpus 1 and the difference is the cost of the extra processes.
+
+    python tools/simsearch_bench.py --query N [--bins 1000000] [--genome-bins 15000000]
+
+times the live query (`similaritySearch_run -q ... -s ...`, similaritySearch_query.py) for N random regions on the same synthetic
+scores file: seconds to read and grid it (`read_s`), ms for the upload + epg_simsearch_reduce (`upload_reduce_ms`), for
+epg_simsearch_slices of all N (`slices_ms`), per region for slices + search one region per call and at the workspace cap's batch
+(`search_ms_per_region`), and for the coordinates and files (`write_ms`).  `genome` has the reduce kernel alone on --genome-bins
+bins made on the device (best of --reps + 1), a device-to-device copy of the same bytes on the same device, the host's
+reduceGenomeIndices + gather of the same array, and slices + search of the N regions on that genome."""
 import argparse
 import csv
 import ctypes as C
@@ -44,8 +53,13 @@ def main():
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--no-stages", action="store_true", help="skip the profiled child run that splits the stages")
     ap.add_argument("--gpus", type=int, default=None, help="time the -b command with --gpus N end to end instead")
-    ap.add_argument("--bins", type=int, default=1_000_000, help="bins of the synthetic scores file (with --gpus)")
+    ap.add_argument("--bins", type=int, default=1_000_000, help="bins of the synthetic scores file (with --gpus, --query)")
+    ap.add_argument("--query", type=int, default=None, help="time the live query of N random regions instead")
+    ap.add_argument("--genome-bins", type=int, default=15_000_000, help="bins of the reduce kernel's own measurement (--query)")
     a = ap.parse_args()
+    if a.query is not None:
+        query_bench(a)
+        return
     if a.gpus is not None:
         build_bench(a)
         return
@@ -125,6 +139,106 @@ def synthetic_scores(path, bins, S):
     off = np.zeros(bins + 1, dtype=np.int64)
     np.cumsum([len(line) for line in lines], out=off[1:])
     _io.write_scores(path, _io.Locations(np.frombuffer(blob, dtype=np.uint8).copy(), off), (x / 1e5).astype(np.float32))
+
+
+def query_bench(a):
+    """The live query's stages on a synthetic scores file, and the reduce kernel against a copy on a genome-size array."""
+    import torch
+    from epilogos_amd import _abi, engine
+    from epilogos_amd import similaritySearch_max_mean as mm
+    from epilogos_amd import similaritySearch_query as sq
+    from epilogos_amd import similaritySearch_write as wr
+    engine.require_gpu()
+    S, N, blockSize, nblk, windowBins = a.states, a.query, 5, 25, 125
+
+    def timed(f, reps=1):
+        best = None
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            out = f()
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t
+            best = dt if best is None else min(best, dt)
+        return best, out
+
+    with tempfile.TemporaryDirectory() as d:
+        sp = Path(d) / "scores.txt.gz"
+        synthetic_scores(sp, a.bins, S)
+        t = time.perf_counter()
+        _scores, inputArr, genome = mm.readScores(sp)
+        read_s = time.perf_counter() - t
+        coords = inputArr[:, :3]
+        torch.zeros(1, device="cuda")                 # the context is not part of the first stage
+        t_reduce, state = timed(lambda: sq.reduceGenome(genome, blockSize))
+        first = np.random.default_rng(1).integers(0, a.bins - windowBins + 1, size=N)
+        sq.slices(state, first[:1], nblk, blockSize)
+        t_slices, _q = timed(lambda: sq.slices(state, first, nblk, blockSize), 1 + a.reps)
+        sq.search(state, first[:1], nblk, blockSize, 100)                     # warm-up (code objects, sort configuration)
+        n1 = min(N, 8)
+        t_one, _ = timed(lambda: sq.search(state, first[:n1], nblk, blockSize, 100, batch=1), a.reps)
+        t_cap, idx = timed(lambda: sq.search(state, first, nblk, blockSize, 100), a.reps)
+        t = time.perf_counter()
+        reducedCoords = wr.reduceGenomeCoords(coords, blockSize)
+        for f, row in zip(first, idx):
+            (Path(d) / ("region_%d_recs.bed" % f)).write_text(sq.recsText(row, reducedCoords, nblk))
+        write_ms = (time.perf_counter() - t) * 1e3
+        Pg = state[1].shape[0]
+    res = {"tool": "simsearch_bench", "mode": "query", "bins": a.bins, "states": S, "regions": N, "positions": int(Pg),
+           "batch_at_cap": calc_batch(Pg, S, nblk, N), "read_s": round(read_s, 2), "upload_reduce_ms": round(t_reduce * 1e3, 3),
+           "slices_ms": round(t_slices * 1e3, 4),
+           "search_ms_per_region": {"batch_1": round(t_one / n1 * 1e3, 4), "batch_at_cap": round(t_cap / N * 1e3, 4)},
+           "write_ms": round(write_ms, 2)}
+    del state
+
+    # the reduce kernel alone at genome size, against a copy of the same bytes and the host code it replaces
+    R = a.genome_bins
+    g0 = torch.Generator(device="cuda").manual_seed(0)
+    base = torch.randint(0, 100000, (40, S), dtype=torch.int32, device="cuda", generator=g0)
+    cls = torch.randint(0, 40, (R,), device="cuda", generator=g0)
+    cls[torch.rand(R, device="cuda", generator=g0) < 0.9] = 0
+    x = base[cls].contiguous()
+    del cls
+    g = torch.empty((-(-R // blockSize), S), dtype=torch.int32, device="cuda")
+    y = torch.empty_like(x)
+    reduce_call = lambda: _abi.call("epg_simsearch_reduce", engine._ptr(x), R, S, blockSize, engine._ptr(g), None, engine._stream())
+    reduce_call()
+    t_k, _ = timed(reduce_call, 1 + a.reps)
+    y.copy_(x)
+    t_c, _ = timed(lambda: y.copy_(x), 1 + a.reps)
+    del y
+    # slices + search at genome size (what a whole-genome -q -s run pays per region), one region per call and at the cap's batch
+    state = (x, g, calc_ranges(g))
+    Pg = g.shape[0]
+    first = np.random.default_rng(2).integers(0, R - windowBins + 1, size=N)
+    sq.search(state, first[:1], nblk, blockSize, 100)
+    t_one, _ = timed(lambda: sq.search(state, first[:n1], nblk, blockSize, 100, batch=1), a.reps)
+    t_cap, _ = timed(lambda: sq.search(state, first, nblk, blockSize, 100), a.reps)
+    t_sl, _ = timed(lambda: sq.slices(state, first, nblk, blockSize), 1 + a.reps)
+    del state
+    xh = x.cpu().numpy().astype(np.int64)
+    t = time.perf_counter()
+    gh = xh[mm.reduceGenomeIndices(xh, blockSize)]
+    host_s = time.perf_counter() - t
+    same = bool(np.array_equal(g.cpu().numpy(), gh))
+    nbytes = R * S * 4
+    res["genome"] = {"bins": R, "bytes_read": nbytes, "reduce_kernel_ms": round(t_k * 1e3, 4),
+                     "reduce_tb_per_s": round((nbytes + nbytes // blockSize) / t_k / 1e12, 3),
+                     "copy_ms": round(t_c * 1e3, 4), "copy_tb_per_s": round(2 * nbytes / t_c / 1e12, 3),
+                     "host_reduce_s": round(host_s, 2), "equal_to_host": same, "positions": int(Pg),
+                     "batch_at_cap": calc_batch(Pg, S, nblk, N), "slices_ms": round(t_sl * 1e3, 4),
+                     "search_ms_per_region": {"batch_1": round(t_one / n1 * 1e3, 4), "batch_at_cap": round(t_cap / N * 1e3, 4)}}
+    print(json.dumps(res), flush=True)
+
+
+def calc_ranges(g):
+    from epilogos_amd import similaritySearch_calc as calc
+    return calc.tensor_ranges(g)
+
+
+def calc_batch(Pg, S, W, R):
+    from epilogos_amd import similaritySearch_calc as calc
+    return calc.batch_rows(Pg, S, W, R, calc.WS_CAP_BYTES)
 
 
 def build_bench(a):
