@@ -1,4 +1,4 @@
-"""ctypes binding of include/epilogos_amd.h.  No fallbacks: a missing library or symbol raises."""
+"""ctypes binding of include/epilogos_amd.h and include/epilogos_scores_text.h.  No fallbacks: a missing library or symbol raises."""
 import ctypes as C
 import re
 from pathlib import Path
@@ -62,7 +62,20 @@ PROTOTYPES = {
     "epg_test_force": (C.c_int, [_i32, _i32]),
 }
 
+# the same for include/epilogos_scores_text.h, the GPU scores-text parser (tests/test_scores_text_host.py checks it)
+TEXT_HEADER = HEADER.with_name("epilogos_scores_text.h")
+TEXT_PROTOTYPES = {
+    "epgt_scores_ws_bytes": (_i64, [_i64]),
+    "epgt_scores_parse": (C.c_int, [_p, _i64, _i32, _i64, _i64, _p, _p, _p, _p, _p, _i64, _p, _p]),
+}
+
 _lib = None
+
+
+def text_header_symbols():
+    """Function names declared in include/epilogos_scores_text.h."""
+    txt = re.sub(r"/\*.*?\*/", "", TEXT_HEADER.read_text(), flags=re.S)
+    return sorted(set(re.findall(r"\b(epgt_[a-z0-9_]+)\s*\(", txt)))
 
 
 def header_symbols():
@@ -101,7 +114,7 @@ def load():
         raise EpilogosHipError(-3, "%s is missing: build it with `python -m epilogos_amd.build` "
                                    "(there is no CPU fallback)" % path)
     lib = C.CDLL(str(path))
-    for name, (res, args) in PROTOTYPES.items():
+    for name, (res, args) in list(PROTOTYPES.items()) + list(TEXT_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = args

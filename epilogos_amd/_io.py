@@ -65,6 +65,14 @@ def load():
     lib.epgio_rolling_max_f64.argtypes = [p, i64, C.c_int32, p, C.c_int32]
     lib.epgio_inflate_mem.restype = i64
     lib.epgio_inflate_mem.argtypes = [p, i64, p, i64, i32]
+    lib.epgio_open_text.restype = p
+    lib.epgio_open_text.argtypes = [C.c_char_p, i32]
+    lib.epgio_text_data.restype = p
+    lib.epgio_text_data.argtypes = [p, C.POINTER(i64)]
+    lib.epgio_close_text.restype = None
+    lib.epgio_close_text.argtypes = [p]
+    lib.epgio_count_newlines.restype = i64
+    lib.epgio_count_newlines.argtypes = [p, i64, i32]
     lib.epgio_release_buffers.restype = None
     lib.epgio_release_buffers.argtypes = [i32]
     lib.epgio_set_reader_plan.restype = None
@@ -137,6 +145,43 @@ def inflate_mem(blob, own=True, cap=None):
     out = C.create_string_buffer(cap)
     n = load().epgio_inflate_mem(blob, len(blob), out, cap, 2 if own == 2 and own is not True else (1 if own else 0))
     return None if n < 0 else out.raw[:n]
+
+
+class Text:
+    """The whole text of a file (inflated when it is gzip) as a read-only uint8 array over the native buffer: `data`; close()
+    gives the buffer back, after which `data` must not be touched."""
+
+    def __init__(self, path, threads=0):
+        _log_io("open_text", path)
+        self._h = load().epgio_open_text(os.fsencode(str(path)), int(threads))
+        if not self._h:
+            raise EpilogosIOError(_err())
+        n = C.c_int64(0)
+        ptr = load().epgio_text_data(self._h, C.byref(n))
+        self.data = (np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(n.value,)) if n.value
+                     else np.zeros(0, dtype=np.uint8))
+        self.data.flags.writeable = False
+
+    def close(self):
+        if self._h:
+            self.data = None
+            load().epgio_close_text(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def count_newlines(a, threads=0):
+    """Number of newline bytes of a contiguous uint8 array."""
+    a = np.ascontiguousarray(a, dtype=np.uint8)
+    n = load().epgio_count_newlines(a.ctypes.data_as(C.c_void_p), a.size, int(threads))
+    if n < 0:
+        raise EpilogosIOError(_err())
+    return int(n)
 
 
 def release_buffers(background=True):

@@ -17,6 +17,8 @@
 #include <atomic>
 #include <memory>
 #include <mutex>
+#include <new>
+#include <stdexcept>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -615,6 +617,56 @@ int64_t epgio_inflate_mem(const void* in, int64_t n, void* out, int64_t cap, int
     if ((int64_t)t.size > cap) return fail("inflate_mem: output %lld > cap %lld", (long long)t.size, (long long)cap);
     if (t.size) memcpy(out, t.data, t.size);
     return (int64_t)t.size;
+}
+
+struct epgio_text {
+    Text t;
+};
+
+epgio_text* epgio_open_text(const char* path, int32_t threads) {
+    if (!path) { fail("open_text: NULL path"); return nullptr; }
+    Census census_;
+    epgio_text* h = new (std::nothrow) epgio_text();
+    if (!h) { fail("out of memory reading %s", path); return nullptr; }
+    try {
+        if (!slurp(path, h->t, threads)) { delete h; return nullptr; }
+    } catch (const std::exception& e) {                          // (the readers' vectors and threads: nothing crosses the C ABI)
+        delete h;
+        fail("reading %s: %s", path, e.what());
+        return nullptr;
+    }
+    return h;
+}
+
+const char* epgio_text_data(const epgio_text* h, int64_t* size) {
+    if (size) *size = h ? (int64_t)h->t.size : 0;
+    return h ? h->t.data : nullptr;
+}
+
+void epgio_close_text(epgio_text* h) { delete h; }
+
+int64_t epgio_count_newlines(const char* p, int64_t n, int32_t threads) {
+    if (n < 0 || (n > 0 && !p)) return fail("count_newlines: bad argument");
+    auto count = [](const char* a, const char* e) {
+        int64_t c = 0;
+        while (a < e && (a = (const char*)memchr(a, '\n', (size_t)(e - a)))) { ++c; ++a; }
+        return c;
+    };
+    const int64_t PIECE = (int64_t)8 << 20;
+    const int T = (int)std::max<int64_t>(1, std::min<int64_t>(n_threads(threads), n / PIECE));
+    Census census_;
+    if (T == 1) return count(p, p + n);
+    std::vector<int64_t> part((size_t)T, 0);
+    {
+        Uncount uncount_;
+        std::vector<std::thread> th;
+        for (int w = 0; w < T; ++w)
+            th.emplace_back([&, w] { Census c_; part[(size_t)w] = count(p + n * w / T, p + n * (w + 1) / T); });
+        join_all(th);
+    }
+    int64_t total = 0;
+    for (int64_t c : part) total += c;
+    return total;
 }
 
 static epgio_table* open_table_impl(const char* path, int64_t row_lo, int64_t row_hi, int32_t threads, int32_t max_state,

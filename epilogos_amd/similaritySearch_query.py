@@ -10,7 +10,11 @@ is taken as given, a longer one gives its central window, a shorter one is grown
 chromosome's bin that contains the anchor; the window is the windowBins bins from there, shifted to lie inside the chromosome
 when it would stick out at either end.  A chromosome's bins are contiguous rows of the scores file (as selfStarts assumes).
 
-The three device steps are module-level functions (reduceGenome, slices, search): a host test puts numpy in their place."""
+The scores file is read by readGrid: on the GPU as text (scoresText.read_scores_device, a strict parser), by pandas
+(similaritySearch_max_mean.readScores) when there is no GPU or the file is outside the parser's grammar.
+
+The device steps are module-level functions (readGrid, reduceGenome, slices, search): a host test puts numpy in place of the
+last three."""
 import ctypes as C
 from pathlib import Path
 from time import time
@@ -50,6 +54,29 @@ def windowFirstBin(table, chrom, start, end, windowBP, windowBins):
     b = int(np.searchsorted(starts, anchor, side="right")) - 1          # the bin that contains the anchor
     b = min(max(b, 0), len(starts) - windowBins)
     return row0 + b
+
+
+def readGrid(scoresPath):
+    """(coords object [R, 3]: chromosome, start, end; genome int64 [R, S]: the scores x 1e5), host arrays with the values of
+    mm.readScores(scoresPath)'s inputArr[:, :3] and third result.  With a GPU the file is parsed there as text; a file the strict
+    parser refuses gets one warning line and is read by mm.readScores, so that it behaves as it always did (to_grid's ValueError
+    for values off the grid included)."""
+    import torch
+    from . import scoresText
+    if torch.cuda.is_available() and _abi.lib_path().exists():
+        try:
+            x, start, end, runs = scoresText.read_scores_device(scoresPath)
+        except scoresText.NotStrict as e:
+            print("            Warning: %s is not a plain \"%%.5f\" scores file (row %d: %s); reading it with pandas"
+                  % (scoresPath, e.row, e.reason), flush=True)
+        else:
+            coords = np.empty((len(start), 3), dtype=object)
+            for name, a, b in runs:
+                coords[a:b, 0] = name
+            coords[:, 1], coords[:, 2] = start, end
+            return coords, x.cpu().numpy().astype(np.int64)
+    _scores, inputArr, genome = mm.readScores(scoresPath)
+    return inputArr[:, :3], genome
 
 
 def reduceGenome(genome, blockSize):
@@ -107,8 +134,7 @@ def liveQuery(query, scoresPath, outputDir, windowBP, nDesiredMatches):
     queryArr = generateRegionArr(query)
     windowBP, windowBins, blockSize = windowParameters(scoresPath, windowBP)
     nblk = windowBins // blockSize
-    _scores, inputArr, genome = mm.readScores(scoresPath)
-    coords = inputArr[:, :3]
+    coords, genome = readGrid(scoresPath)
     table = chromosomeTable(coords[:, 0], coords[:, 1], coords[:, 2])
     print("            Time:", format(time() - readTime, '.0f'), "seconds\n", flush=True)
     print("        Querying regions...", flush=True)

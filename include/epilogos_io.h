@@ -121,6 +121,16 @@ int64_t epgio_gzip_fast(const void* in, int64_t n, void* out, int64_t cap);
  * corrupt / does not fit.  Exposed for the differential fuzz (tools/asan_io.sh, tests/test_native_io.py). */
 int64_t epgio_inflate_mem(const void* in, int64_t n, void* out, int64_t cap, int32_t own);
 
+/* The whole text of a file in memory, inflated by the readers above when it is gzip (BGZF blocks in parallel, any other gzip
+ * with the library's inflate, zlib when that declines): what the GPU scores-text parser (epilogos_scores_text.h) is fed from.
+ * epgio_text_data returns the first byte and stores the size; the text is valid until epgio_close_text.  NULL on error. */
+typedef struct epgio_text epgio_text;
+epgio_text* epgio_open_text(const char* path, int32_t threads);
+const char* epgio_text_data(const epgio_text* t, int64_t* size);
+void epgio_close_text(epgio_text* t);
+/* Number of '\n' in p[0, n), counted by up to `threads` threads (0 = the host budget); < 0 on a bad argument. */
+int64_t epgio_count_newlines(const char* p, int64_t n, int32_t threads);
+
 /* Host budget.  Wherever `threads` is 0 above the library uses epgio_default_threads(): EPILOGOS_HOST_THREADS when that is
  * set (the driver gives every rank of a node its share: cores / LOCAL_WORLD_SIZE, capped by the reference's -c,
  * run.py:36,148), else the hardware threads capped by the cgroup CPU quota and by 64.  epgio_thread_census reports the

@@ -5,6 +5,7 @@
 #   builds the library with -fsanitize=address,undefined -O1 -g into the scratch dir (default /tmp/epg_asan), points the
 #   Python binding at it (EPILOGOS_IO_LIB), preloads libasan into the interpreter and runs
 #     tests/test_native_io.py tests/test_roi.py     (parser, writers, codecs, STEP 4 helpers; incl. the file-level fuzz)
+#     tests/test_scores_text_host.py -k native      (epgio_open_text, epgio_count_newlines: what feeds the GPU scores-text parser)
 #     tools/fuzz_inflate.py --streams 100000          (--quick: 3000; the in-memory differential fuzz against zlib)
 # Exit code 0 = no sanitizer report, no test failure, no fuzz mismatch.  A log of the last full run is kept in profiles/.
 set -euo pipefail
@@ -29,6 +30,7 @@ if [ "$QUICK" = 1 ]; then
     python3 tools/fuzz_inflate.py --streams 3000
 else
     python3 -m pytest tests/test_native_io.py tests/test_roi.py -x -q -p no:cacheprovider
+    python3 -m pytest tests/test_scores_text_host.py -x -q -p no:cacheprovider -k native
     python3 tools/fuzz_inflate.py --streams 100000
 fi
 echo "asan_io: clean"

@@ -22,7 +22,11 @@ GPU work is then the same as with --gpus 1 and the difference is the cost of the
     python tools/simsearch_bench.py --query N [--bins 1000000] [--genome-bins 15000000]
 
 times the live query (`similaritySearch_run -q ... -s ...`, similaritySearch_query.py) for N random regions on the same synthetic
-scores file: seconds to read and grid it (`read_s`), ms for the upload + epg_simsearch_reduce (`upload_reduce_ms`), for
+scores file (multi-member gzip as the scoring path writes it, BGZF with --bgzf): seconds to read it (`read_s`: readGrid, the median
+of --read-reps reads) with its parts (`read_split`: inflate_s = the host's inflate alone, count_s = chunk cutting and row counts, upload_parse_ms = staging,
+upload and the parse kernels between two HIP events, coords_s = coordinates and chromosome names to the host, download_s = the
+int32 grid back to the host as int64, which readGrid's host-array contract costs) next to pandas' read of the same file
+(`pandas_read_s`, mm.readScores, the reads taken in turn), ms for the upload + epg_simsearch_reduce (`upload_reduce_ms`), for
 epg_simsearch_slices of all N (`slices_ms`), per region for slices + search one region per call and at the workspace cap's batch
 (`search_ms_per_region`), and for the coordinates and files (`write_ms`).  `genome` has the reduce kernel alone on --genome-bins
 bins made on the device (best of --reps + 1), a device-to-device copy of the same bytes on the same device, the host's
@@ -56,6 +60,8 @@ def main():
     ap.add_argument("--bins", type=int, default=1_000_000, help="bins of the synthetic scores file (with --gpus, --query)")
     ap.add_argument("--query", type=int, default=None, help="time the live query of N random regions instead")
     ap.add_argument("--genome-bins", type=int, default=15_000_000, help="bins of the reduce kernel's own measurement (--query)")
+    ap.add_argument("--read-reps", type=int, default=5, help="reads of the scores file per reader; the medians are reported (--query)")
+    ap.add_argument("--bgzf", action="store_true", help="write the synthetic scores file as BGZF: its blocks inflate in parallel (--query)")
     a = ap.parse_args()
     if a.query is not None:
         query_bench(a)
@@ -148,6 +154,7 @@ def query_bench(a):
     from epilogos_amd import similaritySearch_max_mean as mm
     from epilogos_amd import similaritySearch_query as sq
     from epilogos_amd import similaritySearch_write as wr
+    from epilogos_amd import scoresText
     engine.require_gpu()
     S, N, blockSize, nblk, windowBins = a.states, a.query, 5, 25, 125
 
@@ -164,12 +171,41 @@ def query_bench(a):
 
     with tempfile.TemporaryDirectory() as d:
         sp = Path(d) / "scores.txt.gz"
+        was = os.environ.get("EPILOGOS_BGZF")
+        if a.bgzf:
+            os.environ["EPILOGOS_BGZF"] = "1"         # for the writer of the synthetic file only
+        else:
+            os.environ.pop("EPILOGOS_BGZF", None)
         synthetic_scores(sp, a.bins, S)
-        t = time.perf_counter()
-        _scores, inputArr, genome = mm.readScores(sp)
-        read_s = time.perf_counter() - t
-        coords = inputArr[:, :3]
+        if was is None:
+            os.environ.pop("EPILOGOS_BGZF", None)
+        else:
+            os.environ["EPILOGOS_BGZF"] = was
         torch.zeros(1, device="cuda")                 # the context is not part of the first stage
+        med = lambda v: round(float(np.median(v)), 4)
+        pandas_s, read_s, split = [], [], {"inflate_s": [], "count_s": [], "upload_parse_ms": [], "coords_s": [], "download_s": []}
+        sq.readGrid(sp)                               # warm-up (code objects, the page-locked buffers' first allocation)
+        for _ in range(a.read_reps):                  # the two readers in turn: other people's work shares the host
+            t = time.perf_counter()
+            _scores, inputArr, genome_pd = mm.readScores(sp)
+            pandas_s.append(time.perf_counter() - t)
+            t = time.perf_counter()
+            coords, genome = sq.readGrid(sp)
+            read_s.append(time.perf_counter() - t)
+            tm = {}
+            x, _start, _end, _runs = scoresText.read_scores_device(sp, timings=tm)
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            x.cpu().numpy().astype(np.int64)          # what readGrid's host-array contract costs on top (the re-upload is
+            tm["download_s"] = time.perf_counter() - t    # upload_reduce_ms below)
+            del x
+            for k in split:
+                split[k].append(tm[k])
+        same = bool(np.array_equal(genome, genome_pd) and (coords == inputArr[:, :3]).all())
+        if not same:
+            sys.exit("simsearch_bench: readGrid and mm.readScores disagree on %s: no timing of a wrong result" % sp)
+        read_s, pandas_read_s, split = med(read_s), med(pandas_s), {k: med(v) for k, v in split.items()}
+        del genome_pd, inputArr
         t_reduce, state = timed(lambda: sq.reduceGenome(genome, blockSize))
         first = np.random.default_rng(1).integers(0, a.bins - windowBins + 1, size=N)
         sq.slices(state, first[:1], nblk, blockSize)
@@ -185,7 +221,8 @@ def query_bench(a):
         write_ms = (time.perf_counter() - t) * 1e3
         Pg = state[1].shape[0]
     res = {"tool": "simsearch_bench", "mode": "query", "bins": a.bins, "states": S, "regions": N, "positions": int(Pg),
-           "batch_at_cap": calc_batch(Pg, S, nblk, N), "read_s": round(read_s, 2), "upload_reduce_ms": round(t_reduce * 1e3, 3),
+           "batch_at_cap": calc_batch(Pg, S, nblk, N), "file": "bgzf" if a.bgzf else "gzip", "read_s": read_s, "read_split": split,
+           "pandas_read_s": pandas_read_s, "read_reps": a.read_reps, "read_equal_to_pandas": same, "upload_reduce_ms": round(t_reduce * 1e3, 3),
            "slices_ms": round(t_slices * 1e3, 4),
            "search_ms_per_region": {"batch_1": round(t_one / n1 * 1e3, 4), "batch_at_cap": round(t_cap / N * 1e3, 4)},
            "write_ms": round(write_ms, 2)}
