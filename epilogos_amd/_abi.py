@@ -1,4 +1,4 @@
-"""ctypes binding of include/epilogos_amd.h and include/epilogos_scores_text.h.  No fallbacks: a missing library or symbol raises."""
+"""ctypes binding of include/epilogos_amd.h, include/epilogos_scores_text.h and include/epilogos_groups.h.  No fallbacks: a missing library or symbol raises."""
 import ctypes as C
 import re
 from pathlib import Path
@@ -69,6 +69,12 @@ TEXT_PROTOTYPES = {
     "epgt_scores_parse": (C.c_int, [_p, _i64, _i32, _i64, _i64, _p, _p, _p, _p, _p, _i64, _p, _p]),
 }
 
+# and for include/epilogos_groups.h, the column-group count pass (tests/test_groups_host.py checks it)
+GROUP_HEADER = HEADER.with_name("epilogos_groups.h")
+GROUP_PROTOTYPES = {
+    "epg_bin_hist_groups": (C.c_int, [_p, _i64, _i32, _i64, _i32, _i32, _p, _p, _p, _p]),
+}
+
 _lib = None
 
 
@@ -76,6 +82,12 @@ def text_header_symbols():
     """Function names declared in include/epilogos_scores_text.h."""
     txt = re.sub(r"/\*.*?\*/", "", TEXT_HEADER.read_text(), flags=re.S)
     return sorted(set(re.findall(r"\b(epgt_[a-z0-9_]+)\s*\(", txt)))
+
+
+def group_header_symbols():
+    """Function names declared in include/epilogos_groups.h."""
+    txt = re.sub(r"/\*.*?\*/", "", GROUP_HEADER.read_text(), flags=re.S)
+    return sorted(set(re.findall(r"\b(epg_[a-z0-9_]+)\s*\(", txt)))
 
 
 def header_symbols():
@@ -114,7 +126,7 @@ def load():
         raise EpilogosHipError(-3, "%s is missing: build it with `python -m epilogos_amd.build` "
                                    "(there is no CPU fallback)" % path)
     lib = C.CDLL(str(path))
-    for name, (res, args) in list(PROTOTYPES.items()) + list(TEXT_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(TEXT_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = args

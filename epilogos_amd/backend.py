@@ -419,15 +419,15 @@ class _HipSingleSession(_HipSession):
         self.N = 0                                       # the widest part's width (an empty file has none)
         self._ws3 = None                                 # S3: ONE workspace for all parts of the session
 
-    def add_part(self, arr, N, ticket):
-        return self.add_device(self._upload(arr, N, ticket), N)
+    def add_part(self, arr, N, ticket, columns=None):
+        return self.add_device(self._upload(arr, N, ticket), N, columns=columns)
 
     # S1 parts of less than a GiB -- the chromosome files of a genome -- are counted in batches (the queue of _HipSession): one
     # epg_bin_hist_parts launch per 8 M rows or 32 parts, histograms in one flat allocation, and later ONE score launch over that
     # allocation.  Per part this was 24 count launches and 24 score launches of 0.1-0.25 ms with their ramps and tails: 3.42 ms
     # per 15 M-bin genome against 2.6 ms as one matrix (bench.py s1_paths, round 6); in batches the same job is two count
     # launches and two score launches.  Same integers, same float32 scores.
-    def add_device(self, X, N, place=None):
+    def add_device(self, X, N, place=None, columns=None):
         """Count pass over a RESIDENT part -- the ONE entry of the command line (add_part, after its upload), of bench.py and of
         library callers.  place=None (everybody's default): engine.alloc_hist decides -- the histogram cache of a matrix of a GiB
         or more goes where its search finds another memory class than the matrix's (a process-lifetime home block, one bounded
@@ -436,7 +436,10 @@ class _HipSingleSession(_HipSession):
         each -- under a GiB up to ~880 columns -- so a whole-genome run of the reference's shape counts with plain allocations
         (bench.py reports that figure as placement.unplaced; its count passes hide under the parse anyway) while a caller that holds
         the genome as one matrix gets the placed cache.  place=False forces a plain allocation and a count launch of the part's
-        own (bench.py's comparison)."""
+        own (bench.py's comparison).  columns (0-based indices into the N columns): the part is that GROUP of the matrix's
+        biosamples -- its width everywhere behind the count pass is the group's (_add_columns)."""
+        if columns is not None:
+            return self._add_columns(X, N, columns, place)
         eng, S = self.eng, self.S
         self.N = max(self.N, N or 0)
         pid = len(self.parts)
@@ -453,6 +456,23 @@ class _HipSingleSession(_HipSession):
             H, _ = eng.bin_hist(X, N, S, counts=self._acc(), H=H) if self.sal == 1 else eng.bin_hist_s2(X, N, S, counts2=self._acc(), H=H)
             self.parts.append(_Part(H))
         return pid
+
+    def _add_columns(self, X, N, columns, place):
+        """A part that is a column group of a resident matrix.  S1 / S2 of a state model: the grouped count pass reads the whole
+        rows once and leaves the histograms of the group's columns (epg_bin_hist_groups); the part then is what a matrix cut
+        to these columns would have left.  S3 (its score pass reads the states) and the wide models: the columns are gathered on
+        the device and the ordinary path runs on the result."""
+        eng, S = self.eng, self.S
+        cols = eng.check_columns(columns, N or 0)
+        n = int(cols.size)
+        if X.shape[0] == 0 or not n or self.sal == 3 or S > eng.GROUPS_MAX_STATES:
+            return self.add_device(eng.select_columns(X, cols), n, place=place)
+        self.N = max(self.N, n)
+        Hs, _ = eng.bin_hist_groups(X, N, S, [cols], counts=self._acc() if self.sal == 1 else None)
+        if self.sal == 2:
+            eng.hist_s2_from_binhist(Hs[0], S, counts=self._acc())
+        self.parts.append(_Part(Hs[0]))
+        return len(self.parts) - 1
 
     def _s3_workspace(self, R, N):
         """The ~8 GB workspace of the S3 matrix-core contraction (count pass) and of the S3 score pass (table, transposed matrix,
@@ -604,6 +624,29 @@ class _HipPairedSession(_HipSession):
         self.parts.append(_Pair(XA, XB, None, None, row0))
         self._queue((pid, NA, NB), XA.shape[0])
         return pid
+
+    def add_columns(self, X, N, colsA, colsB, row0):
+        """One part whose two groups are column groups (0-based indices) of ONE resident matrix: a single grouped launch reads
+        the rows once and leaves both groups' histograms; the null groups are drawn from them (the same draws as from the
+        matrices: they depend on the histograms, the seed and row0 only).  Wide models gather the two groups and go on as
+        add_staged."""
+        eng, S = self.eng, self.S
+        a, b = eng.check_columns(colsA, N or 0), eng.check_columns(colsB, N or 0)
+        NA, NB = int(a.size), int(b.size)
+        if np.intersect1d(a, b).size:                    # (no cut-file run has a biosample in both groups)
+            raise ValueError("column %d is in both groups" % int(np.intersect1d(a, b)[0]))
+        if X.shape[0] == 0 or not NA or not NB or S > eng.GROUPS_MAX_STATES:
+            return self.add_staged(eng.select_columns(X, a), NA, eng.select_columns(X, b), NB, row0)
+        self.NA, self.NB = max(self.NA, NA), max(self.NB, NB)
+        (HA, HB), counts = eng.bin_hist_groups(X, N, S, [a, b])
+        if self.sal == 1:
+            self._acc().add_(counts[0] + counts[1])     # counts over [A|B] = counts of A + counts of B (helpers.py:173)
+        else:
+            eng.hist_s2_from_binhist_pair(HA, HB, S, counts=self._acc())
+        p = _Pair(None, None, HA, HB, row0)
+        self.parts.append(p)
+        self._start_null([p])
+        return len(self.parts) - 1
 
     def _count(self, batch):
         """Count pass of a batch and its null groups.  The default group sizes, a state model and widths the fused kernel takes:

@@ -66,6 +66,8 @@ static inline auto with_constant(int v, F&& f) {
 // The library-internal functions that one source file defines and another calls (the extern "C" entry points are declared in
 // epilogos_amd.h).
 int64_t s1_ws_bytes(int64_t R, int N, int S);                                        // epg_s1.hip
+int grid_for_tiles(long R);                                                           // epg_s1.hip: the count kernels' persistent grid
+long fast_rows(long R, int N, long ldx);                                              // epg_s1.hip: rows whose 16-byte last chunk stays inside X
 int64_t s2_table_bytes(int maxc, int S);                                              // epg_s2.hip
 int64_t s3_ws_bytes(int64_t R, int N, int S);                                         // epg_s3.hip
 // epg_s3_transpose.hip: XT[sample][bin] of a call of R bins, see the definition

@@ -36,9 +36,8 @@ __device__ __forceinline__ u32 dbl(u32 x) {
     return r;
 }
 
-// one group: 8 dwords = 32 state bytes -> cnt[s] += #bytes equal to s
-template <int S>
-__device__ __forceinline__ void count_group(const u32 (&w)[8], u32 (&cnt)[S]) {
+// the bit transpose of one group: 8 dwords = 32 state bytes -> the five planes P[0..4] (bit b of every byte)
+__device__ __forceinline__ void bit_planes(const u32 (&w)[8], u32 (&P)[5]) {
     // stage 1: low nibbles of dword pairs (2i, 2i+1) share a byte
     const u32 n0 = sel(0x0f0f0f0fu, w[0], w[1] << 4);
     const u32 n1 = sel(0x0f0f0f0fu, w[2], w[3] << 4);
@@ -48,29 +47,39 @@ __device__ __forceinline__ void count_group(const u32 (&w)[8], u32 (&cnt)[S]) {
     const u32 m0 = sel(0x33333333u, n0, n1 << 2), m1 = sel(0x33333333u, n2, n3 << 2);
     const u32 r0 = sel(0xccccccccu, n1, n0 >> 2), r1 = sel(0xccccccccu, n3, n2 >> 2);
     // stage 3: single bit planes; sample (dword k = 4a+2g+h, byte j) sits at bit 8j + 4h + 2g + a in every plane
-    const u32 P0 = sel(0x55555555u, m0, dbl(m1)), P1 = sel(0xaaaaaaaau, m1, m0 >> 1);
-    const u32 P2 = sel(0x55555555u, r0, dbl(r1)), P3 = sel(0xaaaaaaaau, r1, r0 >> 1);
+    P[0] = sel(0x55555555u, m0, dbl(m1)); P[1] = sel(0xaaaaaaaau, m1, m0 >> 1);
+    P[2] = sel(0x55555555u, r0, dbl(r1)); P[3] = sel(0xaaaaaaaau, r1, r0 >> 1);
     // bit 4 plane, same sample order; the selects leave no garbage behind
     const u32 c00 = sel(0x10101010u, w[0], dbl(w[4])), c01 = sel(0x10101010u, w[1], dbl(w[5]));
     const u32 c10 = sel(0x10101010u, w[2], dbl(w[6])), c11 = sel(0x10101010u, w[3], dbl(w[7]));
     const u32 d0 = sel(0x30303030u, c00, c10 << 2), d1 = sel(0x30303030u, c01, c11 << 2);
-    const u32 P4 = sel(0xf0f0f0f0u, d1, d0 >> 4);
+    P[4] = sel(0xf0f0f0f0u, d1, d0 >> 4);
+}
 
-    // decode: L[k] = samples whose low three bits equal k (one bitop3 each), then one bitop3 per state for bits 3,4
-    u32 L[8];
-    L[0] = EPG_B3(P0, P1, P2, 0x01); L[1] = EPG_B3(P0, P1, P2, 0x10); L[2] = EPG_B3(P0, P1, P2, 0x04); L[3] = EPG_B3(P0, P1, P2, 0x40);
-    L[4] = EPG_B3(P0, P1, P2, 0x02); L[5] = EPG_B3(P0, P1, P2, 0x20); L[6] = EPG_B3(P0, P1, P2, 0x08); L[7] = EPG_B3(P0, P1, P2, 0x80);
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-        u32 ind;
-        switch (s >> 3) {                       // (bit3, bit4) of s
-            case 0: ind = EPG_B3(L[s & 7], P3, P4, 0x10); break;   // L & ~P3 & ~P4
-            case 1: ind = EPG_B3(L[s & 7], P3, P4, 0x40); break;   // L &  P3 & ~P4
-            case 2: ind = EPG_B3(L[s & 7], P3, P4, 0x20); break;   // L & ~P3 &  P4
-            default: ind = EPG_B3(L[s & 7], P3, P4, 0x80); break;  // L &  P3 &  P4
-        }
-        cnt[s] += (u32)__builtin_popcount(ind);
+// decode, first half: L[k] = samples whose low three bits equal k (one bitop3 each)
+__device__ __forceinline__ void low_three(const u32 (&P)[5], u32 (&L)[8]) {
+    L[0] = EPG_B3(P[0], P[1], P[2], 0x01); L[1] = EPG_B3(P[0], P[1], P[2], 0x10); L[2] = EPG_B3(P[0], P[1], P[2], 0x04); L[3] = EPG_B3(P[0], P[1], P[2], 0x40);
+    L[4] = EPG_B3(P[0], P[1], P[2], 0x02); L[5] = EPG_B3(P[0], P[1], P[2], 0x20); L[6] = EPG_B3(P[0], P[1], P[2], 0x08); L[7] = EPG_B3(P[0], P[1], P[2], 0x80);
+}
+
+// decode, second half: the indicator word of state s (a compile-time value after unrolling), one bitop3 for bits 3,4
+__device__ __forceinline__ u32 indicator(const u32 (&L)[8], const u32 (&P)[5], int s) {
+    switch (s >> 3) {                                            // (bit3, bit4) of s
+        case 0: return EPG_B3(L[s & 7], P[3], P[4], 0x10);       // L & ~P3 & ~P4
+        case 1: return EPG_B3(L[s & 7], P[3], P[4], 0x40);       // L &  P3 & ~P4
+        case 2: return EPG_B3(L[s & 7], P[3], P[4], 0x20);       // L & ~P3 &  P4
+        default: return EPG_B3(L[s & 7], P[3], P[4], 0x80);      // L &  P3 &  P4
     }
+}
+
+// one group: 8 dwords = 32 state bytes -> cnt[s] += #bytes equal to s
+template <int S>
+__device__ __forceinline__ void count_group(const u32 (&w)[8], u32 (&cnt)[S]) {
+    u32 P[5], L[8];
+    bit_planes(w, P);
+    low_three(P, L);
+#pragma unroll
+    for (int s = 0; s < S; ++s) cnt[s] += (u32)__builtin_popcount(indicator(L, P, s));
 }
 
 // Per-launch constants of the row geometry (wave-uniform, live in SGPRs)
@@ -169,8 +178,16 @@ __device__ __forceinline__ void count_row(const char* rowp, int j, const RowGeom
 // Measured alternatives that were NOT faster and were removed: (a) refilling group t of the next tile right after
 // counting it, with inline-asm loads and hand-counted vmcnt (2.46 vs 2.33 ms); (b) flat line-granular loads staged
 // through LDS so that no 128-byte line is requested twice (2.40 ms); (c) nt / sc1 / sc0 sc1 loads (3.1-3.4 ms).
-template <int S, int NG, int NW = 4, typename Epilogue, typename Finish>
-__device__ __forceinline__ void tile_loop(const char* __restrict__ X, long R, int N, long ldx, Epilogue&& epilogue, Finish&& finish) {
+// count(rowp, j, g, cnt) adds one row's share of this lane to cnt[S]: count_row by default; the column-group kernel
+// (epg_groups.hip) passes its own, with S = groups x states counters.
+template <int S, int NG>
+struct CountRow {
+    __device__ __forceinline__ void operator()(const char* rowp, int j, const RowGeom& g, u32 (&cnt)[S]) const { count_row<S, NG>(rowp, j, g, cnt); }
+};
+
+template <int S, int NG, int NW = 4, typename Epilogue, typename Finish, typename Count = CountRow<S, NG>>
+__device__ __forceinline__ void tile_loop(const char* __restrict__ X, long R, int N, long ldx, Epilogue&& epilogue, Finish&& finish,
+                                          Count&& count = Count()) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int j = lane & 3, b = lane >> 2;
@@ -184,7 +201,7 @@ __device__ __forceinline__ void tile_loop(const char* __restrict__ X, long R, in
             u32 cnt[S];
 #pragma unroll
             for (int s = 0; s < S; ++s) cnt[s] = 0;
-            count_row<S, NG>(X + (valid ? row : R - 1) * ldx, j, g, cnt);
+            count(X + (valid ? row : R - 1) * ldx, j, g, cnt);
             epilogue(half, row, valid, cnt);
         }
         const long row0 = st * 32;

@@ -401,7 +401,7 @@ __global__ __launch_bounds__(256) void k_normalise_small(const IT* __restrict__ 
 // persistent grid size in blocks per CU.  Round 3: two blocks (2 waves per SIMD) measure 3-4 % faster than four on 1.9-7.5 M-bin
 // shards and 1 % on 15 M bins (profiles/r03i_*); epg_test_force(4, n) sets another for A/B runs (tools/kbench.py)
 static int blocks_per_cu() { return g_force[FORCE_K1_BLOCKS_PER_CU] > 0 ? g_force[FORCE_K1_BLOCKS_PER_CU] : 2; }
-static int grid_for_tiles(long R) {
+int grid_for_tiles(long R) {
     const long nsuper = (R + 31) >> 5;
     long blocks = (nsuper + 3) / 4;
     const long cap = (long)num_cus() * blocks_per_cu();
@@ -432,7 +432,7 @@ static void with_count_core(int S, int ng, F&& f) {
 }
 
 // rows the fast kernel may touch: all of them unless its 16-byte last chunk could run past the allocation
-static long fast_rows(long R, int N, long ldx) {
+long fast_rows(long R, int N, long ldx) {
     const long chunks = (N + 15) / 16;
     const long over = 16 * chunks - ldx;           // bytes a row's last chunk reaches past the row pitch
     if (over <= 0) return R;

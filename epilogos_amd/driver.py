@@ -495,15 +495,29 @@ class _Single:
     kind, census, upload_note = "scores", "single", ""
     n_payload = 1                                      # arrays of a part that travel to rank 0, besides its Locations
 
-    def __init__(self, files, numStates, saliency, keep_temps):
+    n_widths = 1                                       # widths the session works with: N
+
+    def __init__(self, files, numStates, saliency, keep_temps, columns=None):
         self.groups, self.S, self.sal, self.keep_temps = (files,), numStates, saliency, keep_temps
+        self.columns = None if columns is None else np.ascontiguousarray(columns, dtype=np.int64)   # 0-based: the group IS these columns
 
     def open(self, be):
         return be.open_single(self.S, self.sal)
 
+    def see_width(self, widths, g, n):
+        """A parsed job of file group g has n columns: what that says about the session's widths."""
+        widths[0] = max(widths[0], n if self.columns is None or not n else len(self.columns))
+
+    def default_widths(self):
+        """The widths when this rank parsed nothing that has one."""
+        return [_columns_of(self.groups[0][0]) if self.columns is None else len(self.columns)]
+
     def add(self, sess, t, arr, n, part):
         """A parsed job (its index t, its states) into the session -> the part's session id (None while it is incomplete)."""
-        return sess.add_part(arr, n, t)
+        if self.columns is None:
+            return sess.add_part(arr, n, t)
+        _check_columns_fit(self.columns, n, self.groups[0][part[0]])
+        return sess.add_part(arr, n, t, columns=self.columns)
 
     def part_out(self, sess, pid):
         """-> (the array written as text, [the arrays rank 0 collects]) of a part."""
@@ -522,6 +536,7 @@ class _Paired:
     """Two groups: a part is the same rows of a file of each group; pairwiseDelta_* text; rank 0's result per file is a dict."""
     kind, census, upload_note = "pairwiseDelta", "paired", " x 2 groups"
     n_payload = 4
+    n_widths = 2                                       # NA, NB
 
     def __init__(self, files1, files2, numStates, saliency, quiescentState, groupSize, nullSeed, keep_temps):
         self.groups, self.S, self.sal, self.keep_temps = (files1, files2), numStates, saliency, keep_temps
@@ -530,6 +545,12 @@ class _Paired:
 
     def open(self, be):
         return be.open_paired(self.S, self.sal, self.qstate, self.groupSize, self.seed)
+
+    def see_width(self, widths, g, n):
+        widths[g] = max(widths[g], n)
+
+    def default_widths(self):
+        return [_columns_of(group[0]) for group in self.groups]
 
     def add(self, sess, t, x, n, part):
         staged = (sess.stage(x, n, t), n, x.shape[0])
@@ -562,6 +583,36 @@ class _Paired:
         return {"chrName": chrName, "locations": loc, "nullDistances": null, "quiescenceArr": quies, "distances": dist, "maxDiff": mdiff}
 
 
+class _PairedColumns(_Paired):
+    """Two groups that are column groups of ONE set of files: a part is one parsed file -- parsed and uploaded once -- that
+    feeds both groups (session add_columns).  Outputs, payloads and rank 0's results are paired mode's."""
+    upload_note = ""
+
+    def __init__(self, files, colsA, colsB, numStates, saliency, quiescentState, groupSize, nullSeed, keep_temps):
+        super().__init__(files, (), numStates, saliency, quiescentState, groupSize, nullSeed, keep_temps)
+        self.groups = (files,)
+        self.colsA, self.colsB = np.ascontiguousarray(colsA, dtype=np.int64), np.ascontiguousarray(colsB, dtype=np.int64)
+
+    def see_width(self, widths, g, n):
+        if n:
+            widths[0], widths[1] = len(self.colsA), len(self.colsB)
+
+    def default_widths(self):
+        return [len(self.colsA), len(self.colsB)]
+
+    def add(self, sess, t, x, n, part):
+        fi, lo, _hi = part
+        for cols in (self.colsA, self.colsB):
+            _check_columns_fit(cols, n, self.groups[0][fi])
+        return sess.add_columns(sess.stage(x, n, t), n, self.colsA, self.colsB, shuffle_key(fi, lo))
+
+
+def _check_columns_fit(cols, n, path):
+    """A column group against a parsed file of n columns (an empty file has none and holds nothing to select from)."""
+    if n and len(cols) and int(cols.max()) >= n:
+        raise ValueError("biosample {} is not in {}: the file has {} biosample columns".format(int(cols.max()) + 1, path, n))
+
+
 def _run_groups(mode, outputDir, fileTag, backend, defer_writes):
     """STEP 1-3 of either mode over the bin-range partition -> (exp_freq, results of rank 0 by file stem, else None)."""
     be = backend if backend is not None else _backend.get()
@@ -577,12 +628,12 @@ def _run_groups(mode, outputDir, fileTag, backend, defer_writes):
     sess = mode.open(be)
 
     # STEP 1: every part of this rank is parsed, uploaded once and counted; what the score pass needs stays resident
-    pids, locs, widths = [None] * len(my_parts), [None] * len(my_parts), [0] * len(mode.groups)
+    pids, locs, widths = [None] * len(my_parts), [None] * len(my_parts), [0] * mode.n_widths
     # paired: part k's two groups are jobs 2k and 2k + 1, the second group follows the first one's row ranges
     with closing(_stream_parts([(group[fi], lo, hi) for fi, lo, hi in my_parts for group in mode.groups], sess, mode.S)) as stream:
         for t, arr, n, loc in stream:                  # in order of completion
             k, g = divmod(t, len(mode.groups))
-            widths[g] = max(widths[g], n)              # an empty file has no width: it must not be the one that is remembered
+            mode.see_width(widths, g, n)               # an empty file has no width: it must not be the one that is remembered
             if g == 0:
                 locs[k] = loc
             pids[k] = mode.add(sess, t, arr, n, my_parts[k])
@@ -605,7 +656,7 @@ def _run_groups(mode, outputDir, fileTag, backend, defer_writes):
         plans = plan_partition(rows, d.world) if d.world > 1 else [my_parts]
         tm.lap("parse + upload + expected counts")
     if not widths[0]:
-        widths = [_columns_of(group[0]) for group in mode.groups]
+        widths = mode.default_widths()
     N = sum(widths)                                    # paired: the background counts are over the concatenation [A|B]
     sess.ensure_acc(N)
     sess.all_reduce(d)                                 # the one exchange step; a rank without bins contributes zeros
@@ -665,12 +716,13 @@ def _run_groups(mode, outputDir, fileTag, backend, defer_writes):
 
 
 def run_single_group(files, numStates, saliency, outputDir, fileTag, verbose=False, backend=None, device=None,
-                     keep_temp_scores=True, defer_writes=False):
+                     keep_temp_scores=True, defer_writes=False, columns=None):
     """STEP 1-3 for a single group over `files` (one per chromosome).  Returns (exp_freq float32, results) where results
     (rank 0 only, else None) maps file stem -> (chrName, float32 scores [R, S], _io.Locations) for an in-process STEP 4.
     keep_temp_scores writes the reference's temp_scores_{tag}_{stem}.npz (scores.py:166-169) for a STEP 4 run
-    elsewhere; the command line skips them because its STEP 4 would delete them a moment later."""
-    mode = _Single([Path(f) for f in files], numStates, saliency, keep_temp_scores)
+    elsewhere; the command line skips them because its STEP 4 would delete them a moment later.  columns (0-based indices of
+    biosample columns): the group is these columns of the files; the outputs are those of files cut to them beforehand."""
+    mode = _Single([Path(f) for f in files], numStates, saliency, keep_temp_scores, columns)
     return _run_groups(mode, outputDir, fileTag, backend, defer_writes)
 
 
@@ -686,4 +738,13 @@ def run_paired_groups(files1, files2, numStates, saliency, outputDir, fileTag, q
     side-car of this engine's STEP 4)."""
     mode = _Paired([Path(f) for f in files1], [Path(f) for f in files2], numStates, saliency, quiescentState, groupSize, nullSeed,
                    keep_temps)
+    return _run_groups(mode, outputDir, fileTag, backend, defer_writes)
+
+
+def run_paired_columns(files, colsA, colsB, numStates, saliency, outputDir, fileTag, quiescentState, groupSize, nullSeed,
+                       verbose=False, backend=None, device=None, keep_temps=True, defer_writes=False):
+    """run_paired_groups for two groups that are column groups (0-based indices) of ONE set of files: every file is parsed and
+    uploaded once and feeds both groups.  The partition, the hand-over between ranks and the all-reduce are run_paired_groups':
+    they move histograms and row ranges.  Outputs are those of run_paired_groups on files cut to the groups beforehand."""
+    mode = _PairedColumns([Path(f) for f in files], colsA, colsB, numStates, saliency, quiescentState, groupSize, nullSeed, keep_temps)
     return _run_groups(mode, outputDir, fileTag, backend, defer_writes)

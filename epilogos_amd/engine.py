@@ -423,6 +423,65 @@ def bin_hist_parts(Xs, Ns, S, counts=None, want_hist=True, Hs=None):
     return Hs, counts
 
 
+GROUPS_MAX = 4                      # EPG_GROUPS_MAX of include/epilogos_groups.h: column groups per launch
+GROUPS_MAX_STATES = 31              # the grouped count pass serves the five-bit counting core; wider models gather (select_columns)
+_members = {}                       # (device, N, groups as bytes) -> uint8 [N] membership tensor
+
+
+def check_columns(cols, N):
+    """A group's columns as a contiguous int64 array; 0-based, inside [0, N), no duplicates."""
+    cols = np.ascontiguousarray(np.asarray(cols, dtype=np.int64).reshape(-1))
+    if cols.size and (cols.min() < 0 or cols.max() >= N):
+        raise ValueError("column index outside 0 .. %d" % (N - 1))
+    if np.unique(cols).size != cols.size:
+        raise ValueError("a column is listed twice in one group")
+    return cols
+
+
+def group_members(device, N, groups):
+    """The membership tensor of epg_bin_hist_groups, uint8 [N]: bit g of byte c = column c belongs to groups[g].  Built once per
+    (device, N, groups) and kept (a run passes the same groups for every part)."""
+    groups = [check_columns(g, N) for g in groups]
+    device = torch.device(device)
+    key = (str(device), int(N), tuple(g.tobytes() for g in groups))
+    m = _members.get(key)
+    if m is None:
+        host = np.zeros(N, dtype=np.uint8)
+        for g, cols in enumerate(groups):
+            host[cols] |= np.uint8(1 << g)
+        if len(_members) >= 64:
+            _members.clear()
+        m = _members[key] = torch.from_numpy(host).to(device)
+    return m
+
+
+def bin_hist_groups(X, N, S, groups, counts=None, want_hist=True):
+    """The count pass for column groups of ONE matrix (epg_bin_hist_groups): X is read once, every group gets per-bin
+    histograms of its own columns.  groups: 1 .. GROUPS_MAX int64 arrays of 0-based columns.  -> ([H_g uint16 [R, S] as int16
+    storage] or None, counts int64 [G, S]; counts is added to when given)."""
+    R, ldx = _check_states(X, N)
+    G = len(groups)
+    member = group_members(X.device, N, groups)
+    Hs = hist_rows_alloc([R] * G, S, X.device) if want_hist else None
+    if counts is None:
+        counts = zeros_counts(G * S, device=X.device)
+    _abi.call("epg_bin_hist_groups", _ptr(X), R, N, ldx, S, G, _ptr(member), _ptr_array(Hs) if Hs is not None else None, _ptr(counts),
+              _stream())
+    return Hs, counts.view(G, S)
+
+
+def select_columns(X, cols):
+    """The columns `cols` (0-based int64) of a state matrix as a matrix of its own: int8 [R, padded_width(len(cols))], padding
+    bytes 0xFF.  What the grouped count pass does not serve (S3 needs the states themselves; models of 32 .. 127 states) runs
+    the ordinary path on this.  A device gather, no host copy."""
+    cols = check_columns(cols, X.shape[1])
+    n = int(cols.size)
+    out = torch.full((X.shape[0], padded_width(max(n, 1))), -1, dtype=torch.int8, device=X.device)
+    if n:
+        out[:, :n].copy_(torch.index_select(X, 1, torch.from_numpy(cols).to(X.device)))
+    return out
+
+
 def null_hist_from_binhist_parts(HAs, HBs, n_cols, S, ga, gb, seed, row0s, stream=None):
     """epg_null_hist_from_binhist for several parts in one launch (bit-identical to a call per part); outputs from ONE allocation
     per group.  -> (list of OA, list of OB)."""

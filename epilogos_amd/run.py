@@ -24,6 +24,46 @@ def _natural_key(p):
     return [int(t) if t.isdigit() else t for t in re.split(r"(\d+)", Path(p).name)]
 
 
+def parseColumns(spec):
+    """A SPEC of biosamples -> 0-based column indices (int64, in the order given).  SPEC: comma-separated 1-based biosample
+    numbers and inclusive ranges ("1-379,401,500-620"; biosample k is column k + 3 of the file), or "@path": a text file with one
+    number or range per line, blank lines and # comments allowed.  ValueError (the message names the offence) for an empty or
+    malformed SPEC, a number < 1, a descending range and a biosample listed twice."""
+    import numpy as np
+    if spec is None or not spec.strip():
+        raise ValueError("empty biosample list")
+    spec = spec.strip()
+    if spec.startswith("@"):
+        try:
+            lines = Path(spec[1:]).read_text().splitlines()
+        except OSError as e:
+            raise ValueError("cannot read the biosample list {}: {}".format(spec[1:], e.strerror or e))
+        items = [ln.split("#", 1)[0].strip() for ln in lines]
+        items = [it for it in items if it]
+        if not items:
+            raise ValueError("empty biosample list in {}".format(spec[1:]))
+    else:
+        items = [it.strip() for it in spec.split(",")]
+    out = []
+    for it in items:
+        m = re.fullmatch(r"(\d+)(?:\s*-\s*(\d+))?", it)
+        if m is None:
+            raise ValueError("malformed biosample list: '{}' is neither a number nor a range".format(it))
+        lo = int(m.group(1))
+        hi = int(m.group(2)) if m.group(2) is not None else lo
+        if lo < 1 or hi < 1:
+            raise ValueError("biosample numbers start at 1, got '{}'".format(it))
+        if hi < lo:
+            raise ValueError("malformed biosample list: range '{}' descends".format(it))
+        out.extend(range(lo, hi + 1))
+    seen = set()
+    for k in out:
+        if k in seen:
+            raise ValueError("biosample {} is listed twice".format(k))
+        seen.add(k)
+    return np.asarray(out, dtype=np.int64) - 1
+
+
 def checkArguments(mode, saliency, inputDirPath, inputDirPath2, outputDirPath, numProcesses, numStates, quiescentState,
                    groupSize, numTrials=101, samplingSize=100000, roiWidth=0):
     """Reference run.py:378-451; same exceptions and messages."""
@@ -134,21 +174,55 @@ def _init_device_and_group(world, under_launcher):
               help="GPUs of this node to split the genome over (0 = all visible); replaces the SLURM fan-out of the reference")
 @click.option("--cache-dir", "cacheDir", type=str, default=None,
               help="Keep parsed input matrices (int8 + coordinates) here; later runs on the same files skip the text parse")
+@click.option("--columns", "columns", type=str, default=None,
+              help="Single mode: score only these biosamples of the matrices: 1-based numbers and ranges (1-379,401) or @file")
+@click.option("--columns-a", "columnsA", type=str, default=None,
+              help="Paired mode with -i: the biosamples of group A (as --columns); the matrices are read once for both groups")
+@click.option("--columns-b", "columnsB", type=str, default=None, help="Paired mode with -i: the biosamples of group B")
 def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2, outputDirectory, stateInfo, saliency,
          numProcesses, exitBool, diagnosticBool, numTrials, samplingSize, quiescentState, groupSize, version, partition,
-         pvalBool, roiWidth, fileTag, expFreqMem, expCombMem, scoreMem, roiMem, nullSeed, gpus, cacheDir):
+         pvalBool, roiWidth, fileTag, expFreqMem, expCombMem, scoreMem, roiMem, nullSeed, gpus, cacheDir, columns, columnsA, columnsB):
     """Information-theoretic navigation of multi-tissue functional genomic annotations -- MI355X scoring engine."""
     if version:
         print("Version:", __version__)
         sys.exit()
+    # column groups: the flag combinations that involve the new options come first, so that every combination without them
+    # gets today's message
+    pairedColumns = mode == "paired" and (columnsA is not None or columnsB is not None)
+    if mode == "single" and (columnsA is not None or columnsB is not None):
+        print("ERROR: [--columns-a] and [--columns-b] are only valid in paired mode; single mode takes [--columns]"); sys.exit()
+    if mode == "paired" and columns is not None:
+        print("ERROR: [--columns] is only valid in single mode; paired mode takes [--columns-a] and [--columns-b]"); sys.exit()
+    if pairedColumns:
+        if columnsA is None or columnsB is None:
+            print("ERROR: [--columns-a] and [--columns-b] must be given together"); sys.exit()
+        if inputDirectory1 is not None or inputDirectory2 is not None:
+            print("ERROR: [--columns-a] and [--columns-b] select from [-i, --input-directory]; they cannot be combined with [-a] and [-b]"); sys.exit()
+        if inputDirectory is None:
+            print("ERROR: [-i, --input-directory] is required with [--columns-a] and [--columns-b]"); sys.exit()
+    cols = colsA = colsB = None
+    try:
+        what = "--columns"
+        cols = parseColumns(columns) if columns is not None else None
+        if pairedColumns:
+            what = "--columns-a"
+            colsA = parseColumns(columnsA)
+            what = "--columns-b"
+            colsB = parseColumns(columnsB)
+    except ValueError as e:
+        print("ERROR: [{}] {}".format(what, e)); sys.exit()
+    if pairedColumns:
+        both = sorted(set(colsA.tolist()) & set(colsB.tolist()))
+        if both:
+            print("ERROR: biosample {} is in both [--columns-a] and [--columns-b]".format(both[0] + 1)); sys.exit()
     # flag combinations (reference run.py:328-375)
     if mode == "single" and inputDirectory is None:
         print("ERROR: [-i, --input-directory] is required in single mode"); sys.exit()
     if mode == "single" and (inputDirectory1 is not None or inputDirectory2 is not None):
         print("ERROR: [-a] and [-b] are only valid in paired mode"); sys.exit()
-    if mode == "paired" and (inputDirectory1 is None or inputDirectory2 is None):
+    if mode == "paired" and not pairedColumns and (inputDirectory1 is None or inputDirectory2 is None):
         print("ERROR: [-a, --directory-one] and [-b, --directory-two] are required in paired mode"); sys.exit()
-    if mode == "paired" and inputDirectory is not None:
+    if mode == "paired" and not pairedColumns and inputDirectory is not None:
         print("ERROR: [-i] is only valid in single mode"); sys.exit()
     if outputDirectory is None:
         print("ERROR: [-o, --output-directory] is required"); sys.exit()
@@ -161,8 +235,8 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
         os.environ["EPILOGOS_NUM_CORES"] = str(numProcesses)
     numStates = getNumStates(stateInfo)
     quiescentState = numStates - 1 if quiescentState == -1 else quiescentState - 1     # 1-based -> 0-based, 0 -> off
-    inputDirPath = Path(inputDirectory if mode == "single" else inputDirectory1)
-    inputDirPath2 = Path(inputDirectory2) if mode == "paired" else Path("")
+    inputDirPath = Path(inputDirectory if mode == "single" or pairedColumns else inputDirectory1)
+    inputDirPath2 = (inputDirPath if pairedColumns else Path(inputDirectory2)) if mode == "paired" else Path("")
     if not PurePath(inputDirPath).is_absolute():
         inputDirPath = Path.cwd() / inputDirPath
     if mode == "paired" and not PurePath(inputDirPath2).is_absolute():
@@ -174,6 +248,7 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
                    groupSize, numTrials, samplingSize, roiWidth)
     if fileTag == "null":
         fileTag = ("{}_s{}".format(inputDirPath.name, saliency) if mode == "single"
+                   else "{0}_A_{0}_B_s{1}".format(inputDirPath.name, saliency) if pairedColumns
                    else "{}_{}_s{}".format(inputDirPath.name, inputDirPath2.name, saliency))
     storedExpPath = outputDirPath / "exp_freq_{}.npy".format(fileTag)
 
@@ -192,13 +267,22 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
     under_launcher = "WORLD_SIZE" in os.environ and "RANK" in os.environ
     files = sorted(inputDirPath.glob("*"), key=_natural_key)
     files2 = []
-    if mode == "paired":
+    if mode == "paired" and not pairedColumns:
         for file in files:
             if not list(inputDirPath2.glob(file.name)):
                 raise FileNotFoundError("File not found: {}".format(str(inputDirPath2 / file.name))
                                         + " Please ensure corresponding files within input directories 1 and 2 have the same name")
             files2.append(next(inputDirPath2.glob(file.name)))
     from . import driver, _io
+    if cols is not None or pairedColumns:                     # every biosample asked for must exist in every file
+        top = max(int(c.max()) for c in ((cols,) if cols is not None else (colsA, colsB)))
+        for f in files:
+            try:
+                n = driver._columns_of(f)
+            except Exception:                                    # (an empty or unreadable file: the parse reports it, or it has no rows)
+                continue
+            if n and top >= n:
+                print("ERROR: biosample {} is not in {}: the file has {} biosample columns".format(top + 1, f, n)); sys.exit()
     if world == 1 and not under_launcher and os.environ.get("EPILOGOS_EARLY_READERS", "1") != "0":
         # A single process: the files' readers start NOW -- inflating needs neither torch nor the GPU, and importing the one and
         # initialising the other takes about a second, which a whole-genome run spent before its first byte was read.  A reader
@@ -206,7 +290,7 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
         _io.set_state_limit(numStates)
         jobs = []
         for k, f in enumerate(files):
-            jobs += [(f, 0, None)] + ([(files2[k], 0, None)] if mode == "paired" else [])
+            jobs += [(f, 0, None)] + ([(files2[k], 0, None)] if files2 else [])
         driver.start_readers_early(jobs)
     try:
         device = _init_device_and_group(world, under_launcher)
@@ -225,7 +309,7 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
         say("\nSTEP 1-3: background counts -> all-reduce -> scores (bin-range partition over %d GPU(s))" % world)
         try:
             _, results = run_single_group(files, numStates, saliency, outputDirPath, fileTag, verbose=False, device=device,
-                                          keep_temp_scores=False, defer_writes=True)
+                                          keep_temp_scores=False, defer_writes=True, columns=cols)
         finally:
             driver.abort_early_readers()                         # (nothing to do once the stage driver has taken them over)
         try:
@@ -240,7 +324,7 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
         finally:
             driver.finish_writes()                               # one process: the score text was still being written under STEP 4
     else:
-        from .driver import run_paired_groups
+        from .driver import run_paired_columns, run_paired_groups
         if nullSeed is None:
             import numpy as np
             seed = np.array([int(np.random.SeedSequence().generate_state(1)[0])], dtype=np.int64)
@@ -254,8 +338,12 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
             nullSeed = int(seed[0])
         say("\nSTEP 1-3: background counts over [A|B] -> all-reduce -> scores, null groups, deltas (%d GPU(s))" % world)
         try:
-            _, results = run_paired_groups(files, files2, numStates, saliency, outputDirPath, fileTag, quiescentState, groupSize,
-                                           nullSeed, verbose=False, device=device, keep_temps=False, defer_writes=True)
+            if pairedColumns:
+                _, results = run_paired_columns(files, colsA, colsB, numStates, saliency, outputDirPath, fileTag, quiescentState,
+                                                groupSize, nullSeed, verbose=False, device=device, keep_temps=False, defer_writes=True)
+            else:
+                _, results = run_paired_groups(files, files2, numStates, saliency, outputDirPath, fileTag, quiescentState, groupSize,
+                                               nullSeed, verbose=False, device=device, keep_temps=False, defer_writes=True)
         finally:
             driver.abort_early_readers()
         if pvalBool and max(numProcesses, 1) > 1:
