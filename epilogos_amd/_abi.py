@@ -1,4 +1,5 @@
-"""ctypes binding of include/epilogos_amd.h, include/epilogos_scores_text.h and include/epilogos_groups.h.  No fallbacks: a missing library or symbol raises."""
+"""ctypes binding of include/epilogos_amd.h, include/epilogos_scores_text.h, include/epilogos_groups.h and
+include/epilogos_nulldraws.h.  No fallbacks: a missing library or symbol raises."""
 import ctypes as C
 import re
 from pathlib import Path
@@ -75,6 +76,14 @@ GROUP_PROTOTYPES = {
     "epg_bin_hist_groups": (C.c_int, [_p, _i64, _i32, _i64, _i32, _i32, _p, _p, _p, _p]),
 }
 
+# and for include/epilogos_nulldraws.h, the K-draw null of paired mode (tests/test_null_draws_host.py checks it)
+NULLDRAWS_HEADER = HEADER.with_name("epilogos_nulldraws.h")
+NULLDRAWS_PROTOTYPES = {
+    "epg_null_dist_draws_parts": (C.c_int, [_i32, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _i32, _p, _p]),
+    "epg_null_exceed_ws_bytes": (_i64, [_i64]),
+    "epg_null_exceed": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _i64, _p]),
+}
+
 _lib = None
 
 
@@ -87,6 +96,12 @@ def text_header_symbols():
 def group_header_symbols():
     """Function names declared in include/epilogos_groups.h."""
     txt = re.sub(r"/\*.*?\*/", "", GROUP_HEADER.read_text(), flags=re.S)
+    return sorted(set(re.findall(r"\b(epg_[a-z0-9_]+)\s*\(", txt)))
+
+
+def nulldraws_header_symbols():
+    """Function names declared in include/epilogos_nulldraws.h."""
+    txt = re.sub(r"/\*.*?\*/", "", NULLDRAWS_HEADER.read_text(), flags=re.S)
     return sorted(set(re.findall(r"\b(epg_[a-z0-9_]+)\s*\(", txt)))
 
 
@@ -126,7 +141,8 @@ def load():
         raise EpilogosHipError(-3, "%s is missing: build it with `python -m epilogos_amd.build` "
                                    "(there is no CPU fallback)" % path)
     lib = C.CDLL(str(path))
-    for name, (res, args) in list(PROTOTYPES.items()) + list(TEXT_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()):
+    for name, (res, args) in list(PROTOTYPES.items()) + list(TEXT_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + \
+            list(NULLDRAWS_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = args

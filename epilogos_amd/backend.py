@@ -126,8 +126,8 @@ class HipBackend:
     def open_single(self, S, saliency):
         return _HipSingleSession(self, S, saliency)
 
-    def open_paired(self, S, saliency, quiescentState, groupSize, seed):
-        return _HipPairedSession(self, S, saliency, quiescentState, groupSize, seed)
+    def open_paired(self, S, saliency, quiescentState, groupSize, seed, draws=1):
+        return _HipPairedSession(self, S, saliency, quiescentState, groupSize, seed, draws)
 
 
 def _null_widths(NA, NB, groupSize):
@@ -582,11 +582,22 @@ class _Pair:
 
 
 class _HipPairedSession(_HipSession):
-    def __init__(self, be, S, saliency, quiescentState, groupSize, seed):
+    # --null-draws: the buffers of one chunk of draws (null distances, sort keys, sort temporary) stay under this many bytes
+    NULL_CHUNK_BYTES = 2 << 30
+
+    def __init__(self, be, S, saliency, quiescentState, groupSize, seed, draws=1):
         if saliency not in (1, 2):
             raise ValueError("Please ensure that saliency metric is either 1 or 2 for Pairwise Epilogos")
+        if int(draws) < 1:
+            raise ValueError("the number of null draws per bin must be at least 1")
         super().__init__(be, S, saliency)
         self.qstate, self.groupSize, self.seed = quiescentState, groupSize, seed
+        # K > 1 null draws per bin (_exceed): the results carry "exceed", null_pool is the size of the pooled null
+        self.draws = int(draws)
+        self.null_chunk_bytes = self.NULL_CHUNK_BYTES
+        self.null_chunks = 0                             # chunks the last exceedance pass took
+        self.null_fused = None                           # ... and whether the draws kernel took the shape (False: the loop)
+        self._null_kept = None                           # device scalar: the non-quiescent bins of that pass
         self.NA = self.NB = 0                            # the widest part's widths (an empty file pair has none)
         # rows per batch: the default group sizes take the fused kernel (nothing to overlap: two launches per genome, 4.62 ms per
         # 15 M bins against 4.71 with seven); the two-kernel path overlaps batch k's sampler with batch k + 1's count pass
@@ -744,12 +755,91 @@ class _HipPairedSession(_HipSession):
             quads = [(self.parts[pid].HA, self.parts[pid].HB) + self._null_of(pid) for pid in live]
             out = dict(zip(live, _unless_unsupported(self.eng.pair_scores_s1_parts, quads, self.S, NA, NB, ga, gb, *tabs,
                                                      qstate=self.qstate) or []))
-        return {pid: out[pid] if pid in out else self._separate(pid) for pid in pids}
+        res = {pid: out[pid] if pid in out else self._separate(pid) for pid in pids}
+        if self.draws > 1:
+            self._exceed(pids, res)
+        return res
+
+    @property
+    def null_pool(self):
+        """M, the size of the pooled null of the last exceedance pass: draws x the non-quiescent bins (synchronises)."""
+        return 0 if self._null_kept is None else self.draws * int(self._null_kept.item())
+
+    def _group_scores(self, H, n, N):
+        """Scores of one group's histograms: its width n; S2 keeps the permutation count of the ORIGINAL group of width N (quirk
+        Q9: the null halves, scores.py:397-398,418-421)."""
+        if self.sal == 1:
+            return self._score_s1(H, n)
+        return self.eng.score_s2_from_binhist(H, max(n, N), self.S, self.q, perms=N * (N - 1))[0]
+
+    def _null_dist(self, HnA, HnB):
+        """The null distances of a part from its null groups' histograms, by the separate passes."""
+        ga, gb = _null_widths(self.NA, self.NB, self.groupSize)
+        return self.eng.pair_finish(self._group_scores(HnA, ga, self.NA), self._group_scores(HnB, gb, self.NB))[1]
+
+    def _exceed(self, pids, res):
+        """K = self.draws null draws per bin: res[pid]["exceed"][b] = #{x in pool : x >= |rdist[b]|}, int64, where the pool holds
+        |null_k[b']| of every draw k (seed helpers.null_draw_seeds(seed, K)[k]: draw 0 is the run's own null) and every
+        non-quiescent bin b' of the parts `pids` -- all the parts the session holds.  Runs once their real results exist.
+        The draws go in chunks of whole draws whose buffers stay under null_chunk_bytes; every chunk is drawn (paired S1 of a
+        state model: ONE launch of epg_null_dist_draws_parts, no null histogram in HBM; otherwise seed by seed with the calls of
+        the K = 1 run), sorted once and counted into `exceed` (epg_null_exceed).  Quiescent bins are left out as NaN."""
+        from .helpers import null_draw_seeds
+        t, eng, S = self.torch, self.eng, self.S
+        for pid in pids:
+            res[pid]["exceed"] = t.zeros(res[pid]["rdist"].shape[0], dtype=t.int64, device=self.device)
+        live = [pid for pid in pids if self.parts[pid].HA.shape[0]]
+        self.null_chunks, self.null_fused = 0, None
+        self._null_kept = t.zeros((), dtype=t.int64, device=self.device)
+        if not live:
+            return
+        parts = [self.parts[pid] for pid in live]
+        rows = [p.HA.shape[0] for p in parts]
+        offs = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
+        Rtot = int(offs[-1])
+        masks = [res[pid]["quies"] for pid in live]
+        self._null_kept = Rtot - sum(m.sum(dtype=t.int64) for m in masks)
+        d = t.cat([res[pid]["rdist"] for pid in live])
+        exceed = t.zeros(Rtot, dtype=t.int64, device=self.device)
+        seeds = null_draw_seeds(self.seed, self.draws)
+        per = self.draws                                 # draws per chunk
+        while per > 1 and 4 * per * Rtot + eng.null_exceed_ws_bytes(per * Rtot) > self.null_chunk_bytes:
+            per -= 1
+        flat = t.empty(per * Rtot, dtype=t.float32, device=self.device)
+        ws = t.empty(eng.null_exceed_ws_bytes(per * Rtot), dtype=t.uint8, device=self.device)
+        NA, NB = self.NA, self.NB
+        ga, gb = _null_widths(NA, NB, self.groupSize)
+        nan = float("nan")
+        for k0 in range(0, self.draws, per):
+            ks = seeds[k0:k0 + per]
+            n = len(ks)
+            outs = [flat[n * int(a):n * int(a + r)].view(n, r) for a, r in zip(offs, rows)]
+            if self.null_fused is not False and self.sal == 1:
+                got = _unless_unsupported(eng.null_dist_draws_parts, [p.HA for p in parts], [p.HB for p in parts], [p.row0 for p in parts],
+                                          S, NA, NB, ga, gb, self._s1_table(ga), self._s1_table(gb), ks, masks=masks, outs=outs)
+                self.null_fused = got is not None
+            else:
+                self.null_fused = False
+            if not self.null_fused:
+                for j, seed in enumerate(ks):
+                    if k0 + j == 0:                      # the run's own null
+                        nulls = [res[pid]["null"] for pid in live]
+                    else:
+                        HnAs, HnBs = eng.null_hist_from_binhist_parts([p.HA for p in parts], [p.HB for p in parts], NA + NB, S, ga, gb,
+                                                                      int(seed), [p.row0 for p in parts])
+                        nulls = [self._null_dist(HnA, HnB) for HnA, HnB in zip(HnAs, HnBs)]
+                    for o, x, m in zip(outs, nulls, masks):
+                        o[j].copy_(x)
+                        o[j].masked_fill_(m.bool(), nan)
+            eng.null_exceed(flat[:n * Rtot], d, exceed, ws=ws)
+            self.null_chunks += 1
+        for pid, a, r in zip(live, offs, rows):
+            res[pid]["exceed"] = exceed[int(a):int(a) + r]
 
     def _separate(self, pid):
         """Scores of A, B and the two null groups, deltas, null distances, STEP 4's per-bin reduction and the quiescence mask
         of part `pid` from its resident histograms, one launch after another."""
-        eng, S, NA, NB, q = self.eng, self.S, self.NA, self.NB, self.q
+        eng, S, NA, NB = self.eng, self.S, self.NA, self.NB
         HA, HB = self.parts[pid].HA, self.parts[pid].HB
         if HA.shape[0] == 0:
             t, dv = self.torch, self.device
@@ -757,15 +847,9 @@ class _HipPairedSession(_HipSession):
                     "quies": t.empty(0, dtype=t.uint8, device=dv), "rdist": t.empty(0, dtype=t.float32, device=dv),
                     "mdiff": t.empty(0, dtype=t.int32, device=dv)}
         HnA, HnB = self._null_of(pid)                    # (drawn straight from the real groups' when the part was counted)
-        ga, gb = _null_widths(NA, NB, self.groupSize)
-        if self.sal == 1:
-            sA, sB, nA, nB = (self._score_s1(H, n) for H, n in ((HA, NA), (HB, NB), (HnA, ga), (HnB, gb)))
-        else:                                            # quirk Q9: null halves keep the original groups' permutation counts
-            sA, sB, nA, nB = (eng.score_s2_from_binhist(H, n, S, q, perms=p)[0] for H, n, p in
-                              ((HA, NA, NA * (NA - 1)), (HB, NB, NB * (NB - 1)), (HnA, max(ga, NA), NA * (NA - 1)),
-                               (HnB, max(gb, NB), NB * (NB - 1))))
+        sA, sB = self._group_scores(HA, NA, NA), self._group_scores(HB, NB, NB)
         delta, _ = eng.pair_finish(sA, sB, want_dist=False)
-        _, null = eng.pair_finish(nA, nB)
+        null = self._null_dist(HnA, HnB)
         rdist, mdiff = eng.pair_metrics(delta, roundtrip=True)     # what STEP 4 would recompute from the text
         quies = eng.quiescent_from_binhist(HA, NA, HB, NB, S, self.qstate)
         return {"delta": delta, "null": null, "quies": quies, "rdist": rdist, "mdiff": mdiff}
@@ -784,8 +868,11 @@ class _HipPairedSession(_HipSession):
             self._early.update(self._results([p for p, part in enumerate(self.parts) if part is not None]))
             self._settle()
         r = self._early.pop(pid)
-        return {"delta": r["delta"].cpu().numpy(), "null": r["null"].cpu().numpy(), "quies": r["quies"].cpu().numpy().astype(bool),
-                "rdist": r["rdist"].cpu().numpy(), "mdiff": r["mdiff"].cpu().numpy()}
+        out = {"delta": r["delta"].cpu().numpy(), "null": r["null"].cpu().numpy(), "quies": r["quies"].cpu().numpy().astype(bool),
+               "rdist": r["rdist"].cpu().numpy(), "mdiff": r["mdiff"].cpu().numpy()}
+        if "exceed" in r:                                # (--null-draws K > 1 only)
+            out["exceed"] = r["exceed"].cpu().numpy()
+        return out
 
 
 def get():

@@ -6,6 +6,8 @@
 // permutation.  Randomness: Philox4x32-10 keyed by the seed, counter = (global row, group, column block) -- the result
 // depends only on (seed, row0 + row), never on the launch geometry or on which GPU owns the row.  gfx950 only.
 #include "epg_count.h"
+#include "epg_pairdist.h"
+#include "epilogos_nulldraws.h"
 
 #include <string.h>
 
@@ -868,6 +870,175 @@ extern "C" int epg_null_hist(const int8_t* XA, int32_t NA, int64_t ldxa, const i
     hipLaunchKernelGGL(k_null_hist, dim3((unsigned)((R + 255) / 256)), dim3(256), shmem, st, reinterpret_cast<const char*>(XA), NA,
                        (long)ldxa, reinterpret_cast<const char*>(XB), NB, (long)ldxb, (long)R, S, ga, gb, (u64)seed, (long)row0, HA, HB);
     EPG_LAUNCH_CHECK("k_null_hist");
+    return EPG_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// K null draws per bin, straight to null DISTANCES (include/epilogos_nulldraws.h).  Per draw the two-call form
+// (epg_null_hist_from_binhist_parts, then epg_pair_scores_s1_parts) writes both null groups' histograms to HBM, reads them back
+// next to the real groups' and scores the real groups again.  Here a wave stages its tile's rows once and loops over the seeds:
+// every draw runs the same sampler on NhRng(seeds[k], row key) -- the same groups -- gathers the two null tables from LDS, forms
+// the distance with k_pair_fused_s1's own code (epg_pairdist.h) and stores ONE float per row: no null histogram leaves the CU.
+//
+// What a wave keeps of a row is h = hA + hB: the draws depend on the row's two histograms only through their sum (the law above;
+// both samplers start by forming it), so a draw restores (pa, pb) = (h, 0).  LDS of a block: the two tables ([ga + 1, S] and
+// [gb + 1, S] float32: 52 KB for 379 + 342 biosamples of 18 states), then per wave 64 rows of h, pa and pb (384 S bytes) and the
+// lanes' bit strings (256 NW bytes each): 12.5 KB at the flagship, so eight waves -- two per SIMD -- share a CU with the tables;
+// small tables leave room for sixteen.  The sampler is VALU-bound, the tables are what costs occupancy: a block takes as many
+// waves as fit and one block runs per CU.  Fewer than four waves: EPG_ERR_UNSUPPORTED, the caller loops over the two calls.
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int ND_MAXP = 32, ND_MAXK = 32, ND_WAVES_MAX = 16, ND_WAVES_MIN = 4;
+struct NdParts {
+    const u16* ha[ND_MAXP];
+    const u16* hb[ND_MAXP];
+    const unsigned char* mask[ND_MAXP];    // NULL: every row of the part is drawn
+    float* out[ND_MAXP];                   // [K, rows]: row k0 + k of this launch's seeds at out + k * rows
+    long rows[ND_MAXP];
+    long key[ND_MAXP];
+    long t0[ND_MAXP + 1];                  // first tile (64 rows) of every part, and their total
+    int n;
+};
+struct NdSeeds {
+    u64 seed[ND_MAXK];
+    int n;
+};
+
+template <int MODE>
+__global__ __launch_bounds__(64 * ND_WAVES_MAX) void k_null_dist_draws(const NdParts pt, const NdSeeds sd, int S, int n_cols, int ga, int gb,
+                                                                        const float* __restrict__ TnA, const float* __restrict__ TnB, int NW) {
+#pragma clang fp contract(off)   // (k_pair_fused_s1: numpy squares, rounds, then adds)
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int entA = (ga + 1) * S, entB = (gb + 1) * S;
+    float* tnA = reinterpret_cast<float*>(smem);
+    float* tnB = tnA + entA;
+    for (int e = threadIdx.x; e < entA; e += blockDim.x) tnA[e] = TnA[e];
+    for (int e = threadIdx.x; e < entB; e += blockDim.x) tnB[e] = TnB[e];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwaves = blockDim.x >> 6;
+    const int rowb = 2 * S;
+    const size_t tab_bytes = ((size_t)(entA + entB) * 4 + 15) & ~(size_t)15;
+    const size_t per_wave = (size_t)3 * 64 * rowb + (size_t)MODE * NW * 256;
+    char* sh = smem + tab_bytes + (size_t)wave * per_wave;        // the wave's 64 rows of hA + hB
+    char* sa = sh + 64 * rowb;                                    // staged hA, then the A group's counts of a draw
+    char* sb = sa + 64 * rowb;
+    [[maybe_unused]] u32* bitsA = nullptr;
+    [[maybe_unused]] u32* bitsB = nullptr;
+    if constexpr (MODE != NH_SEQ) {
+        bitsA = reinterpret_cast<u32*>(sb + 64 * rowb) + lane;
+        bitsB = bitsA + NW * 64;
+    }
+    const long ntiles = pt.t0[pt.n];
+    PartCursor at;
+    for (long tile = (long)blockIdx.x * nwaves + wave; tile < ntiles; tile += (long)gridDim.x * nwaves) {
+        const long r0 = at.advance(pt.t0, tile, 64);
+        const long R = pt.rows[at.part];
+        const int rows = (int)(R - r0 < 64 ? R - r0 : 64);
+        nh_stage_in(sa, reinterpret_cast<const char*>(pt.ha[at.part] + r0 * S), rows * rowb, lane);
+        nh_stage_in(sb, reinterpret_cast<const char*>(pt.hb[at.part] + r0 * S), rows * rowb, lane);
+        __builtin_amdgcn_wave_barrier();
+        u16* ph = reinterpret_cast<u16*>(sh + lane * rowb);
+        u16* pa = reinterpret_cast<u16*>(sa + lane * rowb);
+        u16* pb = reinterpret_cast<u16*>(sb + lane * rowb);
+        const unsigned char* mask = pt.mask[at.part];
+        const bool live = lane < rows;
+        const bool skip = live && mask && mask[r0 + lane];
+        if (live)
+            for (int s = 0; s < S; ++s) ph[s] = (u16)((u32)pa[s] + pb[s]);
+        float* out = pt.out[at.part] + r0 + lane;
+        const u64 key = (u64)(pt.key[at.part] + r0 + lane);
+        for (int k = 0; k < sd.n; ++k) {
+            if (live) {
+                float v = __builtin_nanf("");                     // a masked row: no distance (epg_null_exceed leaves NaN out)
+                if (!skip) {
+                    for (int s = 0; s < S; ++s) { pa[s] = ph[s]; pb[s] = 0; }
+                    NhRng rng(sd.seed[k], key);
+                    if constexpr (MODE == NH_SEQ) nh_sample_row_seq(pa, pb, S, n_cols, ga, gb, rng);
+                    else nh_sample_row<MODE == NH_TWO>(pa, pb, bitsA, bitsB, S, n_cols, ga, gb, rng);
+                    // a score = the table entry of (count, state); count 0 scores 0 (k_pair_fused_s1)
+                    auto sc = [S](const float* t, u32 c, int s) { return c ? t[(long)c * S + s] : 0.0f; };
+                    auto nd = [&](int s) { return sc(tnA, pa[s], s) - sc(tnB, pb[s], s); };
+                    v = null_dist_pairwise(S, nd);
+                }
+                out[(long)k * R] = v;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// strings per row of the draws kernel (NH_ONE / NH_TWO, NH_SEQ when a test forces it), or -1: the row is too wide for them
+static int nd_mode(int n_cols, int ga, int gb) {
+    const int NW = (n_cols + 31) / 32;
+    const int strings = ga + gb == n_cols ? 1 : 2;
+    if ((size_t)strings * NW * 256 > 24 * 1024) return -1;
+    return g_force[FORCE_NULL_SEQ] ? NH_SEQ : strings;
+}
+
+// waves per block that fit next to the tables, 0: not even ND_WAVES_MIN
+static int nd_waves(int mode, int S, int n_cols, int ga, int gb, size_t* shmem) {
+    const size_t tab = ((size_t)(ga + 1 + gb + 1) * S * 4 + 15) & ~(size_t)15;
+    const size_t per_wave = (size_t)3 * 64 * 2 * S + (size_t)mode * ((n_cols + 31) / 32) * 256;
+    if (tab + ND_WAVES_MIN * per_wave > 160 * 1024) return 0;
+    int waves = (int)((160 * 1024 - tab) / per_wave);
+    if (waves > ND_WAVES_MAX) waves = ND_WAVES_MAX;
+    *shmem = tab + (size_t)waves * per_wave;
+    return waves;
+}
+
+extern "C" int epg_null_dist_draws_parts(int32_t nparts, const uint16_t* const* HA, const uint16_t* const* HB, const int64_t* R,
+                                         const int64_t* row0, const uint8_t* const* mask, int32_t S, int32_t NA, int32_t NB, int32_t ga,
+                                         int32_t gb, const float* TnA, const float* TnB, const uint64_t* seeds, int32_t K, float* const* out,
+                                         void* stream) {
+    hipStream_t st = (hipStream_t)stream;
+    if (nparts < 0 || S < 1 || S > 127 || NA < 1 || NB < 1 || NA > 65535 || NB > 65535 || K < 1) return fail(EPG_ERR_INVALID_ARG, "null_dist_draws: bad shape");
+    const int n_cols = NA + NB;
+    if (ga < 1 || gb < 1 || (long)ga + gb > n_cols)
+        return fail(EPG_ERR_INVALID_ARG, "null_dist_draws: group sizes %d + %d do not fit the %d columns", ga, gb, n_cols);
+    if (S > 31) return fail(EPG_ERR_UNSUPPORTED, "null_dist_draws: S=%d, the kernel takes at most 31 states", S);
+    const int mode = nd_mode(n_cols, ga, gb);
+    if (mode < 0) return fail(EPG_ERR_UNSUPPORTED, "null_dist_draws: rows of %d columns are beyond the bit-string sampler", n_cols);
+    size_t shmem = 0;
+    const int waves = nd_waves(mode, S, n_cols, ga, gb, &shmem);
+    if (!waves)
+        return fail(EPG_ERR_UNSUPPORTED, "null_dist_draws: the tables of null groups of %d / %d columns leave no room for %d waves in LDS", ga, gb,
+                    ND_WAVES_MIN);
+    if (!seeds || !TnA || !TnB) return fail(EPG_ERR_INVALID_ARG, "null_dist_draws: NULL argument");
+    if (nparts && (!HA || !HB || !R || !row0 || !out)) return fail(EPG_ERR_INVALID_ARG, "null_dist_draws: NULL argument array");
+    for (int p = 0; p < nparts; ++p) {
+        if (R[p] < 0) return fail(EPG_ERR_INVALID_ARG, "null_dist_draws: part %d has %lld rows", p, (long long)R[p]);
+        if (R[p] == 0) continue;
+        if (!HA[p] || !HB[p] || !out[p]) return fail(EPG_ERR_INVALID_ARG, "null_dist_draws: NULL argument in part %d", p);
+        if ((reinterpret_cast<uintptr_t>(HA[p]) | reinterpret_cast<uintptr_t>(HB[p])) & 15)
+            return fail(EPG_ERR_INVALID_ARG, "null_dist_draws: histogram arrays must be 16-byte aligned (part %d)", p);
+        if (reinterpret_cast<uintptr_t>(out[p]) & 3) return fail(EPG_ERR_INVALID_ARG, "null_dist_draws: out of part %d is not aligned", p);
+    }
+    const int NW = (n_cols + 31) / 32;
+    for (int k0 = 0; k0 < K; k0 += ND_MAXK) {                     // ND_MAXK seeds and ND_MAXP parts per launch: they travel in the argument
+        NdSeeds sd;
+        memset(&sd, 0, sizeof(sd));
+        sd.n = K - k0 < ND_MAXK ? K - k0 : ND_MAXK;
+        for (int k = 0; k < sd.n; ++k) sd.seed[k] = (u64)seeds[k0 + k];
+        for (int p0 = 0; p0 < nparts;) {
+            NdParts pt;
+            p0 = pack_parts(pt, p0, nparts, R, 64, [&](int k, int p) {
+                pt.ha[k] = HA[p]; pt.hb[k] = HB[p]; pt.mask[k] = mask ? mask[p] : nullptr;
+                pt.out[k] = out[p] + (long)k0 * R[p];
+                pt.key[k] = row0[p];
+            });
+            if (pt.n == 0) break;
+            long blocks = (pt.t0[pt.n] + waves - 1) / waves;
+            if (blocks > num_cus()) blocks = num_cus();
+            const int rc = with_constant<NH_SEQ, NH_ONE, NH_TWO>(mode, [&](auto MODE) {
+                static DynLds lds_attr;                           // (one per instantiation)
+                EPG_HIP(ensure_dyn_lds(lds_attr, reinterpret_cast<const void*>(k_null_dist_draws<decltype(MODE)::value>), 160 * 1024));
+                hipLaunchKernelGGL(k_null_dist_draws<decltype(MODE)::value>, dim3((unsigned)blocks), dim3(64 * waves), shmem, st, pt, sd, S, n_cols,
+                                   ga, gb, TnA, TnB, NW);
+                return EPG_OK;
+            });
+            if (rc) return rc;
+            EPG_LAUNCH_CHECK("k_null_dist_draws");
+        }
+    }
     return EPG_OK;
 }
 

@@ -1,5 +1,6 @@
 // S2 path (state-pair saliency) from cached per-bin histograms, plus the paired-mode extras.  gfx950 only.
 #include "epg_common.h"
+#include "epg_pairdist.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -420,15 +421,7 @@ __device__ __forceinline__ void load_staged(char* lds, const char* src, int nbyt
     if ((nbytes & 2) && lane == 0) *reinterpret_cast<u16*>(lds + nbytes - 2) = *reinterpret_cast<const u16*>(src + nbytes - 2);
 }
 
-// d * d as numpy computes it -- rounded to float32 BEFORE it is added.  `__fmul_rn` + `__fadd_rn` are ordinary multiplies and adds to
-// the optimiser (hipcc's default -ffp-contract=fast comes with the header they are inlined from, not with this function's pragma):
-// in the loops unrolled for a compile-time S it fused them into v_fma_f32 and STEP 4's distance lost its last bit.  The empty asm is
-// opaque: the product exists as a register value before anything can be added to it.
-__device__ __forceinline__ float sq_nofma(float d) {
-    float p = d * d;
-    asm volatile("" : "+v"(p));
-    return p;
-}
+// (sq_nofma: d * d rounded to float32 before it is added, epg_pairdist.h)
 
 // One lane per row, rows handed over through LDS: a wave's 64 rows of a and b are 64*S contiguous floats each, fetched with
 // whole-line loads (a lane reading its own 72-byte row straight from memory made every load instruction touch 64 lines:
@@ -706,42 +699,7 @@ __global__ __launch_bounds__(64 * PF_WAVES_MAX) __attribute__((amdgpu_waves_per_
             maxdiff[row0 + lane] = arg;
             // the null distance: numpy's pairwise order over nd = nullA - nullB (k_pair_finish)
             auto nd = [&](int s) { return sc(tnA, hna[s], s) - sc(tnB, hnb[s], s); };
-            float nsd, nsq;
-            if (S < 8) {
-                nsd = 0.f;
-                nsq = 0.f;
-                for (int s = 0; s < S; ++s) {
-                    const float d = nd(s);
-                    nsd += d;
-                    nsq += sq_nofma(d);
-                }
-            } else {
-                float rd[8], rq[8];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const float d = nd(k);
-                    rd[k] = d;
-                    rq[k] = sq_nofma(d);
-                }
-                int i = 8;
-                for (; i < S - (S % 8); i += 8) {
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) {
-                        const float d = nd(i + k);
-                        rd[k] += d;
-                        rq[k] += sq_nofma(d);
-                    }
-                }
-                nsd = ((rd[0] + rd[1]) + (rd[2] + rd[3])) + ((rd[4] + rd[5]) + (rd[6] + rd[7]));
-                nsq = ((rq[0] + rq[1]) + (rq[2] + rq[3])) + ((rq[4] + rq[5]) + (rq[6] + rq[7]));
-                for (; i < S; ++i) {
-                    const float d = nd(i);
-                    nsd += d;
-                    nsq += sq_nofma(d);
-                }
-            }
-            const float nsg = nsd > 0.f ? 1.f : (nsd < 0.f ? -1.f : nsd);
-            ndist[row0 + lane] = nsq * nsg;
+            ndist[row0 + lane] = null_dist_pairwise(S, nd);
         }
         __builtin_amdgcn_wave_barrier();
         store_staged_nt(sD, reinterpret_cast<char*>(delta + row0 * S), rows * rowb, lane);

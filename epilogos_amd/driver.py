@@ -538,12 +538,21 @@ class _Paired:
     n_payload = 4
     n_widths = 2                                       # NA, NB
 
-    def __init__(self, files1, files2, numStates, saliency, quiescentState, groupSize, nullSeed, keep_temps):
+    def __init__(self, files1, files2, numStates, saliency, quiescentState, groupSize, nullSeed, keep_temps, nullDraws=1):
         self.groups, self.S, self.sal, self.keep_temps = (files1, files2), numStates, saliency, keep_temps
         self.qstate, self.groupSize, self.seed = quiescentState, groupSize, nullSeed
         self.halves = {}                               # part index -> its group that arrived first
+        # --null-draws K > 1: a part also carries its exceedance counts against the pooled null of K draws per bin, and the
+        # session knows the pool's size (one rank: the counts are additive over ranks, which nothing adds up yet)
+        self.draws, self.pool = int(nullDraws), None
+        if self.draws > 1:
+            self.n_payload = 5
 
     def open(self, be):
+        if self.draws > 1:
+            if _Dist().world > 1:
+                raise ValueError("more than one null draw per bin is not available on several ranks")
+            return be.open_paired(self.S, self.sal, self.qstate, self.groupSize, self.seed, draws=self.draws)
         return be.open_paired(self.S, self.sal, self.qstate, self.groupSize, self.seed)
 
     def see_width(self, widths, g, n):
@@ -568,11 +577,22 @@ class _Paired:
 
     def part_out(self, sess, pid):
         res = sess.results(pid)
-        return res["delta"], [np.asarray(res["null"], dtype=np.float32), np.asarray(res["quies"], dtype=np.bool_),
-                              np.asarray(res["rdist"], dtype=np.float32), np.asarray(res["mdiff"], dtype=np.int32)]
+        arrays = [np.asarray(res["null"], dtype=np.float32), np.asarray(res["quies"], dtype=np.bool_),
+                  np.asarray(res["rdist"], dtype=np.float32), np.asarray(res["mdiff"], dtype=np.int32)]
+        if self.draws > 1:
+            arrays.append(np.asarray(res["exceed"], dtype=np.int64))
+            self.pool = int(sess.null_pool)
+        return res["delta"], arrays
 
     def result(self, temp, chrName, loc, arrays):
         null, quies, dist, mdiff = (_cat(a, np.zeros(0, dtype=t)).astype(t) for a, t in zip(arrays, (np.float32, bool, np.float32, np.int32)))
+        extra = {}
+        if self.draws > 1:
+            # the pool is the whole run's (every file's bins, K draws each): the same number in every file's entry
+            extra = {"nullExceed": _cat(arrays[4], np.zeros(0, dtype=np.int64)).astype(np.int64), "nullPool": int(self.pool or 0)}
+            if self.keep_temps:
+                np.savez_compressed(temp("nullExceed"), chrName=np.array([chrName]), nullExceed=extra["nullExceed"],
+                                    nullPool=np.array([extra["nullPool"]], dtype=np.int64))
         if self.keep_temps:
             np.savez_compressed(temp("nullDistances"), chrName=np.array([chrName]), nullDistances=null)
             np.savez_compressed(temp("quiescence"), chrName=np.array([chrName]), quiescenceArr=quies)
@@ -580,7 +600,8 @@ class _Paired:
             # from the pairwiseDelta text, already computed on the GPU; removed with the other temps
             starts, ends = loc.start_end()
             np.savez_compressed(temp("pairMetrics"), chrName=np.array([chrName]), distances=dist, maxDiff=mdiff, starts=starts, ends=ends)
-        return {"chrName": chrName, "locations": loc, "nullDistances": null, "quiescenceArr": quies, "distances": dist, "maxDiff": mdiff}
+        return {"chrName": chrName, "locations": loc, "nullDistances": null, "quiescenceArr": quies, "distances": dist, "maxDiff": mdiff,
+                **extra}
 
 
 class _PairedColumns(_Paired):
@@ -588,8 +609,8 @@ class _PairedColumns(_Paired):
     feeds both groups (session add_columns).  Outputs, payloads and rank 0's results are paired mode's."""
     upload_note = ""
 
-    def __init__(self, files, colsA, colsB, numStates, saliency, quiescentState, groupSize, nullSeed, keep_temps):
-        super().__init__(files, (), numStates, saliency, quiescentState, groupSize, nullSeed, keep_temps)
+    def __init__(self, files, colsA, colsB, numStates, saliency, quiescentState, groupSize, nullSeed, keep_temps, nullDraws=1):
+        super().__init__(files, (), numStates, saliency, quiescentState, groupSize, nullSeed, keep_temps, nullDraws)
         self.groups = (files,)
         self.colsA, self.colsB = np.ascontiguousarray(colsA, dtype=np.int64), np.ascontiguousarray(colsB, dtype=np.int64)
 
@@ -727,7 +748,7 @@ def run_single_group(files, numStates, saliency, outputDir, fileTag, verbose=Fal
 
 
 def run_paired_groups(files1, files2, numStates, saliency, outputDir, fileTag, quiescentState, groupSize, nullSeed,
-                      verbose=False, backend=None, device=None, keep_temps=True, defer_writes=False):
+                      verbose=False, backend=None, device=None, keep_temps=True, defer_writes=False, nullDraws=1):
     """STEP 1-3 of paired mode (reference run.py:205-221,258-279 + scores.py:172-256) over the bin-range partition.
     Background counts are taken over the column concatenation [A|B] (helpers.py:173) -- from the two groups' own
     histograms, each group is uploaded once -- all-reduced once; each rank then scores A, B and the two shuffled null
@@ -735,16 +756,20 @@ def run_paired_groups(files1, files2, numStates, saliency, outputDir, fileTag, q
     (shuffle_key), so the outputs do not depend on the number of GPUs.  Returns (exp_freq, results); results (rank 0) maps file stem ->
     dict(chrName, locations, nullDistances, quiescenceArr, distances, maxDiff) for an in-process STEP 4; keep_temps
     also writes temp_nullDistances / temp_quiescence (the reference's, scores.py:246-255) and temp_pairMetrics (the
-    side-car of this engine's STEP 4)."""
+    side-car of this engine's STEP 4).  nullDraws K > 1 (one rank): every bin's null groups are drawn K times (seeds
+    helpers.null_draw_seeds(nullSeed, K): draw 0 is the run's own null, every other output is unchanged) and every file's entry
+    also has nullExceed (int64 per bin: how many of the pooled null distances of the non-quiescent bins reach |distance|) and
+    nullPool (their number), from which STEP 4 takes empirical p-values; keep_temps writes them as temp_nullExceed."""
     mode = _Paired([Path(f) for f in files1], [Path(f) for f in files2], numStates, saliency, quiescentState, groupSize, nullSeed,
-                   keep_temps)
+                   keep_temps, nullDraws)
     return _run_groups(mode, outputDir, fileTag, backend, defer_writes)
 
 
 def run_paired_columns(files, colsA, colsB, numStates, saliency, outputDir, fileTag, quiescentState, groupSize, nullSeed,
-                       verbose=False, backend=None, device=None, keep_temps=True, defer_writes=False):
+                       verbose=False, backend=None, device=None, keep_temps=True, defer_writes=False, nullDraws=1):
     """run_paired_groups for two groups that are column groups (0-based indices) of ONE set of files: every file is parsed and
     uploaded once and feeds both groups.  The partition, the hand-over between ranks and the all-reduce are run_paired_groups':
     they move histograms and row ranges.  Outputs are those of run_paired_groups on files cut to the groups beforehand."""
-    mode = _PairedColumns([Path(f) for f in files], colsA, colsB, numStates, saliency, quiescentState, groupSize, nullSeed, keep_temps)
+    mode = _PairedColumns([Path(f) for f in files], colsA, colsB, numStates, saliency, quiescentState, groupSize, nullSeed, keep_temps,
+                          nullDraws)
     return _run_groups(mode, outputDir, fileTag, backend, defer_writes)

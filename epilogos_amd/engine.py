@@ -497,6 +497,40 @@ def null_hist_from_binhist_parts(HAs, HBs, n_cols, S, ga, gb, seed, row0s, strea
     return OAs, OBs
 
 
+def null_dist_draws_parts(HAs, HBs, row0s, S, NA, NB, ga, gb, TnA, TnB, seeds, masks=None, outs=None):
+    """K null distances per bin of several parts in one launch (epg_null_dist_draws_parts, include/epilogos_nulldraws.h):
+    -> list of float32 [K, R_p]; row k is the null distance that null_hist_from_binhist_parts with seeds[k] and
+    pair_scores_s1_parts give.  masks: uint8 [R_p] per part (or None): masked rows are not drawn and hold NaN.  outs: the
+    caller's [K, R_p] buffers.  Raises EpilogosHipError(-2) for shapes outside the kernel's: the two calls give the same."""
+    n = len(HAs)
+    seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+    K = int(seeds.size)
+    rows = [h.shape[0] for h in HAs]
+    if outs is None:
+        dev = HAs[0].device if n else "cuda"
+        outs = [torch.empty((K, r), dtype=torch.float32, device=dev) for r in rows]
+    _abi.call("epg_null_dist_draws_parts", n, _ptr_array(HAs), _ptr_array(HBs), (C.c_int64 * n)(*rows),
+              (C.c_int64 * n)(*[int(r) for r in row0s]), _ptr_array(masks) if masks is not None else None, S, NA, NB, ga, gb, _ptr(TnA),
+              _ptr(TnB), seeds.ctypes.data_as(C.c_void_p), K, _ptr_array(outs), _stream())
+    return outs
+
+
+def null_exceed_ws_bytes(n):
+    return _abi.check(_abi.load().epg_null_exceed_ws_bytes(int(n)))
+
+
+def null_exceed(null, d, exceed, ws=None):
+    """exceed[b] += #{x in null : x is not NaN and |x| >= |d[b]|} (epg_null_exceed): null float32 [n] (any shape, contiguous), d
+    float32 [R], exceed int64 [R], accumulated into.  ws: uint8 workspace of null_exceed_ws_bytes(n) bytes (None: allocated)."""
+    n, R = null.numel(), d.numel()
+    if n == 0 or R == 0:
+        return exceed
+    if ws is None:
+        ws = torch.empty(null_exceed_ws_bytes(n), dtype=torch.uint8, device=null.device)
+    _abi.call("epg_null_exceed", _ptr(null), n, _ptr(d), R, _ptr(exceed), _ptr(ws), ws.numel(), _stream())
+    return exceed
+
+
 def pair_count_null_parts(XAs, XBs, NA, NB, S, seed, row0s, counts=None):
     """Paired mode, default group sizes: count pass of both groups and the null draw of several resident parts in ONE launch
     (epg_pair_count_null_parts).  -> (HAs, HBs, OAs, OBs) lists of [R_p, S] histograms (real groups, null groups).  Raises

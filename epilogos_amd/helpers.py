@@ -43,6 +43,23 @@ def splitRows(totalRows, numProcesses):
     return [(i * totalRows // numProcesses, (i + 1) * totalRows // numProcesses) for i in range(numProcesses)]
 
 
+def null_draw_seeds(seed, K):
+    """The seeds of the K null draws per bin of a paired run (--null-draws K), uint64 [K].  Entry 0 is `seed` itself: draw 0 is
+    the null a run without the option draws.  Entry k >= 1 is splitmix64's output k for the state `seed`, all arithmetic mod
+    2^64: z = seed + k * 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+    z ^= z >> 31."""
+    m = (1 << 64) - 1
+    out = np.empty(int(K), dtype=np.uint64)
+    for k in range(int(K)):
+        z = (int(seed) + k * 0x9E3779B97F4A7C15) & m
+        if k:
+            z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & m
+            z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
+            z ^= z >> 31
+        out[k] = z
+    return out
+
+
 def splitGpusOption(argv):
     """`--gpus N` / `--gpus=N`, anywhere in an argument list -> (N as written, the last one given; None when there is none;
     "" for a trailing `--gpus` without a value) and the list without them.  Shared by the `epilogos` and simsearch command

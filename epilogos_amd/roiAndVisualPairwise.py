@@ -101,12 +101,24 @@ def fitDistances(outputDirPath, numProcesses, numTrials, samplingSize):
     return _fitParams(distanceArrNull, quiescenceArr, numProcesses, numTrials, samplingSize), distanceArrNull, nonQuiescentIdx
 
 
+def empiricalPVals(exceed, pool):
+    """p = (1 + exceed) / (1 + M) in float64: the empirical p-value of a real distance that `exceed` of the M pooled null
+    distances reach (--null-draws K > 1: M = K x non-quiescent bins).  The smallest attainable value is 1 / (1 + M)."""
+    return (1.0 + np.asarray(exceed, dtype=np.float64)) / (1.0 + float(pool))
+
+
 def readInData(outputDirPath, numStates, backend=None):
     """locationArr int64 [R,3] (chromosome number, start, end), signed squared distances float32 [R], 1-based
     largest-difference state int32 [R] and {number: chromosome}, sorted by location (reference :273-356)."""
+    return _readInData(outputDirPath, numStates, backend)[:4]
+
+
+def _readInData(outputDirPath, numStates, backend=None):
+    """readInData, and as a fifth value the empirical p-values of the bins in the same order when every file has its
+    temp_nullExceed_* side-car (a run with more than one null draw per bin), else None."""
     be = backend if backend is not None else _backend.get()
     deltas = sorted(outputDirPath.glob("pairwiseDelta_*.txt.gz"))
-    chunks = {}
+    chunks, exceed = {}, {}
     for f in deltas:
         tail = f.name[len("pairwiseDelta_"):-len(".txt.gz")]
         side = outputDirPath / "temp_pairMetrics_{}.npz".format(tail)
@@ -121,6 +133,10 @@ def readInData(outputDirPath, numStates, backend=None):
             part = (df.iloc[:, 0].to_numpy(dtype=object), df.iloc[:, 1].to_numpy(dtype=np.int64),
                     df.iloc[:, 2].to_numpy(dtype=np.int64), dist, maxdiff)
         chunks[f] = part
+        exc = outputDirPath / "temp_nullExceed_{}.npz".format(tail)
+        if exc.exists():
+            z = np.load(exc)
+            exceed[f] = (z["nullExceed"], int(z["nullPool"][0]))
     chrom = np.concatenate([c[0] for c in chunks.values()]) if chunks else np.zeros(0, dtype=object)
     chrOrder = orderChromosomes(pd.unique(chrom))
     number = {c: i + 1 for i, c in enumerate(chrOrder)}
@@ -132,9 +148,12 @@ def readInData(outputDirPath, numStates, backend=None):
     maxdiff = np.concatenate([c[4] for c in chunks.values()]).astype(np.int32)
     order = np.lexsort((ends, starts, chrNum))                      # sort_values(by=[chr, binStart, binEnd]) :332
     locationArr = np.stack([chrNum[order], starts[order], ends[order]], axis=1)
+    pvals = None
+    if chunks and len(exceed) == len(chunks):
+        pvals = empiricalPVals(np.concatenate([exceed[f][0] for f in chunks]), max(m for _e, m in exceed.values()))[order]
     for file in outputDirPath.glob("temp_*.npz"):
         remove(file)
-    return locationArr, dist[order], maxdiff[order], chrDict
+    return locationArr, dist[order], maxdiff[order], chrDict, pvals
 
 
 def _pvals_chunk(x, beta, loc, scale):
@@ -287,14 +306,14 @@ def _fitParams(distanceArrNull, quiescenceArr, numProcesses, numTrials, sampling
 
 
 def _finish(params, locationArr, distanceArrReal, maxDiffArr, chrDict, stateInfo, outputDirPath, fileTag, pvalBool, roiWidth,
-            expFreqPath, verbose):
-    """Everything of main() after the inputs are in memory (reference :72-169 without the figures)."""
+            expFreqPath, verbose, empirical=None):
+    """Everything of main() after the inputs are in memory (reference :72-169 without the figures).  empirical: the bins'
+    empirical p-values (empiricalPVals); they take the place of the fitted distribution's and `params` is not used."""
     stateNameList = getStateNames(stateInfo)
     roiPath = outputDirPath / "regionsOfInterest_{}.txt".format(fileTag)
     if pvalBool:
-        beta, loc, scale = params[0], params[-2], params[-1]
         t0 = _stage(verbose, "Calculating p-vals")
-        pvals = calculatePVals(distanceArrReal, beta, loc, scale)
+        pvals = empirical if empirical is not None else calculatePVals(distanceArrReal, params[0], params[-2], params[-1])
         _done(verbose, t0)
         t0 = _stage(verbose, "Benjamini-Hochberg procedure")
         mhPvals = benjaminiHochberg(pvals)
@@ -342,8 +361,11 @@ def mainFromArrays(results, stateInfo, outputDir, fileTag, numProcesses, pvalBoo
     byChr = {v["chrName"]: v for v in results.values()}
     chrOrder = orderChromosomes(list(byChr))
     cat = lambda key: np.concatenate([byChr[c][key] for c in chrOrder])
-    params = None
-    if pvalBool:
+    params = empirical = None
+    if pvalBool and byChr and all("nullExceed" in v for v in byChr.values()):
+        # more than one null draw per bin: empirical p-values against the pooled null, no fit
+        empirical = empiricalPVals(cat("nullExceed"), max(int(v["nullPool"]) for v in byChr.values()))
+    elif pvalBool:
         t0 = _stage(verbose, "Fitting distances")
         params = _fitParams(cat("nullDistances"), cat("quiescenceArr"), numProcesses, numTrials, samplingSize)
         _done(verbose, t0)
@@ -360,7 +382,9 @@ def mainFromArrays(results, stateInfo, outputDir, fileTag, numProcesses, pvalBoo
         order = np.lexsort((ends, starts, chrNum))
         locationArr = np.stack([chrNum[order], starts[order], ends[order]], axis=1)
         dist, maxdiff = dist[order], maxdiff[order]
-    _finish(params, locationArr, dist, maxdiff, chrDict, stateInfo, outputDirPath, fileTag, pvalBool, roiWidth, expFreqPath, verbose)
+        empirical = empirical[order] if empirical is not None else None
+    _finish(params, locationArr, dist, maxdiff, chrDict, stateInfo, outputDirPath, fileTag, pvalBool, roiWidth, expFreqPath, verbose,
+            empirical=empirical)
 
 
 def main(group1Name, group2Name, stateInfo, outputDir, fileTag, numProcesses, pvalBool, diagnosticBool, numTrials,
@@ -371,15 +395,19 @@ def main(group1Name, group2Name, stateInfo, outputDir, fileTag, numProcesses, pv
     if numProcesses == 0:
         numProcesses = cpu_count()
     params = None
-    if pvalBool:
+    # temp_nullExceed_* next to the other temporaries (a run with more than one null draw per bin): empirical p-values, no fit
+    empiricalRun = pvalBool and any(outputDirPath.glob("temp_nullExceed_*.npz"))
+    if pvalBool and not empiricalRun:
         t0 = _stage(verbose, "Fitting distances")
         params, _, _ = fitDistances(outputDirPath, numProcesses, numTrials, samplingSize)
         _done(verbose, t0)
     t0 = _stage(verbose, "Reading in files")
-    locationArr, distanceArrReal, maxDiffArr, chrDict = readInData(outputDirPath, numStates, backend)
+    locationArr, distanceArrReal, maxDiffArr, chrDict, empirical = _readInData(outputDirPath, numStates, backend)
     _done(verbose, t0)
+    if empiricalRun and empirical is None:
+        raise ValueError("temp_nullExceed_*.npz is missing for some of the pairwiseDelta files in {}".format(outputDirPath))
     _finish(params, locationArr, distanceArrReal, maxDiffArr, chrDict, stateInfo, outputDirPath, fileTag, pvalBool, roiWidth,
-            expFreqPath, verbose)
+            expFreqPath, verbose, empirical=empirical if empiricalRun else None)
     if verbose: print("Total Time:", time() - tTotal, flush=True)
 
 

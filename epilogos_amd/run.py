@@ -151,9 +151,9 @@ def _init_device_and_group(world, under_launcher):
 @click.option("-x", "--exit", "exitBool", is_flag=True, help="SLURM-only flag; accepted and ignored")
 @click.option("-d", "--diagnostic-figures", "diagnosticBool", is_flag=True, help="Figures are not produced; accepted and ignored")
 @click.option("-t", "--num-trials", "numTrials", type=int, default=101, show_default=True,
-              help="Number of gennorm fits of the null distances (paired mode with -n)")
+              help="Number of gennorm fits of the null distances (paired mode with -n); accepted and unused with --null-draws K > 1")
 @click.option("-z", "--sampling-size", "samplingSize", type=int, default=100000, show_default=True,
-              help="Size of the null sub-sample of each fit (paired mode with -n)")
+              help="Size of the null sub-sample of each fit (paired mode with -n); accepted and unused with --null-draws K > 1")
 @click.option("-q", "--quiescent-state", "quiescentState", type=int, default=-1,
               help="1-based quiescent state for paired filtering; 0 disables it [default: last state]")
 @click.option("-g", "--group-size", "groupSize", type=int, default=-1, show_default=True,
@@ -170,6 +170,10 @@ def _init_device_and_group(world, under_launcher):
 @click.option("--score-mem", "scoreMem", type=int, default=40000, help="SLURM-only; ignored")
 @click.option("--roi-mem", "roiMem", type=int, default=-1, help="SLURM-only; ignored")
 @click.option("--null-seed", "nullSeed", type=int, default=None, help="Seed for the paired-mode null shuffles (default: random)")
+@click.option("--null-draws", "nullDraws", type=int, default=1, show_default=True,
+              help="Paired mode with -n: draw every bin's null groups K times and report empirical p-values, "
+                   "(1 + #{pooled null distances >= |distance|}) / (1 + K x non-quiescent bins), instead of fitting a distribution "
+                   "(no fit: -t and -z are unused); one GPU only.  1: one draw and the fit")
 @click.option("--gpus", "gpus", type=int, default=1, show_default=True,
               help="GPUs of this node to split the genome over (0 = all visible); replaces the SLURM fan-out of the reference")
 @click.option("--cache-dir", "cacheDir", type=str, default=None,
@@ -181,11 +185,21 @@ def _init_device_and_group(world, under_launcher):
 @click.option("--columns-b", "columnsB", type=str, default=None, help="Paired mode with -i: the biosamples of group B")
 def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2, outputDirectory, stateInfo, saliency,
          numProcesses, exitBool, diagnosticBool, numTrials, samplingSize, quiescentState, groupSize, version, partition,
-         pvalBool, roiWidth, fileTag, expFreqMem, expCombMem, scoreMem, roiMem, nullSeed, gpus, cacheDir, columns, columnsA, columnsB):
+         pvalBool, roiWidth, fileTag, expFreqMem, expCombMem, scoreMem, roiMem, nullSeed, nullDraws, gpus, cacheDir, columns, columnsA, columnsB):
     """Information-theoretic navigation of multi-tissue functional genomic annotations -- MI355X scoring engine."""
     if version:
         print("Version:", __version__)
         sys.exit()
+    # --null-draws: its own combinations first, so that every command line without it gets today's messages
+    if nullDraws < 1:
+        print("ERROR: [--null-draws] must be at least 1"); sys.exit()
+    if nullDraws > 1 and mode != "paired":
+        print("ERROR: [--null-draws] greater than 1 is only valid in paired mode"); sys.exit()
+    if nullDraws > 1 and not pvalBool:
+        print("ERROR: [--null-draws] greater than 1 requires [-n, --null-distribution]"); sys.exit()
+    if nullDraws > 1 and (gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        print("ERROR: [--null-draws] greater than 1 runs on one GPU: the exceedance counts of several ranks are not added up yet; "
+              "use [--gpus 1]"); sys.exit()
     # column groups: the flag combinations that involve the new options come first, so that every combination without them
     # gets today's message
     pairedColumns = mode == "paired" and (columnsA is not None or columnsB is not None)
@@ -258,7 +272,7 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
         print("ERROR: Number of GPUs must be positive or zero (0 means use all visible GPUs)"); sys.exit()
     if "WORLD_SIZE" not in os.environ and gpus != 1:
         if gpus == 0:
-            gpus = _visible_gpus()
+            gpus = 1 if nullDraws > 1 else _visible_gpus()   # (--null-draws K > 1 runs on one GPU)
         if gpus > 1:
             sys.exit(_launch(gpus, sys.argv[1:] if _ARGV is None else _ARGV))
 
@@ -340,13 +354,15 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
         try:
             if pairedColumns:
                 _, results = run_paired_columns(files, colsA, colsB, numStates, saliency, outputDirPath, fileTag, quiescentState,
-                                                groupSize, nullSeed, verbose=False, device=device, keep_temps=False, defer_writes=True)
+                                                groupSize, nullSeed, verbose=False, device=device, keep_temps=False, defer_writes=True,
+                                                nullDraws=nullDraws)
             else:
                 _, results = run_paired_groups(files, files2, numStates, saliency, outputDirPath, fileTag, quiescentState, groupSize,
-                                               nullSeed, verbose=False, device=device, keep_temps=False, defer_writes=True)
+                                               nullSeed, verbose=False, device=device, keep_temps=False, defer_writes=True,
+                                               nullDraws=nullDraws)
         finally:
             driver.abort_early_readers()
-        if pvalBool and max(numProcesses, 1) > 1:
+        if pvalBool and max(numProcesses, 1) > 1 and nullDraws == 1:
             driver.finish_writes()                               # -n -c K forks a pool for the fits: not with writer threads running
         try:
             if rank == 0:
