@@ -1,5 +1,5 @@
-"""ctypes binding of include/epilogos_amd.h, include/epilogos_scores_text.h, include/epilogos_groups.h and
-include/epilogos_nulldraws.h.  No fallbacks: a missing library or symbol raises."""
+"""ctypes binding of include/epilogos_amd.h, include/epilogos_scores_text.h, include/epilogos_groups.h,
+include/epilogos_nulldraws.h and include/epilogos_statebyline.h.  No fallbacks: a missing library or symbol raises."""
 import ctypes as C
 import re
 from pathlib import Path
@@ -84,7 +84,22 @@ NULLDRAWS_PROTOTYPES = {
     "epg_null_exceed": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _i64, _p]),
 }
 
+# and for include/epilogos_statebyline.h, the reader of ChromHMM state-by-line calls (tests/test_statebyline_host.py checks it)
+SBL_HEADER = HEADER.with_name("epilogos_statebyline.h")
+SBL_PROTOTYPES = {
+    "epg_sbl_ws_bytes": (_i64, [_i64]),
+    "epg_sbl_constant": (_i32, [_i32]),
+    "epg_sbl_parse": (C.c_int, [_p, _i64, _p, _i64, _p, _p, _i64, _p]),
+    "epg_sbl_transpose": (C.c_int, [_p, _i32, _i64, _i64, _p, _i64, _i64, _p]),
+}
+
 _lib = None
+
+
+def sbl_header_symbols():
+    """Function names declared in include/epilogos_statebyline.h."""
+    txt = re.sub(r"/\*.*?\*/", "", SBL_HEADER.read_text(), flags=re.S)
+    return sorted(set(re.findall(r"\b(epg_[a-z0-9_]+)\s*\(", txt)))
 
 
 def text_header_symbols():
@@ -142,7 +157,7 @@ def load():
                                    "(there is no CPU fallback)" % path)
     lib = C.CDLL(str(path))
     for name, (res, args) in list(PROTOTYPES.items()) + list(TEXT_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + \
-            list(NULLDRAWS_PROTOTYPES.items()):
+            list(NULLDRAWS_PROTOTYPES.items()) + list(SBL_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -22,6 +22,7 @@
 // Nothing here reads outside text[0, nbytes) or writes outside rows row0 .. row0 + rows - 1 of the outputs, whatever the text
 // holds: positions come from the index of THIS text, and every field's thread is bounded by G <= rows * F and by D.
 #include "epg_common.h"
+#include "epg_text_scan.h"                                       // st_block_scan
 #include "epilogos_scores_text.h"
 
 namespace epg {
@@ -55,29 +56,6 @@ __device__ __forceinline__ u32 st_delim_mask(const char* __restrict__ text, long
         }
     }
     return m;
-}
-
-// exclusive scan of v over the workgroup (`NW` waves); *total = the sum.  `part` is LDS, NW words.
-template <int NW>
-__device__ __forceinline__ u32 st_block_scan(u32 v, u32* part, u32* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u32 inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u32 up = __shfl_up(inc, o);
-        if (lane >= o) inc += up;
-    }
-    if (lane == 63) part[wave] = inc;
-    __syncthreads();
-    u32 before = 0, sum = 0;
-    for (int w = 0; w < NW; ++w) {
-        const u32 p = part[w];
-        if (w < wave) before += p;
-        sum += p;
-    }
-    __syncthreads();                                             // part may be written again by the caller's next turn
-    *total = sum;
-    return before + inc - v;
 }
 
 template <bool FILL>

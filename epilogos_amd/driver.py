@@ -370,8 +370,12 @@ def _gather_parts(d, plans, my_payloads, n_arrays):
 
 
 def _cached_rows(path):
-    """Rows of an input file if the --cache-dir side-car of an earlier run knows them (no pass over the file), else None."""
-    from .helpers import _cache_paths
+    """Rows of an input file if the --cache-dir side-car of an earlier run knows them (no pass over the file), else None.  A binary
+    matrix file (stateByLine.py, .epgm) knows them from its header."""
+    from .helpers import _cache_paths, countRows
+    from .stateByLine import is_epgm
+    if is_epgm(path):
+        return countRows(path)
     cache = _cache_paths(path)
     if cache is None or not all(c.exists() for c in cache):
         return None

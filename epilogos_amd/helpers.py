@@ -34,7 +34,11 @@ def strToBool(string):
 
 def countRows(dataFilePath):
     """Number of newline characters in a (gz) file (reference helpers.py:80-99).  Like the reference, a final line
-    without a trailing newline is not counted (quirk Q6).  Native (zlib) reader."""
+    without a trailing newline is not counted (quirk Q6).  Native (zlib) reader.  A binary matrix file (stateByLine.py, .epgm)
+    answers from its header, without a pass over the file."""
+    from . import stateByLine
+    if stateByLine.is_epgm(dataFilePath):
+        return stateByLine.read_epgm_header(dataFilePath)["R"]
     return _io.count_rows(Path(dataFilePath))
 
 
@@ -157,7 +161,11 @@ def readTable(path, rowsToCalc=None, alloc=None, with_range=False, threads=0):
     same input memory-map it instead of inflating and parsing ~1.7 KB of text per bin again.
     alloc(R, N) -> int8 [R, width >= N] supplies the destination (the driver's pinned, row-padded staging; columns >= N
     are set to -1); with_range also returns the (lowest, highest) state value of the WHOLE file as written (1-based);
-    threads = native threads for this one file (0 = all cores; the driver, which reads many files at once, gives each its share)."""
+    threads = native threads for this one file (0 = all cores; the driver, which reads many files at once, gives each its share).
+    A binary matrix file of the preprocessing command (stateByLine.py, `*.epgm`) is memory-mapped and never cached: it is the cache."""
+    from . import stateByLine
+    if stateByLine.is_epgm(path):
+        return stateByLine.read_epgm(path, rowsToCalc, alloc, with_range)
     cache = _cache_paths(path)
     if cache is None:
         return _readTableNative(path, rowsToCalc, threads, alloc, with_range)

@@ -1,0 +1,59 @@
+"""`python -m epilogos_amd.preprocess DATADIR METADATA CHROMSIZES -o OUTDIR` (console script `epilogos-prep`): ChromHMM
+-printstatebyline calls -> one binary state matrix `matrix_<chr>.epgm` per chromosome, on the GPU (stateByLine.py).
+
+The three arguments and the progress lines are those of the reference's bin/preprocess_data_ChromHMM.sh; what comes out is not
+its `matrix_<chr>.txt` (1.7 KB of text per bin) but the matrix itself, 1 byte per cell, which `epilogos -i OUTDIR` reads directly.
+Text matrices are not written.  There is no CPU fallback: without a GPU or the HIP library the command raises."""
+import os
+import sys
+from pathlib import Path
+
+import click
+
+from . import stateByLine
+
+
+def run(datadir, metadata, chromsizes, outdir, out=sys.stdout):
+    """-> the files written.  One progress line per chromosome of `chromsizes`, as the script prints them."""
+    from . import engine
+    engine.require_gpu()
+    outdir = Path(outdir)
+    outdir.mkdir(parents=True, exist_ok=True)
+    written = []
+    for chrom, files in stateByLine.iter_calls(datadir, metadata, chromsizes):
+        out.write("Processing {}: {} files found. ".format(chrom, len(files)))
+        out.flush()
+        if not files:
+            out.write("Skipping.\n")
+            continue
+        X, N, name, rng = stateByLine.build_matrix_device(files)
+        # (the name inside the file is the calls' own, the script's chr=$2; the file is named after the chromsizes entry like the script's)
+        written.append(stateByLine.write_epgm(outdir / "matrix_{}{}".format(chrom, stateByLine.EXT), X[:, :N].contiguous(), name, rng))
+        del X
+        out.write("Done.\n")
+        out.flush()
+    return written
+
+
+@click.command(context_settings={"help_option_names": ["-h", "--help"]})
+@click.argument("datadir", type=click.Path(exists=True, file_okay=False))
+@click.argument("metadata", type=click.Path(exists=True, dir_okay=False))
+@click.argument("chromsizes", type=click.Path(exists=True, dir_okay=False))
+@click.option("-o", "--output-directory", "outdir", required=True, type=click.Path(file_okay=False), help="Where the matrix_<chr>.epgm files go")
+@click.option("-c", "--num-cores", "numCores", type=int, default=0, show_default=True,
+              help="Upper bound on the host cores used for inflating the call files (0 = all the job may use)")
+def main(datadir, metadata, chromsizes, outdir, numCores):
+    """State-by-line ChromHMM calls (one file per biosample and chromosome) -> binary state matrices for `epilogos -i`."""
+    if numCores < 0:
+        raise click.UsageError("Number of cores must be positive or zero (0 means use all cores)")
+    if numCores > 0:
+        os.environ["EPILOGOS_NUM_CORES"] = str(numCores)
+    run(datadir, metadata, chromsizes, outdir)
+
+
+def cli(argv=None):
+    main.main(args=argv, standalone_mode=True)
+
+
+if __name__ == "__main__":
+    cli()

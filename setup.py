@@ -15,5 +15,5 @@ setup(
     package_data={"epilogos_amd": ["csrc/*", "_lib/*.so"]},
     python_requires=">=3.10",
     install_requires=["numpy", "pandas", "scipy", "click", "torch"],
-    entry_points={"console_scripts": ["epilogos = epilogos_amd.run:cli"]},
+    entry_points={"console_scripts": ["epilogos = epilogos_amd.run:cli", "epilogos-prep = epilogos_amd.preprocess:cli"]},
 )
