@@ -17,6 +17,7 @@
 // outside 0..30 as -1 so that files cannot produce an aliasing byte.
 #pragma once
 #include "epg_common.h"
+#include "epg_parts.h"
 
 namespace epg {
 
@@ -209,18 +210,16 @@ __device__ __forceinline__ void tile_loop(const char* __restrict__ X, long R, in
     }
 }
 
-// The same loop over SEVERAL matrices ("parts": the chromosome files of a genome, both groups of a paired run) in one launch:
-// the parts' pointers and shapes travel in the kernel argument, super-tiles are numbered through the parts in order (a
-// super-tile never straddles two parts), a wave's super-tile index ascends, so its part only moves forward.  enter(part)
-// tells the caller which part the following epilogue / finish calls belong to.  Every part must have a width in the
-// instantiation's range (128 (NG - 1) < N <= 128 NG, or NG == 0).
+// The same loop over SEVERAL matrices ("parts", epg_parts.h) in one launch, in super-tiles of 32 rows.  enter(part) tells the
+// caller which part the following epilogue / finish calls belong to.  Every part must have a width in the instantiation's range
+// (128 (NG - 1) < N <= 128 NG, or NG == 0).
 constexpr int KH_MAXP = 48;
 struct KhParts {
     const char* x[KH_MAXP];
     u16* h[KH_MAXP];                       // (not used by the loop: the caller's enter() picks it up)
     long rows[KH_MAXP];
     long ldx[KH_MAXP];
-    long st0[KH_MAXP + 1];                 // first super-tile (32 rows) of every part, and their total
+    long t0[KH_MAXP + 1];                  // first super-tile of every part, and their total
     int n_cols[KH_MAXP];
     int n;
 };
@@ -230,18 +229,20 @@ __device__ __forceinline__ void tile_loop_parts(const KhParts& pt, Enter&& enter
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int j = lane & 3, b = lane >> 2;
-    const long nsuper = pt.st0[pt.n];
+    const long nsuper = pt.t0[pt.n];
+    PartCursor at;
     int part = -1;
     const char* X = nullptr;
-    long R = 0, ldx = 0, base = 0, next = 0;
+    long R = 0, ldx = 0, base = 0;
     RowGeom g = make_geom(16);
     for (long st = (long)blockIdx.x * NW + wave; st < nsuper; st += (long)gridDim.x * NW) {
-        if (st >= next) {
-            do { ++part; next = pt.st0[part + 1]; } while (st >= next);
+        at.advance(pt.t0, st, 32);               // (rows from the cached `base` below: with advance's own result every instantiation takes a VGPR more)
+        if (at.part != part) {
+            part = at.part;
             X = pt.x[part];
             R = pt.rows[part];
             ldx = pt.ldx[part];
-            base = pt.st0[part];
+            base = pt.t0[part];
             g = make_geom(pt.n_cols[part]);
             enter(part);
         }

@@ -441,41 +441,8 @@ __device__ __forceinline__ void nh_sample_row(u16* pa, u16* pb, u32* __restrict_
     pb[modal] = (u16)(TWO ? (((u32)ABm1 + 1u) >> 16) - needA : best - needA);
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// Several parts (the chromosome files of a genome) in ONE launch: pointers, row counts and shuffle keys travel in the kernel
-// argument, tiles of TR rows are numbered through the parts in order and never straddle two parts (the pattern of k_pair_fused_s1
-// and k_bin_hist_parts).  A row's draws are the same numbers as in a launch per part.
-// ---------------------------------------------------------------------------------------------------------------
-// Where a wave is among the parts.  A wave's tile index only ascends, so its part only moves forward.
-struct PartCursor {
-    int part = 0;
-    // `tile` (at or after the last one asked for) -> its first row in its part, `part`; t0 = first tile of every part, and the total
-    __device__ __forceinline__ long advance(const long* t0, long tile, int tile_rows) {
-        while (tile >= t0[part + 1]) ++part;
-        return (tile - t0[part]) * tile_rows;
-    }
-};
-
-// Host side: fills `pt` (an NhParts or a PcParts) with the parts p0, p0 + 1 ... that have rows, as many as it holds; fill(k, p)
-// copies part p's pointers and key into slot k.  -> the first part not taken.
-template <typename Parts, typename Fill>
-static int pack_parts(Parts& pt, int p0, int nparts, const int64_t* R, int tile_rows, Fill&& fill) {
-    constexpr int MAXP = (int)(sizeof(pt.rows) / sizeof(pt.rows[0]));
-    memset(&pt, 0, sizeof(pt));
-    long tiles = 0;
-    int p = p0;
-    for (; p < nparts && pt.n < MAXP; ++p) {
-        if (R[p] == 0) continue;
-        const int k = pt.n++;
-        fill(k, p);
-        pt.rows[k] = R[p];
-        pt.t0[k] = tiles;
-        tiles += (R[p] + tile_rows - 1) / tile_rows;
-    }
-    pt.t0[pt.n] = tiles;
-    return p;
-}
-
+// Several parts in ONE launch (epg_parts.h); `key` is the shuffle key of a part's first row, so a row's draws are the same
+// numbers as in a launch per part.
 constexpr int NH_MAXP = 48;
 struct NhParts {
     const u16* ha[NH_MAXP];
@@ -494,12 +461,33 @@ __device__ __forceinline__ void nh_stage_in(char* lds, const char* src, int nbyt
     for (int o = (nchunks << 4) + 2 * lane; o + 2 <= nbytes; o += 128) *reinterpret_cast<u16*>(lds + o) = *reinterpret_cast<const u16*>(src + o);
 }
 
-// The sampler of a launch = the number of bit strings per row.
-constexpr int NH_SEQ = 0, NH_ONE = 1, NH_TWO = 2;
-static_assert(NH_SEQ == 0 && NH_ONE == 1 && NH_TWO == 2, "nh_lds_bytes and k_null_hist_rows multiply by the mode");
+// The sampler of a launch = the number of bit strings per row; NH_WIDE: the row is too wide for bit strings.
+constexpr int NH_SEQ = 0, NH_ONE = 1, NH_TWO = 2, NH_WIDE = -1;
 
-// dynamic LDS of a block of four waves: a wave's TR rows of both histograms and its 64 lanes' bit strings of NW words
-static size_t nh_lds_bytes(int mode, int TR, int S, int NW) { return 4 * ((size_t)2 * TR * 2 * S + (size_t)mode * NW * 256); }
+// One bit string when the two groups fill the row (the command line without -g), two with -g, while a wave's strings fit its 24 KB
+// of LDS; column by column when a test asks for it on a shape that fits: same draws, same outputs.
+static int nh_mode(int n_cols, int ga, int gb) {
+    const int strings = ga + gb == n_cols ? NH_ONE : NH_TWO;
+    if ((size_t)strings * ((n_cols + 31) / 32) * 256 > 24 * 1024) return NH_WIDE;
+    return g_force[FORCE_NULL_SEQ] ? NH_SEQ : strings;
+}
+
+template <int MODE>
+__device__ __forceinline__ void nh_sample(u16* pa, u16* pb, u32* bitsA, u32* bitsB, int S, int n_cols, int ga, int gb, NhRng& rng) {
+    if constexpr (MODE == NH_SEQ) nh_sample_row_seq(pa, pb, S, n_cols, ga, gb, rng);
+    else nh_sample_row<MODE == NH_TWO>(pa, pb, bitsA, bitsB, S, n_cols, ga, gb, rng);
+}
+
+// A wave's LDS slot: `arrays` staged arrays of `rows` rows of S uint16 -- [sh: hA + hB, only when there are three,] sa, sb -- then
+// its 64 lanes' `mode` bit strings of NW words, [string][word][lane].
+struct NhSlot {
+    int arrays, rows, S, mode, NW;
+    __host__ __device__ int array_bytes() const { return rows * 2 * S; }
+    __host__ __device__ int sa() const { return (arrays - 2) * array_bytes(); }
+    __host__ __device__ int sb() const { return (arrays - 1) * array_bytes(); }
+    __host__ __device__ int bits() const { return arrays * array_bytes(); }
+    __host__ __device__ size_t bytes() const { return (size_t)bits() + (size_t)mode * NW * 256; }
+};
 
 // A lane owns a row, a wave a tile of TR rows.  The rows are handed over through LDS both ways, so that loads and stores cover
 // whole lines.
@@ -514,15 +502,11 @@ __global__ __launch_bounds__(256) void k_null_hist_rows(const NhParts pt, int S,
     __builtin_amdgcn_s_setprio(3);
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int rowb = 2 * S;
-    const size_t per_wave = (size_t)2 * TR * rowb + (size_t)MODE * NW * 256;
-    char* sa = smem + (size_t)wave * per_wave;                    // the wave's TR rows of hA, later of the A group's counts
-    char* sb = sa + TR * rowb;
-    [[maybe_unused]] u32* bitsA = nullptr;                        // [word][lane]
-    [[maybe_unused]] u32* bitsB = nullptr;
-    if constexpr (MODE != NH_SEQ) {
-        bitsA = reinterpret_cast<u32*>(sb + TR * rowb) + lane;
-        bitsB = bitsA + NW * 64;
-    }
+    const NhSlot slot{2, TR, S, MODE, NW};
+    char* sa = smem + (size_t)wave * slot.bytes();                // the wave's TR rows of hA, later of the A group's counts
+    char* sb = sa + slot.sb();
+    u32* bitsA = reinterpret_cast<u32*>(sa + slot.bits()) + lane; // [word][lane] (no sampler touches more strings than MODE)
+    u32* bitsB = bitsA + NW * 64;
     const long ntiles = pt.t0[pt.n];
     PartCursor at;
     for (long tile = (long)blockIdx.x * 4 + wave; tile < ntiles; tile += (long)gridDim.x * 4) {
@@ -536,8 +520,7 @@ __global__ __launch_bounds__(256) void k_null_hist_rows(const NhParts pt, int S,
             u16* pa = reinterpret_cast<u16*>(sa + lane * rowb);
             u16* pb = reinterpret_cast<u16*>(sb + lane * rowb);
             NhRng rng(seed, (u64)(pt.key[at.part] + r0 + lane));
-            if constexpr (MODE == NH_SEQ) nh_sample_row_seq(pa, pb, S, n_cols, ga, gb, rng);
-            else nh_sample_row<MODE == NH_TWO>(pa, pb, bitsA, bitsB, S, n_cols, ga, gb, rng);
+            nh_sample<MODE>(pa, pb, bitsA, bitsB, S, n_cols, ga, gb, rng);
         }
         __builtin_amdgcn_wave_barrier();
         store_staged(sa, reinterpret_cast<char*>(pt.oa[at.part] + r0 * S), rows * rowb, lane);
@@ -554,7 +537,7 @@ static int launch_null_hist_rows(const NhParts& pt, int S, int n_cols, int ga, i
         static DynLds lds_attr;                              // (one per instantiation)
         EPG_HIP(ensure_dyn_lds(lds_attr, reinterpret_cast<const void*>(k_null_hist_rows<MODE>), 160 * 1024));
     }
-    hipLaunchKernelGGL(k_null_hist_rows<MODE>, dim3((unsigned)blocks), dim3(256), nh_lds_bytes(MODE, TR, S, NW), st, pt, S, n_cols, ga, gb, seed,
+    hipLaunchKernelGGL(k_null_hist_rows<MODE>, dim3((unsigned)blocks), dim3(256), (4 * NhSlot{2, TR, S, MODE, NW}.bytes()), st, pt, S, n_cols, ga, gb, seed,
                        TR, NW);
     EPG_LAUNCH_CHECK("k_null_hist_rows");
     return EPG_OK;
@@ -572,18 +555,16 @@ extern "C" int epg_null_hist_from_binhist_parts(int32_t nparts, const uint16_t* 
         if (R[p] < 0) return fail(EPG_ERR_INVALID_ARG, "null_hist_from_binhist: bad shape");
         if (R[p] == 0) continue;
         if (!HA[p] || !HB[p] || !OA[p] || !OB[p]) return fail(EPG_ERR_INVALID_ARG, "null_hist_from_binhist: NULL argument");
-        if ((reinterpret_cast<uintptr_t>(HA[p]) | reinterpret_cast<uintptr_t>(HB[p]) | reinterpret_cast<uintptr_t>(OA[p]) | reinterpret_cast<uintptr_t>(OB[p])) & 15)
+        if (misaligned16(HA[p], HB[p], OA[p], OB[p]))
             return fail(EPG_ERR_INVALID_ARG, "null_hist_from_binhist: histogram arrays must be 16-byte aligned");
     }
     const int TR = tile_rows(2 * 2 * S);
-    // one bit string when the two groups fill the row (the command line without -g), two with -g, while a wave's strings fit its
-    // 24 KB of LDS; otherwise -- or when a test asks for it on a shape that fits -- column by column: same draws, same outputs
     const int NW = (n_cols + 31) / 32;
-    const int strings = ga + gb == n_cols ? 1 : 2;
-    const int mode = !g_force[FORCE_NULL_SEQ] && (size_t)strings * NW * 256 <= 24 * 1024 ? strings : NH_SEQ;
+    int mode = nh_mode(n_cols, ga, gb);
+    if (mode == NH_WIDE) mode = NH_SEQ;                      // column by column takes any row
     for (int p0 = 0; p0 < nparts;) {
         NhParts pt;
-        p0 = pack_parts(pt, p0, nparts, R, TR, [&](int k, int p) {
+        p0 = pack_parts(pt, p0, nparts, TR, [&](int p) { return (long)R[p]; }, [&](int k, int p) {
             pt.ha[k] = HA[p]; pt.hb[k] = HB[p]; pt.oa[k] = OA[p]; pt.ob[k] = OB[p];
             pt.key[k] = row0[p];
         });
@@ -656,10 +637,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     __shared__ u64 s_cnt[S + 1];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int j = lane & 3, b = lane >> 2;
-    const size_t per_wave = (size_t)2 * 64 * ROWB + (size_t)NW * 256;
-    char* sa = smem + (size_t)wave * per_wave;
-    char* sb = sa + 64 * ROWB;
-    u32* bitsA = reinterpret_cast<u32*>(sb + 64 * ROWB) + lane;
+    const NhSlot slot{2, 64, S, NH_ONE, NW};
+    char* sa = smem + (size_t)wave * slot.bytes();
+    char* sb = sa + slot.sb();
+    u32* bitsA = reinterpret_cast<u32*>(sa + slot.bits()) + lane;
     if (threadIdx.x <= S) s_cnt[threadIdx.x] = 0;
     __syncthreads();
     u32 accp[ND];
@@ -776,7 +757,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 template <int S, int NG>
 static int launch_pair_count_null(const PcParts& pt, int NA, int NB, u64* counts, u64 seed, hipStream_t st) {
     const int NW = (NA + NB + 31) / 32;
-    const size_t shmem = nh_lds_bytes(NH_ONE, 64, S, NW);
+    const size_t shmem = 4 * NhSlot{2, 64, S, NH_ONE, NW}.bytes();
     static DynLds lds_attr;                                  // (one per <S, NG> instantiation)
     EPG_HIP(ensure_dyn_lds(lds_attr, reinterpret_cast<const void*>(k_pair_count_null<S, NG>), 160 * 1024 - 1024));   // (the kernel also holds a small static array)
     long blocks = (pt.t0[pt.n] + 3) / 4;
@@ -804,7 +785,7 @@ extern "C" int epg_pair_count_null_parts(int32_t nparts, const int8_t* const* XA
         if (R[p] < 0) return fail(EPG_ERR_INVALID_ARG, "pair_count_null: bad shape of part %d", p);
         if (R[p] == 0) continue;
         if (!XA[p] || !XB[p] || !HA[p] || !HB[p] || !OA[p] || !OB[p]) return fail(EPG_ERR_INVALID_ARG, "pair_count_null: NULL argument of part %d", p);
-        if ((reinterpret_cast<uintptr_t>(HA[p]) | reinterpret_cast<uintptr_t>(HB[p]) | reinterpret_cast<uintptr_t>(OA[p]) | reinterpret_cast<uintptr_t>(OB[p])) & 15)
+        if (misaligned16(HA[p], HB[p], OA[p], OB[p]))
             return fail(EPG_ERR_INVALID_ARG, "pair_count_null: histogram arrays must be 16-byte aligned");
         // the 16-byte loads of a row's last chunk must stay inside the row pitch (engine.alloc_states pads to 16)
         if (ldxa[p] < 16L * ((NA + 15) / 16) || ldxb[p] < 16L * ((NB + 15) / 16))
@@ -813,7 +794,7 @@ extern "C" int epg_pair_count_null_parts(int32_t nparts, const int8_t* const* XA
     u64* cnt = reinterpret_cast<u64*>(counts);
     for (int p0 = 0; p0 < nparts;) {
         PcParts pt;
-        p0 = pack_parts(pt, p0, nparts, R, 64, [&](int k, int p) {
+        p0 = pack_parts(pt, p0, nparts, 64, [&](int p) { return (long)R[p]; }, [&](int k, int p) {
             pt.xa[k] = reinterpret_cast<const char*>(XA[p]); pt.xb[k] = reinterpret_cast<const char*>(XB[p]);
             pt.ha[k] = HA[p]; pt.hb[k] = HB[p]; pt.oa[k] = OA[p]; pt.ob[k] = OB[p];
             pt.ldxa[k] = ldxa[p]; pt.ldxb[k] = ldxb[p]; pt.key[k] = row0[p];
@@ -917,16 +898,12 @@ __global__ __launch_bounds__(64 * ND_WAVES_MAX) void k_null_dist_draws(const NdP
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nwaves = blockDim.x >> 6;
     const int rowb = 2 * S;
     const size_t tab_bytes = ((size_t)(entA + entB) * 4 + 15) & ~(size_t)15;
-    const size_t per_wave = (size_t)3 * 64 * rowb + (size_t)MODE * NW * 256;
-    char* sh = smem + tab_bytes + (size_t)wave * per_wave;        // the wave's 64 rows of hA + hB
-    char* sa = sh + 64 * rowb;                                    // staged hA, then the A group's counts of a draw
-    char* sb = sa + 64 * rowb;
-    [[maybe_unused]] u32* bitsA = nullptr;
-    [[maybe_unused]] u32* bitsB = nullptr;
-    if constexpr (MODE != NH_SEQ) {
-        bitsA = reinterpret_cast<u32*>(sb + 64 * rowb) + lane;
-        bitsB = bitsA + NW * 64;
-    }
+    const NhSlot slot{3, 64, S, MODE, NW};
+    char* sh = smem + tab_bytes + (size_t)wave * slot.bytes();    // the wave's 64 rows of hA + hB
+    char* sa = sh + slot.sa();                                    // staged hA, then the A group's counts of a draw
+    char* sb = sh + slot.sb();
+    u32* bitsA = reinterpret_cast<u32*>(sh + slot.bits()) + lane;
+    u32* bitsB = bitsA + NW * 64;
     const long ntiles = pt.t0[pt.n];
     PartCursor at;
     for (long tile = (long)blockIdx.x * nwaves + wave; tile < ntiles; tile += (long)gridDim.x * nwaves) {
@@ -952,8 +929,7 @@ __global__ __launch_bounds__(64 * ND_WAVES_MAX) void k_null_dist_draws(const NdP
                 if (!skip) {
                     for (int s = 0; s < S; ++s) { pa[s] = ph[s]; pb[s] = 0; }
                     NhRng rng(sd.seed[k], key);
-                    if constexpr (MODE == NH_SEQ) nh_sample_row_seq(pa, pb, S, n_cols, ga, gb, rng);
-                    else nh_sample_row<MODE == NH_TWO>(pa, pb, bitsA, bitsB, S, n_cols, ga, gb, rng);
+                    nh_sample<MODE>(pa, pb, bitsA, bitsB, S, n_cols, ga, gb, rng);
                     // a score = the table entry of (count, state); count 0 scores 0 (k_pair_fused_s1)
                     auto sc = [S](const float* t, u32 c, int s) { return c ? t[(long)c * S + s] : 0.0f; };
                     auto nd = [&](int s) { return sc(tnA, pa[s], s) - sc(tnB, pb[s], s); };
@@ -966,18 +942,10 @@ __global__ __launch_bounds__(64 * ND_WAVES_MAX) void k_null_dist_draws(const NdP
     }
 }
 
-// strings per row of the draws kernel (NH_ONE / NH_TWO, NH_SEQ when a test forces it), or -1: the row is too wide for them
-static int nd_mode(int n_cols, int ga, int gb) {
-    const int NW = (n_cols + 31) / 32;
-    const int strings = ga + gb == n_cols ? 1 : 2;
-    if ((size_t)strings * NW * 256 > 24 * 1024) return -1;
-    return g_force[FORCE_NULL_SEQ] ? NH_SEQ : strings;
-}
-
 // waves per block that fit next to the tables, 0: not even ND_WAVES_MIN
 static int nd_waves(int mode, int S, int n_cols, int ga, int gb, size_t* shmem) {
     const size_t tab = ((size_t)(ga + 1 + gb + 1) * S * 4 + 15) & ~(size_t)15;
-    const size_t per_wave = (size_t)3 * 64 * 2 * S + (size_t)mode * ((n_cols + 31) / 32) * 256;
+    const size_t per_wave = NhSlot{3, 64, S, mode, (n_cols + 31) / 32}.bytes();
     if (tab + ND_WAVES_MIN * per_wave > 160 * 1024) return 0;
     int waves = (int)((160 * 1024 - tab) / per_wave);
     if (waves > ND_WAVES_MAX) waves = ND_WAVES_MAX;
@@ -995,8 +963,8 @@ extern "C" int epg_null_dist_draws_parts(int32_t nparts, const uint16_t* const* 
     if (ga < 1 || gb < 1 || (long)ga + gb > n_cols)
         return fail(EPG_ERR_INVALID_ARG, "null_dist_draws: group sizes %d + %d do not fit the %d columns", ga, gb, n_cols);
     if (S > 31) return fail(EPG_ERR_UNSUPPORTED, "null_dist_draws: S=%d, the kernel takes at most 31 states", S);
-    const int mode = nd_mode(n_cols, ga, gb);
-    if (mode < 0) return fail(EPG_ERR_UNSUPPORTED, "null_dist_draws: rows of %d columns are beyond the bit-string sampler", n_cols);
+    const int mode = nh_mode(n_cols, ga, gb);
+    if (mode == NH_WIDE) return fail(EPG_ERR_UNSUPPORTED, "null_dist_draws: rows of %d columns are beyond the bit-string sampler", n_cols);
     size_t shmem = 0;
     const int waves = nd_waves(mode, S, n_cols, ga, gb, &shmem);
     if (!waves)
@@ -1008,7 +976,7 @@ extern "C" int epg_null_dist_draws_parts(int32_t nparts, const uint16_t* const* 
         if (R[p] < 0) return fail(EPG_ERR_INVALID_ARG, "null_dist_draws: part %d has %lld rows", p, (long long)R[p]);
         if (R[p] == 0) continue;
         if (!HA[p] || !HB[p] || !out[p]) return fail(EPG_ERR_INVALID_ARG, "null_dist_draws: NULL argument in part %d", p);
-        if ((reinterpret_cast<uintptr_t>(HA[p]) | reinterpret_cast<uintptr_t>(HB[p])) & 15)
+        if (misaligned16(HA[p], HB[p]))
             return fail(EPG_ERR_INVALID_ARG, "null_dist_draws: histogram arrays must be 16-byte aligned (part %d)", p);
         if (reinterpret_cast<uintptr_t>(out[p]) & 3) return fail(EPG_ERR_INVALID_ARG, "null_dist_draws: out of part %d is not aligned", p);
     }
@@ -1020,7 +988,7 @@ extern "C" int epg_null_dist_draws_parts(int32_t nparts, const uint16_t* const* 
         for (int k = 0; k < sd.n; ++k) sd.seed[k] = (u64)seeds[k0 + k];
         for (int p0 = 0; p0 < nparts;) {
             NdParts pt;
-            p0 = pack_parts(pt, p0, nparts, R, 64, [&](int k, int p) {
+            p0 = pack_parts(pt, p0, nparts, 64, [&](int p) { return (long)R[p]; }, [&](int k, int p) {
                 pt.ha[k] = HA[p]; pt.hb[k] = HB[p]; pt.mask[k] = mask ? mask[p] : nullptr;
                 pt.out[k] = out[p] + (long)k0 * R[p];
                 pt.key[k] = row0[p];

@@ -523,43 +523,29 @@ extern "C" int epg_bin_hist_parts(int32_t nparts, const int8_t* const* X, const 
         return EPG_OK;
     }
     u64* cnt = reinterpret_cast<u64*>(counts);
+    for (int p = 0; p < nparts; ++p) {             // trailing rows the 16-byte loads could run past: byte-granular kernel
+        const long Rf = R[p] ? fast_rows(R[p], N[p], ldx[p]) : 0;
+        if (Rf == R[p]) continue;
+        hipLaunchKernelGGL(k_bin_hist_safe, dim3((unsigned)((R[p] - Rf + 3) / 4 < 1024 ? (R[p] - Rf + 3) / 4 : 1024)), dim3(256), 0, st,
+                           reinterpret_cast<const char*>(X[p]), Rf, (long)R[p], N[p], (long)ldx[p], S, H ? H[p] : nullptr, cnt);
+        EPG_LAUNCH_CHECK("k_bin_hist_safe");
+    }
     // schedule class of a part: groups per row (1..8), 0 = any width; classes are launched one after the other
     auto cls = [](int n) { const int ng = (n + 127) / 128; return ng <= 8 ? ng : 0; };
-    bool seen[9] = {false, false, false, false, false, false, false, false, false};
-    for (int p = 0; p < nparts; ++p)
-        if (R[p]) seen[cls(N[p])] = true;
     for (int c = 0; c <= 8; ++c) {
-        if (!seen[c]) continue;
         for (int p0 = 0; p0 < nparts;) {
             KhParts pt;
-            memset(&pt, 0, sizeof(pt));
-            long supers = 0;
-            int nmax = 1, p = p0;
-            for (; p < nparts && pt.n < KH_MAXP; ++p) {
-                if (!R[p] || cls(N[p]) != c) continue;
-                const long Rf = fast_rows(R[p], N[p], ldx[p]);
-                if (Rf < R[p]) {                   // trailing rows the 16-byte loads could run past: byte-granular kernel
-                    hipLaunchKernelGGL(k_bin_hist_safe, dim3((unsigned)((R[p] - Rf + 3) / 4 < 1024 ? (R[p] - Rf + 3) / 4 : 1024)), dim3(256), 0, st,
-                                       reinterpret_cast<const char*>(X[p]), Rf, (long)R[p], N[p], (long)ldx[p], S, H ? H[p] : nullptr, cnt);
-                    EPG_LAUNCH_CHECK("k_bin_hist_safe");
-                }
-                if (Rf == 0) continue;
-                const int k = pt.n++;
-                pt.x[k] = reinterpret_cast<const char*>(X[p]);
-                pt.h[k] = H ? H[p] : nullptr;
-                pt.rows[k] = Rf;
-                pt.ldx[k] = ldx[p];
-                pt.n_cols[k] = N[p];
-                pt.st0[k] = supers;
-                supers += (Rf + 31) / 32;
-                if (N[p] > nmax) nmax = N[p];
-            }
-            pt.st0[pt.n] = supers;
-            p0 = p;
+            int nmax = 1;
+            p0 = pack_parts(pt, p0, nparts, 32, [&](int p) { return R[p] && cls(N[p]) == c ? fast_rows(R[p], N[p], ldx[p]) : 0L; },
+                            [&](int k, int p) {
+                                pt.x[k] = reinterpret_cast<const char*>(X[p]); pt.h[k] = H ? H[p] : nullptr;
+                                pt.ldx[k] = ldx[p]; pt.n_cols[k] = N[p];
+                                if (N[p] > nmax) nmax = N[p];
+                            });
             if (pt.n == 0) break;
             with_count_core(S, c, [&](auto SC, auto NG, auto) {
                 // (the any-width instantiation stores column by column, like the one-matrix kernel of another model size)
-                hipLaunchKernelGGL((k_bin_hist_parts<SC, NG, (NG > 0 && (SC & 1) == 0)>), dim3(grid_for_tiles(supers * 32)), dim3(256), 0, st, pt, S,
+                hipLaunchKernelGGL((k_bin_hist_parts<SC, NG, (NG > 0 && (SC & 1) == 0)>), dim3(grid_for_tiles(pt.t0[pt.n] * 32)), dim3(256), 0, st, pt, S,
                                    cnt, nmax);
             });
             EPG_LAUNCH_CHECK("k_bin_hist_parts");

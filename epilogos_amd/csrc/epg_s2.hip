@@ -1,6 +1,7 @@
 // S2 path (state-pair saliency) from cached per-bin histograms, plus the paired-mode extras.  gfx950 only.
 #include "epg_common.h"
 #include "epg_pairdist.h"
+#include "epg_parts.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -564,7 +565,7 @@ struct PfParts {
     int* maxdiff[PF_MAXP];
     unsigned char* mask[PF_MAXP];          // NULL: no mask for this part
     long rows[PF_MAXP];
-    long tile0[PF_MAXP + 1];               // first tile (64 rows) of every part, and their total
+    long t0[PF_MAXP + 1];                  // first tile (64 rows) of every part, and their total (epg_parts.h)
     int n;
 };
 
@@ -592,7 +593,7 @@ __global__ __launch_bounds__(64 * PF_WAVES_MAX) __attribute__((amdgpu_waves_per_
     const int nwaves = blockDim.x >> 6;
     char* stage = smem + tab_bytes + (size_t)wave * 64 * (4 * hb + (SC ? 0 : rowb));
     char* sA = stage, *sB = sA + 64 * hb, *snA = sB + 64 * hb, *snB = snA + 64 * hb, *sD = SC ? sA : snB + 64 * hb;
-    const long ntiles = pt.tile0[pt.n];
+    const long ntiles = pt.t0[pt.n];
     int part = 0;
     // Round 5: the NEXT tile's four histogram blocks are fetched into registers before this tile is worked on (compile-time S,
     // whole tiles of 64 rows only: 8 S chunks of 16 bytes per array, ceil(S / 8) per lane).  Before, a wave loaded, waited,
@@ -604,7 +605,7 @@ __global__ __launch_bounds__(64 * PF_WAVES_MAX) __attribute__((amdgpu_waves_per_
     bool have_pre = false;
     const long tstride = (long)gridDim.x * nwaves;
     for (long tile = (long)blockIdx.x * nwaves + wave; tile < ntiles; tile += tstride) {
-        while (tile >= pt.tile0[part + 1]) ++part;                   // (a wave's tiles ascend: the part only moves forward)
+        while (tile >= pt.t0[part + 1]) ++part;   // (PartCursor::advance written out, as for the next tile below: with the cursor SC = 15, 18 take two more VGPRs)
         const u16* __restrict__ HA = pt.ha[part];
         const u16* __restrict__ HB = pt.hb[part];
         const u16* __restrict__ HnA = pt.hna[part];
@@ -615,7 +616,7 @@ __global__ __launch_bounds__(64 * PF_WAVES_MAX) __attribute__((amdgpu_waves_per_
         int* __restrict__ maxdiff = pt.maxdiff[part];
         unsigned char* __restrict__ mask = pt.mask[part];
         const long R = pt.rows[part];
-        const long row0 = (tile - pt.tile0[part]) * 64;
+        const long row0 = (tile - pt.t0[part]) * 64;
         const int rows = (int)(R - row0 < 64 ? R - row0 : 64);
         if (SC && have_pre) {
 #pragma unroll
@@ -639,8 +640,8 @@ __global__ __launch_bounds__(64 * PF_WAVES_MAX) __attribute__((amdgpu_waves_per_
             const long nt = tile + tstride;
             if (nt < ntiles) {
                 int np = part;
-                while (nt >= pt.tile0[np + 1]) ++np;
-                const long nrow0 = (nt - pt.tile0[np]) * 64;
+                while (nt >= pt.t0[np + 1]) ++np;
+                const long nrow0 = (nt - pt.t0[np]) * 64;
                 if (pt.rows[np] - nrow0 >= 64) {                     // a whole tile: its loads run under this tile's arithmetic
                     const char* g0 = reinterpret_cast<const char*>(pt.ha[np] + nrow0 * S);
                     const char* g1 = reinterpret_cast<const char*>(pt.hb[np] + nrow0 * S);
@@ -723,8 +724,7 @@ extern "C" int epg_pair_scores_s1_parts(int32_t nparts, const uint16_t* const* H
         if (R[p] == 0) continue;
         if (!HA[p] || !HB[p] || !HnA[p] || !HnB[p] || !delta[p] || !ndist[p] || !rdist[p] || !maxdiff[p])
             return fail(EPG_ERR_INVALID_ARG, "pair_scores_s1: NULL argument in part %d", p);
-        if ((reinterpret_cast<uintptr_t>(HA[p]) | reinterpret_cast<uintptr_t>(HB[p]) | reinterpret_cast<uintptr_t>(HnA[p]) |
-             reinterpret_cast<uintptr_t>(HnB[p]) | reinterpret_cast<uintptr_t>(delta[p])) & 15)
+        if (misaligned16(HA[p], HB[p], HnA[p], HnB[p], delta[p]))
             return fail(EPG_ERR_INVALID_ARG, "pair_scores_s1: histograms and delta must be 16-byte aligned (part %d)", p);
     }
     const int entA = (NA + 1) * S, entB = (NB + 1) * S, entnA = (ga + 1) * S, entnB = (gb + 1) * S;
@@ -745,23 +745,13 @@ extern "C" int epg_pair_scores_s1_parts(int32_t nparts, const uint16_t* const* H
     const size_t shmem = tab + (size_t)waves * per_wave;
     for (int p0 = 0; p0 < nparts;) {                                                  // PF_MAXP parts with rows per launch
         PfParts pt;
-        memset(&pt, 0, sizeof(pt));
-        long tiles = 0;
-        int p = p0;
-        for (; p < nparts && pt.n < PF_MAXP; ++p) {
-            if (R[p] == 0) continue;
-            const int k = pt.n++;
+        p0 = pack_parts(pt, p0, nparts, 64, [&](int p) { return (long)R[p]; }, [&](int k, int p) {
             pt.ha[k] = HA[p]; pt.hb[k] = HB[p]; pt.hna[k] = HnA[p]; pt.hnb[k] = HnB[p];
             pt.delta[k] = delta[p]; pt.ndist[k] = ndist[p]; pt.rdist[k] = rdist[p]; pt.maxdiff[k] = maxdiff[p];
             pt.mask[k] = mask ? mask[p] : nullptr;
-            pt.rows[k] = R[p];
-            pt.tile0[k] = tiles;
-            tiles += (R[p] + 63) / 64;
-        }
-        pt.tile0[pt.n] = tiles;
-        p0 = p;
+        });
         if (pt.n == 0) break;
-        long blocks = (tiles + waves - 1) / waves;
+        long blocks = (pt.t0[pt.n] + waves - 1) / waves;
         if (blocks > num_cus()) blocks = num_cus();
         // S at compile time for the reference's models, 0 = any S
         const int rc = with_constant<0, 18, 15, 25>(S, [&](auto SC) {
@@ -945,7 +935,7 @@ extern "C" int epg_pair_finish(const float* a, const float* b, int64_t R, int32_
     if (R < 0 || S < 1 || S > 127) return fail(EPG_ERR_INVALID_ARG, "pair_finish: bad shape");   // numpy's pairwise sum recurses above 128
     if (R == 0) return EPG_OK;
     if (!a || !b || !delta) return fail(EPG_ERR_INVALID_ARG, "pair_finish: NULL argument");
-    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(delta)) & 15)
+    if (misaligned16(a, b, delta))
         return fail(EPG_ERR_INVALID_ARG, "pair_finish: a, b and delta must be 16-byte aligned");
     const int TR = tile_rows(2 * S * 4);
     long blocks = ((R + TR - 1) / TR + 3) / 4;
