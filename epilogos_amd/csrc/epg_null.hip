@@ -145,7 +145,8 @@ __global__ __launch_bounds__(256) void k_null_hist(const char* __restrict__ XA, 
 // Philox4x32-10 keyed by the seed; counter = (row key low, row key high, call number, tag), one tag per stream, where the row key
 // is row0 of the part + the row's index in it.  The draws are a pure function of (seed, row key, the row's two histograms): not
 // of the launch geometry, the GPU count, the batch of parts or the kernel that a shape selects.  All three samplers below give
-// the SAME groups (tests/test_hip_s3_null.py compares them, tests/test_hip_null_draws.py pins the groups themselves).
+// the SAME groups (tests/test_hip_s3_null.py compares them, tests/test_hip_null_draws.py pins the groups themselves,
+// tests/test_hip_null_sampler_exact.py holds them against the host restatement of this comment, tests/null_sampler_ref.py).
 //
 // Two samplers:
 //  * nh_sample_row_seq walks the columns with the category bookkeeping in the loop (an LDS store + load and a divergent inner
