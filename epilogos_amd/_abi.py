@@ -1,5 +1,5 @@
 """ctypes binding of include/epilogos_amd.h, include/epilogos_scores_text.h, include/epilogos_groups.h,
-include/epilogos_nulldraws.h and include/epilogos_statebyline.h.  No fallbacks: a missing library or symbol raises."""
+include/epilogos_nulldraws.h, include/epilogos_statebyline.h and include/epilogos_segments.h.  No fallbacks: a missing library or symbol raises."""
 import ctypes as C
 import re
 from pathlib import Path
@@ -93,7 +93,22 @@ SBL_PROTOTYPES = {
     "epg_sbl_transpose": (C.c_int, [_p, _i32, _i64, _i64, _p, _i64, _i64, _p]),
 }
 
+# and for include/epilogos_segments.h, the reader of ChromHMM segment files (tests/test_segments_host.py checks it)
+SEG_HEADER = HEADER.with_name("epilogos_segments.h")
+SEG_PROTOTYPES = {
+    "epg_seg_ws_bytes": (_i64, [_i64, _i32]),
+    "epg_seg_constant": (_i32, [_i32]),
+    "epg_seg_parse": (C.c_int, [_p, _i64, _p, _i32, _i32, _p, _p, _i64, _p, _p, _p, _i64, _p]),
+    "epg_seg_expand": (C.c_int, [_p, _p, _p, _i32, _p, _i64, _p]),
+}
+
 _lib = None
+
+
+def seg_header_symbols():
+    """Function names declared in include/epilogos_segments.h."""
+    txt = re.sub(r"/\*.*?\*/", "", SEG_HEADER.read_text(), flags=re.S)
+    return sorted(set(re.findall(r"\b(epg_[a-z0-9_]+)\s*\(", txt)))
 
 
 def sbl_header_symbols():
@@ -157,7 +172,7 @@ def load():
                                    "(there is no CPU fallback)" % path)
     lib = C.CDLL(str(path))
     for name, (res, args) in list(PROTOTYPES.items()) + list(TEXT_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + \
-            list(NULLDRAWS_PROTOTYPES.items()) + list(SBL_PROTOTYPES.items()):
+            list(NULLDRAWS_PROTOTYPES.items()) + list(SBL_PROTOTYPES.items()) + list(SEG_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = args

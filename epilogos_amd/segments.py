@@ -1,0 +1,365 @@
+"""ChromHMM segment files (`<cell>_<n>_segments.bed`: one file per biosample for the whole genome, one line
+`chrom TAB start TAB end TAB label` per run of equal states) -> the [bins, biosamples] state matrix of every chromosome, on the GPU
+(csrc/epg_segments.hip, include/epilogos_segments.h), for `python -m epilogos_amd.preprocess --segments`.
+
+find_segments         which file is which biosample's (the rule of stateByLine.iter_calls, for one file per biosample)
+read_chromsizes       the chromosome table: names in file order, sizes where the file gives them
+parse_host            one file on the host, for what the strict device grammar refuses
+check_files           the rules across files: the same chromosomes in every file, the same R_c, R_c within the chromosome
+build_matrices_device the files -> {chromosome: (X int8 [R_c, ldx] on the device, (lo, hi))}
+
+The parser on the device is strict (the grammar is written out in the header).  A file it refuses is named in one warning line
+and parsed on the host, which also takes '\\r\\n', blanks around fields, track / browser / # lines, more than four fields and
+labels that are names (--state-names); errors of content raise ValueError with file and line on either path."""
+import ctypes as C
+import fnmatch
+import os
+import re
+from pathlib import Path
+
+import numpy as np
+
+from . import _abi, _io
+from .stateByLine import BIN_WIDTH, _align, _first_fields
+
+NAME_BYTES = 80
+_LABEL = re.compile(r"^[A-Za-z]?([0-9]{1,3})(_.*)?$", re.S)
+_PREFIX = re.compile(r"^[0-9]+_")
+
+
+# ---- which files ---------------------------------------------------------------------------------------------------------------
+
+def find_segments(datadir, metadata):
+    """[files in metadata order]: biosamples are column 1 of `metadata` behind its header line, a biosample's file is the one
+    name of `datadir` that matches `*{biosample}*segments.bed*` (no leading dot); a biosample without one has no column; two
+    matches raise."""
+    datadir = Path(datadir)
+    names = sorted(n for n in os.listdir(datadir) if not n.startswith("."))
+    files = []
+    for b in _first_fields(metadata, skip=1):
+        hits = [n for n in names if fnmatch.fnmatchcase(n, "*{}*segments.bed*".format(b))]
+        if len(hits) > 1:
+            raise ValueError("biosample {} has more than one segment file: {} and {}".format(b, datadir / hits[0], datadir / hits[1]))
+        if hits:
+            files.append(datadir / hits[0])
+    return files
+
+
+def read_chromsizes(chromsizes):
+    """-> (names in file order, {name: size in bp} for the lines that give one)."""
+    names, sizes = [], {}
+    with open(chromsizes, "r", newline="\n") as fh:
+        for line in fh.read().split("\n"):
+            f = line.split("\t")
+            first = f[0].split()
+            if not first:
+                continue
+            names.extend(first)
+            if len(first) == 1 and len(f) > 1 and f[1].strip().isdigit():
+                sizes[first[0]] = int(f[1])
+    return names, sizes
+
+
+def read_state_names(path):
+    """--state-names: a state metadata TSV whose header has `one_index` and `short_name` -> {short_name: state 1..127}."""
+    with open(path, "r") as fh:
+        lines = [l.rstrip("\r\n").split("\t") for l in fh if l.strip()]
+    if not lines or "one_index" not in lines[0] or "short_name" not in lines[0]:
+        raise ValueError("{}: no header with one_index and short_name columns".format(path))
+    i, k = lines[0].index("one_index"), lines[0].index("short_name")
+    table = {}
+    for n, f in enumerate(lines[1:], 2):
+        if len(f) <= max(i, k) or not f[i].strip().isdigit():
+            raise ValueError("{}:{}: not a state line".format(path, n))
+        table[f[k].strip()] = int(f[i])
+    return table
+
+
+# ---- one file on the host ------------------------------------------------------------------------------------------------------
+
+def _state_of(label, table, where):
+    m = _LABEL.match(label)
+    if m:
+        v = int(m.group(1))
+    else:
+        v = None
+        if table:
+            v = table.get(label)
+            if v is None:
+                v = table.get(_PREFIX.sub("", label, count=1))
+        if v is None:
+            raise ValueError("{}: the label {!r} is neither a state number nor a name of --state-names".format(where, label))
+    if not 1 <= v <= 127:
+        raise ValueError("{}: state {} outside 1..127".format(where, v))
+    return v
+
+
+def parse_host(a, path, chroms, width=BIN_WIDTH, state_names=None):
+    """The text `a` (uint8 array or bytes) of one segment file, leniently: '\\r' and blanks around fields dropped, empty lines and
+    track / browser / # lines skipped, fields behind the fourth ignored, labels that are names looked up in `state_names` (whole,
+    or behind a leading `<digits>_`).  -> {chromosome: (int8 column of state - 1, lo, hi)} for the chromosomes of `chroms` the file
+    holds.  Errors of content raise ValueError naming `path` and the 1-based line; runs of other chromosomes are skipped."""
+    text = bytes(a.tobytes() if hasattr(a, "tobytes") else a).decode("latin-1")
+    want = set(chroms)
+    out, done = {}, set()
+    cur, keep, starts, ends, states, prev_end = None, False, [], [], [], 0
+
+    def close():
+        if cur is not None and keep:
+            s, e, v = np.array(starts, dtype=np.int64), np.array(ends, dtype=np.int64), np.array(states, dtype=np.int64)
+            out[cur] = (np.repeat((v - 1).astype(np.int8), e - s), int(v.min()), int(v.max()))
+
+    for no, line in enumerate(text.split("\n"), 1):
+        line = line.strip(" \r")
+        if not line.strip() or line.startswith(("track", "browser", "#")):
+            continue
+        where = "{}:{}".format(path, no)
+        f = [x.strip() for x in line.split("\t")]
+        if len(f) < 4:
+            raise ValueError("{}: {} fields, a segment line has chrom, start, end and label".format(where, len(f)))
+        chrom = f[0]
+        if chrom != cur:
+            close()
+            if cur is not None:
+                done.add(cur)
+            if chrom in done and chrom in want:
+                raise ValueError("{}: chromosome {} comes in two runs of lines".format(where, chrom))
+            cur, keep, starts, ends, states, prev_end = chrom, chrom in want, [], [], [], None
+        if not keep:
+            continue
+        if not (f[1].isdigit() and f[2].isdigit() and f[1].isascii() and f[2].isascii()):
+            raise ValueError("{}: start and end must be whole numbers".format(where))
+        s, e = int(f[1]), int(f[2])
+        if s % width or e % width:
+            raise ValueError("{}: {}..{} is off the grid of {} bp bins".format(where, s, e, width))
+        if e <= s:
+            raise ValueError("{}: end {} is not behind start {}".format(where, e, s))
+        if e // width >= 1 << 31:
+            raise ValueError("{}: end {} is beyond 2^31 bins".format(where, e))
+        if prev_end is None:
+            if s != 0:
+                raise ValueError("{}: the first segment of {} starts at {}, not at 0".format(where, chrom, s))
+        elif s != prev_end:
+            raise ValueError("{}: a {} of {} bp: the segment starts at {}, the one before it ends at {}".format(
+                where, "gap" if s > prev_end else "overlap", abs(s - prev_end), s, prev_end))
+        states.append(_state_of(f[3], state_names, where))
+        starts.append(s // width), ends.append(e // width)
+        prev_end = e
+    close()
+    return out
+
+
+# ---- the rules across files ----------------------------------------------------------------------------------------------------
+
+def check_files(files, chroms, rows, width=BIN_WIDTH, sizes=None):
+    """rows[k] = {chromosome: R_c} of the table's chromosomes file k holds.  -> {chromosome: R_c} of the chromosomes the files hold,
+    in table order.  Raises ValueError for a chromosome that some files hold and others do not (column k must be the same
+    biosample in every matrix), for an R_c that differs between two files and for an R_c beyond ceil(size / width)."""
+    out = {}
+    for c in chroms:
+        have = [k for k in range(len(files)) if c in rows[k]]
+        if not have:
+            continue
+        if len(have) < len(files):
+            lack = next(k for k in range(len(files)) if c not in rows[k])
+            raise ValueError("chromosome {} is in {} but not in {}: every segment file must hold the same chromosomes".format(
+                c, files[have[0]], files[lack]))
+        R = rows[have[0]][c]
+        for k in have[1:]:
+            if rows[k][c] != R:
+                raise ValueError("{} holds {} bins of {}, {} holds {}: the files must end a chromosome at the same place".format(
+                    files[have[0]], R, c, files[k], rows[k][c]))
+        if sizes and c in sizes and R > -(-sizes[c] // width):
+            raise ValueError("{} holds {} bins of {}, which is {} bp long: {} bins of {} bp at most".format(
+                files[have[0]], R, c, sizes[c], -(-sizes[c] // width), width))
+        out[c] = R
+    return out
+
+
+def name_table(chroms):
+    """The chromosome table epg_seg_parse takes: uint8 [nchrom, 80], NUL-padded."""
+    t = np.zeros((len(chroms), NAME_BYTES), dtype=np.uint8)
+    for i, c in enumerate(chroms):
+        b = str(c).encode()
+        if not b or len(b) >= NAME_BYTES or b"\0" in b:
+            raise ValueError("chromosome name {!r} does not fit the table (1..79 bytes)".format(c))
+        t[i, :len(b)] = np.frombuffer(b, dtype=np.uint8)
+    return t
+
+
+def count_lines(a):
+    if len(a) == 0:
+        return 0
+    return _io.count_newlines(a, 1) + (1 if a[-1] != 10 else 0)
+
+
+# ---- the files on the device ---------------------------------------------------------------------------------------------------
+
+def build_matrices_device(files, chroms, width=BIN_WIDTH, sizes=None, state_names=None, timings=None, threads=None):
+    """files: one segment file per biosample, in column order; chroms: the chromosome table.
+    -> {chromosome: (X int8 [R_c, ldx] on the current device with ldx = N rounded up to 16 and -1 in columns >= N, (lo, hi))} for
+    the chromosomes the files hold, in table order.  The host inflates the files `_io.host_budget()` at a time; a batch of up to
+    64 texts is uploaded at once through two pinned slots, each text is parsed (epg_seg_parse), and for every chromosome the
+    batch's columns are expanded (epg_seg_expand) and transposed into its resident matrix (epg_sbl_transpose).  R_c comes from
+    the first file (one synchronisation); every matrix stays resident until the caller has written it.  `timings` (a dict)
+    receives inflate_s, upload_ms, parse_ms, expand_ms and transpose_ms (HIP events, summed over the batches)."""
+    import torch
+    from concurrent.futures import ThreadPoolExecutor
+    from time import perf_counter
+    from . import engine
+    engine.require_gpu()
+    files = [Path(f) for f in files]
+    chroms = list(chroms)
+    if not files:
+        raise ValueError("no segment files")
+    if width <= 0:
+        raise ValueError("the bin width must be positive")
+    N, nchrom = len(files), len(chroms)
+    if nchrom > int(_abi.call("epg_seg_constant", 3)):
+        raise ValueError("{} chromosomes, the table holds {} at most".format(nchrom, int(_abi.call("epg_seg_constant", 3))))
+    threads = max(1, int(threads or _io.host_budget()))
+    batch = int(_abi.call("epg_sbl_constant", 3))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    main = torch.cuda.current_stream()
+    names = torch.from_numpy(name_table(chroms)).to(dev) if nchrom else torch.zeros(1, dtype=torch.uint8, device=dev)
+    t_wait = 0.0
+    ev = {k: [] for k in ("upload", "parse", "expand", "transpose")}
+
+    def mark():
+        e = torch.cuda.Event(enable_timing=True)
+        e.record(main)
+        return e
+
+    def inflate(k):
+        return _io.Text(files[k], 1)
+
+    def host_file(k, line):
+        print("epilogos_amd: {}: line {} is not a strict segment line -- reading this file on the host (slow)".format(files[k], line), flush=True)
+        with _io.Text(files[k], 1) as tx:
+            return parse_host(tx.data, files[k], chroms, width, state_names)
+
+    infos = torch.zeros((N, 4), dtype=torch.int64, device=dev)
+    runs = torch.zeros((N, max(nchrom, 1), 3), dtype=torch.int64, device=dev)
+    sizes_b, caps = [0] * N, [0] * N
+    host_cols = {}                                               # file -> what parse_host gave
+    ref = X = cols = col_pitch = None                            # ref: {chromosome index: R_c} of the first file
+    ldx = _align(N, 16)
+    slots = []                                                   # per parity: [pinned, device text, event "the batch has left the device text"]
+    with ThreadPoolExecutor(max_workers=threads) as pool:
+        starts = list(range(0, N, batch))
+        futs = {0: [pool.submit(inflate, k) for k in range(0, min(batch, N))]}
+        try:
+            for bi, k0 in enumerate(starts):
+                nb = min(batch, N - k0)
+                t0 = perf_counter()
+                texts = [f.result() for f in futs.pop(bi)]
+                try:
+                    offs = np.zeros(nb + 1, dtype=np.int64)
+                    loff = np.zeros(nb + 1, dtype=np.int64)
+                    for j, tx in enumerate(texts):
+                        sizes_b[k0 + j] = len(tx.data)
+                        caps[k0 + j] = count_lines(tx.data)
+                        offs[j + 1] = offs[j] + _align(len(tx.data), 16)
+                        loff[j + 1] = loff[j] + _align(max(caps[k0 + j], 1), 16)
+                    total = int(offs[-1])
+                    s = bi % 2
+                    if len(slots) <= s:
+                        slots.append([None, None, None])
+                    pinned, dtext, done = slots[s]
+                    if done is not None:
+                        done.synchronize()
+                    if pinned is None or pinned.numel() < total:
+                        room = _align(total + total // 8, 4096)
+                        pinned = torch.empty(room, dtype=torch.uint8).pin_memory()
+                        dtext = torch.empty(room, dtype=torch.uint8, device=dev)
+                    host = pinned.numpy()
+
+                    def stage(j):
+                        host[offs[j]:offs[j] + sizes_b[k0 + j]] = texts[j].data
+                    list(pool.map(stage, range(nb)))
+                    if bi + 1 < len(starts):                     # the next batch inflates while this one is on the device
+                        k1 = starts[bi + 1]
+                        futs[bi + 1] = [pool.submit(inflate, k) for k in range(k1, min(k1 + batch, N))]
+                finally:
+                    for tx in texts:
+                        tx.close()
+                t_wait += perf_counter() - t0
+                wsb = max(int(_abi.call("epg_seg_ws_bytes", sizes_b[k0 + j], nchrom)) for j in range(nb))
+                ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+                first = torch.empty(int(loff[-1]), dtype=torch.int32, device=dev)
+                state = torch.empty(int(loff[-1]), dtype=torch.int8, device=dev)
+                e0 = mark()
+                dtext[:total].copy_(pinned[:total], non_blocking=True)
+                e1 = mark()
+                for j in range(nb):
+                    k = k0 + j
+                    _abi.call("epg_seg_parse", C.c_void_p(dtext.data_ptr() + int(offs[j])), sizes_b[k], engine._ptr(names), nchrom, int(width),
+                              C.c_void_p(first.data_ptr() + 4 * int(loff[j])), C.c_void_p(state.data_ptr() + int(loff[j])), caps[k],
+                              C.c_void_p(runs.data_ptr() + 24 * max(nchrom, 1) * k), C.c_void_p(infos.data_ptr() + 32 * k),
+                              engine._ptr(ws), wsb, engine._stream())
+                e2 = mark()
+                slots[s] = [pinned, dtext, e2]
+                ev["upload"].append((e0, e1)), ev["parse"].append((e1, e2))
+                if ref is None:                                  # R_c, to allocate: the one synchronisation before the last
+                    bad = int(infos[0, 3].item())
+                    if bad >= 0:
+                        host_cols[0] = host_file(0, bad + 1)
+                        ref = {i: len(host_cols[0][c][0]) for i, c in enumerate(chroms) if c in host_cols[0]}
+                    else:
+                        r0 = runs[0].cpu().numpy()
+                        ref = {i: int(r0[i, 2]) for i in range(nchrom) if r0[i, 1] > 0}
+                    col_pitch = max(_align(max(ref.values(), default=0), 16), 16)
+                    need = sum(ref.values()) * ldx + batch * col_pitch
+                    free = torch.cuda.mem_get_info(dev)[0]
+                    if need > free:
+                        raise RuntimeError("the matrices of {} chromosomes and {} biosamples take {:.2f} GB of device memory, {:.2f} GB are free".format(
+                            len(ref), N, need / 1e9, free / 1e9))
+                    X = {i: torch.full((R, ldx), -1, dtype=torch.int8, device=dev) for i, R in ref.items()}
+                    cols = torch.empty((batch, col_pitch), dtype=torch.int8, device=dev)
+                for i, R in ref.items():
+                    e3 = mark()
+                    for j in range(nb):
+                        _abi.call("epg_seg_expand", C.c_void_p(first.data_ptr() + 4 * int(loff[j])), C.c_void_p(state.data_ptr() + int(loff[j])),
+                                  C.c_void_p(runs.data_ptr() + 24 * max(nchrom, 1) * (k0 + j)), i, C.c_void_p(cols.data_ptr() + j * col_pitch), R,
+                                  engine._stream())
+                    e4 = mark()
+                    _abi.call("epg_sbl_transpose", engine._ptr(cols), nb, col_pitch, R, engine._ptr(X[i]), ldx, k0, engine._stream())
+                    e5 = mark()
+                    ev["expand"].append((e3, e4)), ev["transpose"].append((e4, e5))
+        finally:
+            for fs in futs.values():                             # an error on the way: give the inflated buffers back
+                for f in fs:
+                    try:
+                        f.result().close()
+                    except Exception:
+                        pass
+    info = infos.cpu().numpy()                                   # the one synchronisation behind the batches
+    run = runs.cpu().numpy()
+    if timings is not None:
+        timings["inflate_s"] = t_wait
+        for k, pairs in ev.items():
+            timings[k + "_ms"] = float(sum(a.elapsed_time(b) for a, b in pairs))
+    rows = []
+    for k in range(N):
+        lines, _lo, _hi, bad = (int(v) for v in info[k])
+        if bad >= 0 and k not in host_cols:
+            host_cols[k] = host_file(k, bad + 1)
+        if k in host_cols:
+            rows.append({c: len(v[0]) for c, v in host_cols[k].items()})
+        else:
+            if lines != caps[k]:
+                raise RuntimeError("{}: {} lines on the device, {} on the host".format(files[k], lines, caps[k]))
+            rows.append({c: int(run[k, i, 2]) for i, c in enumerate(chroms) if run[k, i, 1] > 0})
+    held = check_files(files, chroms, rows, width, sizes)
+    out = {}
+    for i, c in enumerate(chroms):
+        if c not in held:
+            continue
+        for k, got in host_cols.items():
+            col = torch.empty(col_pitch, dtype=torch.int8, device=dev)
+            col[:held[c]].copy_(torch.from_numpy(got[c][0]))
+            _abi.call("epg_sbl_transpose", engine._ptr(col), 1, col_pitch, held[c], engine._ptr(X[i]), ldx, k, engine._stream())
+        lo, hi = torch.aminmax(X[i][:, :N])                      # every cell is a state of the grammar: the range as written is this + 1
+        out[c] = (X[i], (int(lo) + 1, int(hi) + 1))
+    torch.cuda.synchronize()
+    return out
