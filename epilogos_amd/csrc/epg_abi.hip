@@ -14,7 +14,10 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
+int g_force[FORCE_COUNT] = {0};
+
 int num_cus() {
+    if (g_force[FORCE_CUS] > 0) return g_force[FORCE_CUS];    // the tests' grid cap: before the cache, so set and reset act at once
     static thread_local int cached_dev = -1;
     static thread_local int cached_cus = 0;
     int dev = 0;
@@ -27,8 +30,6 @@ int num_cus() {
     }
     return cached_cus;
 }
-
-int g_force[FORCE_COUNT] = {0};
 
 }  // namespace epg
 

@@ -31,7 +31,15 @@ static inline const char* exp_env(const char* name) { return getenv(name); }
 static inline const char* exp_env(const char*) { return nullptr; }
 #endif
 
-enum Force { FORCE_NULL_SEQ = 0, FORCE_S3_SCORE_BINS, FORCE_S3_CONTRACTION, FORCE_S3_HIST_LDS, FORCE_K1_BLOCKS_PER_CU, FORCE_COUNT };
+// FORCE_CUS (5): num_cus() answers this value instead of the device's.  Every persistent grid is capped at num_cus() x something, so
+// with 1 a matrix of a few megabytes gives every wave tens of tiles: the tile-to-tile state of the persistent loops (prefetched
+// tiles, packed running sums and their flush, part cursors, reused LDS staging areas) runs at test sizes
+// (tests/test_hip_persistent_loops.py).  Results do not depend on it.  Every num_cus() site was read for values >= 1: the only
+// division by it is the split heuristic of epg_s3_gemm.hip (by a count >= 1, its result clamped to 1 .. nstages), every cap is
+// >= 1 and applied to a block count that is >= 1 (calls of no rows return before), and every capped kernel walks its tiles with a
+// gridDim stride, none assumes a minimum grid.  k_s3_score, k_s3_score_bl, k_s3_hist and the S3 contraction take one slice / task
+// per workgroup: their grids do not come from num_cus() and the switch does not change them.
+enum Force { FORCE_NULL_SEQ = 0, FORCE_S3_SCORE_BINS, FORCE_S3_CONTRACTION, FORCE_S3_HIST_LDS, FORCE_K1_BLOCKS_PER_CU, FORCE_CUS, FORCE_COUNT };
 extern int g_force[FORCE_COUNT];
 
 #define EPG_HIP(expr)                                                                         \

@@ -52,7 +52,9 @@ extern "C" {
  *   2  round 6: epg_test_force switch 4 replaces the undeclared epg_debug_set_variant; epg_ws_bytes(3, ...) quotes operand chunks
  *      of 2 M bins (1 M before); S3 score tables are correctly rounded float32 (the device's log2f before)
  *      (still 2: epg_simsearch_reduce and epg_simsearch_slices were ADDED for the live query; nothing a caller of version 2 relies on
- *      changed, and a library without them fails to load by its missing symbols) */
+ *      changed, and a library without them fails to load by its missing symbols)
+ *      (still 2: epg_test_force switch 5, the compute-unit count the grids are sized by, was ADDED for the tests; no entry point and
+ *      nothing a caller relies on changed) */
 #define EPG_ABI_VERSION 2
 
 int epg_version(void);
@@ -269,7 +271,11 @@ int epg_simsearch_slices(const int32_t* X, int64_t R, int32_t S, int32_t blockSi
  * on any shape so that the tests can compare it with the default on theirs.  which: 0 = the column-by-column null sampler
  * (value 1), 1 = the bin-per-lane S3 score kernel (1), 2 = the S3 contraction (1 = over all S states, 2 = the reduced one
  * whatever the call's size), 3 = the LDS-counter S3 count kernel (1), 4 = blocks per CU of the count pass's persistent grid (value =
- * the number; an A/B measurement switch, same results).  value 0 = the library decides (the default). */
+ * the number; an A/B measurement switch, same results), 5 = the compute-unit count every persistent grid is capped by (value =
+ * the count; epg_device_cus() reports it while it is set): with 1 a few thousand rows give every wave many tiles, so that the state
+ * the kernels carry from one tile to the next -- prefetched tiles, packed running counts and their flush, the cursor through
+ * several parts, re-used LDS staging areas -- runs at test sizes (tests/test_hip_persistent_loops.py); same results for every
+ * value.  value 0 = the library decides (the default). */
 int epg_test_force(int32_t which, int32_t value);
 
 #ifdef __cplusplus

@@ -179,6 +179,31 @@ def _parts(na, nb, S, rows):
     return [(_states(rng, r, na, S), _states(rng, r, nb, S)) for r in rows]
 
 
+dominant_states, hist = _states, _hist          # (the names other test modules use)
+
+
+def exceed_inputs(seed, n, R=513):
+    """A pool of n null distances (exact zeros of either sign, NaN = left out) and R observed ones with exact ties, zeros and
+    values beyond every null: the inputs of the epg_null_exceed tests."""
+    rng = np.random.default_rng([seed, n])
+    x = (rng.normal(size=n) * 3).astype(np.float32)
+    x[rng.random(n) < 0.3] = 0.0                                                # many exact zeros
+    x[rng.random(n) < 0.1] = -0.0
+    x[rng.random(n) < 0.2] = np.nan                                             # left out
+    d = (rng.normal(size=R) * 3).astype(np.float32)
+    d[:100] = rng.choice(x, 100) * rng.choice([-1.0, 1.0], 100).astype(np.float32)   # exact ties with pool values, either sign
+    d[100:110] = 0.0
+    d[110:115] = -0.0
+    d[115:120] = np.float32(1e6)                                                # larger than every null: 0
+    return x, d
+
+
+def exceed_np(x, d):
+    """#{non-NaN x : |x| >= |d[b]|} per b"""
+    a = np.sort(np.abs(x[~np.isnan(x)]))
+    return (len(a) - np.searchsorted(a, np.abs(d), side="left")).astype(np.int64)
+
+
 def _keys(rows):
     return [KEYS[i] if len(rows) == len(KEYS) else 1000 * i for i in range(len(rows))]
 

@@ -23,6 +23,11 @@ tests/golden/null_draws.json where a case is one of them.
 Out of reach of guard bands: a READ outside a buffer that changes no result (the clamped 16-byte load of a packed last row's
 last chunk, say) -- that needs an address sanitizer.  Stream ordering is not tested here either.
 
+CAPPED is a second, short list: the same builders on the one-CU grid of epg_test_force(5, 1) (tests/grid_cap.py), with row counts
+that give every wave three tiles and more and ragged multi-part layouts.  There a wave carries state from tile to tile -- tiles
+fetched one iteration ahead, staged tiles in re-used LDS -- and hostile padding and dirty memory are what shows a prefetch that
+reads a neighbour's rows or pad bytes as states, or a store of a stale staged tile.
+
 tests/test_abi_arena.py (no GPU) checks that every entry point of the header with a pointer parameter has a case here."""
 import collections
 import ctypes as C
@@ -38,6 +43,7 @@ torch = pytest.importorskip("torch")
 from oracle import oracle_np as onp
 from tests import simsearch_ref as ssr
 from tests.abi_arena import Arena
+from tests.grid_cap import FORCE_CUS, count_grid, pair_count_null_waves, pair_fused_waves, tile_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -208,6 +214,8 @@ def run_case(spec, abi):
     if spec.force:
         abi.call("epg_test_force", *spec.force)
     try:
+        if spec.force and spec.force[0] == FORCE_CUS:
+            assert abi.call("epg_device_cus") == spec.force[1], "the grid cap is not live"
         if spec.error is not None:                                         # the header promises an error code: nothing is touched
             run("refused", pad="random", prefill="random", seed=1)
             return
@@ -936,6 +944,55 @@ for _s, _r, _bs, _nb, _b in [(18, 1003, 5, 25, 1), (18, 1003, 5, 25, 257), (150,
     case("epg_simsearch_slices", b_slices, _s, _r, _bs, _nb, _b)
 
 
+# -- the one-CU grid.  tiles = (tiles of the launch that matters, waves of its capped grid), the waves from the dispatch code as
+#    tests/grid_cap.py restates it
+CAPPED = []
+
+
+def capped(entry, builder, *args, tiles, **kw):
+    ntiles, waves = tiles
+    assert ntiles // waves >= 3, "%s: %d tiles on %d waves" % (entry, ntiles, waves)
+    ident = "%s-%s" % (entry[4:], "-".join([str(a).replace(" ", "") for a in args] + ["%s=%s" % (k, str(v).replace(" ", "")) for k, v in kw.items()]))
+    CAPPED.append(pytest.param(entry, builder, args, kw, id=ident[:120]))
+
+
+def _tiles(rows, tile):
+    return sum((r + tile - 1) // tile for r in rows)
+
+
+def _count_waves(rows):                      # the count kernels: grid_for_tiles workgroups of 4 waves, tiles of 32 rows
+    return 4 * count_grid(32 * _tiles(rows, 32), 1)
+
+
+_W8 = 1 * 8 * 4                                              # k_s2_hist_wave, k_null_hist_rows: num_cus() x 8 workgroups of 4 waves, tiles of 64 rows
+assert tile_rows(2 * 2 * 18) == tile_rows(2 * 2 * 15) == 64
+
+
+_RAGGED = [2 * 768 + 5, 1, 130, 768 + 63, 0, 64, 777]                                      # whole, ragged and one-row tiles; an empty part
+capped("epg_bin_hist", b_count, "epg_bin_hist", 18, 833, 3 * 256 + 37, pitch="pad", tiles=(_tiles([805], 32), _count_waves([805])))
+capped("epg_bin_hist", b_count, "epg_bin_hist", 15, 129, 4 * 256 + 1, pitch=0, mis=3, tiles=(_tiles([1025], 32), _count_waves([1025])))
+capped("epg_bin_hist", b_count, "epg_bin_hist", 25, 4100, 3 * 256 + 5, pitch=5, tiles=(_tiles([773], 32), _count_waves([773])))
+capped("epg_bin_hist_s2", b_count, "epg_bin_hist_s2", 18, 379, 3 * 256 + 33, pitch="pad", tiles=(_tiles([801], 32), _count_waves([801])))
+capped("epg_bin_hist_s2", b_count, "epg_bin_hist_s2", 25, 1024, 3 * 256 + 1, pitch="wide", mis=9, tiles=(_tiles([769], 32), _count_waves([769])))
+capped("epg_bin_hist_s2", b_count, "epg_bin_hist_s2", 15, 1025, 3 * 256 + 1, pitch="pad", tiles=(_tiles([769], 32), _count_waves([769])))   # two passes
+# (parts: three groups per row -- 773 + 1 + 31 + 300 rows -- and seven -- 129 + 700 --, one launch each)
+capped("epg_bin_hist_parts", b_parts, 18, [(3 * 256 + 5, 379, "pad", 0), (1, 342, 0, 0), (0, 40, "pad", 0), (31, 379, 5, 3), (300, 342, "wide", 0),
+                                           (129, 833, "pad", 0), (700, 800, 0, 7)], tiles=(_tiles([129, 700], 32), _count_waves([129, 700])))
+capped("epg_bin_hist_parts", b_parts, 15, [(700, 1100, 0, 7), (33, 4100, "pad", 0), (1, 1025, 3, 0), (3 * 256 + 5, 1200, "pad", 0)],
+       tiles=(_tiles([700, 33, 1, 773], 32), _count_waves([700, 33, 1, 773])))                                          # the any-width loop
+capped("epg_pair_scores_s1_parts", b_pair_scores, 18, 70, 53, 70, 53, _RAGGED, parts=True, qstate=3, alias=True, tiles=(_tiles(_RAGGED, 64), pair_fused_waves(18, 70, 53, 70, 53)))
+capped("epg_pair_scores_s1_parts", b_pair_scores, 15, 40, 33, 20, 20, _RAGGED, parts=True, qstate=-1, tiles=(_tiles(_RAGGED, 64), pair_fused_waves(15, 40, 33, 20, 20)))
+capped("epg_pair_scores_s1_parts", b_pair_scores, 21, 12, 9, 6, 6, _RAGGED, parts=True, tiles=(_tiles(_RAGGED, 64), pair_fused_waves(21, 12, 9, 6, 6)))
+capped("epg_pair_count_null_parts", b_pair_count_null, 18, 379, 342, _RAGGED, pa="wide", mis=3, tiles=(_tiles(_RAGGED, 64), pair_count_null_waves(18, 379 + 342, 1)))
+capped("epg_pair_count_null_parts", b_pair_count_null, 25, 300, 257, _RAGGED + _RAGGED, tiles=(_tiles(_RAGGED + _RAGGED, 64), pair_count_null_waves(25, 300 + 257, 1)))
+capped("epg_null_hist_from_binhist_parts", b_null_from_hist, 18, 70, 53, [4100, 1, 0, 63, 2049], parts=True, tiles=(_tiles([4100, 1, 63, 2049], 64), _W8))
+capped("epg_null_hist_from_binhist_parts", b_null_from_hist, 15, 70, 53, [4100, 1, 0, 63, 2049], parts=True, ga=20, gb=20,
+       tiles=(_tiles([4100, 1, 63, 2049], 64), _W8))
+capped("epg_hist_s2_from_binhist", b_s2_from_hist, 18, 3 * 2048 + 70, 65536, tiles=(_tiles([3 * 2048 + 70], 64), _W8))
+capped("epg_hist_s2_from_binhist", b_s2_from_hist, 31, 3 * 2048 + 7, 4095, tiles=(_tiles([3 * 2048 + 7], 64), _W8))
+capped("epg_hist_s2_from_binhist_pair", b_s2_from_hist, 15, 3 * 2048 + 70, 30000, pair=True, tiles=(_tiles([3 * 2048 + 70], 64), _W8))
+
+
 @pytest.fixture(scope="module")
 def abi():
     from epilogos_amd import _abi, engine
@@ -947,6 +1004,18 @@ def abi():
 def test_contract(abi, entry, builder, args, kw):
     rng = np.random.default_rng(zlib.crc32(repr((entry, args, sorted(kw.items()))).encode()))
     run_case(builder(abi, rng, *args, **kw), abi)
+
+
+@pytest.mark.parametrize("entry,builder,args,kw", CAPPED)
+def test_contract_on_the_one_cu_grid(abi, entry, builder, args, kw):
+    rng = np.random.default_rng(zlib.crc32(repr(("one CU", entry, args, sorted(kw.items()))).encode()))
+    spec = builder(abi, rng, *args, **kw)
+    assert spec.force is None and spec.error is None
+    spec.force = (FORCE_CUS, 1)
+    real = abi.call("epg_device_cus")
+    assert real > 1
+    run_case(spec, abi)
+    assert abi.call("epg_device_cus") == real
 
 
 def test_a_store_into_a_guard_is_reported():

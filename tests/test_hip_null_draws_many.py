@@ -115,23 +115,7 @@ def test_draws_refuse_other_shapes_and_touch_nothing(eng, NA, NB, S):
 
 
 # ------------------------------------------------------------------------------------------------ (b) the exceedance counts
-def _exceed_np(x, d):
-    a = np.sort(np.abs(x[~np.isnan(x)]))
-    return (len(a) - np.searchsorted(a, np.abs(d), side="left")).astype(np.int64)
-
-
-def _exceed_inputs(seed, n, R=513):
-    rng = np.random.default_rng([seed, n])
-    x = (rng.normal(size=n) * 3).astype(np.float32)
-    x[rng.random(n) < 0.3] = 0.0                                                # many exact zeros
-    x[rng.random(n) < 0.1] = -0.0
-    x[rng.random(n) < 0.2] = np.nan                                             # left out
-    d = (rng.normal(size=R) * 3).astype(np.float32)
-    d[:100] = rng.choice(x, 100) * rng.choice([-1.0, 1.0], 100).astype(np.float32)   # exact ties with pool values, either sign
-    d[100:110] = 0.0
-    d[110:115] = -0.0
-    d[115:120] = np.float32(1e6)                                                # larger than every null: 0
-    return x, d
+from tests.null_sampler_ref import exceed_inputs as _exceed_inputs, exceed_np as _exceed_np   # noqa: E402  (shared with test_hip_persistent_loops.py)
 
 
 @pytest.mark.parametrize("seed", [1, 2])
