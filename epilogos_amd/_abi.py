@@ -1,5 +1,5 @@
 """ctypes binding of include/epilogos_amd.h, include/epilogos_scores_text.h, include/epilogos_groups.h,
-include/epilogos_nulldraws.h, include/epilogos_statebyline.h and include/epilogos_segments.h.  No fallbacks: a missing library or symbol raises."""
+include/epilogos_nulldraws.h, include/epilogos_statebyline.h, include/epilogos_segments.h and include/epilogos_simsearch_pick.h.  No fallbacks: a missing library or symbol raises."""
 import ctypes as C
 import re
 from pathlib import Path
@@ -102,7 +102,32 @@ SEG_PROTOTYPES = {
     "epg_seg_expand": (C.c_int, [_p, _p, _p, _i32, _p, _i64, _p]),
 }
 
+# and for include/epilogos_simsearch_pick.h, the device STEP 1 of simsearch -b (tests/test_simsearch_pick_host.py checks it)
+PICK_HEADER = HEADER.with_name("epilogos_simsearch_pick.h")
+PICK_PROTOTYPES = {
+    "epg_simsearch_rowscore": (C.c_int, [_p, _i64, _i32, _p, _p]),
+    "epg_simsearch_rolling_max": (C.c_int, [_p, _i64, _i32, _p, _p]),
+    "epg_simsearch_rank_ws_bytes": (_i64, [_i64]),
+    "epg_simsearch_rank": (C.c_int, [_p, _p, _p, _i64, _p, _p, _i64, _p]),
+    "epg_simsearch_pick_ws_bytes": (_i64, [_i64, _i32]),
+    "epg_simsearch_pick": (C.c_int, [_p, _i64, _i32, _i64, _p, _p, _p, _p, _i64, _p]),
+}
+
 _lib = None
+
+
+def pick_header_symbols():
+    """Function names declared in include/epilogos_simsearch_pick.h."""
+    txt = re.sub(r"/\*.*?\*/", "", PICK_HEADER.read_text(), flags=re.S)
+    return sorted(set(re.findall(r"\b(epg_[a-z0-9_]+)\s*\(", txt)))
+
+
+def pick_header_constant(name):
+    """The value of `#define name <integer>` of include/epilogos_simsearch_pick.h (EPG_PICK_TILE, EPG_PICK_MAX_W)."""
+    m = re.search(r"^#define\s+%s\s+(\d+)" % re.escape(name), PICK_HEADER.read_text(), flags=re.M)
+    if m is None:
+        raise RuntimeError("%s not found in %s" % (name, PICK_HEADER))
+    return int(m.group(1))
 
 
 def seg_header_symbols():
@@ -172,7 +197,7 @@ def load():
                                    "(there is no CPU fallback)" % path)
     lib = C.CDLL(str(path))
     for name, (res, args) in list(PROTOTYPES.items()) + list(TEXT_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + \
-            list(NULLDRAWS_PROTOTYPES.items()) + list(SBL_PROTOTYPES.items()) + list(SEG_PROTOTYPES.items()):
+            list(NULLDRAWS_PROTOTYPES.items()) + list(SBL_PROTOTYPES.items()) + list(SEG_PROTOTYPES.items()) + list(PICK_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = args

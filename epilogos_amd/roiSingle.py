@@ -39,31 +39,11 @@ def findSign(x):
     return "+" if x >= 0 else "-"
 
 
-def maxMean(chrom, start, end, score, roiWidth, maxRegions, _first_candidates=None):
-    """Top `maxRegions` non-overlapping windows of `roiWidth` bins by (rolling max, rolling mean, centre score).
-    Restates filter_regions.Filter.maxmean (:375-448) + helpers.maxMean (:253-274) on plain arrays.
-    Returns (chromosome, window start, window end, score = rolling max, original centre index), best first."""
-    W, h = int(roiWidth), int(roiWidth) // 2
-    R = len(score)
-    score = np.asarray(score, dtype=np.float64)
-    # window coordinates: Start of the bin h to the left, End of the bin h (odd W) / h-1 (even W) to the right
-    e_off = h if W % 2 else h - 1
-    lo, hi = h, R - e_off                      # rows that have both shifted coordinates (Series.shift + dropna)
-    if hi <= lo:
-        return [np.array([])] * 5
-    orig = np.arange(lo, hi)
-    w_start = np.asarray(start)[orig - h]
-    w_end = np.asarray(end)[orig + e_off]
-    sc = score[lo:hi]
-    # the rolling MEAN stays pandas' own (an online add/remove sum with compensation: its last bits depend on the whole history,
-    # and they break ties); the rolling MAX is exact in any implementation -- the native one is pandas' deque, threaded
-    rmean = pd.Series(sc).rolling(W, center=True).mean().to_numpy()
-    rmax = _io.rolling_max(sc, W)
-    ok = ~np.isnan(rmax)                       # incomplete edge windows
-    ok &= ~(np.asarray(w_start, dtype=np.int64) >= np.asarray(w_end, dtype=np.int64))   # windows spanning two chromosomes
-    keep = np.nonzero(ok)[0]
-    orig, w_start, w_end, sc, rmax, rmean = orig[keep], w_start[keep], w_end[keep], sc[keep], rmax[keep], rmean[keep]
-    n = len(keep)
+def greedyWalk(sc, rmean, rmax, W, maxRegions, _first_candidates=None):
+    """The positions (int64, ascending) of the top `maxRegions` non-overlapping windows of W among n candidates with the keys
+    (rmax, rmean, sc): walked best first, a window is taken when none of its W positions is covered yet."""
+    h = W // 2
+    n = len(rmax)
     # descending by (max, mean, score); ties keep genomic order (pandas' multi-key sort is stable).  The greedy pick only
     # consumes a PREFIX of that order, so instead of sorting all n windows (a whole genome has 15 M) the windows whose
     # rolling max reaches the m-th largest are sorted -- every one of them, ties at the threshold included, so their order
@@ -89,8 +69,35 @@ def maxMean(chrom, start, end, score, roiWidth, maxRegions, _first_candidates=No
         if len(chosen) >= maxRegions or len(cand) == n:
             break
         m_try = min(n, 8 * m_try)
-    chosen = np.array(sorted(chosen), dtype=np.int64)        # back to genomic order, then best first (stable)
-    # helpers.py:272 sorts by [RollingMax, RollingMean, Score], but by then Filter.filter has overwritten Score with RollingMax
+    return np.array(sorted(chosen), dtype=np.int64)        # back to genomic order
+
+
+def maxMean(chrom, start, end, score, roiWidth, maxRegions, _first_candidates=None):
+    """Top `maxRegions` non-overlapping windows of `roiWidth` bins by (rolling max, rolling mean, centre score).
+    Restates filter_regions.Filter.maxmean (:375-448) + helpers.maxMean (:253-274) on plain arrays.
+    Returns (chromosome, window start, window end, score = rolling max, original centre index), best first."""
+    W, h = int(roiWidth), int(roiWidth) // 2
+    R = len(score)
+    score = np.asarray(score, dtype=np.float64)
+    # window coordinates: Start of the bin h to the left, End of the bin h (odd W) / h-1 (even W) to the right
+    e_off = h if W % 2 else h - 1
+    lo, hi = h, R - e_off                      # rows that have both shifted coordinates (Series.shift + dropna)
+    if hi <= lo:
+        return [np.array([])] * 5
+    orig = np.arange(lo, hi)
+    w_start = np.asarray(start)[orig - h]
+    w_end = np.asarray(end)[orig + e_off]
+    sc = score[lo:hi]
+    # the rolling MEAN stays pandas' own (an online add/remove sum with compensation: its last bits depend on the whole history,
+    # and they break ties); the rolling MAX is exact in any implementation -- the native one is pandas' deque, threaded
+    rmean = pd.Series(sc).rolling(W, center=True).mean().to_numpy()
+    rmax = _io.rolling_max(sc, W)
+    ok = ~np.isnan(rmax)                       # incomplete edge windows
+    ok &= ~(np.asarray(w_start, dtype=np.int64) >= np.asarray(w_end, dtype=np.int64))   # windows spanning two chromosomes
+    keep = np.nonzero(ok)[0]
+    orig, w_start, w_end, sc, rmax, rmean = orig[keep], w_start[keep], w_end[keep], sc[keep], rmax[keep], rmean[keep]
+    chosen = greedyWalk(sc, rmean, rmax, W, maxRegions, _first_candidates)
+    # best first (stable): helpers.py:272 sorts by [RollingMax, RollingMean, Score], but by then Filter.filter has overwritten Score with RollingMax
     # (filter_regions.py:215-216, aggregation "max"): the third key repeats the first, windows that tie on max and mean stay
     # in genomic order (pinned by tests/golden/roi.npz roi_tie_*; sorting by the centre score instead does NOT match)
     final = chosen[np.lexsort((-rmean[chosen], -rmax[chosen]))]

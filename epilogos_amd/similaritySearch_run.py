@@ -5,6 +5,8 @@ sizes :288-345).  -b runs the three stages in this process (STEP 2 on the GPU) i
 the host thread pools (torch's; the process is not pinned).  `--gpus N` (cli(), not an option of main: main's options are the
 reference's) splits STEP 2 over N GPUs of the node instead: one child process per GPU, each running the module's argv interface
 (the reference's SLURM job) on its contiguous share of the ROIs, while this process stays GPU-free and runs STEP 1 and 3.
+`--step1 gpu` (cli() again; default `host`) picks the salient regions on the GPU instead (similaritySearch_step1.py: the same files);
+with --gpus N > 1 as one fresh child process on GPU 0 that finishes before STEP 2's children start.
 -q writes one similarity_search_region_*_recs.bed per query region: with -m, for the regions found in a built simsearch.bed.gz (the
 reference's lookup); with -s and no -m, for ANY region, searched live on the GPU against the scores file
 (similaritySearch_query.py)."""
@@ -23,6 +25,8 @@ import numpy as np
 import pandas as pd
 
 from .helpers import splitGpusOption
+
+STEP1_CHOICES = ("host", "gpu")
 
 BLOCK_SIZES_200 = {5000: 1, 10000: 2, 25000: 5, 50000: 10, 75000: 15, 100000: 20}
 BLOCK_SIZES_20 = {500: 1, 1000: 2, 2500: 5, 5000: 10, 7500: 15, 10000: 20}
@@ -69,9 +73,13 @@ def generateRegionArr(query):
                      + "or path to bed file containing query regions)")
 
 
-def buildSimSearch(scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatches, filterState, filterScore, gpus=1):
-    """STEP 1-3.  gpus > 1: STEP 2 as that many child processes, one per GPU (runChildren); nJobs (-j) is ignored either way."""
+def buildSimSearch(scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatches, filterState, filterScore, gpus=1, step1="host"):
+    """STEP 1-3.  gpus > 1: STEP 2 as that many child processes, one per GPU (runChildren); nJobs (-j) is ignored either way.
+    step1 "gpu": STEP 1 on the GPU (similaritySearch_step1), in this process with one GPU, as one child process (step1Job) with
+    more: this process then stays GPU-free."""
     from . import similaritySearch_calc, similaritySearch_max_mean, similaritySearch_write
+    if step1 not in STEP1_CHOICES:
+        raise ValueError("step1 must be one of %s, not %r" % (", ".join(STEP1_CHOICES), step1))
     print("\n\n\n        Building Similarity Search Results...", flush=True)
     windowBP, windowBins, blockSize = windowParameters(scoresPath, windowBP)
     if gpus > 1:
@@ -80,7 +88,13 @@ def buildSimSearch(scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatch
         import torch
         torch.set_num_threads(nCores)
     print("\n        STEP 1: Salient Region Selection", flush=True)
-    similaritySearch_max_mean.main(outputDir, scoresPath, windowBins, blockSize, windowBP, filterState, filterScore)
+    if step1 == "host":
+        similaritySearch_max_mean.main(outputDir, scoresPath, windowBins, blockSize, windowBP, filterState, filterScore)
+    elif gpus > 1:
+        runChildren([step1Job(outputDir, scoresPath, windowBins, blockSize, windowBP, filterState, filterScore, nCores)], step="STEP 1")
+    else:
+        from . import similaritySearch_step1
+        similaritySearch_step1.main(outputDir, scoresPath, windowBins, blockSize, windowBP, filterState, filterScore)
     print("\n        STEP 2: Similarity Search Calculation", flush=True)
     if gpus > 1:
         for stale in Path(outputDir).glob("simsearch_indices_*.npy"):     # an earlier build's: STEP 3 would merge them in
@@ -128,6 +142,21 @@ def childJobs(outputDir, windowBins, blockSize, nCores, nDesiredMatches, gpus):
     return jobs
 
 
+def step1Job(outputDir, scoresPath, windowBins, blockSize, windowBP, filterState, filterScore, nCores):
+    """(argv, env) of the STEP 1 child of a `--gpus N --step1 gpu` build: `python -m epilogos_amd.similaritySearch_step1` on GPU
+    LOCAL_RANK = 0, with the whole host thread budget (it runs alone, before STEP 2's children)."""
+    from ._io import node_cores
+    budget = min(nCores, node_cores()) if nCores > 0 else node_cores()
+    root = str(Path(__file__).resolve().parents[1])
+    env = dict(os.environ)
+    env["LOCAL_RANK"] = "0"
+    env["OMP_NUM_THREADS"] = str(budget)
+    env["PYTHONPATH"] = root + (os.pathsep + env["PYTHONPATH"] if env.get("PYTHONPATH") else "")
+    argv = [sys.executable, "-m", "epilogos_amd.similaritySearch_step1", str(Path(outputDir).resolve()), str(Path(scoresPath).resolve()),
+            str(windowBins), str(blockSize), str(windowBP), str(filterState), str(filterScore)]
+    return argv, env
+
+
 def _stop(procs, grace=10.0):
     """SIGTERM, up to `grace` seconds for all of them together, then SIGKILL."""
     for p in procs:
@@ -151,10 +180,10 @@ def _status(rc):
     return "exited with status %d" % rc
 
 
-def runChildren(jobs, poll=0.05, tail=20):
+def runChildren(jobs, poll=0.05, tail=20, step="STEP 2"):
     """Start every (argv, env) job, wait for all of them, and pass their stderr on.  The first that fails ends the build:
     the others are stopped (_stop) and SystemExit names the child, its status and the last lines of its stderr.  A failed
-    child is never started again.  A SIGTERM to this process ends the build the same way (the children are stopped)."""
+    child is never started again.  `step` names the children's step in that message.  A SIGTERM to this process ends the build the same way (the children are stopped)."""
     procs, errs = [], []
 
     def terminated(signum, _frame):
@@ -177,8 +206,8 @@ def runChildren(jobs, poll=0.05, tail=20):
                 if rc != 0:
                     _stop([procs[j] for j in running])
                     last = "\n".join(err.splitlines()[-tail:])
-                    raise SystemExit("ERROR: similarity search STEP 2 child %d of %d %s; STEP 3 is skipped: no simsearch.bed.gz "
-                                     "was written.%s" % (i, len(procs), _status(rc),
+                    raise SystemExit("ERROR: similarity search %s child %d of %d %s; STEP 3 is skipped: no simsearch.bed.gz "
+                                     "was written.%s" % (step, i, len(procs), _status(rc),
                                                          "\nLast lines of its stderr:\n" + last if last else ""))
                 if err:
                     sys.stderr.write(err)
@@ -253,6 +282,9 @@ def main(buildBool, scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatc
     gpus = (click.get_current_context().obj or {}).get("gpus")        # cli()'s --gpus: None when not given
     if gpus is not None and query != "":
         raise click.UsageError("--gpus applies to -b only: query mode does not use a GPU")
+    step1 = (click.get_current_context().obj or {}).get("step1")      # cli()'s --step1: None when not given
+    if step1 is not None and query != "":
+        raise click.UsageError("--step1 applies to -b only: query mode builds no index")
     if query != "" and simSearchPath is None and scoresPath is None:
         raise click.UsageError("-q needs either -m simsearch.bed.gz (look the region up in a built index) or -s scores.txt.gz "
                                "(search the region live on the GPU)")
@@ -263,7 +295,7 @@ def main(buildBool, scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatc
         raise NotADirectoryError("Given path is not a directory: {}".format(str(outputDir)))
     if buildBool:
         buildSimSearch(scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatches, filterState, filterScore,
-                       gpus=1 if gpus is None else gpus)
+                       gpus=1 if gpus is None else gpus, step1="host" if step1 is None else step1)
     elif simSearchPath is not None:
         querySimSearch(query, simSearchPath, outputDir)
     else:
@@ -279,17 +311,36 @@ def resolveGpus(value):
     return run._visible_gpus() if n == 0 else n
 
 
+def splitStep1Option(argv):
+    """`--step1 V` / `--step1=V`, anywhere in an argument list -> (V as written, the last one given; None when there is none; ""
+    for a trailing `--step1`) and the list without them (splitGpusOption's rule)."""
+    value, out, skip = None, [], False
+    for a in argv:
+        if skip:
+            value, skip = a, False
+        elif a == "--step1":
+            value, skip = "", True
+        elif a.startswith("--step1="):
+            value = a[len("--step1="):]
+        else:
+            out.append(a)
+    return value, out
+
+
 def cli(argv=None):
-    """`python -m epilogos_amd.similaritySearch_run`: main with `--gpus N` / `--gpus=N` taken out of the arguments first (main's
-    click options stay the reference's); the value reaches main through click's ctx.obj."""
+    """`python -m epilogos_amd.similaritySearch_run`: main with `--gpus N` / `--gpus=N` and `--step1 {host,gpu}` taken out of the
+    arguments first (main's click options stay the reference's); the values reach main through click's ctx.obj."""
     argv = sys.argv[1:] if argv is None else list(argv)
     value, rest = splitGpusOption(argv)
+    step1, rest = splitStep1Option(rest)
     try:
         gpus = None if value is None else resolveGpus(value)
+        if step1 is not None and step1 not in STEP1_CHOICES:
+            raise click.UsageError("--step1 takes one of %s, not %r" % (", ".join(STEP1_CHOICES), step1))
     except click.UsageError as e:
         e.show()
         sys.exit(e.exit_code)
-    main.main(args=rest, prog_name="python -m epilogos_amd.similaritySearch_run", obj={"gpus": gpus})
+    main.main(args=rest, prog_name="python -m epilogos_amd.similaritySearch_run", obj={"gpus": gpus, "step1": step1})
 
 
 if __name__ == "__main__":

@@ -30,7 +30,17 @@ int32 grid back to the host as int64, which readGrid's host-array contract costs
 epg_simsearch_slices of all N (`slices_ms`), per region for slices + search one region per call and at the workspace cap's batch
 (`search_ms_per_region`), and for the coordinates and files (`write_ms`).  `genome` has the reduce kernel alone on --genome-bins
 bins made on the device (best of --reps + 1), a device-to-device copy of the same bytes on the same device, the host's
-reduceGenomeIndices + gather of the same array, and slices + search of the N regions on that genome."""
+reduceGenomeIndices + gather of the same array, and slices + search of the N regions on that genome.
+
+    python tools/simsearch_bench.py --step1 [--bins 1000000] [--genome-bins 15000000]
+
+times STEP 1 of the build both ways on the same synthetic scores file, one JSON line per path: the host's
+(similaritySearch_max_mean: read, pick = roiSingle.maxMean, slices = makeSlice per region + removeRegions, reduce, the
+genome_stats write) and the device's (similaritySearch_step1: read, rowscore, the pandas rolling mean with its download and
+upload, rolling max, compaction, rank, pick with its sweeps, final order, slices, reduce, the genome_stats write on its thread), and
+stops if the two paths' files differ.  A third line has the rank and the pick alone on --genome-bins windows whose three keys are
+made in memory, with one plateau of 90 000 tied windows, against roiSingle.greedyWalk (maxMean's sort and walk) on the same
+keys; it stops if the two picks differ."""
 import argparse
 import csv
 import ctypes as C
@@ -62,7 +72,11 @@ def main():
     ap.add_argument("--genome-bins", type=int, default=15_000_000, help="bins of the reduce kernel's own measurement (--query)")
     ap.add_argument("--read-reps", type=int, default=5, help="reads of the scores file per reader; the medians are reported (--query)")
     ap.add_argument("--bgzf", action="store_true", help="write the synthetic scores file as BGZF: its blocks inflate in parallel (--query)")
+    ap.add_argument("--step1", action="store_true", help="time STEP 1 of the build on the host and on the device instead")
     a = ap.parse_args()
+    if a.step1:
+        step1_bench(a)
+        return
     if a.query is not None:
         query_bench(a)
         return
@@ -266,6 +280,88 @@ def query_bench(a):
                      "batch_at_cap": calc_batch(Pg, S, nblk, N), "slices_ms": round(t_sl * 1e3, 4),
                      "search_ms_per_region": {"batch_1": round(t_one / n1 * 1e3, 4), "batch_at_cap": round(t_cap / N * 1e3, 4)}}
     print(json.dumps(res), flush=True)
+
+
+def step1_bench(a):
+    """STEP 1 of `-b` on the host and on the device (--step1 gpu): the stages of both, the files compared; then rank + pick at
+    genome size against roiSingle.greedyWalk."""
+    import torch
+    from epilogos_amd import engine, roiSingle
+    from epilogos_amd import similaritySearch_max_mean as mm
+    from epilogos_amd import similaritySearch_step1 as step1
+    engine.require_gpu()
+    S, blockSize, windowBins, windowBP = a.states, 5, 125, 25000
+    r3 = lambda d: {k: (round(v, 3) if isinstance(v, float) else v) for k, v in d.items()}
+    with tempfile.TemporaryDirectory() as d:
+        sp = Path(d) / "scores.txt.gz"
+        synthetic_scores(sp, a.bins, S)
+        host, dev = Path(d) / "host", Path(d) / "dev"
+        host.mkdir(), dev.mkdir()
+        torch.zeros(1, device="cuda")                 # the context is not part of the first stage
+        tm = {}
+        t0 = t = time.perf_counter()
+        stateScores, inputArr, genome = mm.readScores(sp)
+        tm["read_s"] = time.perf_counter() - t; t = time.perf_counter()
+        np.savez_compressed(host / "genome_stats", scores=stateScores, coords=inputArr[:, :3])
+        tm["genome_stats_write_s"] = time.perf_counter() - t; t = time.perf_counter()
+        chrom, start, end, _sc, orig = roiSingle.maxMean(inputArr[:, 0], inputArr[:, 1], inputArr[:, 2], inputArr[:, 3].astype(np.float64),
+                                                         windowBins, genome.shape[0] // windowBins)
+        tm["pick_s"] = time.perf_counter() - t; t = time.perf_counter()
+        roiCoords = np.empty((len(orig), 3), dtype=object)
+        roiCoords[:, 0], roiCoords[:, 1], roiCoords[:, 2] = chrom, start, end
+        roiCube = np.stack([mm.makeSlice(genome, i, windowBins, blockSize) for i in orig])
+        roiCoords, roiCube = mm.removeRegions(roiCoords, roiCube, -1, -1)
+        np.savez_compressed(file=host / "simsearch_cube", scores=roiCube / mm.SCALE, coords=roiCoords)
+        tm["slices_s"] = time.perf_counter() - t; t = time.perf_counter()
+        mm.reduceGenome(host, genome, blockSize)
+        tm["reduce_s"] = time.perf_counter() - t
+        tm["total_s"] = time.perf_counter() - t0
+        print(json.dumps(dict({"tool": "simsearch_bench", "mode": "step1", "path": "host", "bins": a.bins, "states": S,
+                               "regions": int(len(roiCoords))}, **r3(tm))), flush=True)
+        del stateScores, inputArr, genome, roiCube
+
+        import contextlib
+        import io
+        with contextlib.redirect_stdout(io.StringIO()):
+            step1.main(dev, sp, windowBins, blockSize, windowBP, -1, -1)          # warm-up (code objects, sort configuration)
+            tm = {}
+            t0 = time.perf_counter()
+            step1.main(dev, sp, windowBins, blockSize, windowBP, -1, -1, timings=tm)
+            tm["total_s"] = time.perf_counter() - t0
+        for f in ("genome_stats.npz", "simsearch_cube.npz"):
+            x, y = np.load(host / f, allow_pickle=True), np.load(dev / f, allow_pickle=True)
+            if not (x["scores"].tobytes() == y["scores"].tobytes() and x["coords"].shape == y["coords"].shape and (x["coords"] == y["coords"]).all()):
+                sys.exit("simsearch_bench: the host's and the device's %s differ: no timing of a wrong result" % f)
+        if (host / "reduced_genome.npy").read_bytes() != (dev / "reduced_genome.npy").read_bytes():
+            sys.exit("simsearch_bench: the host's and the device's reduced_genome.npy differ: no timing of a wrong result")
+        print(json.dumps(dict({"tool": "simsearch_bench", "mode": "step1", "path": "gpu", "bins": a.bins, "states": S,
+                               "files_equal_to_host": True}, **r3(tm))), flush=True)
+
+    # rank + pick alone at genome size: keys made in memory, one plateau of 90 000 windows tied on all three
+    n, W, plateau = a.genome_bins, windowBins, 90000
+    rng = np.random.default_rng(3)
+    rmax = rng.integers(0, 40000, size=n) / 16.0                  # a few thousand equal maxima each: the means decide
+    rmean, sc = rng.random(n), rng.random(n)
+    p0 = n // 3
+    rmax[p0:p0 + plateau], rmean[p0:p0 + plateau], sc[p0:p0 + plateau] = 2600.0, 0.5, 0.5      # the best windows of all
+    maxRegions = n // W
+    t = time.perf_counter()
+    want = roiSingle.greedyWalk(sc, rmean, rmax, W, maxRegions)
+    host_s = time.perf_counter() - t
+    k = [torch.from_numpy(v).cuda() for v in (rmax, rmean, sc)]
+    step1.pickWindows(step1.rankWindows(*[v[:100000] for v in k]), W, 100)        # warm-up
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    rank = step1.rankWindows(*k)
+    torch.cuda.synchronize()
+    rank_s = time.perf_counter() - t; t = time.perf_counter()
+    got, launches = step1.pickWindows(rank, W, maxRegions)
+    pick_s = time.perf_counter() - t
+    if not np.array_equal(got, want):
+        sys.exit("simsearch_bench: the device's pick and roiSingle.greedyWalk differ at %d windows: no timing of a wrong result" % n)
+    print(json.dumps({"tool": "simsearch_bench", "mode": "step1", "path": "rank_pick", "windows": n, "W": W, "plateau": plateau,
+                      "maxRegions": maxRegions, "picked": int(len(got)), "host_sort_walk_s": round(host_s, 2), "gpu_rank_ms": round(rank_s * 1e3, 2),
+                      "gpu_pick_ms": round(pick_s * 1e3, 2), "pick_launches": launches, "equal_to_host": True}), flush=True)
 
 
 def calc_ranges(g):
