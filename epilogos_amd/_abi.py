@@ -1,5 +1,6 @@
 """ctypes binding of include/epilogos_amd.h, include/epilogos_scores_text.h, include/epilogos_groups.h,
-include/epilogos_nulldraws.h, include/epilogos_statebyline.h, include/epilogos_segments.h and include/epilogos_simsearch_pick.h.  No fallbacks: a missing library or symbol raises."""
+include/epilogos_nulldraws.h, include/epilogos_statebyline.h, include/epilogos_segments.h, include/epilogos_simsearch_pick.h and
+include/epilogos_census.h.  No fallbacks: a missing library or symbol raises."""
 import ctypes as C
 import re
 from pathlib import Path
@@ -113,7 +114,19 @@ PICK_PROTOTYPES = {
     "epg_simsearch_pick": (C.c_int, [_p, _i64, _i32, _i64, _p, _p, _p, _p, _i64, _p]),
 }
 
+# and for include/epilogos_census.h, the per-biosample state census (tests/test_census_host.py checks it)
+CENSUS_HEADER = HEADER.with_name("epilogos_census.h")
+CENSUS_PROTOTYPES = {
+    "epg_state_census": (C.c_int, [_p, _i64, _i32, _i64, _i32, _p, _p, _p, _p]),
+}
+
 _lib = None
+
+
+def census_header_symbols():
+    """Function names declared in include/epilogos_census.h."""
+    txt = re.sub(r"/\*.*?\*/", "", CENSUS_HEADER.read_text(), flags=re.S)
+    return sorted(set(re.findall(r"\b(epg_[a-z0-9_]+)\s*\(", txt)))
 
 
 def pick_header_symbols():
@@ -197,7 +210,8 @@ def load():
                                    "(there is no CPU fallback)" % path)
     lib = C.CDLL(str(path))
     for name, (res, args) in list(PROTOTYPES.items()) + list(TEXT_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + \
-            list(NULLDRAWS_PROTOTYPES.items()) + list(SBL_PROTOTYPES.items()) + list(SEG_PROTOTYPES.items()) + list(PICK_PROTOTYPES.items()):
+            list(NULLDRAWS_PROTOTYPES.items()) + list(SBL_PROTOTYPES.items()) + list(SEG_PROTOTYPES.items()) + list(PICK_PROTOTYPES.items()) + \
+            list(CENSUS_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -192,6 +192,11 @@ class _HipSession:
         self._pending, self._pending_rows = [], 0        # queued parts (what _count needs of each) and their rows
         self._launched = False                           # launch() ran: STEP 2 is on the device, STEP 3 of `_early` parts enqueued
         self._early = {}                                 # part id -> its device results, computed before the host-side checks
+        # --check-states: every uploaded matrix is censused where it first sits on the device (_upload); ticket -> (other [N],
+        # first_bad [1], the byte at first_bad [1]), device tensors, read by state_offenders()
+        self.check_states = False
+        self.state_checks = {}
+        self._census_scratch = {}
 
     @property
     def pool(self):
@@ -245,7 +250,35 @@ class _HipSession:
             self._release_later(ev, buf)
         self.n_uploads += 1
         self.upload_bytes += X.numel()
+        if self.check_states and R and N:
+            self._check_upload(X, N, ticket)
         return X
+
+    def _check_upload(self, X, N, ticket):
+        """--check-states: the census of a matrix just uploaded, all N columns of it.  The per-state counts go to a scratch table
+        nobody reads (the ABI wants one); `other`, `first_bad` and the offending byte itself -- fetched now, the matrix may be
+        gone when the verdict is taken -- stay on the device, nothing synchronises."""
+        t, eng = self.torch, self.eng
+        scratch = self._census_scratch.get(N)
+        if scratch is None:
+            scratch = self._census_scratch[N] = t.zeros((N, self.S), dtype=t.int64, device=self.device)
+        _c, other, fb = eng.state_census(X, N, self.S, census=scratch)
+        at = t.where(fb == eng.FIRST_BAD_NONE, t.zeros_like(fb), fb)
+        self.state_checks[ticket] = (other, fb, X[at // N, at % N])
+
+    def state_offenders(self):
+        """{ticket: (row, column, byte 0 .. 255, how many bytes)} of the uploaded matrices that hold a byte that is no state
+        (row and column 0-based, of the first such byte in row-major order).  Synchronises."""
+        out = {}
+        for ticket, (other, fb, byte) in self.state_checks.items():
+            n = int(other.sum().item())
+            if n:
+                N = other.numel()
+                at = int(fb.item())
+                out[ticket] = (at // N, at % N, int(byte.item()) & 0xff, n)
+        self.state_checks = {}
+        self._census_scratch = {}
+        return out
 
     def _release_later(self, ev, buf):
         import queue

@@ -187,9 +187,10 @@ class _Readers:
     workers and parts handed over in file order: every part waited behind chr1, whose inflate -- the longest job, started
     together with 23 others on 16 cores -- took 7 s instead of 3; the count pass does not care about the order."""
 
-    def __init__(self, jobs):
+    def __init__(self, jobs, raw=False):
         import threading
         self.jobs = [(Path(p), lo, hi) for p, lo, hi in jobs]
+        self.raw = bool(raw)                               # --check-states: .epgm bytes as they are (helpers.readTable raw=True)
         self.sess = None
         self.ready = threading.Event()
         self.failed = False
@@ -246,7 +247,7 @@ class _Readers:
             # largest files).  (With every reader fanning its short parse phases out to all cores next to fifteen inflating
             # threads, a cgroup CPU quota throttles the whole process for the rest of each 100 ms period: phases that take
             # 0.03 s alone took 1 s.)
-            arr, loc, rng = readTable(path, None if hi is None else (lo, hi), alloc=alloc, with_range=True, threads=0)
+            arr, loc, rng = readTable(path, None if hi is None else (lo, hi), alloc=alloc, with_range=True, threads=0, raw=self.raw)
         except BaseException:
             if self.sess is not None:
                 self.sess.skip(ticket)
@@ -279,11 +280,11 @@ class _Readers:
 _early = None
 
 
-def start_readers_early(jobs):
+def start_readers_early(jobs, raw=False):
     """Called by the command line before it imports torch: the rank's readers start on `jobs` now; the stage driver picks them
     up if it arrives at the same job list (`_stream_parts`), else they are aborted and fresh ones start."""
     global _early
-    _early = _Readers(jobs)
+    _early = _Readers(jobs, raw)
     return _early
 
 
@@ -294,17 +295,17 @@ def abort_early_readers():
         _early = None
 
 
-def _stream_parts(jobs, sess, numStates):
+def _stream_parts(jobs, sess, numStates, raw=False):
     """-> generator of (ticket, states, N, Locations) in order of completion (see _Readers)."""
     global _early
     jobs = [(Path(p), lo, hi) for p, lo, hi in jobs]
     readers, _early = _early, None
-    if readers is not None and readers.jobs != jobs:
+    if readers is not None and (readers.jobs != jobs or readers.raw != bool(raw)):
         readers.abort()
         readers.pool.shutdown(wait=True)
         readers = None
     if readers is None:
-        readers = _Readers(jobs)
+        readers = _Readers(jobs, raw)
     readers.attach(sess)
     return readers.parts(numStates)
 
@@ -500,6 +501,7 @@ class _Single:
     n_payload = 1                                      # arrays of a part that travel to rank 0, besides its Locations
 
     n_widths = 1                                       # widths the session works with: N
+    check_states = False                               # --check-states (set by the run_* functions)
 
     def __init__(self, files, numStates, saliency, keep_temps, columns=None):
         self.groups, self.S, self.sal, self.keep_temps = (files,), numStates, saliency, keep_temps
@@ -541,6 +543,7 @@ class _Paired:
     kind, census, upload_note = "pairwiseDelta", "paired", " x 2 groups"
     n_payload = 4
     n_widths = 2                                       # NA, NB
+    check_states = False
 
     def __init__(self, files1, files2, numStates, saliency, quiescentState, groupSize, nullSeed, keep_temps, nullDraws=1):
         self.groups, self.S, self.sal, self.keep_temps = (files1, files2), numStates, saliency, keep_temps
@@ -638,6 +641,65 @@ def _check_columns_fit(cols, n, path):
         raise ValueError("biosample {} is not in {}: the file has {} biosample columns".format(int(cols.max()) + 1, path, n))
 
 
+class StateCheckFailed(SystemExit):
+    """--check-states found a byte that is no state: every rank leaves with this (exit status 1), rank 0 has printed the message."""
+
+
+_KEY_NONE = (1 << 62)                                  # above every key of _verdict_key
+
+
+def state_check_message(path, row, column, byte, S):
+    return ("ERROR: [--check-states] {}: row {} (0-based), biosample {}: byte {} is not a state of the {}-state model "
+            "(a state byte is 0..{})".format(path, row, column, byte, S, S - 1))
+
+
+def _verdict_key(fi, row, col, g):
+    """(file in run order, row, column, group) packed so that integer order is that order (paired mode: group A before B as the
+    last tie-break); None when a field does not fit (14, 31, 16 bits and 1)."""
+    if not (0 <= fi < 1 << 14 and 0 <= row < 1 << 31 and 0 <= col < 1 << 16 and 0 <= g < 2):
+        return None
+    return (((fi << 31 | row) << 16 | col) << 1) | g
+
+
+def _verdict_fields(key):
+    """-> (fi, row, col, g) of a key."""
+    return key >> 48, (key >> 17) & 0x7fffffff, (key >> 1) & 0xffff, key & 1
+
+
+def _state_verdict(d, sess, mode, jobs):
+    """--check-states, after STEP 1: the smallest (file in run order, row, biosample) whose byte is no state, over every matrix
+    any rank uploaded (paired mode: group A before group B at the same position).  jobs: this rank's (file index, first row, ...)
+    per part, as parsed.  Every rank takes part in the same two all-reduces (the minimum of the packed position together with
+    "a position did not fit the key", then the byte of the rank that holds the minimum), so all of them learn the one verdict and
+    stop together -- no rank raises on its own; rank 0 prints the one message, the same for any number of ranks."""
+    G = len(mode.groups)
+    key, byte, unfit = _KEY_NONE, 0, 0
+    for t, (row, col, b, _n) in sess.state_offenders().items():
+        k, g = divmod(t, G)
+        cand = _verdict_key(jobs[k][0], jobs[k][1] + row, col, g)
+        if cand is None:                               # (beyond 16 384 files or 2^31 rows a file: every rank hears of it below)
+            unfit = 1
+        elif cand < key:
+            key, byte = cand, b
+    if d.world > 1:
+        first, unfit = d.max_ints([-key, unfit])
+        first = -first
+    else:
+        first = key
+    if unfit:
+        raise ValueError("--check-states: a byte that is no state lies beyond file 16384 or row 2^31 of a file: its position does not "
+                         "fit the verdict's key")
+    if first == _KEY_NONE:
+        return
+    if d.world > 1:
+        byte = d.max_ints([byte if key == first else 0])[0]
+    fi, row, col, g = _verdict_fields(first)
+    if d.rank == 0:
+        print(state_check_message(mode.groups[g][fi], row, col + 1, byte, mode.S), flush=True)
+    d.barrier()                                        # the message is out before any rank's exit makes a launcher end the others
+    raise StateCheckFailed(1)
+
+
 def _run_groups(mode, outputDir, fileTag, backend, defer_writes):
     """STEP 1-3 of either mode over the bin-range partition -> (exp_freq, results of rank 0 by file stem, else None)."""
     be = backend if backend is not None else _backend.get()
@@ -651,17 +713,22 @@ def _run_groups(mode, outputDir, fileTag, backend, defer_writes):
     d.barrier()
     layout, rows, my_parts, owner = _plan(files, d, tm, *mode.groups[1:])
     sess = mode.open(be)
+    if mode.check_states:
+        sess.check_states = True                       # (--check-states: every uploaded matrix is censused, see _state_verdict)
 
     # STEP 1: every part of this rank is parsed, uploaded once and counted; what the score pass needs stays resident
     pids, locs, widths = [None] * len(my_parts), [None] * len(my_parts), [0] * mode.n_widths
     # paired: part k's two groups are jobs 2k and 2k + 1, the second group follows the first one's row ranges
-    with closing(_stream_parts([(group[fi], lo, hi) for fi, lo, hi in my_parts for group in mode.groups], sess, mode.S)) as stream:
+    with closing(_stream_parts([(group[fi], lo, hi) for fi, lo, hi in my_parts for group in mode.groups], sess, mode.S,
+                               raw=mode.check_states)) as stream:
         for t, arr, n, loc in stream:                  # in order of completion
             k, g = divmod(t, len(mode.groups))
             mode.see_width(widths, g, n)               # an empty file has no width: it must not be the one that is remembered
             if g == 0:
                 locs[k] = loc
             pids[k] = mode.add(sess, t, arr, n, my_parts[k])
+    if mode.check_states:                              # before anything of this run is written
+        _state_verdict(d, sess, mode, my_parts)
     if layout == "whole":                              # single rank: the row counts come from the parse
         rows = [len(l) for l in locs]
         my_parts = [(fi, 0, rows[fi]) for fi in range(len(files))]
@@ -741,18 +808,19 @@ def _run_groups(mode, outputDir, fileTag, backend, defer_writes):
 
 
 def run_single_group(files, numStates, saliency, outputDir, fileTag, verbose=False, backend=None, device=None,
-                     keep_temp_scores=True, defer_writes=False, columns=None):
+                     keep_temp_scores=True, defer_writes=False, columns=None, checkStates=False):
     """STEP 1-3 for a single group over `files` (one per chromosome).  Returns (exp_freq float32, results) where results
     (rank 0 only, else None) maps file stem -> (chrName, float32 scores [R, S], _io.Locations) for an in-process STEP 4.
     keep_temp_scores writes the reference's temp_scores_{tag}_{stem}.npz (scores.py:166-169) for a STEP 4 run
     elsewhere; the command line skips them because its STEP 4 would delete them a moment later.  columns (0-based indices of
     biosample columns): the group is these columns of the files; the outputs are those of files cut to them beforehand."""
     mode = _Single([Path(f) for f in files], numStates, saliency, keep_temp_scores, columns)
+    mode.check_states = bool(checkStates)
     return _run_groups(mode, outputDir, fileTag, backend, defer_writes)
 
 
 def run_paired_groups(files1, files2, numStates, saliency, outputDir, fileTag, quiescentState, groupSize, nullSeed,
-                      verbose=False, backend=None, device=None, keep_temps=True, defer_writes=False, nullDraws=1):
+                      verbose=False, backend=None, device=None, keep_temps=True, defer_writes=False, nullDraws=1, checkStates=False):
     """STEP 1-3 of paired mode (reference run.py:205-221,258-279 + scores.py:172-256) over the bin-range partition.
     Background counts are taken over the column concatenation [A|B] (helpers.py:173) -- from the two groups' own
     histograms, each group is uploaded once -- all-reduced once; each rank then scores A, B and the two shuffled null
@@ -766,14 +834,16 @@ def run_paired_groups(files1, files2, numStates, saliency, outputDir, fileTag, q
     nullPool (their number), from which STEP 4 takes empirical p-values; keep_temps writes them as temp_nullExceed."""
     mode = _Paired([Path(f) for f in files1], [Path(f) for f in files2], numStates, saliency, quiescentState, groupSize, nullSeed,
                    keep_temps, nullDraws)
+    mode.check_states = bool(checkStates)
     return _run_groups(mode, outputDir, fileTag, backend, defer_writes)
 
 
 def run_paired_columns(files, colsA, colsB, numStates, saliency, outputDir, fileTag, quiescentState, groupSize, nullSeed,
-                       verbose=False, backend=None, device=None, keep_temps=True, defer_writes=False, nullDraws=1):
+                       verbose=False, backend=None, device=None, keep_temps=True, defer_writes=False, nullDraws=1, checkStates=False):
     """run_paired_groups for two groups that are column groups (0-based indices) of ONE set of files: every file is parsed and
     uploaded once and feeds both groups.  The partition, the hand-over between ranks and the all-reduce are run_paired_groups':
     they move histograms and row ranges.  Outputs are those of run_paired_groups on files cut to the groups beforehand."""
     mode = _PairedColumns([Path(f) for f in files], colsA, colsB, numStates, saliency, quiescentState, groupSize, nullSeed, keep_temps,
                           nullDraws)
+    mode.check_states = bool(checkStates)
     return _run_groups(mode, outputDir, fileTag, backend, defer_writes)

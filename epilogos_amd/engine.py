@@ -470,6 +470,30 @@ def bin_hist_groups(X, N, S, groups, counts=None, want_hist=True):
     return Hs, counts.view(G, S)
 
 
+FIRST_BAD_NONE = np.iinfo(np.int64).max     # what first_bad holds while no byte of the matrix is "not a state"
+
+
+def state_census(X, N, S, census=None, other=None, first_bad=None, want_other=True, want_first_bad=True):
+    """The per-biosample census of a state matrix (epg_state_census): -> (census int64 [N, S], other int64 [N], first_bad int64 [1]).
+    census[n, s] = rows whose column n holds state s, other[n] = rows whose byte there is no state (the WHOLE byte is compared:
+    0xFF, S .. 31 and the bytes 32 .. 254 that the count kernels would alias), first_bad = the smallest row * N + column of such a
+    byte, FIRST_BAD_NONE when there is none.  Tensors given are added to (first_bad: minimised); want_other / want_first_bad
+    False pass NULL and return None in their place."""
+    R, ldx = _check_states(X, N)
+    if census is None:
+        census = torch.zeros((N, S), dtype=torch.int64, device=X.device)
+    if other is None and want_other:
+        other = torch.zeros(N, dtype=torch.int64, device=X.device)
+    if first_bad is None and want_first_bad:
+        first_bad = torch.full((1,), FIRST_BAD_NONE, dtype=torch.int64, device=X.device)
+    for name, t, n in (("census", census, N * S), ("other", other, N), ("first_bad", first_bad, 1)):
+        if t is not None and (t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous() or t.numel() != n):
+            raise ValueError("%s must be a contiguous int64 CUDA tensor of %d elements" % (name, n))
+    if N > 0:                                                    # (an empty census tensor has no address to hand over)
+        _abi.call("epg_state_census", _ptr(X), R, N, max(ldx, 1), S, _ptr(census), _ptr(other), _ptr(first_bad), _stream())
+    return census.view(N, S), other, first_bad
+
+
 def select_columns(X, cols):
     """The columns `cols` (0-based int64) of a state matrix as a matrix of its own: int8 [R, padded_width(len(cols))], padding
     bytes 0xFF.  What the grouped count pass does not serve (S3 needs the states themselves; models of 32 .. 127 states) runs

@@ -152,7 +152,7 @@ def _readTableNative(path, rowsToCalc, threads, alloc, with_range):
         return _readTablePandas(path, rowsToCalc, alloc, with_range)
 
 
-def readTable(path, rowsToCalc=None, alloc=None, with_range=False, threads=0):
+def readTable(path, rowsToCalc=None, alloc=None, with_range=False, threads=0, raw=False):
     """Rows [lo, hi) of a matrix file through the native multi-threaded parser: int8 0-based states
     [rows, N] and the rows' first three columns as written (a _io.Locations); a file the strict native parser refuses but pandas
     reads (blank lines, blanks around numbers, "+1", "1.0") is read through pandas like the reference's (_readTablePandas).
@@ -162,10 +162,12 @@ def readTable(path, rowsToCalc=None, alloc=None, with_range=False, threads=0):
     alloc(R, N) -> int8 [R, width >= N] supplies the destination (the driver's pinned, row-padded staging; columns >= N
     are set to -1); with_range also returns the (lowest, highest) state value of the WHOLE file as written (1-based);
     threads = native threads for this one file (0 = all cores; the driver, which reads many files at once, gives each its share).
-    A binary matrix file of the preprocessing command (stateByLine.py, `*.epgm`) is memory-mapped and never cached: it is the cache."""
+    A binary matrix file of the preprocessing command (stateByLine.py, `*.epgm`) is memory-mapped and never cached: it is the cache;
+    raw=True (this read only) leaves its bytes as they are (stateByLine.read_epgm).  Text inputs and their caches know no raw form: the
+    parser has stored what is no state as -1."""
     from . import stateByLine
     if stateByLine.is_epgm(path):
-        return stateByLine.read_epgm(path, rowsToCalc, alloc, with_range)
+        return stateByLine.read_epgm(path, rowsToCalc, alloc, with_range, raw=raw)
     cache = _cache_paths(path)
     if cache is None:
         return _readTableNative(path, rowsToCalc, threads, alloc, with_range)

@@ -14,16 +14,47 @@ import click
 from . import segments as segmentFiles, stateByLine
 
 
-def run_segments(datadir, metadata, chromsizes, outdir, out=sys.stdout, width=stateByLine.BIN_WIDTH, state_names=None):
+class _Census:
+    """--census FILE: the table of epilogos_amd.census from the matrices while they are on the device.  A matrix is censused with
+    the states it holds itself (its range's upper end); the table's state columns are those of the widest, or of --state-names."""
+
+    def __init__(self, path, state_names=None):
+        self.path, self.entries = path, []
+        self.table = state_names or {}
+
+    def add(self, chrom, X, N, rng, names):
+        """A finished matrix, still resident; names: the biosample of every column (what selected its file)."""
+        from . import engine
+        c, other, _fb = engine.state_census(X, N, min(max(int(rng[1]), 1), 127))
+        self.entries.append((chrom, c, other, X.shape[0], list(names)))
+
+    def write(self):
+        import numpy as np
+        from . import census
+        S = max([e[1].shape[1] for e in self.entries] + [v for v in self.table.values() if 1 <= v <= 127] + [1])
+        heads = [str(k) for k in range(1, S + 1)]
+        for name, k in self.table.items():
+            if 1 <= k <= S:
+                heads[k - 1] = name
+        wide = []
+        for chrom, c, other, R, names in self.entries:
+            full = np.zeros((c.shape[0], S), dtype=np.int64)
+            full[:, :c.shape[1]] = c.cpu().numpy()
+            wide.append((chrom, full, other.cpu().numpy(), R, names))
+        census.write_table(self.path, wide, heads)
+
+
+def run_segments(datadir, metadata, chromsizes, outdir, out=sys.stdout, width=stateByLine.BIN_WIDTH, state_names=None, census=None):
     """`run` for segment files: every chromosome's matrix is built in one pass over the files, then written in `chromsizes` order."""
     from . import engine
     engine.require_gpu()
     outdir = Path(outdir)
     outdir.mkdir(parents=True, exist_ok=True)
-    files = segmentFiles.find_segments(datadir, metadata)
+    files, names = segmentFiles.find_segments_named(datadir, metadata)
     chroms, sizes = segmentFiles.read_chromsizes(chromsizes)
     table = segmentFiles.read_state_names(state_names) if state_names else None
     mats = segmentFiles.build_matrices_device(files, chroms, width, sizes=sizes, state_names=table) if files else {}
+    tally = _Census(census, table) if census else None
     written = []
     for chrom in dict.fromkeys(chroms):
         found = chrom in mats
@@ -33,34 +64,44 @@ def run_segments(datadir, metadata, chromsizes, outdir, out=sys.stdout, width=st
             out.write("Skipping.\n")
             continue
         X, rng = mats.pop(chrom)
+        if tally:
+            tally.add(chrom, X, len(files), rng, names)
         written.append(stateByLine.write_epgm(outdir / "matrix_{}{}".format(chrom, stateByLine.EXT), X[:, :len(files)].contiguous(), chrom, rng, width))
         del X
         out.write("Done.\n")
         out.flush()
+    if tally:
+        tally.write()
     return written
 
 
-def run(datadir, metadata, chromsizes, outdir, out=sys.stdout, segments=False, width=stateByLine.BIN_WIDTH, state_names=None):
-    """-> the files written.  One progress line per chromosome of `chromsizes`, as the script prints them."""
+def run(datadir, metadata, chromsizes, outdir, out=sys.stdout, segments=False, width=stateByLine.BIN_WIDTH, state_names=None, census=None):
+    """-> the files written.  One progress line per chromosome of `chromsizes`, as the script prints them.  census: where the
+    per-biosample state census of the matrices goes (epilogos_amd.census's table), None: none is taken."""
     if segments:
-        return run_segments(datadir, metadata, chromsizes, outdir, out, width, state_names)
+        return run_segments(datadir, metadata, chromsizes, outdir, out, width, state_names, census)
     from . import engine
     engine.require_gpu()
     outdir = Path(outdir)
     outdir.mkdir(parents=True, exist_ok=True)
     written = []
-    for chrom, files in stateByLine.iter_calls(datadir, metadata, chromsizes):
+    tally = _Census(census) if census else None
+    for chrom, files, names in stateByLine.iter_calls_named(datadir, metadata, chromsizes):
         out.write("Processing {}: {} files found. ".format(chrom, len(files)))
         out.flush()
         if not files:
             out.write("Skipping.\n")
             continue
         X, N, name, rng = stateByLine.build_matrix_device(files)
+        if tally:
+            tally.add(name, X, N, rng, names)
         # (the name inside the file is the calls' own, the script's chr=$2; the file is named after the chromsizes entry like the script's)
         written.append(stateByLine.write_epgm(outdir / "matrix_{}{}".format(chrom, stateByLine.EXT), X[:, :N].contiguous(), name, rng))
         del X
         out.write("Done.\n")
         out.flush()
+    if tally:
+        tally.write()
     return written
 
 
@@ -75,7 +116,9 @@ def run(datadir, metadata, chromsizes, outdir, out=sys.stdout, segments=False, w
 @click.option("--bin-width", "binWidth", type=int, default=None, help="With --segments: the bin width in bp  [default: 200]")
 @click.option("--state-names", "stateNames", type=click.Path(exists=True, dir_okay=False), default=None,
               help="With --segments: a state metadata TSV (one_index, short_name) for labels that are names")
-def main(datadir, metadata, chromsizes, outdir, numCores, segments, binWidth, stateNames):
+@click.option("--census", "census", type=click.Path(dir_okay=False), default=None,
+              help="Also write the per-biosample state census of the matrices (the table of `python -m epilogos_amd.census`) here")
+def main(datadir, metadata, chromsizes, outdir, numCores, segments, binWidth, stateNames, census):
     """ChromHMM calls -> binary state matrices for `epilogos -i`: state-by-line files (one per biosample and chromosome) or,
     with --segments, segment files (one per biosample)."""
     if binWidth is not None and binWidth <= 0:
@@ -86,7 +129,9 @@ def main(datadir, metadata, chromsizes, outdir, numCores, segments, binWidth, st
         raise click.UsageError("Number of cores must be positive or zero (0 means use all cores)")
     if numCores > 0:
         os.environ["EPILOGOS_NUM_CORES"] = str(numCores)
-    run(datadir, metadata, chromsizes, outdir, segments=segments, width=binWidth or stateByLine.BIN_WIDTH, state_names=stateNames)
+    # without the option the call is, keyword for keyword, the one it was (tests/test_segments_host.py pins it)
+    extra = {"census": census} if census else {}
+    run(datadir, metadata, chromsizes, outdir, segments=segments, width=binWidth or stateByLine.BIN_WIDTH, state_names=stateNames, **extra)
 
 
 def cli(argv=None):

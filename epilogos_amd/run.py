@@ -183,9 +183,12 @@ def _init_device_and_group(world, under_launcher):
 @click.option("--columns-a", "columnsA", type=str, default=None,
               help="Paired mode with -i: the biosamples of group A (as --columns); the matrices are read once for both groups")
 @click.option("--columns-b", "columnsB", type=str, default=None, help="Paired mode with -i: the biosamples of group B")
+@click.option("--check-states", "checkStates", is_flag=True,
+              help="Census every input matrix on the GPU and stop after STEP 1, before anything is written, if a byte of it is "
+                   "not a state of the model; the message names the first such byte (file, row, biosample, value)")
 def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2, outputDirectory, stateInfo, saliency,
          numProcesses, exitBool, diagnosticBool, numTrials, samplingSize, quiescentState, groupSize, version, partition,
-         pvalBool, roiWidth, fileTag, expFreqMem, expCombMem, scoreMem, roiMem, nullSeed, nullDraws, gpus, cacheDir, columns, columnsA, columnsB):
+         pvalBool, roiWidth, fileTag, expFreqMem, expCombMem, scoreMem, roiMem, nullSeed, nullDraws, gpus, cacheDir, columns, columnsA, columnsB, checkStates):
     """Information-theoretic navigation of multi-tissue functional genomic annotations -- MI355X scoring engine."""
     if version:
         print("Version:", __version__)
@@ -305,7 +308,7 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
         jobs = []
         for k, f in enumerate(files):
             jobs += [(f, 0, None)] + ([(files2[k], 0, None)] if files2 else [])
-        driver.start_readers_early(jobs)
+        driver.start_readers_early(jobs, raw=checkStates)     # (--check-states: .epgm bytes reach the device as they are)
     try:
         device = _init_device_and_group(world, under_launcher)
     except BaseException:
@@ -323,7 +326,7 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
         say("\nSTEP 1-3: background counts -> all-reduce -> scores (bin-range partition over %d GPU(s))" % world)
         try:
             _, results = run_single_group(files, numStates, saliency, outputDirPath, fileTag, verbose=False, device=device,
-                                          keep_temp_scores=False, defer_writes=True, columns=cols)
+                                          keep_temp_scores=False, defer_writes=True, columns=cols, checkStates=checkStates)
         finally:
             driver.abort_early_readers()                         # (nothing to do once the stage driver has taken them over)
         try:
@@ -355,11 +358,11 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
             if pairedColumns:
                 _, results = run_paired_columns(files, colsA, colsB, numStates, saliency, outputDirPath, fileTag, quiescentState,
                                                 groupSize, nullSeed, verbose=False, device=device, keep_temps=False, defer_writes=True,
-                                                nullDraws=nullDraws)
+                                                nullDraws=nullDraws, checkStates=checkStates)
             else:
                 _, results = run_paired_groups(files, files2, numStates, saliency, outputDirPath, fileTag, quiescentState, groupSize,
                                                nullSeed, verbose=False, device=device, keep_temps=False, defer_writes=True,
-                                               nullDraws=nullDraws)
+                                               nullDraws=nullDraws, checkStates=checkStates)
         finally:
             driver.abort_early_readers()
         if pvalBool and max(numProcesses, 1) > 1 and nullDraws == 1:

@@ -33,16 +33,22 @@ def find_segments(datadir, metadata):
     """[files in metadata order]: biosamples are column 1 of `metadata` behind its header line, a biosample's file is the one
     name of `datadir` that matches `*{biosample}*segments.bed*` (no leading dot); a biosample without one has no column; two
     matches raise."""
+    return find_segments_named(datadir, metadata)[0]
+
+
+def find_segments_named(datadir, metadata):
+    """find_segments with the biosample of every file: ([files], [biosample names])."""
     datadir = Path(datadir)
     names = sorted(n for n in os.listdir(datadir) if not n.startswith("."))
-    files = []
+    files, found = [], []
     for b in _first_fields(metadata, skip=1):
         hits = [n for n in names if fnmatch.fnmatchcase(n, "*{}*segments.bed*".format(b))]
         if len(hits) > 1:
             raise ValueError("biosample {} has more than one segment file: {} and {}".format(b, datadir / hits[0], datadir / hits[1]))
         if hits:
             files.append(datadir / hits[0])
-    return files
+            found.append(b)
+    return files, found
 
 
 def read_chromsizes(chromsizes):

@@ -41,11 +41,17 @@ def _first_fields(path, skip=0):
 
 def iter_calls(datadir, metadata, chromsizes):
     """(chromosome, [files]) for EVERY chromosome of `chromsizes`, an empty list where the directory holds none of its files."""
+    for chrom, files, _names in iter_calls_named(datadir, metadata, chromsizes):
+        yield chrom, files
+
+
+def iter_calls_named(datadir, metadata, chromsizes):
+    """iter_calls with the biosample of every file: (chromosome, [files], [biosample names])."""
     datadir = Path(datadir)
     names = sorted(n for n in os.listdir(datadir) if not n.startswith("."))          # (a glob's order; `*` does not match a leading dot)
     biosamples = _first_fields(metadata, skip=1)
     for chrom in _first_fields(chromsizes):
-        files = []
+        files, found = [], []
         for b in biosamples:
             hits = [n for n in names if fnmatch.fnmatchcase(n, "*{}*{}_*.txt*".format(b, chrom))]
             if len(hits) > 1:
@@ -53,7 +59,8 @@ def iter_calls(datadir, metadata, chromsizes):
                     b, chrom, datadir / hits[0], datadir / hits[1]))
             if hits:
                 files.append(datadir / hits[0])
-        yield chrom, files
+                found.append(b)
+        yield chrom, files, found
 
 
 def find_calls(datadir, metadata, chromsizes):
@@ -298,9 +305,11 @@ def synth_locations(chrom, lo, hi, width=BIN_WIDTH):
     return _io.Locations(mat[keep], off)
 
 
-def read_epgm(path, rows=None, alloc=None, with_range=False):
+def read_epgm(path, rows=None, alloc=None, with_range=False, raw=False):
     """helpers.readTable for a .epgm file: rows [lo, hi) out of the memory-mapped body into alloc(R, N) (pad columns -1), values
-    above _io.state_limit() as -1, the rows' Locations synthesised."""
+    above _io.state_limit() as -1, the rows' Locations synthesised.  raw=True hands the file's bytes on AS THEY ARE instead: what
+    `epilogos --check-states` and the census command ask for, which report a byte that is no state by its value.  An argument of
+    this one read, not a switch: every other read of the process stores what is no state as -1."""
     h = read_epgm_header(path)
     R, N = h["R"], h["N"]
     _io._log_io("read_epgm", path, *((0, -1) if rows is None else rows))
@@ -311,8 +320,9 @@ def read_epgm(path, rows=None, alloc=None, with_range=False):
     out = np.empty((n, N), dtype=np.int8) if alloc is None else alloc(n, N)
     dest = out[:, :N]
     dest[...] = body[lo:hi]
-    limit = _io.state_limit()
-    dest[(dest >= limit) | (dest < 0)] = -1                      # (0-based: a value above the limit as written)
+    if not raw:
+        limit = _io.state_limit()
+        dest[(dest >= limit) | (dest < 0)] = -1                  # (0-based: a value above the limit as written)
     if alloc is not None:
         out[:, N:] = -1
     loc = synth_locations(h["chrom"], lo, hi, h["width"])

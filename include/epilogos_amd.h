@@ -23,6 +23,8 @@
  *     it: sum(counts) != R*N); the S1/S2 kernels decode only the low five bits, so other byte values are outside the
  *     contract (libepilogos_io's parser stores every file value outside 1..31 as -1).  A model of 32..127 states is handed
  *     to plain kernels that decode the whole byte (csrc/epg_wide.hip): any byte outside [0, S) is then "not a state".
+ *     The validator of this contract is epg_state_census (epilogos_census.h): one pass that compares WHOLE bytes and reports,
+ *     per column, the bytes that are no state and the position of the first -- the aliasing bytes 32..254 included.
  *   - `counts` outputs ACCUMULATE (+=) so that per-chromosome calls sum into one vector exactly like
  *     expectedCombination.py:30-35; zero them first.  They are what the single RCCL all-reduce runs on.
  *   - One host thread per device; calls on different devices/streams are independent.
