@@ -494,6 +494,33 @@ def state_census(X, N, S, census=None, other=None, first_bad=None, want_other=Tr
     return census.view(N, S), other, first_bad
 
 
+def concordance_ws_bytes(R, N, S):
+    return max(int(_abi.call("epg_concordance_ws_bytes", R, N, S)), 256)
+
+
+def concordance(X, N, S, agree=None, both=None, want_both=True, ws=None):
+    """Pairwise state agreement of the biosample columns of a state matrix (epg_concordance): -> (agree, both), int64 [N, N].
+    agree[i, j] = bins in which columns i and j hold the same state, both[i, j] = bins in which both hold a state (the WHOLE byte
+    is compared, as in state_census); both triangles and the diagonal, agree[i, i] == both[i, i] == the valid bins of column i.
+    Tensors given are added to; want_both False passes NULL and returns None in its place.  The workspace is sized and owned
+    here unless `ws` (uint8, at least concordance_ws_bytes(R, N, S)) is handed in."""
+    R, ldx = _check_states(X, N)
+    if N < 1:
+        raise ValueError("concordance needs at least one biosample column")
+    if agree is None:
+        agree = torch.zeros((N, N), dtype=torch.int64, device=X.device)
+    if both is None and want_both:
+        both = torch.zeros((N, N), dtype=torch.int64, device=X.device)
+    for name, t in (("agree", agree), ("both", both)):
+        if t is not None and (t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous() or t.numel() != N * N):
+            raise ValueError("%s must be a contiguous int64 CUDA tensor of %d elements" % (name, N * N))
+    if R > 0:
+        if ws is None:
+            ws = torch.empty(concordance_ws_bytes(R, N, S), dtype=torch.uint8, device=X.device)
+        _abi.call("epg_concordance", _ptr(X), R, N, ldx, S, _ptr(agree), _ptr(both), _ptr(ws), ws.numel(), _stream())
+    return agree.view(N, N), (both.view(N, N) if both is not None else None)
+
+
 def select_columns(X, cols):
     """The columns `cols` (0-based int64) of a state matrix as a matrix of its own: int8 [R, padded_width(len(cols))], padding
     bytes 0xFF.  What the grouped count pass does not serve (S3 needs the states themselves; models of 32 .. 127 states) runs

@@ -44,7 +44,25 @@ class _Census:
         census.write_table(self.path, wide, heads)
 
 
-def run_segments(datadir, metadata, chromsizes, outdir, out=sys.stdout, width=stateByLine.BIN_WIDTH, state_names=None, census=None):
+class _Concordance:
+    """--concordance PREFIX: the two tables of epilogos_amd.concordance, summed over the matrices while they are on the device.  A
+    matrix is counted with the states it holds itself (its range's upper end), as the census is."""
+
+    def __init__(self, prefix):
+        from . import concordance
+        self.prefix, self.tally, self.names = prefix, concordance.Tally(), None
+
+    def add(self, chrom, X, N, rng, names):
+        self.tally.add(X if X.shape[0] else None, N, min(max(int(rng[1]), 1), 127), "the matrix of {}".format(chrom))
+        if self.names is None:
+            self.names = list(names)
+
+    def write(self):
+        self.tally.write(self.prefix, self.names)
+
+
+def run_segments(datadir, metadata, chromsizes, outdir, out=sys.stdout, width=stateByLine.BIN_WIDTH, state_names=None, census=None,
+                 concordance=None):
     """`run` for segment files: every chromosome's matrix is built in one pass over the files, then written in `chromsizes` order."""
     from . import engine
     engine.require_gpu()
@@ -55,6 +73,7 @@ def run_segments(datadir, metadata, chromsizes, outdir, out=sys.stdout, width=st
     table = segmentFiles.read_state_names(state_names) if state_names else None
     mats = segmentFiles.build_matrices_device(files, chroms, width, sizes=sizes, state_names=table) if files else {}
     tally = _Census(census, table) if census else None
+    pairs = _Concordance(concordance) if concordance else None
     written = []
     for chrom in dict.fromkeys(chroms):
         found = chrom in mats
@@ -66,26 +85,33 @@ def run_segments(datadir, metadata, chromsizes, outdir, out=sys.stdout, width=st
         X, rng = mats.pop(chrom)
         if tally:
             tally.add(chrom, X, len(files), rng, names)
+        if pairs:
+            pairs.add(chrom, X, len(files), rng, names)
         written.append(stateByLine.write_epgm(outdir / "matrix_{}{}".format(chrom, stateByLine.EXT), X[:, :len(files)].contiguous(), chrom, rng, width))
         del X
         out.write("Done.\n")
         out.flush()
     if tally:
         tally.write()
+    if pairs:
+        pairs.write()
     return written
 
 
-def run(datadir, metadata, chromsizes, outdir, out=sys.stdout, segments=False, width=stateByLine.BIN_WIDTH, state_names=None, census=None):
+def run(datadir, metadata, chromsizes, outdir, out=sys.stdout, segments=False, width=stateByLine.BIN_WIDTH, state_names=None, census=None,
+        concordance=None):
     """-> the files written.  One progress line per chromosome of `chromsizes`, as the script prints them.  census: where the
-    per-biosample state census of the matrices goes (epilogos_amd.census's table), None: none is taken."""
+    per-biosample state census of the matrices goes (epilogos_amd.census's table), None: none is taken.  concordance: the PREFIX
+    of the pairwise tables of epilogos_amd.concordance, None: none are written."""
     if segments:
-        return run_segments(datadir, metadata, chromsizes, outdir, out, width, state_names, census)
+        return run_segments(datadir, metadata, chromsizes, outdir, out, width, state_names, census, concordance)
     from . import engine
     engine.require_gpu()
     outdir = Path(outdir)
     outdir.mkdir(parents=True, exist_ok=True)
     written = []
     tally = _Census(census) if census else None
+    pairs = _Concordance(concordance) if concordance else None
     for chrom, files, names in stateByLine.iter_calls_named(datadir, metadata, chromsizes):
         out.write("Processing {}: {} files found. ".format(chrom, len(files)))
         out.flush()
@@ -95,6 +121,8 @@ def run(datadir, metadata, chromsizes, outdir, out=sys.stdout, segments=False, w
         X, N, name, rng = stateByLine.build_matrix_device(files)
         if tally:
             tally.add(name, X, N, rng, names)
+        if pairs:
+            pairs.add(name, X, N, rng, names)
         # (the name inside the file is the calls' own, the script's chr=$2; the file is named after the chromsizes entry like the script's)
         written.append(stateByLine.write_epgm(outdir / "matrix_{}{}".format(chrom, stateByLine.EXT), X[:, :N].contiguous(), name, rng))
         del X
@@ -102,6 +130,8 @@ def run(datadir, metadata, chromsizes, outdir, out=sys.stdout, segments=False, w
         out.flush()
     if tally:
         tally.write()
+    if pairs:
+        pairs.write()
     return written
 
 
@@ -118,7 +148,10 @@ def run(datadir, metadata, chromsizes, outdir, out=sys.stdout, segments=False, w
               help="With --segments: a state metadata TSV (one_index, short_name) for labels that are names")
 @click.option("--census", "census", type=click.Path(dir_okay=False), default=None,
               help="Also write the per-biosample state census of the matrices (the table of `python -m epilogos_amd.census`) here")
-def main(datadir, metadata, chromsizes, outdir, numCores, segments, binWidth, stateNames, census):
+@click.option("--concordance", "concordance", type=click.Path(dir_okay=False), default=None,
+              help="Also write the pairwise biosample concordance of the matrices (the two tables of `python -m epilogos_amd.concordance`) "
+                   "as PREFIX.agree.tsv and PREFIX.both.tsv")
+def main(datadir, metadata, chromsizes, outdir, numCores, segments, binWidth, stateNames, census, concordance):
     """ChromHMM calls -> binary state matrices for `epilogos -i`: state-by-line files (one per biosample and chromosome) or,
     with --segments, segment files (one per biosample)."""
     if binWidth is not None and binWidth <= 0:
@@ -131,6 +164,8 @@ def main(datadir, metadata, chromsizes, outdir, numCores, segments, binWidth, st
         os.environ["EPILOGOS_NUM_CORES"] = str(numCores)
     # without the option the call is, keyword for keyword, the one it was (tests/test_segments_host.py pins it)
     extra = {"census": census} if census else {}
+    if concordance:
+        extra["concordance"] = concordance
     run(datadir, metadata, chromsizes, outdir, segments=segments, width=binWidth or stateByLine.BIN_WIDTH, state_names=stateNames, **extra)
 
 
