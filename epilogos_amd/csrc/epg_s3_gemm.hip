@@ -454,6 +454,14 @@ __global__ __launch_bounds__(256) void k_s3_reconstruct(const int* __restrict__ 
     }
 }
 
+// Zero n16 16-byte pieces at a 16-byte aligned address.  A kernel of our own and not hipMemsetAsync: recorded into a graph
+// (stream capture), a memset of this size replays with a stale fill pattern from the second launch on -- the ROCm 7.0 runtime
+// was seen to fill the 1.0 MB of a 21-biosample call with the 32-bit value of an earlier copy's byte count, the flag included,
+// and the gated kernels below then add nothing (tests/test_hip_abi_streams.py; memsets up to 258 KB replayed correctly).
+__global__ __launch_bounds__(256) void k_s3_zero16(uint4* __restrict__ p, long n16) {
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n16; i += gridDim.x * 256L) p[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
 static int64_t g_reduced_bytes(int N, int S) {      // reduced counts | marginals [N][32] | flag
     return align_up((int64_t)N * N * (S - 1) * (S - 1) * 4, 1024) + align_up((int64_t)N * 32 * 4, 1024) + 1024;
 }
@@ -512,7 +520,13 @@ int hist_s3_gemm(const char* X, int64_t R, int32_t N, int64_t ldx, int32_t S, in
     int* dirty = marg + (align_up((int64_t)N * 32 * 4, 1024) / 4);
     const long KC = chunk_bins(tail - E4);
     if (KC < 512) return fail(EPG_ERR_WORKSPACE, "hist_s3: workspace too small for the precomputed-operand kernel");
-    EPG_HIP(hipMemsetAsync(tail, 0, (size_t)red - 1024 + 64, st));        // reduced counts, marginals, flag
+    {                                                                      // reduced counts, marginals, flag (tail is aligned as ws is: 16 bytes)
+        const long n16 = (long)(red - 1024 + 64) / 16;
+        long blocks = (n16 + 255) / 256;
+        if (blocks > num_cus() * 16L) blocks = num_cus() * 16L;
+        hipLaunchKernelGGL(k_s3_zero16, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<uint4*>(tail), n16);
+        EPG_LAUNCH_CHECK("k_s3_zero16");
+    }
     int rc = transpose_states(X, R, N, ldx, S, XT, Rp, 0, 31, dirty, st);
     if (rc) return rc;
     // clean call: the contraction without state S - 1 (same XT: a byte S - 1 matches none of the N (S - 1) rows), then the rest

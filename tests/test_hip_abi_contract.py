@@ -21,7 +21,8 @@ clean layout (-1 padding, zeroed outputs) plus the properties that do not depend
 tests/golden/null_draws.json where a case is one of them.
 
 Out of reach of guard bands: a READ outside a buffer that changes no result (the clamped 16-byte load of a packed last row's
-last chunk, say) -- that needs an address sanitizer.  Stream ordering is not tested here either.
+last chunk, say) -- that needs an address sanitizer.  Streams are tests/test_hip_abi_streams.py's: the same cases on a side stream,
+captured into a graph and replayed, and pairs of them on two streams at once.
 
 CAPPED is a second, short list: the same builders on the one-CU grid of epg_test_force(5, 1) (tests/grid_cap.py), with row counts
 that give every wave three tiles and more and ragged multi-part layouts.  There a wave carries state from tile to tile -- tiles
@@ -76,6 +77,7 @@ class Spec:
         self.clean_pad = False       # null draws: the baseline is the clean layout (-1 padding, zeroed outputs)
         self.error = None            # the EPG_ERR_* code the header promises for this shape
         self.call = self.verify = None
+        self.host = []               # the HOST arrays the last call handed over (pointer tables, rows, keys ...), see keep()
 
     def mat(self, name, x, ldx, mis=0):
         """int8 state matrix [R, ldx], exactly R * ldx bytes, base `mis` bytes off a 256-byte boundary."""
@@ -100,9 +102,14 @@ class Spec:
         """A workspace of exactly `nbytes` bytes."""
         self.bufs.append(Buf(name, "ws", int(nbytes), 256, mis, None))
 
-
     def nbytes(self, name):
         return [b.nbytes for b in self.bufs if b.name == name][0]
+
+    def keep(self, array):
+        """Register a host array that `call` hands to the entry point: it stays alive behind the call, and the stream tests
+        overwrite it to show that the library kept no pointer to it.  -> the array."""
+        self.host.append(array)
+        return array
 
 
 def ptr_array(P, prefix, n):
@@ -151,11 +158,13 @@ class Run:
         for b in spec.bufs:
             self.arena.add(b.name, b.nbytes, role="in" if b.kind in ("mat", "in", "fin") else "ws" if b.kind == "ws" else "out", align=b.align, misalign=b.mis)
         self.arena.build()
+        self.message = ""            # of the last call that returned an error code
 
-    def __call__(self, what, pad="const", prefill=None, acc_start=None, nulls=(), seed=0):
-        """One call.  pad: "const" (the guard byte, a valid state), "clean" (-1), "random" (valid states, hostile guards too);
-        prefill: byte or "random" for workspaces and plain outputs (None: the guard byte); acc_start: name -> start values;
-        nulls: outputs not handed over.  -> name -> host array of every output that was handed over."""
+    def prepare(self, pad="const", prefill=None, acc_start=None, nulls=(), seed=0, freeze=False):
+        """Fill every buffer for one call and take the snapshot.  pad: "const" (the guard byte, a valid state), "clean" (-1),
+        "random" (valid states, hostile guards too); prefill: byte or "random" for workspaces and plain outputs (None: the guard
+        byte); acc_start: name -> start values; nulls: outputs not handed over; freeze: every output and workspace must stay as
+        it is (a call that may not execute yet: tests/test_hip_abi_streams.py).  -> name -> pointer, what spec.call takes."""
         spec, ar, S = self.spec, self.arena, self.spec.S
         rng = np.random.default_rng([seed, 12345])
         ar.reset()
@@ -182,17 +191,27 @@ class Run:
                 ar.fill(name, prefill, rng)
             elif spec.clean_pad and kind == "out":
                 ar.fill(name, 0)
-        ar.snapshot(frozen=nulls if spec.error is None else [b.name for b in spec.bufs])
-        P = {b.name: None if b.name in nulls or b.nbytes == 0 else ar.ptr(b.name) for b in spec.bufs}
+        self.freeze(nulls if spec.error is None and not freeze else [b.name for b in spec.bufs])
+        return {b.name: None if b.name in nulls or b.nbytes == 0 else ar.ptr(b.name) for b in spec.bufs}
+
+    def freeze(self, frozen=()):
+        """(Re)take the snapshot: arena.check() then wants the guards, the inputs and the buffers of `frozen` unchanged."""
+        self.arena.snapshot(frozen=frozen)
+
+    def call(self, P, stream=None):
+        """Enqueue the call on `stream` (a handle; None: torch's current stream), without waiting for it.  -> the code it returned."""
+        self.spec.host = []                                                   # the host arrays of THIS call (Spec.keep)
         try:
-            spec.call(self.abi, P, _stream())
-            code = 0
+            self.spec.call(self.abi, P, _stream() if stream is None else stream)
+            return 0
         except self.abi.EpilogosHipError as e:
-            code = e.code
-        torch.cuda.synchronize()
-        assert code == (spec.error or 0), "%s: the call returned %d" % (what, code)
-        outs = {}
-        for name, kind, _n, _a, _m, payload in spec.bufs:
+            self.message = str(e)
+            return e.code
+
+    def collect(self, what, nulls=()):
+        """After the work is done: name -> host array of every output that was handed over; guards and inputs checked."""
+        ar, outs = self.arena, {}
+        for name, kind, _n, _a, _m, payload in self.spec.bufs:
             if name in nulls or kind not in ("out", "acc", "inout"):
                 continue
             outs[name] = ar.read(name, payload if kind == "out" else payload[0] if kind == "acc" else payload.dtype)
@@ -201,6 +220,14 @@ class Run:
         except AssertionError as e:
             raise AssertionError("%s: %s" % (what, e)) from None
         return outs
+
+    def __call__(self, what, pad="const", prefill=None, acc_start=None, nulls=(), seed=0, stream=None):
+        """One call, waited for and checked (the arguments of prepare()).  -> the outputs, as collect()."""
+        P = self.prepare(pad, prefill, acc_start, nulls, seed)
+        code = self.call(P, stream)
+        torch.cuda.synchronize()
+        assert code == (self.spec.error or 0), "%s: the call returned %d" % (what, code)
+        return self.collect(what, nulls)
 
 
 def same(what, got, want):
@@ -296,10 +323,10 @@ def b_parts(abi, rng, S, shapes):
     sp.optional = [("H%d" % live[0],), tuple("H%d" % k for k in live)] + ([("H%d" % live[-1], "H%d" % live[1])] if len(live) > 2 else [])
 
     def call(abi, P, st):
-        arr = lambda pre: ptr_array(P, pre, n)
+        arr = lambda pre: sp.keep(ptr_array(P, pre, n))
         Hs = arr("H") if any(P.get("H%d" % k) for k in range(n)) else None                 # (every entry NULL: the array itself is)
-        abi.call("epg_bin_hist_parts", n, arr("X"), (C.c_int64 * n)(*[s[0] for s in shapes]), (C.c_int32 * n)(*[s[1] for s in shapes]),
-                 (C.c_int64 * n)(*[pitch_of(s[1], s[2]) for s in shapes]), S, Hs, P["counts"], st)
+        abi.call("epg_bin_hist_parts", n, arr("X"), sp.keep((C.c_int64 * n)(*[s[0] for s in shapes])), sp.keep((C.c_int32 * n)(*[s[1] for s in shapes])),
+                 sp.keep((C.c_int64 * n)(*[pitch_of(s[1], s[2]) for s in shapes])), S, Hs, P["counts"], st)
     sp.call = call
 
     def verify(o):
@@ -534,9 +561,9 @@ def b_pair_scores(abi, rng, S, NA, NB, ga, gb, rows, parts=False, qstate=None, a
         if not parts:
             return abi.call("epg_pair_scores_s1_from_binhist", P["HA0"], P["HB0"], P["HnA0"], P["HnB0"], rows[0], S, NA, NB, ga, gb, P["TA"], P["TB"],
                             *tn, P["delta0"], P["null0"], P["dist0"], P["maxdiff0"], st)
-        arr = lambda pre: ptr_array(P, pre, n)
+        arr = lambda pre: sp.keep(ptr_array(P, pre, n))
         mask = arr("mask") if qstate is not None and any(P.get("mask%d" % k) for k in range(n)) else None
-        abi.call("epg_pair_scores_s1_parts", n, arr("HA"), arr("HB"), arr("HnA"), arr("HnB"), (C.c_int64 * n)(*rows), S, NA, NB, ga, gb, P["TA"], P["TB"],
+        abi.call("epg_pair_scores_s1_parts", n, arr("HA"), arr("HB"), arr("HnA"), arr("HnB"), sp.keep((C.c_int64 * n)(*rows)), S, NA, NB, ga, gb, P["TA"], P["TB"],
                  *tn, arr("delta"), arr("null"), arr("dist"), arr("maxdiff"), mask, -1 if qstate is None else qstate, st)
     sp.call = call
 
@@ -664,9 +691,9 @@ def b_null_from_hist(abi, rng, S, NA, NB, rows, ga=None, gb=None, parts=False, f
     def call(abi, P, st):
         if not parts:
             return abi.call("epg_null_hist_from_binhist", P["HA0"], P["HB0"], rows[0], S, NA + NB, ga, gb, seed, keys[0], P["OA0"], P["OB0"], st)
-        arr = lambda pre: ptr_array(P, pre, n)
-        abi.call("epg_null_hist_from_binhist_parts", n, arr("HA"), arr("HB"), (C.c_int64 * n)(*rows), S, NA + NB, ga, gb, seed, (C.c_int64 * n)(*keys),
-                 arr("OA"), arr("OB"), st)
+        arr = lambda pre: sp.keep(ptr_array(P, pre, n))
+        abi.call("epg_null_hist_from_binhist_parts", n, arr("HA"), arr("HB"), sp.keep((C.c_int64 * n)(*rows)), S, NA + NB, ga, gb, seed,
+                 sp.keep((C.c_int64 * n)(*keys)), arr("OA"), arr("OB"), st)
     sp.call = call
 
     def verify(o):
@@ -710,9 +737,10 @@ def b_pair_count_null(abi, rng, S, NA, NB, rows, pa="pad", pb="pad", mis=0, gold
     sp.clean_pad, sp.error = True, error
 
     def call(abi, P, st):
-        arr = lambda pre: ptr_array(P, pre, n)
-        abi.call("epg_pair_count_null_parts", n, arr("XA"), arr("XB"), (C.c_int64 * n)(*rows), NA, NB, (C.c_int64 * n)(*[la] * n), (C.c_int64 * n)(*[lb] * n),
-                 S, arr("HA"), arr("HB"), P["counts"], seed, (C.c_int64 * n)(*keys), arr("OA"), arr("OB"), st)
+        arr = lambda pre: sp.keep(ptr_array(P, pre, n))
+        i64s = lambda v: sp.keep((C.c_int64 * n)(*v))
+        abi.call("epg_pair_count_null_parts", n, arr("XA"), arr("XB"), i64s(rows), NA, NB, i64s([la] * n), i64s([lb] * n),
+                 S, arr("HA"), arr("HB"), P["counts"], seed, i64s(keys), arr("OA"), arr("OB"), st)
     sp.call = call
 
     def verify(o):
@@ -800,7 +828,7 @@ def b_slices(abi, rng, S, R, bs, nblk, B):
     want = np.stack([X[_best_rows(X, int(f), bs, nblk)] for f in first])
     sp.inp("X", X)
     sp.out("Q", I32, B * nblk * S, mis=4)
-    sp.call = lambda abi, P, st: abi.call("epg_simsearch_slices", P["X"], R, S, bs, nblk, (C.c_int64 * B)(*first.tolist()), B, P["Q"], st)
+    sp.call = lambda abi, P, st: abi.call("epg_simsearch_slices", P["X"], R, S, bs, nblk, sp.keep((C.c_int64 * B)(*first.tolist())), B, P["Q"], st)
     sp.verify = lambda o: np.testing.assert_array_equal(o["Q"].reshape(B, nblk, S), want)
     return sp
 
@@ -1000,10 +1028,21 @@ def abi():
     return _abi
 
 
+_SPECS = {}
+
+
+def spec_of(abi, entry, builder, args, kw):
+    """The Spec of a case of CASES, built once per process: tests/test_hip_abi_streams.py runs the same cases, and the oracle's
+    share of a case is most of its time.  No run changes a Spec."""
+    key = repr((entry, args, sorted(kw.items())))
+    if key not in _SPECS:
+        _SPECS[key] = builder(abi, np.random.default_rng(zlib.crc32(key.encode())), *args, **kw)
+    return _SPECS[key]
+
+
 @pytest.mark.parametrize("entry,builder,args,kw", CASES)
 def test_contract(abi, entry, builder, args, kw):
-    rng = np.random.default_rng(zlib.crc32(repr((entry, args, sorted(kw.items()))).encode()))
-    run_case(builder(abi, rng, *args, **kw), abi)
+    run_case(spec_of(abi, entry, builder, args, kw), abi)
 
 
 @pytest.mark.parametrize("entry,builder,args,kw", CAPPED)
