@@ -123,45 +123,54 @@ __device__ __forceinline__ void load_slot(const char* rowp, int i, int j, const 
     }
 }
 
-// Count one row's states for this lane's share of chunks.  NG > 0: compile-time number of groups
-// (128*(NG-1) < N <= 128*NG), all 2*NG loads are issued up front.  NG == 0: any N, one group in flight.
+// both load slots of group t (32 bytes per lane) into w[8]
+template <bool MAYBE_TAIL>
+__device__ __forceinline__ void load_group(const char* rowp, int t, int j, const RowGeom& g, u32 (&w)[8]) {
+    load_slot<MAYBE_TAIL>(rowp, 2 * t, j, g, &w[0]);
+    load_slot<MAYBE_TAIL>(rowp, 2 * t + 1, j, g, &w[4]);
+}
+
+// All 2*NG loads of a row of NG groups (128*(NG-1) < N <= 128*NG); only the last group can touch the row end.
+template <int NG>
+__device__ __forceinline__ void load_groups(const char* rowp, int j, const RowGeom& g, u32 (&w)[NG][8]) {
+#pragma unroll
+    for (int t = 0; t < NG; ++t) {
+        if (t < NG - 1) load_group<false>(rowp, t, j, g, w[t]);
+        else load_group<true>(rowp, t, j, g, w[t]);
+    }
+}
+
+// A row of any width: group(t, w, cnt) for every group t of the row, in batches of four, the batch's eight loads issued before its
+// first group is counted (one group at a time measured 2.81-2.86 ms against 2.40 ms for 7.5 M bins x 1698 on one box).
+// (cnt goes through as an argument: a callable that CAPTURES it costs k_bin_hist<18, 0> 3 VGPRs and k_score_s1<18, 0> 14.)
+template <int NC, typename Group>
+__device__ __forceinline__ void for_each_group(const char* rowp, int j, const RowGeom& g, u32 (&cnt)[NC], Group group) {
+    const int ngroups = (g.chunks + 7) >> 3;
+    for (int t0 = 0; t0 < ngroups; t0 += 4) {
+        u32 w[4][8];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int t = t0 + k;
+            if (t < ngroups - 1) load_group<false>(rowp, t, j, g, w[k]);          // wave-uniform
+            else if (t == ngroups - 1) load_group<true>(rowp, t, j, g, w[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (t0 + k < ngroups) group(t0 + k, w[k], cnt);
+    }
+}
+
+// Count one row's states for this lane's share of chunks.  NG > 0: compile-time number of groups, all 2*NG loads are issued up
+// front (load_groups).  NG == 0: any N, four groups in flight (for_each_group).
 template <int S, int NG>
 __device__ __forceinline__ void count_row(const char* rowp, int j, const RowGeom& g, u32 (&cnt)[S]) {
     if constexpr (NG > 0) {
         u32 w[NG][8];
-#pragma unroll
-        for (int t = 0; t < NG; ++t) {
-            if (t < NG - 1) {
-                load_slot<false>(rowp, 2 * t, j, g, &w[t][0]);
-                load_slot<false>(rowp, 2 * t + 1, j, g, &w[t][4]);
-            } else {
-                load_slot<true>(rowp, 2 * t, j, g, &w[t][0]);
-                load_slot<true>(rowp, 2 * t + 1, j, g, &w[t][4]);
-            }
-        }
+        load_groups<NG>(rowp, j, g, w);
 #pragma unroll
         for (int t = 0; t < NG; ++t) count_group<S>(w[t], cnt);
     } else {
-        // any N: groups in batches of four, the batch's eight loads issued before its first count (one group at a time
-        // measured 2.81-2.86 ms against 2.40 ms for 7.5 M bins x 1698 on one box)
-        const int ngroups = (g.chunks + 7) >> 3;
-        for (int t0 = 0; t0 < ngroups; t0 += 4) {
-            u32 w[4][8];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int t = t0 + k;
-                if (t < ngroups - 1) {                               // wave-uniform
-                    load_slot<false>(rowp, 2 * t, j, g, &w[k][0]);
-                    load_slot<false>(rowp, 2 * t + 1, j, g, &w[k][4]);
-                } else if (t == ngroups - 1) {
-                    load_slot<true>(rowp, 2 * t, j, g, &w[k][0]);
-                    load_slot<true>(rowp, 2 * t + 1, j, g, &w[k][4]);
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (t0 + k < ngroups) count_group<S>(w[k], cnt);
-        }
+        for_each_group(rowp, j, g, cnt, [](int, const u32 (&w)[8], u32 (&c)[S]) { count_group<S>(w, c); });
     }
 }
 
@@ -186,6 +195,24 @@ struct CountRow {
     __device__ __forceinline__ void operator()(const char* rowp, int j, const RowGeom& g, u32 (&cnt)[S]) const { count_row<S, NG>(rowp, j, g, cnt); }
 };
 
+// one super-tile: local index lst of a matrix X[R, ldx], the lane's row b of each 16-bin half, quad lane j
+template <int S, typename Count, typename Epilogue, typename Finish>
+__device__ __forceinline__ void super_tile(const char* __restrict__ X, long R, long ldx, const RowGeom& g, long lst, int j, int b, Count&& count,
+                                           Epilogue&& epilogue, Finish&& finish) {
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const long row = lst * 32 + half * 16 + b;
+        const bool valid = row < R;
+        u32 cnt[S];
+#pragma unroll
+        for (int s = 0; s < S; ++s) cnt[s] = 0;
+        count(X + (valid ? row : R - 1) * ldx, j, g, cnt);
+        epilogue(half, row, valid, cnt);
+    }
+    const long row0 = lst * 32;
+    finish(lst, row0, (int)(R - row0 < 32 ? R - row0 : 32));
+}
+
 template <int S, int NG, int NW = 4, typename Epilogue, typename Finish, typename Count = CountRow<S, NG>>
 __device__ __forceinline__ void tile_loop(const char* __restrict__ X, long R, int N, long ldx, Epilogue&& epilogue, Finish&& finish,
                                           Count&& count = Count()) {
@@ -194,20 +221,8 @@ __device__ __forceinline__ void tile_loop(const char* __restrict__ X, long R, in
     const int j = lane & 3, b = lane >> 2;
     const RowGeom g = make_geom(N);
     const long nsuper = (R + 31) >> 5;
-    for (long st = (long)blockIdx.x * NW + wave; st < nsuper; st += (long)gridDim.x * NW) {
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            const long row = st * 32 + half * 16 + b;
-            const bool valid = row < R;
-            u32 cnt[S];
-#pragma unroll
-            for (int s = 0; s < S; ++s) cnt[s] = 0;
-            count(X + (valid ? row : R - 1) * ldx, j, g, cnt);
-            epilogue(half, row, valid, cnt);
-        }
-        const long row0 = st * 32;
-        finish(st, row0, (int)(R - row0 < 32 ? R - row0 : 32));
-    }
+    for (long st = (long)blockIdx.x * NW + wave; st < nsuper; st += (long)gridDim.x * NW)
+        super_tile<S>(X, R, ldx, g, st, j, b, count, epilogue, finish);
 }
 
 // The same loop over SEVERAL matrices ("parts", epg_parts.h) in one launch, in super-tiles of 32 rows.  enter(part) tells the
@@ -246,19 +261,7 @@ __device__ __forceinline__ void tile_loop_parts(const KhParts& pt, Enter&& enter
             g = make_geom(pt.n_cols[part]);
             enter(part);
         }
-        const long lst = st - base;
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            const long row = lst * 32 + half * 16 + b;
-            const bool valid = row < R;
-            u32 cnt[S];
-#pragma unroll
-            for (int s = 0; s < S; ++s) cnt[s] = 0;
-            count_row<S, NG>(X + (valid ? row : R - 1) * ldx, j, g, cnt);
-            epilogue(half, row, valid, cnt);
-        }
-        const long row0 = lst * 32;
-        finish(lst, row0, (int)(R - row0 < 32 ? R - row0 : 32));
+        super_tile<S>(X, R, ldx, g, st - base, j, b, CountRow<S, NG>(), epilogue, finish);
     }
 }
 
@@ -280,5 +283,76 @@ __device__ __forceinline__ u32 sel4(u32 x0, u32 x1, u32 x2, u32 x3, int j) {
     const u32 hi = (j & 1) ? x3 : x2;
     return (j & 2) ? hi : lo;
 }
+
+// lane j of the quad takes the count of state 4k + j out of the packed d[] (0 past the last state).  Both halves are read before
+// the pick: written as j & 2 ? d[2k + 1] : d[2k] the compiler picks between two ADDRESSES and d[] stays in memory (the 15- and
+// 31-state count kernels held it in 8 KB of LDS or 48-80 bytes of scratch per lane).
+template <int ND>
+__device__ __forceinline__ u32 quad_state_count(const u32 (&d)[ND], int k, int j) {
+    const u32 lo = d[2 * k], hi = 2 * k + 1 < ND ? d[2 * k + 1] : 0u;
+    const u32 v = (j & 2) ? hi : lo;
+    return (j & 1) ? v >> 16 : v & 0xffffu;
+}
+
+// Stage a bin's uint16 row of H (Sout <= S columns) at srow: d[] already is that layout, one dword per pair of states.
+// WHOLE_DWORDS (even S, Sout == S): a quad lane stores whole dwords; else uint16 by uint16.
+template <int S, bool WHOLE_DWORDS>
+__device__ __forceinline__ void stage_hist_row(char* srow, const u32 (&d)[(S + 1) / 2], int j, int Sout) {
+    constexpr int ND = (S + 1) / 2;
+    if constexpr (WHOLE_DWORDS) {
+        static_assert((S & 1) == 0, "whole dwords need an even row");
+#pragma unroll
+        for (int k = 0; k < (ND + 3) / 4; ++k) {
+            const u32 v = sel4(d[4 * k], 4 * k + 1 < ND ? d[4 * k + 1] : 0u, 4 * k + 2 < ND ? d[4 * k + 2] : 0u, 4 * k + 3 < ND ? d[4 * k + 3] : 0u, j);
+            if (4 * k + j < ND) *reinterpret_cast<u32*>(srow + 4 * (4 * k + j)) = v;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < (S + 3) / 4; ++k) {
+            const u32 c = quad_state_count(d, k, j);
+            if (4 * k + j < Sout) *reinterpret_cast<u16*>(srow + 2 * (4 * k + j)) = (u16)c;
+        }
+    }
+}
+
+// Running state totals of the bins a lane has counted, as packed uint16 pairs like d[]: added per epilogue, flushed into the
+// block's s_cnt[S + 1] (u64, __shared__, zeroed by the kernel) before a half can overflow -- every flush_every epilogues, from the
+// WIDEST row of the launch (nmax).  Every lane of a quad holds the same totals; lane j == 0 adds them.
+template <int S>
+struct StateTotals {
+    static constexpr int ND = (S + 1) / 2;
+    u32 accp[ND];
+    int since, flush_every;
+    __device__ __forceinline__ void init(int nmax) {
+#pragma unroll
+        for (int m = 0; m < ND; ++m) accp[m] = 0;
+        flush_every = 65535 / nmax > 1 ? 65535 / nmax - 1 : 1;
+        since = 0;
+    }
+    __device__ __forceinline__ void flush(u64* s_cnt, int j) {
+        if (j == 0) {
+#pragma unroll
+            for (int m = 0; m < ND; ++m) {
+                const u32 lo = accp[m] & 0xffffu, hi = accp[m] >> 16;
+                if (lo) atomicAdd(&s_cnt[2 * m], (u64)lo);
+                if (hi) atomicAdd(&s_cnt[2 * m + 1], (u64)hi);
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < ND; ++m) accp[m] = 0;
+        since = 0;
+    }
+    __device__ __forceinline__ void add(const u32 (&d)[ND], bool valid, u64* s_cnt, int j) {
+#pragma unroll
+        for (int m = 0; m < ND; ++m) accp[m] += valid ? d[m] : 0u;
+        if (++since >= flush_every) flush(s_cnt, j);
+    }
+    // the whole block, after its loop: the last flush, then one global atomic per state
+    __device__ __forceinline__ void commit(u64* s_cnt, int j, u64* __restrict__ counts, int Sout) {
+        flush(s_cnt, j);
+        __syncthreads();
+        if ((int)threadIdx.x < Sout && s_cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], s_cnt[threadIdx.x]);
+    }
+};
 
 }  // namespace epg

@@ -1,5 +1,6 @@
 // Column groups: per-bin histograms of up to four column subsets of ONE matrix in one pass (include/epilogos_groups.h).
-// gfx950 only.  The counting core, the tile loop and the store of whole lines are those of k_bin_hist (epg_count.h, epg_s1.hip):
+// gfx950 only.  The counting core, the tile loop and the store of whole lines are k_bin_hist's (epg_count.h: count_group's decode,
+// for_each_group, tile_loop, quad_state_count):
 // a row is loaded once, transposed once and decoded once per state; a group costs one AND with the lane's membership word and one
 // v_bcnt per state on top (2 VALU per state, group and 32 bytes).
 #include "epg_count.h"
@@ -46,30 +47,13 @@ __device__ __forceinline__ void count_group_members(const u32 (&w)[8], const uin
     }
 }
 
-// The row counter tile_loop calls: count_row's any-width load schedule (four 32-byte groups in flight), the membership words of
-// group t and quad lane j read from the block's LDS table as one ds_read_b128.
+// The row counter tile_loop calls: the any-width load schedule (for_each_group, epg_count.h: four 32-byte groups in flight), the
+// membership words of group t and quad lane j read from the block's LDS table as one ds_read_b128.
 template <int S, int G>
 struct CountRowGroups {
     const uint4* mtab;               // [ngroups][4 quad lanes]
     __device__ __forceinline__ void operator()(const char* rowp, int j, const RowGeom& g, u32 (&cnt)[G * S]) const {
-        const int ngroups = (g.chunks + 7) >> 3;
-        for (int t0 = 0; t0 < ngroups; t0 += 4) {
-            u32 w[4][8];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int t = t0 + k;
-                if (t < ngroups - 1) {                               // wave-uniform
-                    load_slot<false>(rowp, 2 * t, j, g, &w[k][0]);
-                    load_slot<false>(rowp, 2 * t + 1, j, g, &w[k][4]);
-                } else if (t == ngroups - 1) {
-                    load_slot<true>(rowp, 2 * t, j, g, &w[k][0]);
-                    load_slot<true>(rowp, 2 * t + 1, j, g, &w[k][4]);
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (t0 + k < ngroups) count_group_members<S, G>(w[k], mtab[(t0 + k) * 4 + j], cnt);
-        }
+        for_each_group(rowp, j, g, cnt, [m = mtab, j](int t, const u32 (&w)[8], u32 (&c)[G * S]) { count_group_members<S, G>(w, m[t * 4 + j], c); });
     }
 };
 
@@ -127,9 +111,8 @@ __global__ __launch_bounds__(256, 2) void k_bin_hist_groups(const char* __restri
             for (int k = 0; k < (S + 3) / 4; ++k) {
                 const u32 c0 = cnt[gg * S + 4 * k], c1 = 4 * k + 1 < S ? cnt[gg * S + 4 * k + 1] : 0u;
                 const u32 c2 = 4 * k + 2 < S ? cnt[gg * S + 4 * k + 2] : 0u, c3 = 4 * k + 3 < S ? cnt[gg * S + 4 * k + 3] : 0u;
-                const u32 lo = quad_sum(c0 | (c1 << 16)), hi = quad_sum(c2 | (c3 << 16));
-                const u32 v = (j & 2) ? hi : lo;
-                const u32 c = (j & 1) ? v >> 16 : v & 0xffffu;
+                const u32 d[2] = {quad_sum(c0 | (c1 << 16)), quad_sum(c2 | (c3 << 16))};
+                const u32 c = quad_state_count(d, 0, j);
                 if (4 * k + j < Sout) *reinterpret_cast<u16*>(srow + 2 * (4 * k + j)) = (u16)c;
             }
         }

@@ -611,25 +611,6 @@ struct PcParts {
     int n;
 };
 
-template <int S>
-__device__ __forceinline__ void pc_stage_row(char* srow, const u32 (&d)[(S + 1) / 2], int j) {
-    constexpr int ND = (S + 1) / 2;
-    if constexpr ((S & 1) == 0) {                        // even S: whole dwords
-#pragma unroll
-        for (int k = 0; k < (ND + 3) / 4; ++k) {
-            const u32 v = sel4(d[4 * k], 4 * k + 1 < ND ? d[4 * k + 1] : 0u, 4 * k + 2 < ND ? d[4 * k + 2] : 0u, 4 * k + 3 < ND ? d[4 * k + 3] : 0u, j);
-            if (4 * k + j < ND) *reinterpret_cast<u32*>(srow + 4 * (4 * k + j)) = v;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < (S + 3) / 4; ++k) {
-            const u32 v = (j & 2) ? (2 * k + 1 < ND ? d[2 * k + 1] : 0u) : d[2 * k];
-            const u32 c = (j & 1) ? v >> 16 : v & 0xffffu;
-            if (4 * k + j < S) *reinterpret_cast<u16*>(srow + 2 * (4 * k + j)) = (u16)c;
-        }
-    }
-}
-
 template <int S, int NG>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_pair_count_null(const PcParts pt, int NA, int NB, u64* __restrict__ counts, u64 seed, int NW) {
     constexpr int ND = (S + 1) / 2;
@@ -644,25 +625,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     u32* bitsA = reinterpret_cast<u32*>(sa + slot.bits()) + lane;
     if (threadIdx.x <= S) s_cnt[threadIdx.x] = 0;
     __syncthreads();
-    u32 accp[ND];
-#pragma unroll
-    for (int m = 0; m < ND; ++m) accp[m] = 0;
-    const int nmax = NA > NB ? NA : NB;
-    const int flush_every = 65535 / nmax > 1 ? 65535 / nmax - 1 : 1;
-    int since = 0;
-    auto flush = [&]() {
-        if (j == 0) {
-#pragma unroll
-            for (int m = 0; m < ND; ++m) {
-                const u32 lo = accp[m] & 0xffffu, hi = accp[m] >> 16;
-                if (lo) atomicAdd(&s_cnt[2 * m], (u64)lo);
-                if (hi) atomicAdd(&s_cnt[2 * m + 1], (u64)hi);
-            }
-        }
-#pragma unroll
-        for (int m = 0; m < ND; ++m) accp[m] = 0;
-        since = 0;
-    };
+    StateTotals<S> totals;
+    totals.init(NA > NB ? NA : NB);
     const RowGeom gA = make_geom(NA), gB = make_geom(NB);
     const int n_cols = NA + NB;
     const long ntiles = pt.t0[pt.n];
@@ -680,17 +644,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     u32 wa[NG][8], wb[NG][8];
     auto issue = [&](const char* X, long ldx, long R_, long r0, int sub, const RowGeom& g, u32 (&w)[NG][8]) {
         const long row = r0 + 16 * sub + b;
-        const char* rowp = X + (row < R_ ? row : R_ - 1) * ldx;
-#pragma unroll
-        for (int t = 0; t < NG; ++t) {
-            if (t < NG - 1) {
-                load_slot<false>(rowp, 2 * t, j, g, &w[t][0]);
-                load_slot<false>(rowp, 2 * t + 1, j, g, &w[t][4]);
-            } else {
-                load_slot<true>(rowp, 2 * t, j, g, &w[t][0]);
-                load_slot<true>(rowp, 2 * t + 1, j, g, &w[t][4]);
-            }
-        }
+        load_groups<NG>(X + (row < R_ ? row : R_ - 1) * ldx, j, g, w);
     };
     auto count_into = [&](u32 (&w)[NG][8], char* srow, bool valid) {
         u32 cnt[S];
@@ -700,12 +654,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         for (int t = 0; t < NG; ++t) count_group<S>(w[t], cnt);
         u32 d[ND];
         pack_reduce<S>(cnt, d);
-        pc_stage_row<S>(srow, d, j);
-        if (counts) {
-#pragma unroll
-            for (int m = 0; m < ND; ++m) accp[m] += valid ? d[m] : 0u;
-            if (++since >= flush_every) flush();
-        }
+        stage_hist_row<S, (S & 1) == 0>(srow, d, j, S);
+        if (counts) totals.add(d, valid, s_cnt, j);
     };
     long tile = (long)blockIdx.x * 4 + wave;
     Tile cur, nx;
@@ -748,11 +698,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         __builtin_amdgcn_wave_barrier();
         cur = nx;
     }
-    if (counts) {
-        flush();
-        __syncthreads();
-        if ((int)threadIdx.x < S && s_cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], s_cnt[threadIdx.x]);
-    }
+    if (counts) totals.commit(s_cnt, j, counts, S);
 }
 
 template <int S, int NG>

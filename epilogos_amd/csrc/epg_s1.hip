@@ -1,13 +1,12 @@
 // S1 path: per-bin histogram (K1), expected S1 counts, S1 score (direct and from cached histograms).
 // gfx950 only.  See epg_count.h for the counting core and DESIGN.md for the roofline of each kernel.
 #include "epg_count.h"
+#include "epg_paircount.h"
 
 #include <stdlib.h>
 #include <string.h>
 
 namespace epg {
-
-typedef unsigned short k1_v2u16 __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------------------------------------------------------
 // K1: X[R, ldx] int8 -> H[R, S] uint16 (+ counts[S] += column sums).  HBM-bound: N bytes read, 2*S written per bin.
@@ -23,8 +22,8 @@ typedef unsigned short k1_v2u16 __attribute__((ext_vector_type(2)));
 // PAIRS (S2 jobs, round 5): the same launch also adds the S2 state-pair counts of its bins into counts2[S * S] --
 // C[i,j] += sum_b h_i h_j (i != j), h_i (h_i - 1) (i == j), expected.py:146-158 -- from the 32 rows of a super-tile that are
 // staged in LDS for the H store anyway: re-packed as bin PAIRS per state (word (i, k) = counts of state i in bins 2k and 2k + 1)
-// and contracted with v_dot2_u32_u16 in register tiles like k_s2_hist_wave (epg_s2.hip: a lane owns a 3 x 3 block of state pairs
-// and every third pair word) -- ~5 wave instructions per bin on top of the counting core's ~45, instead of a pass of its own over
+// and contracted with v_dot2_u32_u16 in register tiles (epg_paircount.h: a lane owns a 3 x 3 block of state pairs and every
+// PSLICE-th pair word) -- ~5 wave instructions per bin on top of the counting core's ~45, instead of a pass of its own over
 // H (0.23 ms per 15 M bins, at 0.29 of its bytes: VERDICT r4).  Needs FULL (a compile-time row width) and counts < 4096.
 constexpr int K1P_LD = 17;                             // pair-matrix row stride in words (16 pair words + 1: rows on different banks)
 
@@ -55,11 +54,7 @@ __device__ __forceinline__ void bin_hist_body(int Sout_, u64* __restrict__ count
     if (PAIRS) {
         const int role = lane < PROLES * PSLICE ? lane / PSLICE : -1;
         pkq = lane % PSLICE;
-        if (role >= 0) {
-            int t = role, i = 0;
-            while (t >= PG - i) { t -= PG - i; ++i; }
-            pgi = i; pgj = i + t;
-        }
+        if (role >= 0) pair_role(role, PG, pgi, pgj);
 #pragma unroll
         for (int c = 0; c < 9; ++c) pacc[c] = 0;
 #pragma unroll
@@ -76,24 +71,8 @@ __device__ __forceinline__ void bin_hist_body(int Sout_, u64* __restrict__ count
         }
         __builtin_amdgcn_wave_barrier();
         if (pgi >= 0) {
-            const u32* pi = sp + 3 * pgi * K1P_LD;
-            const u32* pj = sp + 3 * pgj * K1P_LD;
-            u32 part[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, ps[3] = {0, 0, 0};
-            const bool diag = pgi == pgj;
-            for (int k = pkq; k < 16; k += PSLICE) {
-                const u32 av[3] = {pi[k], pi[K1P_LD + k], pi[2 * K1P_LD + k]};
-                const u32 bv[3] = {pj[k], pj[K1P_LD + k], pj[2 * K1P_LD + k]};
-#pragma unroll
-                for (int t = 0; t < 3; ++t)
-#pragma unroll
-                    for (int u = 0; u < 3; ++u)
-                        part[3 * t + u] = __builtin_amdgcn_udot2(__builtin_bit_cast(k1_v2u16, av[t]), __builtin_bit_cast(k1_v2u16, bv[u]), part[3 * t + u], false);
-                if (diag) {
-#pragma unroll
-                    for (int t = 0; t < 3; ++t)
-                        ps[t] = __builtin_amdgcn_udot2(__builtin_bit_cast(k1_v2u16, av[t]), __builtin_bit_cast(k1_v2u16, 0x00010001u), ps[t], false);
-                }
-            }
+            u32 part[9], ps[3];
+            pair_tile_dot(sp + 3 * pgi * K1P_LD, sp + 3 * pgj * K1P_LD, K1P_LD, pkq, 16, PSLICE, pgi == pgj, part, ps);
 #pragma unroll
             for (int c = 0; c < 9; ++c) pacc[c] += part[c];          // (6 words x 2 bins x 4095^2 < 2^32 per super-tile)
 #pragma unroll
@@ -102,54 +81,15 @@ __device__ __forceinline__ void bin_hist_body(int Sout_, u64* __restrict__ count
         __builtin_amdgcn_wave_barrier();
     };
 
-    // running state counts of this lane's bins, as packed uint16 pairs; flushed to LDS before a half can overflow
-    u32 accp[ND];
-#pragma unroll
-    for (int m = 0; m < ND; ++m) accp[m] = 0;
-    const int flush_every = 65535 / nmax > 1 ? 65535 / nmax - 1 : 1;
-    int since = 0;
-    auto flush = [&]() {
-        if (j == 0) {
-#pragma unroll
-            for (int m = 0; m < ND; ++m) {
-                const u32 lo = accp[m] & 0xffffu, hi = accp[m] >> 16;
-                if (lo) atomicAdd(&s_cnt[2 * m], (u64)lo);
-                if (hi) atomicAdd(&s_cnt[2 * m + 1], (u64)hi);
-            }
-        }
-#pragma unroll
-        for (int m = 0; m < ND; ++m) accp[m] = 0;
-        since = 0;
-    };
+    StateTotals<S> totals;                             // running state counts of this lane's bins
+    totals.init(nmax);
 
     auto enter = [&](u16* Hpart) { H = Hpart; };
     auto epilogue = [&](int half, long row, bool valid, u32 (&cnt)[S]) {
         u32 d[ND];
         pack_reduce<S>(cnt, d);
-        if (counts) {
-#pragma unroll
-            for (int m = 0; m < ND; ++m) accp[m] += valid ? d[m] : 0u;
-            if (++since >= flush_every) flush();
-        }
-        if (H) {
-            // stage the bin's uint16 row: d[] already is that layout, one dword per pair of states
-            char* srow = &s_stage[wave][(half * 16 + b) * ROWB];
-            if constexpr (FULL && (S & 1) == 0) {        // even, full width: whole dwords
-#pragma unroll
-                for (int k = 0; k < (ND + 3) / 4; ++k) {
-                    const u32 v = sel4(d[4 * k], 4 * k + 1 < ND ? d[4 * k + 1] : 0u, 4 * k + 2 < ND ? d[4 * k + 2] : 0u,
-                                       4 * k + 3 < ND ? d[4 * k + 3] : 0u, j);
-                    if (4 * k + j < ND) *reinterpret_cast<u32*>(srow + 4 * (4 * k + j)) = v;
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < (S + 3) / 4; ++k) {
-                    const u32 v = (j & 2) ? (2 * k + 1 < ND ? d[2 * k + 1] : 0u) : d[2 * k];
-                    const u32 c = (j & 1) ? v >> 16 : v & 0xffffu;
-                    if (4 * k + j < Sout) *reinterpret_cast<u16*>(srow + 2 * (4 * k + j)) = (u16)c;
-                }
-            }
-        }
+        if (counts) totals.add(d, valid, s_cnt, j);
+        if (H) stage_hist_row<S, FULL && (S & 1) == 0>(&s_stage[wave][(half * 16 + b) * ROWB], d, j, Sout);
     };
     auto finish = [&](long st, long row0, int rows) {
         if (H) store_staged(s_stage[wave], reinterpret_cast<char*>(H) + row0 * ROWB, rows * ROWB, lane);
@@ -157,31 +97,10 @@ __device__ __forceinline__ void bin_hist_body(int Sout_, u64* __restrict__ count
     };
     loop(enter, epilogue, finish);
 
-    if (counts) {
-        flush();
-        __syncthreads();
-        if ((int)threadIdx.x < Sout && s_cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], s_cnt[threadIdx.x]);
-    }
+    if (counts) totals.commit(s_cnt, j, counts, Sout);
     if constexpr (PAIRS) {
-        // C[i,j] = sum h_i h_j (both orders);  C[i,i] = sum h_i^2 - sum h_i.  The block's lanes meet in an LDS copy of C, then one
-        // global atomic per cell and block (k_s2_hist_wave's epilogue)
-        if (pgi >= 0) {
-            const bool diag = pgi == pgj;
-#pragma unroll
-            for (int t = 0; t < 3; ++t)
-#pragma unroll
-                for (int u = 0; u < 3; ++u) {
-                    const int i = 3 * pgi + t, jj = 3 * pgj + u;
-                    u64 v = pacc[3 * t + u];
-                    if (diag && t == u) v -= prs[t];             // two's complement
-                    if (i >= S || jj >= S || !v) continue;
-                    atomicAdd(&s_c2[i * S + jj], v);
-                    if (!diag) atomicAdd(&s_c2[jj * S + i], v);
-                }
-        }
-        __syncthreads();
-        for (int e = threadIdx.x; e < S * S; e += 256)
-            if (s_c2[e]) atomicAdd(&counts2[e], s_c2[e]);
+        if (pgi >= 0) pair_fold(pacc, prs, pgi, pgj, S, s_c2);
+        pair_commit(s_c2, S, counts2);
     }
 }
 
@@ -269,8 +188,7 @@ __global__ __launch_bounds__(256) void k_score_s1(const char* __restrict__ X, lo
         OT* srow = reinterpret_cast<OT*>(&s_stage[wave][(half * 16 + b) * ROWB]);
 #pragma unroll
         for (int k = 0; k < (S + 3) / 4; ++k) {
-            const u32 v = (j & 2) ? (2 * k + 1 < ND ? d[2 * k + 1] : 0u) : d[2 * k];
-            const u32 c = (j & 1) ? v >> 16 : v & 0xffffu;
+            const u32 c = quad_state_count(d, k, j);
             const int s = 4 * k + j;
             if (s < S) srow[s] = (c && valid) ? T[(long)c * S + s] : (OT)0;
         }

@@ -1,5 +1,6 @@
 // S2 path (state-pair saliency) from cached per-bin histograms, plus the paired-mode extras.  gfx950 only.
 #include "epg_common.h"
+#include "epg_paircount.h"
 #include "epg_pairdist.h"
 #include "epg_parts.h"
 
@@ -14,15 +15,13 @@ namespace epg {
 // (Round 1's block-wide kernel -- one thread per pair, three block barriers per 128 bins: 70 % of the wave cycles waiting -- was
 // replaced by the wave-level kernel below in round 2 and deleted in round 5.)
 // ---------------------------------------------------------------------------------------------------------------
-typedef unsigned short v2u16 __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------------------------------------------------------
 // Every WAVE on its own.  A wave owns tiles of 64 bins:
 // it fetches a tile's 128*S bytes one tile ahead with whole-line loads, parks them in its own LDS slot, re-packs them as
 // bin PAIRS per state (word (i, k) = counts of state i in bins 2k and 2k+1, row stride 33 words) and contracts them with
-// v_dot2_u32_u16 in REGISTER TILES: a lane owns a 3 x 3 block of state pairs (groups gi <= gj of three states) and every
-// third pair-word k, so six LDS words feed nine dot products (the one-pair-per-thread form read two words per product).
-// Diagonal blocks also sum their three states' counts (the -sum h_i of the diagonal).  Only wave-level barriers.
+// v_dot2_u32_u16 in REGISTER TILES (epg_paircount.h): a lane owns a 3 x 3 block of state pairs (groups gi <= gj of three states)
+// and every nslice-th pair-word k.  Only wave-level barriers.
 // Exact: a lane's partial sums are < 2^32 while counts are < 4096 (11 words x 2 products); a tile holding a larger count
 // takes a plain u64 path.  H2 (may be NULL): a second histogram array of the same shape, added bin by bin before the products --
 // the counts of the column concatenation [A|B] of paired mode (helpers.py:173) from the two groups' histograms (halves cannot
@@ -50,11 +49,7 @@ __global__ __launch_bounds__(256, S2W_MAXPASS == 1 ? 4 : 2) void k_s2_hist_wave(
     for (int p = 0; p < S2W_MAXPASS; ++p) {
         const int role = nroles <= 64 ? (p == 0 && lane < nroles * nslice ? lane / nslice : -1) : lane + 64 * p;
         gi[p] = -1; gj[p] = 0; kq[p] = nroles <= 64 ? lane % nslice : 0;
-        if (role >= 0 && role < nroles) {
-            int t = role, i = 0;
-            while (t >= ng - i) { t -= ng - i; ++i; }
-            gi[p] = i; gj[p] = i + t;
-        }
+        if (role >= 0 && role < nroles) pair_role(role, ng, gi[p], gj[p]);
 #pragma unroll
         for (int c = 0; c < 9; ++c) acc[p][c] = 0;
 #pragma unroll
@@ -112,25 +107,8 @@ __global__ __launch_bounds__(256, S2W_MAXPASS == 1 ? 4 : 2) void k_s2_hist_wave(
 #pragma unroll
             for (int p = 0; p < S2W_MAXPASS; ++p) {
                 if (gi[p] < 0) continue;
-                const u32* pi = s_p + 3 * gi[p] * S2W_LD;
-                const u32* pj = s_p + 3 * gj[p] * S2W_LD;
-                u32 part[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, ps[3] = {0, 0, 0};
-                const bool diag = gi[p] == gj[p];
-                for (int k = kq[p]; k < 32; k += nslice) {
-                    const u32 a0 = pi[k], a1 = pi[S2W_LD + k], a2 = pi[2 * S2W_LD + k];
-                    const u32 b0 = pj[k], b1 = pj[S2W_LD + k], b2 = pj[2 * S2W_LD + k];
-                    const u32 av[3] = {a0, a1, a2}, bv[3] = {b0, b1, b2};
-#pragma unroll
-                    for (int t = 0; t < 3; ++t)
-#pragma unroll
-                        for (int u = 0; u < 3; ++u)
-                            part[3 * t + u] = __builtin_amdgcn_udot2(__builtin_bit_cast(v2u16, av[t]), __builtin_bit_cast(v2u16, bv[u]), part[3 * t + u], false);
-                    if (diag) {
-#pragma unroll
-                        for (int t = 0; t < 3; ++t)
-                            ps[t] = __builtin_amdgcn_udot2(__builtin_bit_cast(v2u16, av[t]), __builtin_bit_cast(v2u16, 0x00010001u), ps[t], false);
-                    }
-                }
+                u32 part[9], ps[3];
+                pair_tile_dot(s_p + 3 * gi[p] * S2W_LD, s_p + 3 * gj[p] * S2W_LD, S2W_LD, kq[p], 32, nslice, gi[p] == gj[p], part, ps);
 #pragma unroll
                 for (int c = 0; c < 9; ++c) acc[p][c] += part[c];
 #pragma unroll
@@ -158,32 +136,15 @@ __global__ __launch_bounds__(256, S2W_MAXPASS == 1 ? 4 : 2) void k_s2_hist_wave(
             }
         }
     }
-    // C[i,j] = sum h_i h_j (both orders);  C[i,i] = sum h_i^2 - sum h_i.  The block's lanes first meet in an LDS copy of C
-    // (the staging memory is free now), then one global atomic per cell and block: with every lane adding its nine sums
-    // straight to global memory 7.7 M atomics queued up on 324 addresses and the kernel took 3.9 ms.
+    // the block's lanes meet in an LDS copy of C (pair_fold; the staging memory is free now)
     __syncthreads();
     u64* s_c = reinterpret_cast<u64*>(smem);
     for (int e = threadIdx.x; e < S * S; e += 256) s_c[e] = 0;
     __syncthreads();
 #pragma unroll
-    for (int p = 0; p < S2W_MAXPASS; ++p) {
-        if (gi[p] < 0) continue;
-        const bool diag = gi[p] == gj[p];
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-#pragma unroll
-            for (int u = 0; u < 3; ++u) {
-                const int i = 3 * gi[p] + t, j = 3 * gj[p] + u;
-                u64 v = acc[p][3 * t + u];
-                if (diag && t == u) v -= rs[p][t];             // two's complement
-                if (i >= S || j >= S || !v) continue;
-                atomicAdd(&s_c[i * S + j], v);
-                if (!diag) atomicAdd(&s_c[j * S + i], v);
-            }
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < S * S; e += 256)
-        if (s_c[e]) atomicAdd(&counts[e], s_c[e]);
+    for (int p = 0; p < S2W_MAXPASS; ++p)
+        if (gi[p] >= 0) pair_fold(acc[p], rs[p], gi[p], gj[p], S, s_c);
+    pair_commit(s_c, S, counts);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
