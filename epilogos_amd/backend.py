@@ -254,6 +254,31 @@ class _HipSession:
             self._check_upload(X, N, ticket)
         return X
 
+    def stage(self, arr, N, ticket):
+        """A parsed matrix -> HBM, the one upload of it (paired mode: one group's matrix of a part, as soon as it is parsed -- its
+        staging buffer goes back to the pool at once: a part must not sit on two of the few buffers while its other half is
+        still being inflated).  The result feeds add_device / add_staged / add_columns, of this session or -- it is read, never
+        written -- of later ones (driver.run_groupings keeps it between its groupings)."""
+        return self._upload(arr, N, ticket)
+
+    def close(self):
+        """Give back what the session holds: its parts (histograms, state rows, null groups), the early results, the count
+        accumulator, exp_freq and the S1 tables, the census scratch, and the page-locked staging buffers with the thread that
+        returns them.  The matrices a caller passed to add_device / add_columns are the caller's.  A closed session takes no
+        further calls."""
+        self._pending, self._pending_rows = [], 0
+        self.parts, self._early, self._t1, self._t1_verified = [], {}, {}, set()
+        self.acc = self.q = self._pending_check = None
+        self.state_checks, self._census_scratch = {}, {}
+        if self._releaser is not None:                   # (waits for the uploads in flight: their staging buffers come back)
+            self._release_q.put(None)
+            self._releaser.join()
+            self._releaser = None
+        self.held = {}
+        if self._pool is not None:
+            self._pool.close()
+            self._pool = None
+
     def _check_upload(self, X, N, ticket):
         """--check-states: the census of a matrix just uploaded, all N columns of it.  The per-state counts go to a scratch table
         nobody reads (the ABI wants one); `other`, `first_bad` and the offending byte itself -- fetched now, the matrix may be
@@ -507,6 +532,10 @@ class _HipSingleSession(_HipSession):
         self.parts.append(_Part(Hs[0]))
         return len(self.parts) - 1
 
+    def close(self):
+        self._ws3 = None
+        super().close()
+
     def _s3_workspace(self, R, N):
         """The ~8 GB workspace of the S3 matrix-core contraction (count pass) and of the S3 score pass (table, transposed matrix,
         cells), grown to the largest part (round 2 allocated and freed one per part: freed device memory is scrubbed at every
@@ -640,13 +669,12 @@ class _HipPairedSession(_HipSession):
             be._null_stream = self.torch.cuda.Stream(device=self.device)
         self.null_stream = be._null_stream
 
-    def stage(self, arr, N, ticket):
-        """One group's matrix of a part -> HBM as soon as it is parsed (its staging buffer goes back to the pool at once: a
-        part must not sit on two of the few buffers while its other half is still being inflated)."""
-        return self._upload(arr, N, ticket)
-
     def add_part(self, arrA, NA, ticketA, arrB, NB, ticketB, row0):
         return self.add_staged(self._upload(arrA, NA, ticketA), NA, self._upload(arrB, NB, ticketB), NB, row0)
+
+    def close(self):
+        self._null_kept = None
+        super().close()
 
     # a batch of parts is counted in ONE launch (epg_bin_hist_parts over the A and the B matrices of all its parts) and its null
     # groups are drawn in ONE launch on the second stream, under the count pass of the next batch (the sampler is VALU-bound,

@@ -525,6 +525,11 @@ class _Single:
         _check_columns_fit(self.columns, n, self.groups[0][part[0]])
         return sess.add_part(arr, n, t, columns=self.columns)
 
+    def add_resident(self, sess, X, n, part):
+        """add() for a job whose matrix is on the device already (run_groupings: uploaded by this or an earlier grouping)."""
+        _check_columns_fit(self.columns, n, self.groups[0][part[0]])
+        return sess.add_device(X, n, columns=self.columns)
+
     def part_out(self, sess, pid):
         """-> (the array written as text, [the arrays rank 0 collects]) of a part."""
         sc = sess.scores(pid)
@@ -634,6 +639,12 @@ class _PairedColumns(_Paired):
             _check_columns_fit(cols, n, self.groups[0][fi])
         return sess.add_columns(sess.stage(x, n, t), n, self.colsA, self.colsB, shuffle_key(fi, lo))
 
+    def add_resident(self, sess, X, n, part):
+        fi, lo, _hi = part
+        for cols in (self.colsA, self.colsB):
+            _check_columns_fit(cols, n, self.groups[0][fi])
+        return sess.add_columns(X, n, self.colsA, self.colsB, shuffle_key(fi, lo))
+
 
 def _check_columns_fit(cols, n, path):
     """A column group against a parsed file of n columns (an empty file has none and holds nothing to select from)."""
@@ -700,33 +711,54 @@ def _state_verdict(d, sess, mode, jobs):
     raise StateCheckFailed(1)
 
 
-def _run_groups(mode, outputDir, fileTag, backend, defer_writes):
-    """STEP 1-3 of either mode over the bin-range partition -> (exp_freq, results of rank 0 by file stem, else None)."""
+def _run_groups(mode, outputDir, fileTag, backend, defer_writes, store=None):
+    """STEP 1-3 of either mode over the bin-range partition -> (exp_freq, results of rank 0 by file stem, else None).
+    store (a _ResidentStore, run_groupings): the partition is the store's -- planned by the run's first grouping -- and STEP 1
+    takes its parts from the store's replayable source (_ResidentStore.parts), which keeps the uploaded matrices for the groupings
+    to come; the session is closed on the way out.  Everything behind the count pass is the same code."""
     be = backend if backend is not None else _backend.get()
     _io.set_state_limit(mode.S)                        # above 31 states the parser keeps values up to 127 (wide kernels)
     d = _Dist()
-    files = mode.groups[0]
     outputDir = Path(outputDir)
     tm = _Timer(d.rank)
     if d.rank == 0:
         _clean_parts(outputDir, mode.kind, fileTag)
     d.barrier()
-    layout, rows, my_parts, owner = _plan(files, d, tm, *mode.groups[1:])
+    if store is None:
+        plan = _plan(mode.groups[0], d, tm, *mode.groups[1:])
+    else:
+        if store.plan is None:                         # once per run: a side-car the first pass writes must not change the second's
+            store.plan = _plan(mode.groups[0], d, tm)
+        plan = store.plan
     sess = mode.open(be)
+    try:
+        return _run_session(mode, sess, d, tm, plan, outputDir, fileTag, defer_writes, store)
+    finally:
+        if store is not None:
+            store.uploads = int(getattr(sess, "n_uploads", 0))
+            sess.close()                               # histograms, null groups and results go before the next grouping's session opens
+
+
+def _run_session(mode, sess, d, tm, plan, outputDir, fileTag, defer_writes, store):
+    """_run_groups, from the open session on."""
+    files = mode.groups[0]
+    layout, rows, my_parts, owner = plan
     if mode.check_states:
         sess.check_states = True                       # (--check-states: every uploaded matrix is censused, see _state_verdict)
 
     # STEP 1: every part of this rank is parsed, uploaded once and counted; what the score pass needs stays resident
     pids, locs, widths = [None] * len(my_parts), [None] * len(my_parts), [0] * mode.n_widths
     # paired: part k's two groups are jobs 2k and 2k + 1, the second group follows the first one's row ranges
-    with closing(_stream_parts([(group[fi], lo, hi) for fi, lo, hi in my_parts for group in mode.groups], sess, mode.S,
-                               raw=mode.check_states)) as stream:
-        for t, arr, n, loc in stream:                  # in order of completion
+    jobs = [(group[fi], lo, hi) for fi, lo, hi in my_parts for group in mode.groups]
+    # a store (run_groupings; one file group) hands out matrices that are on the device: its own, or read and uploaded just now
+    stream = (store.parts if store is not None else _stream_parts)(jobs, sess, mode.S, raw=mode.check_states)
+    with closing(stream) as stream:
+        for t, x, n, loc in stream:                    # in order of completion
             k, g = divmod(t, len(mode.groups))
             mode.see_width(widths, g, n)               # an empty file has no width: it must not be the one that is remembered
             if g == 0:
                 locs[k] = loc
-            pids[k] = mode.add(sess, t, arr, n, my_parts[k])
+            pids[k] = mode.add(sess, t, x, n, my_parts[k]) if store is None else mode.add_resident(sess, x, n, my_parts[k])
     if mode.check_states:                              # before anything of this run is written
         _state_verdict(d, sess, mode, my_parts)
     if layout == "whole":                              # single rank: the row counts come from the parse
@@ -805,6 +837,131 @@ def _run_groups(mode, outputDir, fileTag, backend, defer_writes):
     _io.log_thread_census("%s s%d rank %d of %d" % (mode.census, mode.sal, d.rank, d.world))
     d.barrier()
     return q, results
+
+
+def _nbytes(X):
+    return int(X.nbytes) if isinstance(X, np.ndarray) else int(X.numel() * X.element_size())
+
+
+def _device_free(X):
+    """Free bytes of the device X lives on, None when X is no device tensor (the host stand-ins of the tests)."""
+    if isinstance(X, np.ndarray) or not X.is_cuda:
+        return None
+    import torch
+    return int(torch.cuda.mem_get_info(X.device)[0])
+
+
+class _ResidentStore:
+    """The input matrices of a run_groupings run on this rank's device, between its groupings: job (path, lo, hi) -> (matrix,
+    its width, its Locations), plus the run's partition plan.  `parts` is the replayable source STEP 1 reads from: a kept job comes
+    from the store -- no parse, no staging buffer, no upload -- any other job goes through the ordinary readers and one upload,
+    on every pass.
+
+    Admission is per job, on the pass that first reads it.  A matrix is kept unless
+      - the device's free memory at that moment is below FREE_FACTOR x its bytes + FREE_SLACK (a grouping's session needs
+        histograms, null groups and results next to the matrices: up to 36 B per bin and group against N B per bin), or
+      - the kept bytes would exceed EPILOGOS_RESIDENT_BYTES (per rank; 0 = keep nothing, unset = no cap).
+    FREE_FACTOR and FREE_SLACK are a choice, not a measurement: twice the matrix plus 2 GiB is room that every session measured
+    so far fits in many times over at 833 biosamples; nobody has looked for the smallest values that work.
+    The cap is applied IN JOB ORDER, whatever order the readers finish in (a matrix that arrives early waits, on the device, for
+    the verdicts of the jobs before it), so that what is kept does not depend on the timing of the parser threads."""
+    FREE_FACTOR, FREE_SLACK = 2, 2 << 30
+
+    def __init__(self):
+        cap = os.environ.get("EPILOGOS_RESIDENT_BYTES", "")
+        self.cap = int(cap) if cap.strip() else None
+        self.plan = None
+        self.kept, self.bytes, self.refused = {}, 0, []
+        self._seen, self._wait, self._next = set(), {}, 0
+        self.uploads = self.parsed = 0                 # of the grouping under way
+
+    def _offer(self, t, job, X, n, loc):
+        nbytes, free = _nbytes(X), _device_free(X)
+        room = free is None or free >= self.FREE_FACTOR * nbytes + self.FREE_SLACK
+        self._wait[t] = (job, X if room else None, n, loc, nbytes)
+        while self._next in self._wait:
+            job, X, n, loc, nbytes = self._wait.pop(self._next)
+            self._next += 1
+            if X is not None and (self.cap is None or self.bytes + nbytes <= self.cap):
+                self.kept[job] = (X, n, loc)
+                self.bytes += nbytes
+            else:
+                self.refused.append(job)
+
+    def parts(self, jobs, sess, numStates, raw=False):
+        """-> generator of (index in jobs, matrix on the device, N, Locations): the kept jobs first, then the others as their
+        readers finish."""
+        jobs = [(Path(p), lo, hi) for p, lo, hi in jobs]
+        self.uploads = self.parsed = 0
+        first = not self._seen                         # the pass that admits: every job is new to it
+        todo = [t for t, job in enumerate(jobs) if job not in self.kept]
+        if first:
+            self._seen.update(jobs)
+            self._wait, self._next = {}, 0
+        for t, job in enumerate(jobs):
+            if job in self.kept:
+                X, n, loc = self.kept[job]
+                yield t, X, n, loc
+        if not todo:
+            return
+        with closing(_stream_parts([jobs[t] for t in todo], sess, numStates, raw=raw)) as stream:
+            for rt, arr, n, loc in stream:             # (rt: the reader's ticket, which is what the staging buffer is held under)
+                X = sess.stage(arr, n, rt)
+                self.parsed += 1
+                if first:
+                    self._offer(todo[rt], jobs[todo[rt]], X, n, loc)
+                yield todo[rt], X, n, loc
+
+
+def run_groupings(files, groupings, numStates, saliency, outputDir, fileTag, quiescentState=None, groupSize=-1, nullSeed=None,
+                  verbose=False, backend=None, device=None, keep_temps=True, defer_writes=False, nullDraws=1, checkStates=False):
+    """Many groupings of the biosample columns of ONE set of files in one run: every file is parsed and uploaded once, its matrix
+    stays on the device (_ResidentStore: unless the admission rule refuses it), and every grouping runs STEP 1-3 from the resident
+    matrices with a session of its own.  groupings: [(name, cols)] -- each what run_single_group(columns=cols) computes -- or
+    [(name, colsA, colsB)] -- run_paired_columns -- with 0-based column indices (helpers.parseGroupings); the outputs of a
+    grouping go to outputDir/name, the files and bytes of that function called with that directory.  The remaining arguments are
+    those functions'; nullSeed=None draws one seed for the whole run (one rank; several ranks must be given the same seed).
+    A GENERATOR: yields (name, exp_freq, results, info) as each grouping is done -- results as the run_* function returns them
+    (rank 0, else None) -- so a caller finishes a grouping (STEP 4, finish_writes()) before the next one begins.  info:
+    uploads (H2D matrix copies this rank made for the grouping), parsed_files (passes over input files this rank made for it),
+    resident_bytes (bytes of input matrices this rank holds on the device after it), kept_files / refused_files (this rank's jobs
+    in and not in the store).  checkStates censuses every matrix on the first pass, which is the pass that uploads them all.
+    A grouping that raises ends the run; the directories of the groupings before it are complete."""
+    files = [Path(f) for f in files]
+    groupings = [tuple(g) for g in groupings]
+    if not groupings:
+        raise ValueError("no groupings")
+    paired = len(groupings[0]) == 3
+    if any(len(g) != len(groupings[0]) or len(g) not in (2, 3) for g in groupings):
+        raise ValueError("a grouping is (name, columns) or (name, columns A, columns B), the same kind for the whole run")
+    d = _Dist()
+    if paired and nullSeed is None:
+        if d.world > 1:
+            raise ValueError("several ranks must be given the same null seed")
+        nullSeed = int(np.random.SeedSequence().generate_state(1)[0])
+    store = _ResidentStore()
+    try:
+        for k, g in enumerate(groupings):
+            out = Path(outputDir) / g[0]
+            out.mkdir(parents=True, exist_ok=True)
+            if paired:
+                mode = _PairedColumns(files, g[1], g[2], numStates, saliency, quiescentState, groupSize, nullSeed, keep_temps, nullDraws)
+            else:
+                mode = _Single(files, numStates, saliency, keep_temps, g[1])
+            mode.check_states = bool(checkStates) and k == 0
+            q, results = _run_groups(mode, out, fileTag, backend, defer_writes, store)
+            if k == 0 and len(groupings) > 1:
+                # what did not fit is said once, by rank 0, for all ranks (a collective: every rank is here after its first grouping)
+                kept, refused = (int(v) for v in d.all_reduce_counts(np.array([len(store.kept), len(store.refused)], dtype=np.int64)))
+                if refused and d.rank == 0:
+                    print("epilogos_amd: {} of {} input matrices stay on the device between the groupings; {} do not (free device "
+                          "memory or EPILOGOS_RESIDENT_BYTES) and are read, parsed and uploaded again by every grouping"
+                          .format(kept, kept + refused, refused), flush=True)
+            yield g[0], q, results, {"uploads": store.uploads, "parsed_files": store.parsed, "resident_bytes": store.bytes,
+                                     "kept_files": len(store.kept), "refused_files": len(store.refused)}
+    finally:
+        abort_early_readers()
+        store.kept = {}
 
 
 def run_single_group(files, numStates, saliency, outputDir, fileTag, verbose=False, backend=None, device=None,

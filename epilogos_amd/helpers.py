@@ -3,6 +3,7 @@
 belong to ROI/plotting.  States come back as int8 (0-based) instead of the reference's int64: that is the layout the
 GPU kernels stream."""
 import os
+import re
 from pathlib import Path
 
 import numpy as np
@@ -61,6 +62,90 @@ def null_draw_seeds(seed, K):
             z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & m
             z ^= z >> 31
         out[k] = z
+    return out
+
+
+def parseColumns(spec):
+    """A SPEC of biosamples -> 0-based column indices (int64, in the order given).  SPEC: comma-separated 1-based biosample
+    numbers and inclusive ranges ("1-379,401,500-620"; biosample k is column k + 3 of the file), or "@path": a text file with one
+    number or range per line, blank lines and # comments allowed.  ValueError (the message names the offence) for an empty or
+    malformed SPEC, a number < 1, a descending range and a biosample listed twice."""
+    if spec is None or not spec.strip():
+        raise ValueError("empty biosample list")
+    spec = spec.strip()
+    if spec.startswith("@"):
+        try:
+            lines = Path(spec[1:]).read_text().splitlines()
+        except OSError as e:
+            raise ValueError("cannot read the biosample list {}: {}".format(spec[1:], e.strerror or e))
+        items = [ln.split("#", 1)[0].strip() for ln in lines]
+        items = [it for it in items if it]
+        if not items:
+            raise ValueError("empty biosample list in {}".format(spec[1:]))
+    else:
+        items = [it.strip() for it in spec.split(",")]
+    out = []
+    for it in items:
+        m = re.fullmatch(r"(\d+)(?:\s*-\s*(\d+))?", it)
+        if m is None:
+            raise ValueError("malformed biosample list: '{}' is neither a number nor a range".format(it))
+        lo = int(m.group(1))
+        hi = int(m.group(2)) if m.group(2) is not None else lo
+        if lo < 1 or hi < 1:
+            raise ValueError("biosample numbers start at 1, got '{}'".format(it))
+        if hi < lo:
+            raise ValueError("malformed biosample list: range '{}' descends".format(it))
+        out.extend(range(lo, hi + 1))
+    seen = set()
+    for k in out:
+        if k in seen:
+            raise ValueError("biosample {} is listed twice".format(k))
+        seen.add(k)
+    return np.asarray(out, dtype=np.int64) - 1
+
+
+_GROUPING_NAME = re.compile(r"[A-Za-z0-9._-]+")
+
+
+def parseGroupings(path, mode):
+    """The groupings file of `epilogos --groupings` -> [(name, cols)] (mode "single") or [(name, colsA, colsB)] ("paired"), in file
+    order, cols as parseColumns gives them (0-based int64).  Tab-separated text: NAME<TAB>SPEC, or NAME<TAB>SPEC_A<TAB>SPEC_B; blank
+    lines and lines whose first non-blank character is # are skipped.  NAME names the grouping's output directory:
+    [A-Za-z0-9._-]+, not "." or "..", unique in the file.  ValueError, with the line's number, for a line with another number of
+    fields, a bad or repeated NAME, a SPEC parseColumns refuses and a biosample in both groups of a paired line; without a line
+    number for a file that cannot be read or holds no grouping."""
+    try:
+        lines = Path(path).read_text().splitlines()
+    except (OSError, UnicodeDecodeError) as e:
+        raise ValueError("cannot read the groupings file {}: {}".format(path, getattr(e, "strerror", None) or e))
+    fields_of = {"single": ("NAME", "SPEC"), "paired": ("NAME", "SPEC_A", "SPEC_B")}[mode]
+    out, seen = [], {}
+    for no, line in enumerate(lines, 1):
+        if not line.strip() or line.lstrip().startswith("#"):
+            continue
+        fields = [f.strip() for f in line.split("\t")]
+        if len(fields) != len(fields_of):
+            raise ValueError("line {}: {} field(s); a line of {} mode is {}".format(no, len(fields), mode, "<TAB>".join(fields_of)))
+        name = fields[0]
+        if _GROUPING_NAME.fullmatch(name) is None or name in (".", ".."):
+            raise ValueError("line {}: '{}' cannot name an output directory (letters, digits, '.', '_' and '-'; not '.' or '..')"
+                             .format(no, name))
+        if name in seen:
+            raise ValueError("line {}: the name '{}' is used by line {} already".format(no, name, seen[name]))
+        seen[name] = no
+        groups = []
+        for what, spec in zip(fields_of[1:], fields[1:]):
+            try:
+                groups.append(parseColumns(spec))
+            except ValueError as e:
+                raise ValueError("line {}: [{}] {}".format(no, what, e))
+        if len(groups) == 2:
+            both = sorted(set(groups[0].tolist()) & set(groups[1].tolist()))
+            if both:
+                raise ValueError("line {}: biosample {} is in both groups".format(no, both[0] + 1))
+        out.append((name,) + tuple(groups))
+    if not out:
+        raise ValueError("no groupings in {}".format(path))
     return out
 
 

@@ -17,51 +17,11 @@ _T_START = _time.time()
 import click
 
 from . import __version__
-from .helpers import getNumStates
+from .helpers import getNumStates, parseColumns
 
 
 def _natural_key(p):
     return [int(t) if t.isdigit() else t for t in re.split(r"(\d+)", Path(p).name)]
-
-
-def parseColumns(spec):
-    """A SPEC of biosamples -> 0-based column indices (int64, in the order given).  SPEC: comma-separated 1-based biosample
-    numbers and inclusive ranges ("1-379,401,500-620"; biosample k is column k + 3 of the file), or "@path": a text file with one
-    number or range per line, blank lines and # comments allowed.  ValueError (the message names the offence) for an empty or
-    malformed SPEC, a number < 1, a descending range and a biosample listed twice."""
-    import numpy as np
-    if spec is None or not spec.strip():
-        raise ValueError("empty biosample list")
-    spec = spec.strip()
-    if spec.startswith("@"):
-        try:
-            lines = Path(spec[1:]).read_text().splitlines()
-        except OSError as e:
-            raise ValueError("cannot read the biosample list {}: {}".format(spec[1:], e.strerror or e))
-        items = [ln.split("#", 1)[0].strip() for ln in lines]
-        items = [it for it in items if it]
-        if not items:
-            raise ValueError("empty biosample list in {}".format(spec[1:]))
-    else:
-        items = [it.strip() for it in spec.split(",")]
-    out = []
-    for it in items:
-        m = re.fullmatch(r"(\d+)(?:\s*-\s*(\d+))?", it)
-        if m is None:
-            raise ValueError("malformed biosample list: '{}' is neither a number nor a range".format(it))
-        lo = int(m.group(1))
-        hi = int(m.group(2)) if m.group(2) is not None else lo
-        if lo < 1 or hi < 1:
-            raise ValueError("biosample numbers start at 1, got '{}'".format(it))
-        if hi < lo:
-            raise ValueError("malformed biosample list: range '{}' descends".format(it))
-        out.extend(range(lo, hi + 1))
-    seen = set()
-    for k in out:
-        if k in seen:
-            raise ValueError("biosample {} is listed twice".format(k))
-        seen.add(k)
-    return np.asarray(out, dtype=np.int64) - 1
 
 
 def checkArguments(mode, saliency, inputDirPath, inputDirPath2, outputDirPath, numProcesses, numStates, quiescentState,
@@ -103,6 +63,18 @@ def checkArguments(mode, saliency, inputDirPath, inputDirPath2, outputDirPath, n
     if groupSize < -1 or groupSize == 0:
         print("ERROR: Group size must be positive")
         sys.exit()
+
+
+def _check_biosamples_exist(files, top):
+    """The command line's pre-check of column groups: biosample top + 1, the largest asked for, is a column of every file."""
+    from . import driver
+    for f in files:
+        try:
+            n = driver._columns_of(f)
+        except Exception:                                        # (an empty or unreadable file: the parse reports it, or it has no rows)
+            continue
+        if n and top >= n:
+            print("ERROR: biosample {} is not in {}: the file has {} biosample columns".format(top + 1, f, n)); sys.exit()
 
 
 def _init_device_and_group(world, under_launcher):
@@ -186,9 +158,14 @@ def _init_device_and_group(world, under_launcher):
 @click.option("--check-states", "checkStates", is_flag=True,
               help="Census every input matrix on the GPU and stop after STEP 1, before anything is written, if a byte of it is "
                    "not a state of the model; the message names the first such byte (file, row, biosample, value)")
+@click.option("--groupings", "groupingsFile", type=str, default=None,
+              help="Score many biosample groupings of the matrices of [-i] in one run: a tab-separated file with one line per grouping, "
+                   "NAME<TAB>SPEC (single mode) or NAME<TAB>SPEC_A<TAB>SPEC_B (paired mode), SPEC as --columns takes it.  Every file is "
+                   "read and uploaded once; grouping NAME is written to OUTPUT/NAME/ as its own --columns command would write it")
 def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2, outputDirectory, stateInfo, saliency,
          numProcesses, exitBool, diagnosticBool, numTrials, samplingSize, quiescentState, groupSize, version, partition,
-         pvalBool, roiWidth, fileTag, expFreqMem, expCombMem, scoreMem, roiMem, nullSeed, nullDraws, gpus, cacheDir, columns, columnsA, columnsB, checkStates):
+         pvalBool, roiWidth, fileTag, expFreqMem, expCombMem, scoreMem, roiMem, nullSeed, nullDraws, gpus, cacheDir, columns, columnsA, columnsB, checkStates,
+         groupingsFile):
     """Information-theoretic navigation of multi-tissue functional genomic annotations -- MI355X scoring engine."""
     if version:
         print("Version:", __version__)
@@ -203,14 +180,29 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
     if nullDraws > 1 and (gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
         print("ERROR: [--null-draws] greater than 1 runs on one GPU: the exceedance counts of several ranks are not added up yet; "
               "use [--gpus 1]"); sys.exit()
+    # --groupings: as above, its own combinations and its file's errors before everything else -- nothing is read but that file
+    groupings = None
+    if groupingsFile is not None:
+        from .helpers import parseGroupings
+        for given, opt in ((columns, "--columns"), (columnsA, "--columns-a"), (columnsB, "--columns-b"), (inputDirectory1, "-a"),
+                           (inputDirectory2, "-b")):
+            if given is not None:
+                print("ERROR: [--groupings] names the biosamples of every grouping itself; it cannot be combined with [{}]".format(opt))
+                sys.exit()
+        if inputDirectory is None:
+            print("ERROR: [-i, --input-directory] is required with [--groupings]"); sys.exit()
+        try:
+            groupings = parseGroupings(groupingsFile, mode)
+        except ValueError as e:
+            print("ERROR: [--groupings] {}".format(e)); sys.exit()
     # column groups: the flag combinations that involve the new options come first, so that every combination without them
     # gets today's message
-    pairedColumns = mode == "paired" and (columnsA is not None or columnsB is not None)
+    pairedColumns = mode == "paired" and (columnsA is not None or columnsB is not None or groupings is not None)
     if mode == "single" and (columnsA is not None or columnsB is not None):
         print("ERROR: [--columns-a] and [--columns-b] are only valid in paired mode; single mode takes [--columns]"); sys.exit()
     if mode == "paired" and columns is not None:
         print("ERROR: [--columns] is only valid in single mode; paired mode takes [--columns-a] and [--columns-b]"); sys.exit()
-    if pairedColumns:
+    if pairedColumns and groupings is None:
         if columnsA is None or columnsB is None:
             print("ERROR: [--columns-a] and [--columns-b] must be given together"); sys.exit()
         if inputDirectory1 is not None or inputDirectory2 is not None:
@@ -221,14 +213,14 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
     try:
         what = "--columns"
         cols = parseColumns(columns) if columns is not None else None
-        if pairedColumns:
+        if pairedColumns and groupings is None:
             what = "--columns-a"
             colsA = parseColumns(columnsA)
             what = "--columns-b"
             colsB = parseColumns(columnsB)
     except ValueError as e:
         print("ERROR: [{}] {}".format(what, e)); sys.exit()
-    if pairedColumns:
+    if pairedColumns and groupings is None:
         both = sorted(set(colsA.tolist()) & set(colsB.tolist()))
         if both:
             print("ERROR: biosample {} is in both [--columns-a] and [--columns-b]".format(both[0] + 1)); sys.exit()
@@ -261,6 +253,9 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
     outputDirPath = Path(outputDirectory)
     if not PurePath(outputDirPath).is_absolute():
         outputDirPath = Path.cwd() / outputDirPath
+    if groupings is not None and inputDirPath.is_dir():
+        # the largest biosample number of the file against every matrix's columns, before the first directory is made
+        _check_biosamples_exist(sorted(inputDirPath.glob("*"), key=_natural_key), max(int(c.max()) for g in groupings for c in g[1:]))
     checkArguments(mode, saliency, inputDirPath, inputDirPath2, outputDirPath, numProcesses, numStates, quiescentState,
                    groupSize, numTrials, samplingSize, roiWidth)
     if fileTag == "null":
@@ -291,15 +286,8 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
                                         + " Please ensure corresponding files within input directories 1 and 2 have the same name")
             files2.append(next(inputDirPath2.glob(file.name)))
     from . import driver, _io
-    if cols is not None or pairedColumns:                     # every biosample asked for must exist in every file
-        top = max(int(c.max()) for c in ((cols,) if cols is not None else (colsA, colsB)))
-        for f in files:
-            try:
-                n = driver._columns_of(f)
-            except Exception:                                    # (an empty or unreadable file: the parse reports it, or it has no rows)
-                continue
-            if n and top >= n:
-                print("ERROR: biosample {} is not in {}: the file has {} biosample columns".format(top + 1, f, n)); sys.exit()
+    if groupings is None and (cols is not None or pairedColumns):     # every biosample asked for must exist in every file
+        _check_biosamples_exist(files, max(int(c.max()) for c in ((cols,) if cols is not None else (colsA, colsB))))
     if world == 1 and not under_launcher and os.environ.get("EPILOGOS_EARLY_READERS", "1") != "0":
         # A single process: the files' readers start NOW -- inflating needs neither torch nor the GPU, and importing the one and
         # initialising the other takes about a second, which a whole-genome run spent before its first byte was read.  A reader
@@ -321,7 +309,64 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
         print("    [timing] %-34s %7.2f s" % ("imports + device init (since process start)", time.time() - _T_START), flush=True)
 
     say("State Model =", numStates, " Saliency level =", saliency, " GPUs =", world)
-    if mode == "single":
+    def step4_single(results, outDir):
+        try:
+            if rank == 0:
+                say("\nSTEP 4: Finding regions of interest", flush=True)
+                import time
+                t0 = time.perf_counter()
+                from .roiSingle import mainFromArrays as roiSingle
+                roiSingle(results, outDir, stateInfo, fileTag, outDir / storedExpPath.name, roiWidth if roiWidth else 50, False)
+                if os.environ.get("EPILOGOS_TIMING"):
+                    print("    [timing] %-34s %7.2f s" % ("STEP 4", time.perf_counter() - t0), flush=True)
+        finally:
+            driver.finish_writes()                               # one process: the score text was still being written under STEP 4
+
+    def step4_paired(results, outDir):
+        if pvalBool and max(numProcesses, 1) > 1 and nullDraws == 1:
+            driver.finish_writes()                               # -n -c K forks a pool for the fits: not with writer threads running
+        try:
+            if rank == 0:
+                say("\nSTEP 4: Generating p-values & regions of interest (figures are not produced)", flush=True)
+                import time
+                t0 = time.perf_counter()
+                from .roiAndVisualPairwise import mainFromArrays as roiPairwise
+                roiPairwise(results, stateInfo, outDir, fileTag, max(numProcesses, 1), pvalBool, numTrials, samplingSize,
+                            outDir / storedExpPath.name, roiWidth if roiWidth else 125, False)
+                if os.environ.get("EPILOGOS_TIMING"):
+                    print("    [timing] %-34s %7.2f s" % ("STEP 4", time.perf_counter() - t0), flush=True)
+        finally:
+            driver.finish_writes()
+
+    if mode == "paired" and nullSeed is None:
+        import numpy as np
+        seed = np.array([int(np.random.SeedSequence().generate_state(1)[0])], dtype=np.int64)
+        if world > 1:                                            # every rank must shuffle with the same seed
+            import torch
+            import torch.distributed as dist
+            t = torch.from_numpy(seed)
+            t = t.to(device) if device is not None else t
+            dist.broadcast(t, src=0)
+            seed = t.cpu().numpy()
+        nullSeed = int(seed[0])                                  # (--groupings: the one seed of every grouping)
+    if groupings is not None:
+        # every file is parsed and uploaded once; the groupings then run one after another from the resident matrices, each with
+        # STEP 4 and its text complete before the next begins (driver.run_groupings yields as it goes)
+        say("\nSTEP 1-3 of %d grouping(s): background counts -> all-reduce -> scores%s, from one read of the matrices (%d GPU(s))"
+            % (len(groupings), ", null groups, deltas" if mode == "paired" else "", world))
+        runs = driver.run_groupings(files, groupings, numStates, saliency, outputDirPath, fileTag, quiescentState, groupSize, nullSeed,
+                                    verbose=False, device=device, keep_temps=False, defer_writes=True, nullDraws=nullDraws,
+                                    checkStates=checkStates)
+        try:
+            for k, g in enumerate(groupings):
+                say("\nGrouping %d of %d: %s" % (k + 1, len(groupings), g[0]), flush=True)
+                name, _q, results, _info = next(runs)
+                (step4_single if mode == "single" else step4_paired)(results, outputDirPath / name)
+        finally:
+            runs.close()
+            driver.abort_early_readers()
+            driver.finish_writes()
+    elif mode == "single":
         from .driver import run_single_group
         say("\nSTEP 1-3: background counts -> all-reduce -> scores (bin-range partition over %d GPU(s))" % world)
         try:
@@ -329,30 +374,9 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
                                           keep_temp_scores=False, defer_writes=True, columns=cols, checkStates=checkStates)
         finally:
             driver.abort_early_readers()                         # (nothing to do once the stage driver has taken them over)
-        try:
-            if rank == 0:
-                say("\nSTEP 4: Finding regions of interest", flush=True)
-                import time
-                t0 = time.perf_counter()
-                from .roiSingle import mainFromArrays as roiSingle
-                roiSingle(results, outputDirPath, stateInfo, fileTag, storedExpPath, roiWidth if roiWidth else 50, False)
-                if os.environ.get("EPILOGOS_TIMING"):
-                    print("    [timing] %-34s %7.2f s" % ("STEP 4", time.perf_counter() - t0), flush=True)
-        finally:
-            driver.finish_writes()                               # one process: the score text was still being written under STEP 4
+        step4_single(results, outputDirPath)
     else:
         from .driver import run_paired_columns, run_paired_groups
-        if nullSeed is None:
-            import numpy as np
-            seed = np.array([int(np.random.SeedSequence().generate_state(1)[0])], dtype=np.int64)
-            if world > 1:                                        # every rank must shuffle with the same seed
-                import torch
-                import torch.distributed as dist
-                t = torch.from_numpy(seed)
-                t = t.to(device) if device is not None else t
-                dist.broadcast(t, src=0)
-                seed = t.cpu().numpy()
-            nullSeed = int(seed[0])
         say("\nSTEP 1-3: background counts over [A|B] -> all-reduce -> scores, null groups, deltas (%d GPU(s))" % world)
         try:
             if pairedColumns:
@@ -365,20 +389,7 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
                                                nullDraws=nullDraws, checkStates=checkStates)
         finally:
             driver.abort_early_readers()
-        if pvalBool and max(numProcesses, 1) > 1 and nullDraws == 1:
-            driver.finish_writes()                               # -n -c K forks a pool for the fits: not with writer threads running
-        try:
-            if rank == 0:
-                say("\nSTEP 4: Generating p-values & regions of interest (figures are not produced)", flush=True)
-                import time
-                t0 = time.perf_counter()
-                from .roiAndVisualPairwise import mainFromArrays as roiPairwise
-                roiPairwise(results, stateInfo, outputDirPath, fileTag, max(numProcesses, 1), pvalBool, numTrials, samplingSize,
-                            storedExpPath, roiWidth if roiWidth else 125, False)
-                if os.environ.get("EPILOGOS_TIMING"):
-                    print("    [timing] %-34s %7.2f s" % ("STEP 4", time.perf_counter() - t0), flush=True)
-        finally:
-            driver.finish_writes()
+        step4_paired(results, outputDirPath)
     from .helpers import flushCacheWrites
     flushCacheWrites()                                           # --cache-dir: files of first-time reads, written in the background
     if os.environ.get("EPILOGOS_TIMING") and rank == 0:
