@@ -261,15 +261,22 @@ class _HipSession:
         written -- of later ones (driver.run_groupings keeps it between its groupings)."""
         return self._upload(arr, N, ticket)
 
+    def check_resident(self, X, N, ticket):
+        """--check-states for a matrix that reached the device without an upload of this session (driver.run_groupings with
+        resident matrices): the census _upload takes, under the ticket the verdict will look it up by."""
+        if self.check_states and X.shape[0] and N:
+            self._check_upload(X, N, ticket)
+
     def close(self):
         """Give back what the session holds: its parts (histograms, state rows, null groups), the early results, the count
-        accumulator, exp_freq and the S1 tables, the census scratch, and the page-locked staging buffers with the thread that
-        returns them.  The matrices a caller passed to add_device / add_columns are the caller's.  A closed session takes no
+        accumulator, exp_freq and the S1 tables, the census scratch, the engine's kept membership bytes of its column groups, and
+        the page-locked staging buffers with the thread that returns them.  The matrices a caller passed to add_device / add_columns are the caller's.  A closed session takes no
         further calls."""
         self._pending, self._pending_rows = [], 0
         self.parts, self._early, self._t1, self._t1_verified = [], {}, {}, set()
         self.acc = self.q = self._pending_check = None
         self.state_checks, self._census_scratch = {}, {}
+        self.eng.forget_group_members()                  # (the membership bytes of this session's column groups)
         if self._releaser is not None:                   # (waits for the uploads in flight: their staging buffers come back)
             self._release_q.put(None)
             self._releaser.join()

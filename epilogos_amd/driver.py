@@ -526,7 +526,10 @@ class _Single:
         return sess.add_part(arr, n, t, columns=self.columns)
 
     def add_resident(self, sess, X, n, part):
-        """add() for a job whose matrix is on the device already (run_groupings: uploaded by this or an earlier grouping)."""
+        """add() for a job whose matrix is on the device already (run_groupings: uploaded by this or an earlier grouping, or handed
+        in by the caller).  No columns: the group is the whole matrix, as in add()."""
+        if self.columns is None:
+            return sess.add_device(X, n)
         _check_columns_fit(self.columns, n, self.groups[0][part[0]])
         return sess.add_device(X, n, columns=self.columns)
 
@@ -864,7 +867,11 @@ class _ResidentStore:
     FREE_FACTOR and FREE_SLACK are a choice, not a measurement: twice the matrix plus 2 GiB is room that every session measured
     so far fits in many times over at 833 biosamples; nobody has looked for the smallest values that work.
     The cap is applied IN JOB ORDER, whatever order the readers finish in (a matrix that arrives early waits, on the device, for
-    the verdicts of the jobs before it), so that what is kept does not depend on the timing of the parser threads."""
+    the verdicts of the jobs before it), so that what is kept does not depend on the timing of the parser threads.
+
+    `seed` is the way in for matrices that never were files (run_groupings(resident=...)): they are kept from the start under the
+    jobs of their virtual paths, so no pass reads, parses or uploads anything.  Whether they fit is the caller's question, asked
+    once for all of them with the same rule (`fits`); EPILOGOS_RESIDENT_BYTES does not apply -- there is no file to fall back to."""
     FREE_FACTOR, FREE_SLACK = 2, 2 << 30
 
     def __init__(self):
@@ -875,9 +882,25 @@ class _ResidentStore:
         self._seen, self._wait, self._next = set(), {}, 0
         self.uploads = self.parsed = 0                 # of the grouping under way
 
+    @classmethod
+    def fits(cls, nbytes, free):
+        """The admission rule: `free` bytes of device memory (None: not a device) leave room for a session next to nbytes of matrices."""
+        return free is None or free >= cls.FREE_FACTOR * nbytes + cls.FREE_SLACK
+
+    def seed(self, files, resident):
+        """Matrices that are on the device already: resident[path] = (X, N, Locations) for every path of `files` (one rank, whole
+        files: the plan is made from what is here, no header is read)."""
+        resident = {Path(p): v for p, v in resident.items()}
+        for f in files:
+            X, n, loc = resident[Path(f)]
+            self.kept[(Path(f), 0, None)] = (X, n, loc)
+            self.bytes += _nbytes(X)
+        self._seen.update(self.kept)
+        self.plan = ("whole", None, [(fi, 0, None) for fi in range(len(files))], None)
+
     def _offer(self, t, job, X, n, loc):
         nbytes, free = _nbytes(X), _device_free(X)
-        room = free is None or free >= self.FREE_FACTOR * nbytes + self.FREE_SLACK
+        room = self.fits(nbytes, free)
         self._wait[t] = (job, X if room else None, n, loc, nbytes)
         while self._next in self._wait:
             job, X, n, loc, nbytes = self._wait.pop(self._next)
@@ -901,6 +924,8 @@ class _ResidentStore:
         for t, job in enumerate(jobs):
             if job in self.kept:
                 X, n, loc = self.kept[job]
+                if raw:                                # (--check-states, the first pass: only a seeded matrix is kept by then)
+                    sess.check_resident(X, n, t)
                 yield t, X, n, loc
         if not todo:
             return
@@ -914,7 +939,8 @@ class _ResidentStore:
 
 
 def run_groupings(files, groupings, numStates, saliency, outputDir, fileTag, quiescentState=None, groupSize=-1, nullSeed=None,
-                  verbose=False, backend=None, device=None, keep_temps=True, defer_writes=False, nullDraws=1, checkStates=False):
+                  verbose=False, backend=None, device=None, keep_temps=True, defer_writes=False, nullDraws=1, checkStates=False,
+                  resident=None, flat=False):
     """Many groupings of the biosample columns of ONE set of files in one run: every file is parsed and uploaded once, its matrix
     stays on the device (_ResidentStore: unless the admission rule refuses it), and every grouping runs STEP 1-3 from the resident
     matrices with a session of its own.  groupings: [(name, cols)] -- each what run_single_group(columns=cols) computes -- or
@@ -926,7 +952,13 @@ def run_groupings(files, groupings, numStates, saliency, outputDir, fileTag, qui
     uploads (H2D matrix copies this rank made for the grouping), parsed_files (passes over input files this rank made for it),
     resident_bytes (bytes of input matrices this rank holds on the device after it), kept_files / refused_files (this rank's jobs
     in and not in the store).  checkStates censuses every matrix on the first pass, which is the pass that uploads them all.
-    A grouping that raises ends the run; the directories of the groupings before it are complete."""
+    A grouping that raises ends the run; the directories of the groupings before it are complete.
+    resident ({path: (X, N, Locations)} for every path of `files`, one rank): the matrices are on the device already -- built there,
+    never files -- and `files` only names them (output stems, messages, the run order that keys the null shuffle).  The store is
+    seeded with them: no reader starts, nothing is parsed or uploaded, every grouping's info says uploads == parsed_files == 0, and
+    checkStates censuses them where they are.  They are read, never written.
+    flat (one grouping): its outputs go to outputDir itself -- a plain run, --columns or --columns-a/-b over resident matrices is
+    a one-grouping run of this function; a single-mode grouping whose columns are None is the whole matrix."""
     files = [Path(f) for f in files]
     groupings = [tuple(g) for g in groupings]
     if not groupings:
@@ -939,10 +971,16 @@ def run_groupings(files, groupings, numStates, saliency, outputDir, fileTag, qui
         if d.world > 1:
             raise ValueError("several ranks must be given the same null seed")
         nullSeed = int(np.random.SeedSequence().generate_state(1)[0])
+    if flat and len(groupings) != 1:
+        raise ValueError("a run without subdirectories has one grouping")
     store = _ResidentStore()
+    if resident is not None:
+        if d.world > 1:
+            raise ValueError("resident matrices are one rank's: sharing them out over several ranks is not available")
+        store.seed(files, resident)
     try:
         for k, g in enumerate(groupings):
-            out = Path(outputDir) / g[0]
+            out = Path(outputDir) if flat else Path(outputDir) / g[0]
             out.mkdir(parents=True, exist_ok=True)
             if paired:
                 mode = _PairedColumns(files, g[1], g[2], numStates, saliency, quiescentState, groupSize, nullSeed, keep_temps, nullDraws)

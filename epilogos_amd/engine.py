@@ -455,6 +455,12 @@ def group_members(device, N, groups):
     return m
 
 
+def forget_group_members():
+    """Drop the kept membership tensors (a closed session's groups: a run of many groupings would otherwise leave one per
+    grouping on the device until 64 have gathered)."""
+    _members.clear()
+
+
 def bin_hist_groups(X, N, S, groups, counts=None, want_hist=True):
     """The count pass for column groups of ONE matrix (epg_bin_hist_groups): X is read once, every group gets per-bin
     histograms of its own columns.  groups: 1 .. GROUPS_MAX int64 arrays of 0-based columns.  -> ([H_g uint16 [R, S] as int16

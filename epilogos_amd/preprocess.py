@@ -61,6 +61,68 @@ class _Concordance:
         self.tally.write(self.prefix, self.names)
 
 
+def iter_matrices(datadir, metadata, chromsizes, out=sys.stdout, segments=False, width=stateByLine.BIN_WIDTH, table=None):
+    """The matrices of a ChromHMM output directory as they are built, each still on the device: yields (chromosome of `chromsizes`,
+    X int8 [R, ldx], N, the chromosome name the matrix file stores, (lo, hi), the biosample of every column, bin width) and writes
+    the progress lines -- "Processing ...: n files found. " before a matrix is built, "Done." when the consumer comes back for the
+    next, "Skipping." for a chromosome without files.  `epilogos-prep` is this plus write_epgm, --census and --concordance (run,
+    run_segments); `epilogos --chromhmm` is this plus the hand-over to the run (epilogos_amd/run.py).  State-by-line calls: one
+    chromosome is built at a time.  segments (table: the parsed --state-names, or None): every chromosome's matrix is built in
+    one pass over the files, then handed out in `chromsizes` order.  A consumer that drops X frees it."""
+    from . import engine
+    engine.require_gpu()
+    if segments:
+        files, names = segmentFiles.find_segments_named(datadir, metadata)
+        chroms, sizes = segmentFiles.read_chromsizes(chromsizes)
+        mats = segmentFiles.build_matrices_device(files, chroms, width, sizes=sizes, state_names=table) if files else {}
+        for chrom in dict.fromkeys(chroms):
+            found = chrom in mats
+            out.write("Processing {}: {} files found. ".format(chrom, len(files) if found else 0))
+            out.flush()
+            if not found:
+                out.write("Skipping.\n")
+                continue
+            X, rng = mats.pop(chrom)
+            yield chrom, X, len(files), chrom, rng, names, width
+            del X
+            out.write("Done.\n")
+            out.flush()
+        return
+    for chrom, files, names in stateByLine.iter_calls_named(datadir, metadata, chromsizes):
+        out.write("Processing {}: {} files found. ".format(chrom, len(files)))
+        out.flush()
+        if not files:
+            out.write("Skipping.\n")
+            continue
+        # (the name inside the file is the calls' own, the script's chr=$2; the file is named after the chromsizes entry like the script's)
+        X, N, name, rng = stateByLine.build_matrix_device(files)
+        yield chrom, X, N, name, rng, names, stateByLine.BIN_WIDTH
+        del X
+        out.write("Done.\n")
+        out.flush()
+
+
+def matrix_path(outdir, chrom):
+    return Path(outdir) / "matrix_{}{}".format(chrom, stateByLine.EXT)
+
+
+def _write_all(matrices, outdir, tally, pairs):
+    """run / run_segments behind their arguments: every matrix of `matrices` (iter_matrices) censused, tallied and written."""
+    written = []
+    for chrom, X, N, name, rng, names, width in matrices:
+        if tally:
+            tally.add(name, X, N, rng, names)
+        if pairs:
+            pairs.add(name, X, N, rng, names)
+        written.append(stateByLine.write_epgm(matrix_path(outdir, chrom), X[:, :N].contiguous(), name, rng, width))
+        del X
+    if tally:
+        tally.write()
+    if pairs:
+        pairs.write()
+    return written
+
+
 def run_segments(datadir, metadata, chromsizes, outdir, out=sys.stdout, width=stateByLine.BIN_WIDTH, state_names=None, census=None,
                  concordance=None):
     """`run` for segment files: every chromosome's matrix is built in one pass over the files, then written in `chromsizes` order."""
@@ -68,34 +130,10 @@ def run_segments(datadir, metadata, chromsizes, outdir, out=sys.stdout, width=st
     engine.require_gpu()
     outdir = Path(outdir)
     outdir.mkdir(parents=True, exist_ok=True)
-    files, names = segmentFiles.find_segments_named(datadir, metadata)
-    chroms, sizes = segmentFiles.read_chromsizes(chromsizes)
     table = segmentFiles.read_state_names(state_names) if state_names else None
-    mats = segmentFiles.build_matrices_device(files, chroms, width, sizes=sizes, state_names=table) if files else {}
     tally = _Census(census, table) if census else None
     pairs = _Concordance(concordance) if concordance else None
-    written = []
-    for chrom in dict.fromkeys(chroms):
-        found = chrom in mats
-        out.write("Processing {}: {} files found. ".format(chrom, len(files) if found else 0))
-        out.flush()
-        if not found:
-            out.write("Skipping.\n")
-            continue
-        X, rng = mats.pop(chrom)
-        if tally:
-            tally.add(chrom, X, len(files), rng, names)
-        if pairs:
-            pairs.add(chrom, X, len(files), rng, names)
-        written.append(stateByLine.write_epgm(outdir / "matrix_{}{}".format(chrom, stateByLine.EXT), X[:, :len(files)].contiguous(), chrom, rng, width))
-        del X
-        out.write("Done.\n")
-        out.flush()
-    if tally:
-        tally.write()
-    if pairs:
-        pairs.write()
-    return written
+    return _write_all(iter_matrices(datadir, metadata, chromsizes, out, True, width, table), outdir, tally, pairs)
 
 
 def run(datadir, metadata, chromsizes, outdir, out=sys.stdout, segments=False, width=stateByLine.BIN_WIDTH, state_names=None, census=None,
@@ -109,30 +147,9 @@ def run(datadir, metadata, chromsizes, outdir, out=sys.stdout, segments=False, w
     engine.require_gpu()
     outdir = Path(outdir)
     outdir.mkdir(parents=True, exist_ok=True)
-    written = []
     tally = _Census(census) if census else None
     pairs = _Concordance(concordance) if concordance else None
-    for chrom, files, names in stateByLine.iter_calls_named(datadir, metadata, chromsizes):
-        out.write("Processing {}: {} files found. ".format(chrom, len(files)))
-        out.flush()
-        if not files:
-            out.write("Skipping.\n")
-            continue
-        X, N, name, rng = stateByLine.build_matrix_device(files)
-        if tally:
-            tally.add(name, X, N, rng, names)
-        if pairs:
-            pairs.add(name, X, N, rng, names)
-        # (the name inside the file is the calls' own, the script's chr=$2; the file is named after the chromsizes entry like the script's)
-        written.append(stateByLine.write_epgm(outdir / "matrix_{}{}".format(chrom, stateByLine.EXT), X[:, :N].contiguous(), name, rng))
-        del X
-        out.write("Done.\n")
-        out.flush()
-    if tally:
-        tally.write()
-    if pairs:
-        pairs.write()
-    return written
+    return _write_all(iter_matrices(datadir, metadata, chromsizes, out), outdir, tally, pairs)
 
 
 @click.command(context_settings={"help_option_names": ["-h", "--help"]})

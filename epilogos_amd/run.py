@@ -5,7 +5,10 @@ node: `--gpus N` starts one process per GPU (a child `python -m torch.distribute
 touches a GPU) the way the reference's one command fans out over SLURM by itself; a process that finds itself under
 torch.distributed.run (WORLD_SIZE set) joins the group.  Console script: `epilogos` (pyproject.toml -> run:cli).  Single mode
 also runs STEP 4 (regionsOfInterest_*.txt, epilogos_amd/roiSingle.py); paired mode runs the STEP 4 of
-epilogos_amd/roiAndVisualPairwise.py (pairwiseMetrics, regionsOfInterest, significantLoci; no figures)."""
+epilogos_amd/roiAndVisualPairwise.py (pairwiseMetrics, regionsOfInterest, significantLoci; no figures).
+`--chromhmm DIR --metadata FILE --chromsizes FILE` takes the place of `-i`: the matrices are built on the GPU from ChromHMM output by
+epilogos-prep's own generator (preprocess.iter_matrices) and scored where they sit (driver.run_groupings(resident=...)); the run
+sees them as the files matrix_{chr}.epgm of a directory named like DIR."""
 import os
 import re
 import sys
@@ -75,6 +78,87 @@ def _check_biosamples_exist(files, top):
             continue
         if n and top >= n:
             print("ERROR: biosample {} is not in {}: the file has {} biosample columns".format(top + 1, f, n)); sys.exit()
+
+
+def _check_chromhmm_flags(mode, chromhmm, metadata, chromsizes, segments, binWidth, stateNames, keepMatrices, inputDirectory,
+                          inputDirectory1, inputDirectory2, columnsA, columnsB, groupingsFile, cacheDir, gpus):
+    """The usage errors of [--chromhmm] and the options that go with it.  Silent for a command line that has none of them."""
+    def refuse(text):
+        print("ERROR: [--chromhmm] " + text); sys.exit()
+    if chromhmm is None:
+        for given, opt in ((metadata, "--metadata"), (chromsizes, "--chromsizes"), (segments or None, "--segments"), (binWidth, "--bin-width"),
+                           (stateNames, "--state-names"), (keepMatrices, "--keep-matrices")):
+            if given is not None:
+                refuse("is required with [{}]: the option describes a ChromHMM output directory".format(opt))
+        return
+    for given, opt in ((inputDirectory, "-i"), (inputDirectory1, "-a"), (inputDirectory2, "-b")):
+        if given is not None:
+            refuse("takes the place of the input directories; it cannot be combined with [{}]".format(opt))
+    for given, opt in ((metadata, "--metadata"), (chromsizes, "--chromsizes")):
+        if given is None:
+            refuse("requires [{}]".format(opt))
+    for given, opt in ((binWidth, "--bin-width"), (stateNames, "--state-names")):
+        if given is not None and not segments:
+            refuse("[{}] goes with [--segments]".format(opt))
+    if binWidth is not None and binWidth <= 0:
+        refuse("the bin width must be positive")
+    if mode == "paired" and columnsA is None and columnsB is None and groupingsFile is None:
+        refuse("builds one set of matrices: paired mode needs [--columns-a] and [--columns-b], or [--groupings], to name the two groups")
+    if cacheDir is not None:
+        refuse("cannot be combined with [--cache-dir]: the matrices are built on the GPU, there is no parsed text to cache")
+    if gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        refuse("runs on one GPU: it builds and holds the matrices, sharing them out over several ranks is not done yet; "
+               "use [--gpus 1]")
+
+
+def _selects_a_file(datadir, metadata, chromsizes, segments):
+    """Whether epilogos-prep's selection rule finds any file of the directory (host only; two files for one biosample raise here
+    what they raise there)."""
+    from . import segments as segmentFiles, stateByLine
+    if segments:
+        return bool(segmentFiles.find_segments_named(datadir, metadata)[0])
+    return any(files for _chrom, files, _names in stateByLine.iter_calls_named(datadir, metadata, chromsizes))
+
+
+def _build_resident(chromhmm, metadata, chromsizes, segments, binWidth, stateNames, keepMatrices, numStates, checkStates):
+    """[--chromhmm]: the matrices of the ChromHMM output directory, built on the device by epilogos-prep's own generator
+    (preprocess.iter_matrices, which prints its progress lines) and kept there.  -> (files, resident): the virtual paths
+    `matrix_{chr}.epgm` the run sees them under -- in OUTDIR with [--keep-matrices], where they are then also written, as built --
+    in the natural-key order in which [-i] would run those files, and {path: (X, N, Locations)} for driver.run_groupings.
+    Without [--check-states] a matrix is handed over as stateByLine.read_epgm would have read its file: what is no state of the
+    parser's limit is -1.  A state range outside the model raises what the readers of the files raise.  The matrices must fit on
+    the device next to a session by the resident store's own rule, applied once to their total; if not, the run ends here."""
+    from . import _io, driver, preprocess, segments as segmentFiles, stateByLine
+    _io.set_state_limit(numStates)
+    table = segmentFiles.read_state_names(stateNames) if stateNames else None
+    outdir = None
+    if keepMatrices is not None:
+        outdir = Path(keepMatrices)
+        outdir.mkdir(parents=True, exist_ok=True)
+    resident, ranges = {}, {}
+    for chrom, X, N, name, rng, _names, width in preprocess.iter_matrices(chromhmm, metadata, chromsizes, sys.stdout, segments,
+                                                                          binWidth or stateByLine.BIN_WIDTH, table):
+        path = preprocess.matrix_path(outdir if outdir is not None else "", chrom)
+        if outdir is not None:
+            stateByLine.write_epgm(path, X[:, :N].contiguous(), name, rng, width)
+        if not checkStates and rng[1] > _io.state_limit():       # (a byte is a state value - 1; the pad columns are -1 as built)
+            X[(X >= _io.state_limit()) | (X < 0)] = -1
+        resident[path] = (X, N, stateByLine.synth_locations(name, 0, X.shape[0], width))
+        ranges[path] = rng
+        del X
+    files = sorted(resident, key=_natural_key)
+    for f in files:
+        driver._check_range(f, ranges[f], numStates)
+    if files:
+        nbytes = sum(driver._nbytes(resident[f][0]) for f in files)
+        free = driver._device_free(resident[files[0]][0])
+        if not driver._ResidentStore.fits(nbytes, free):
+            print("ERROR: [--chromhmm] the matrices do not fit on the device next to a run: they are {} bytes and need {} bytes free "
+                  "({} x the matrices + {}), {} bytes are free.  Use the two commands instead: epilogos-prep -o MATRICES, then "
+                  "epilogos -i MATRICES".format(nbytes, driver._ResidentStore.FREE_FACTOR * nbytes + driver._ResidentStore.FREE_SLACK,
+                                                driver._ResidentStore.FREE_FACTOR, driver._ResidentStore.FREE_SLACK, free))
+            sys.exit(1)
+    return files, resident
 
 
 def _init_device_and_group(world, under_launcher):
@@ -162,14 +246,33 @@ def _init_device_and_group(world, under_launcher):
               help="Score many biosample groupings of the matrices of [-i] in one run: a tab-separated file with one line per grouping, "
                    "NAME<TAB>SPEC (single mode) or NAME<TAB>SPEC_A<TAB>SPEC_B (paired mode), SPEC as --columns takes it.  Every file is "
                    "read and uploaded once; grouping NAME is written to OUTPUT/NAME/ as its own --columns command would write it")
+@click.option("--chromhmm", "chromhmm", type=str, default=None,
+              help="In place of [-i]: score straight from a ChromHMM output directory (the first argument of epilogos-prep).  The state "
+                   "matrices are built on the GPU and scored where they sit; no matrix file is written or read.  Needs [--metadata] and "
+                   "[--chromsizes]; one GPU")
+@click.option("--metadata", "metadata", type=str, default=None, help="With --chromhmm: the biosample table (the second argument of epilogos-prep)")
+@click.option("--chromsizes", "chromsizes", type=str, default=None, help="With --chromhmm: the chromosome sizes (the third argument of epilogos-prep)")
+@click.option("--segments", "segments", is_flag=True,
+              help="With --chromhmm: the directory holds ChromHMM segment files (one *_segments.bed per biosample, whole genome)")
+@click.option("--bin-width", "binWidth", type=int, default=None, help="With --chromhmm --segments: the bin width in bp  [default: 200]")
+@click.option("--state-names", "stateNames", type=str, default=None,
+              help="With --chromhmm --segments: a state metadata TSV (one_index, short_name) for labels that are names")
+@click.option("--keep-matrices", "keepMatrices", type=str, default=None,
+              help="With --chromhmm: also write the matrix_<chr>.epgm files of epilogos-prep here")
 def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2, outputDirectory, stateInfo, saliency,
          numProcesses, exitBool, diagnosticBool, numTrials, samplingSize, quiescentState, groupSize, version, partition,
          pvalBool, roiWidth, fileTag, expFreqMem, expCombMem, scoreMem, roiMem, nullSeed, nullDraws, gpus, cacheDir, columns, columnsA, columnsB, checkStates,
-         groupingsFile):
+         groupingsFile, chromhmm, metadata, chromsizes, segments, binWidth, stateNames, keepMatrices):
     """Information-theoretic navigation of multi-tissue functional genomic annotations -- MI355X scoring engine."""
     if version:
         print("Version:", __version__)
         sys.exit()
+    # --chromhmm and what goes with it: its own combinations before all others, so that every command line without these options
+    # gets today's messages; nothing is read and no directory is made
+    _check_chromhmm_flags(mode, chromhmm, metadata, chromsizes, segments, binWidth, stateNames, keepMatrices, inputDirectory,
+                          inputDirectory1, inputDirectory2, columnsA, columnsB, groupingsFile, cacheDir, gpus)
+    if chromhmm is not None:
+        inputDirectory = chromhmm                         # from here on the run's input directory: required-ness, tag, emptiness
     # --null-draws: its own combinations first, so that every command line without it gets today's messages
     if nullDraws < 1:
         print("ERROR: [--null-draws] must be at least 1"); sys.exit()
@@ -253,9 +356,16 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
     outputDirPath = Path(outputDirectory)
     if not PurePath(outputDirPath).is_absolute():
         outputDirPath = Path.cwd() / outputDirPath
-    if groupings is not None and inputDirPath.is_dir():
+    if groupings is not None and inputDirPath.is_dir() and chromhmm is None:
         # the largest biosample number of the file against every matrix's columns, before the first directory is made
         _check_biosamples_exist(sorted(inputDirPath.glob("*"), key=_natural_key), max(int(c.max()) for g in groupings for c in g[1:]))
+    if chromhmm is not None:
+        for given, opt in ((metadata, "--metadata"), (chromsizes, "--chromsizes"), (stateNames, "--state-names")):
+            if given is not None and not Path(given).is_file():
+                print("ERROR: [{}] is not a file: {}".format(opt, given)); sys.exit()
+        if inputDirPath.is_dir() and list(inputDirPath.glob("*")) and not _selects_a_file(inputDirPath, metadata, chromsizes, segments):
+            # no file of the directory is anybody's: epilogos-prep would leave an empty directory, which [-i] refuses like this
+            raise OSError("Ensure that directory is not empty: {}".format(str(inputDirPath)))
     checkArguments(mode, saliency, inputDirPath, inputDirPath2, outputDirPath, numProcesses, numStates, quiescentState,
                    groupSize, numTrials, samplingSize, roiWidth)
     if fileTag == "null":
@@ -277,7 +387,7 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
     # one process per GPU when launched under torch.distributed.run
     world = int(os.environ.get("WORLD_SIZE", "1"))
     under_launcher = "WORLD_SIZE" in os.environ and "RANK" in os.environ
-    files = sorted(inputDirPath.glob("*"), key=_natural_key)
+    files = sorted(inputDirPath.glob("*"), key=_natural_key) if chromhmm is None else []    # (--chromhmm: named once they are built)
     files2 = []
     if mode == "paired" and not pairedColumns:
         for file in files:
@@ -288,7 +398,7 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
     from . import driver, _io
     if groupings is None and (cols is not None or pairedColumns):     # every biosample asked for must exist in every file
         _check_biosamples_exist(files, max(int(c.max()) for c in ((cols,) if cols is not None else (colsA, colsB))))
-    if world == 1 and not under_launcher and os.environ.get("EPILOGOS_EARLY_READERS", "1") != "0":
+    if chromhmm is None and world == 1 and not under_launcher and os.environ.get("EPILOGOS_EARLY_READERS", "1") != "0":
         # A single process: the files' readers start NOW -- inflating needs neither torch nor the GPU, and importing the one and
         # initialising the other takes about a second, which a whole-genome run spent before its first byte was read.  A reader
         # asks for its (page-locked) destination only after its inflate; the session is attached when it exists.
@@ -307,6 +417,23 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
     if os.environ.get("EPILOGOS_TIMING") and rank == 0:
         import time
         print("    [timing] %-34s %7.2f s" % ("imports + device init (since process start)", time.time() - _T_START), flush=True)
+
+    resident = None
+    if chromhmm is not None:
+        # epilogos-prep's part of the job, its progress lines included, before the run's own output
+        t_build = _time.time()
+        files, resident = _build_resident(inputDirPath, metadata, chromsizes, segments, binWidth, stateNames, keepMatrices, numStates,
+                                          checkStates)
+        if os.environ.get("EPILOGOS_TIMING"):
+            print("    [timing] %-34s %7.2f s" % ("matrices built on the device", _time.time() - t_build), flush=True)
+        if not files:                                            # (segment files that hold no chromosome of the sizes file)
+            raise OSError("Ensure that directory is not empty: {}".format(str(inputDirPath)))
+        asked = [c for g in groupings for c in g[1:]] if groupings is not None else [c for c in (cols, colsA, colsB) if c is not None]
+        top = max([int(c.max()) for c in asked] + [-1])
+        for f in files:
+            n = resident[f][1]
+            if n and top >= n:
+                print("ERROR: biosample {} is not in {}: the matrix has {} biosample columns".format(top + 1, f, n)); sys.exit()
 
     say("State Model =", numStates, " Saliency level =", saliency, " GPUs =", world)
     def step4_single(results, outDir):
@@ -349,17 +476,28 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
             dist.broadcast(t, src=0)
             seed = t.cpu().numpy()
         nullSeed = int(seed[0])                                  # (--groupings: the one seed of every grouping)
-    if groupings is not None:
+    if groupings is not None or resident is not None:
         # every file is parsed and uploaded once; the groupings then run one after another from the resident matrices, each with
-        # STEP 4 and its text complete before the next begins (driver.run_groupings yields as it goes)
-        say("\nSTEP 1-3 of %d grouping(s): background counts -> all-reduce -> scores%s, from one read of the matrices (%d GPU(s))"
-            % (len(groupings), ", null groups, deltas" if mode == "paired" else "", world))
+        # STEP 4 and its text complete before the next begins (driver.run_groupings yields as it goes).  --chromhmm: the matrices
+        # are resident before the first grouping, and a run without --groupings is one grouping written to the output directory itself
+        flat = groupings is None
+        if not flat:
+            say("\nSTEP 1-3 of %d grouping(s): background counts -> all-reduce -> scores%s, from one read of the matrices (%d GPU(s))"
+                % (len(groupings), ", null groups, deltas" if mode == "paired" else "", world))
+        elif mode == "single":
+            groupings = [("", cols)]
+            say("\nSTEP 1-3: background counts -> all-reduce -> scores (bin-range partition over %d GPU(s))" % world)
+        else:
+            groupings = [("", colsA, colsB)]
+            say("\nSTEP 1-3: background counts over [A|B] -> all-reduce -> scores, null groups, deltas (%d GPU(s))" % world)
         runs = driver.run_groupings(files, groupings, numStates, saliency, outputDirPath, fileTag, quiescentState, groupSize, nullSeed,
                                     verbose=False, device=device, keep_temps=False, defer_writes=True, nullDraws=nullDraws,
-                                    checkStates=checkStates)
+                                    checkStates=checkStates, **({} if resident is None else {"resident": resident, "flat": flat}))
+        resident = None                                          # (the store's from here on: gone with the run)
         try:
             for k, g in enumerate(groupings):
-                say("\nGrouping %d of %d: %s" % (k + 1, len(groupings), g[0]), flush=True)
+                if not flat:
+                    say("\nGrouping %d of %d: %s" % (k + 1, len(groupings), g[0]), flush=True)
                 name, _q, results, _info = next(runs)
                 (step4_single if mode == "single" else step4_paired)(results, outputDirPath / name)
         finally:
