@@ -1,6 +1,6 @@
 """ctypes binding of include/epilogos_amd.h, include/epilogos_scores_text.h, include/epilogos_groups.h,
 include/epilogos_nulldraws.h, include/epilogos_statebyline.h, include/epilogos_segments.h, include/epilogos_simsearch_pick.h,
-include/epilogos_census.h and include/epilogos_concordance.h.  No fallbacks: a missing library or symbol raises."""
+include/epilogos_census.h, include/epilogos_concordance.h and include/epilogos_gennorm.h.  No fallbacks: a missing library or symbol raises."""
 import ctypes as C
 import re
 from pathlib import Path
@@ -127,7 +127,21 @@ CONCORDANCE_PROTOTYPES = {
     "epg_concordance": (C.c_int, [_p, _i64, _i32, _i64, _i32, _p, _p, _p, _i64, _p]),
 }
 
+# and for include/epilogos_gennorm.h, the device fit of the paired null distribution (tests/test_gennorm_host.py checks it)
+GENNORM_HEADER = HEADER.with_name("epilogos_gennorm.h")
+GENNORM_PROTOTYPES = {
+    "epgf_gennorm_ws_bytes": (_i64, [_i64, _i32, _i64]),
+    "epgf_gennorm_fit": (C.c_int, [_p, _i64, _p, _i32, _i64, _p, _p, _p, _p, _i64, _p]),
+    "epgf_gennorm_nnlf": (C.c_int, [_p, _i64, _p, _i32, _p, _p, _i64, _p]),
+}
+
 _lib = None
+
+
+def gennorm_header_symbols():
+    """Function names declared in include/epilogos_gennorm.h."""
+    txt = re.sub(r"/\*.*?\*/", "", GENNORM_HEADER.read_text(), flags=re.S)
+    return sorted(set(re.findall(r"\b(epgf_[a-z0-9_]+)\s*\(", txt)))
 
 
 def concordance_header_symbols():
@@ -224,7 +238,7 @@ def load():
     lib = C.CDLL(str(path))
     for name, (res, args) in list(PROTOTYPES.items()) + list(TEXT_PROTOTYPES.items()) + list(GROUP_PROTOTYPES.items()) + \
             list(NULLDRAWS_PROTOTYPES.items()) + list(SBL_PROTOTYPES.items()) + list(SEG_PROTOTYPES.items()) + list(PICK_PROTOTYPES.items()) + \
-            list(CENSUS_PROTOTYPES.items()) + list(CONCORDANCE_PROTOTYPES.items()):
+            list(CENSUS_PROTOTYPES.items()) + list(CONCORDANCE_PROTOTYPES.items()) + list(GENNORM_PROTOTYPES.items()):
         fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
         fn.restype = res
         fn.argtypes = args

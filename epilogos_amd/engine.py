@@ -527,6 +527,60 @@ def concordance(X, N, S, agree=None, both=None, want_both=True, ws=None):
     return agree.view(N, N), (both.view(N, N) if both is not None else None)
 
 
+def gennorm_ws_bytes(M, T, n=0):
+    return max(int(_abi.call("epgf_gennorm_ws_bytes", M, T, n)), 256)
+
+
+def _check_gennorm_x(x):
+    if x.dtype != torch.float32 or x.dim() != 1 or not x.is_cuda or not x.is_contiguous() or x.numel() < 1:
+        raise ValueError("x must be a non-empty contiguous 1-D float32 CUDA tensor")
+    return x.numel()
+
+
+def gennorm_fit(x, idx=None, n=None, ws=None):
+    """T generalised-normal maximum-likelihood fits on the device (epgf_gennorm_fit, include/epilogos_gennorm.h): trial t fits
+    x[idx[t]] (idx: int32 [T, n], every index in 0 .. M-1, checked here); idx None: one trial on all of x.
+    -> (params float64 [T, 3] = (beta, loc, scale), fval float64 [T], info int32 [T, 2] = (evaluations, flag)); flag 0 converged,
+    1 stopped at the cap, 2 degenerate sample (params NaN).  Current stream, no synchronisation beyond the index check's."""
+    M = _check_gennorm_x(x)
+    if idx is None:
+        T, n = 1, M if n is None else int(n)
+    else:
+        if idx.dtype != torch.int32 or idx.dim() != 2 or not idx.is_cuda or not idx.is_contiguous():
+            raise ValueError("idx must be a contiguous 2-D int32 CUDA tensor [T, n]")
+        T = idx.shape[0]
+        if n is not None and int(n) != idx.shape[1]:
+            raise ValueError("n=%d is not the row length %d of idx" % (n, idx.shape[1]))
+        n = idx.shape[1]
+        if T < 1 or n < 1:
+            raise ValueError("idx must hold at least one trial of at least two indices")
+        lo, hi = torch.aminmax(idx)
+        if int(lo) < 0 or int(hi) >= M:
+            raise ValueError("idx holds an index outside 0 .. %d" % (M - 1))
+    params = torch.empty((T, 3), dtype=torch.float64, device=x.device)
+    fval = torch.empty(T, dtype=torch.float64, device=x.device)
+    info = torch.empty((T, 2), dtype=torch.int32, device=x.device)
+    if ws is None:
+        ws = torch.empty(gennorm_ws_bytes(M, T, n), dtype=torch.uint8, device=x.device)
+    _abi.call("epgf_gennorm_fit", _ptr(x), M, _ptr(idx), T, n, _ptr(params), _ptr(fval), _ptr(info), _ptr(ws), ws.numel(), _stream())
+    return params, fval, info
+
+
+def gennorm_nnlf(x, params, ws=None):
+    """Negative log-likelihood of ALL of x under each of the T parameter sets (epgf_gennorm_nnlf): params float64 [T, 3] ->
+    float64 [T]; +inf for a set with beta <= 0, scale <= 0 or a NaN.  One pass over x."""
+    M = _check_gennorm_x(x)
+    if params.dtype != torch.float64 or params.dim() != 2 or params.shape[1] != 3 or not params.is_cuda or not params.is_contiguous() \
+            or params.shape[0] < 1:
+        raise ValueError("params must be a contiguous float64 CUDA tensor [T, 3]")
+    T = params.shape[0]
+    out = torch.empty(T, dtype=torch.float64, device=x.device)
+    if ws is None:
+        ws = torch.empty(gennorm_ws_bytes(M, T, 0), dtype=torch.uint8, device=x.device)
+    _abi.call("epgf_gennorm_nnlf", _ptr(x), M, _ptr(params), T, _ptr(out), _ptr(ws), ws.numel(), _stream())
+    return out
+
+
 def select_columns(X, cols):
     """The columns `cols` (0-based int64) of a state matrix as a matrix of its own: int8 [R, padded_width(len(cols))], padding
     bytes 0xFF.  What the grouped count pass does not serve (S3 needs the states themselves; models of 32 .. 127 states) runs

@@ -87,7 +87,12 @@ def _fitOnSharedData(samplingSize):
     return fitOnSubSample(_FIT_DATA, samplingSize)
 
 
-def fitDistances(outputDirPath, numProcesses, numTrials, samplingSize):
+def _fitOptions(fit, seed):
+    """What _fitParams is handed beyond its five arguments: nothing for the host fit, which is called as it always was."""
+    return {} if fit == "host" else dict(fit=fit, seed=seed)
+
+
+def fitDistances(outputDirPath, numProcesses, numTrials, samplingSize, fit="host", seed=None):
     """Null distances of the non-quiescent bins in chromosome order, `numTrials` fits, the one with the median
     negative log-likelihood wins (reference :175-221)."""
     nulls, quies = {}, {}
@@ -98,7 +103,7 @@ def fitDistances(outputDirPath, numProcesses, numTrials, samplingSize):
     _, distanceArrNull = _ordered_concat(nulls)
     _, quiescenceArr = _ordered_concat(quies)
     nonQuiescentIdx = np.where(np.invert(quiescenceArr.astype(bool)))[0]
-    return _fitParams(distanceArrNull, quiescenceArr, numProcesses, numTrials, samplingSize), distanceArrNull, nonQuiescentIdx
+    return _fitParams(distanceArrNull, quiescenceArr, numProcesses, numTrials, samplingSize, **_fitOptions(fit, seed)), distanceArrNull, nonQuiescentIdx
 
 
 def empiricalPVals(exceed, pool):
@@ -279,9 +284,60 @@ def _done(verbose, t0):
         print("\t[Done]", flush=True)
 
 
-def _fitParams(distanceArrNull, quiescenceArr, numProcesses, numTrials, samplingSize):
-    """Median-likelihood gennorm fit of the non-quiescent null distances (reference :196-221)."""
+def medianTrial(nnlf):
+    """The trial whose negative log-likelihood is the median one: the lower median of a stable ascending sort (reference :216-221)."""
+    nnlf = np.asarray(nnlf, dtype=np.float64)
+    return int(np.argsort(nnlf, kind="stable")[int((len(nnlf) - 1) / 2)])
+
+
+FIT_SEED_TAG = 0x666974                              # "fit": the sub-samples' stream of a run's seed, apart from the null shuffles'
+
+
+def fitIndices(M, numTrials, samplingSize, seed):
+    """The sub-samples of the device fit: int32 [numTrials, samplingSize], row t = trial t's indices into the M null distances,
+    drawn without replacement, trial after trial, from default_rng([seed, FIT_SEED_TAG]); None when M <= samplingSize (every
+    trial fits all of them).  seed None: fresh OS entropy."""
+    if M <= samplingSize:
+        return None
+    if seed is None:
+        seed = int(np.random.SeedSequence().generate_state(1, dtype=np.uint64)[0])
+    rng = np.random.default_rng([int(seed) & 0xFFFFFFFFFFFFFFFF, FIT_SEED_TAG])
+    return np.stack([rng.choice(M, size=samplingSize, replace=False) for _ in range(numTrials)]).astype(np.int32)
+
+
+def _fitParamsGpu(data, numTrials, samplingSize, seed):
+    """The fit="gpu" branch of _fitParams: one upload, one fit call, one nnlf call (include/epilogos_gennorm.h), the median pick on
+    the host.  -> (beta, loc, scale), or None when a trial's sub-sample was degenerate (flag 2) or there is nothing to fit."""
+    import torch
+    from . import engine
+    engine.require_gpu()
+    values = np.ascontiguousarray(data, dtype=np.float32)
+    if values.size < 2:
+        return None
+    x = torch.from_numpy(values).cuda()
+    idx = fitIndices(values.size, numTrials, samplingSize, seed)
+    # M <= samplingSize: every trial fits the same values and has the same likelihood; one trial's work stands for all
+    params, _fval, info = engine.gennorm_fit(x, None if idx is None else torch.from_numpy(idx).cuda())
+    nnlf = engine.gennorm_nnlf(x, params)
+    if bool((info[:, 1] == 2).any()):
+        return None
+    params, nnlf = params.cpu().numpy(), nnlf.cpu().numpy()
+    return tuple(params[medianTrial(nnlf) if idx is not None else 0])
+
+
+def _fitParams(distanceArrNull, quiescenceArr, numProcesses, numTrials, samplingSize, fit="host", seed=None):
+    """Median-likelihood gennorm fit of the non-quiescent null distances (reference :196-221).  fit="gpu": the trials and their
+    likelihoods on the device, the sub-samples seeded from `seed` (fitIndices); no pool is forked."""
     data = distanceArrNull[np.where(np.invert(quiescenceArr.astype(bool)))[0]]
+    if fit == "gpu":
+        params = _fitParamsGpu(data, numTrials, samplingSize, seed)
+        if params is not None:
+            return params
+        print("WARNING: a sub-sample of the null distances is constant or holds a value that is not finite; fitting on the host instead",
+              flush=True)
+        numProcesses = 1                             # in this process: the caller did not stop its writer threads for a fork
+    elif fit != "host":
+        raise ValueError("fit must be 'host' or 'gpu', not {!r}".format(fit))
     if numProcesses > 1 and numTrials > 1:
         # the reference pickles the whole array into every one of the numTrials tasks (:206-208, 43 MB x 101 at genome scale);
         # forked workers already have it
@@ -301,8 +357,7 @@ def _fitParams(distanceArrNull, quiescenceArr, numProcesses, numTrials, sampling
             pool.join()
     else:
         results = [fitOnSubSample(data, samplingSize) for _ in range(numTrials)]
-    nnlf = np.array([r[1] for r in results], dtype=np.float64)
-    return tuple(results[np.argsort(nnlf, kind="stable")[int((numTrials - 1) / 2)]][0])
+    return tuple(results[medianTrial([r[1] for r in results])][0])
 
 
 def _finish(params, locationArr, distanceArrReal, maxDiffArr, chrDict, stateInfo, outputDirPath, fileTag, pvalBool, roiWidth,
@@ -352,7 +407,7 @@ def _is_location_sorted(chrNum, starts, ends):
 
 
 def mainFromArrays(results, stateInfo, outputDir, fileTag, numProcesses, pvalBool, numTrials, samplingSize, expFreqPath,
-                   roiWidth, verbose):
+                   roiWidth, verbose, fit="host", seed=None):
     """main() on the arrays driver.run_paired_groups hands back ({stem: dict(chrName, locations, nullDistances,
     quiescenceArr, distances, maxDiff)}) instead of the temp_*.npz / pairwiseDelta text round trip."""
     outputDirPath = Path(outputDir)
@@ -367,7 +422,7 @@ def mainFromArrays(results, stateInfo, outputDir, fileTag, numProcesses, pvalBoo
         empirical = empiricalPVals(cat("nullExceed"), max(int(v["nullPool"]) for v in byChr.values()))
     elif pvalBool:
         t0 = _stage(verbose, "Fitting distances")
-        params = _fitParams(cat("nullDistances"), cat("quiescenceArr"), numProcesses, numTrials, samplingSize)
+        params = _fitParams(cat("nullDistances"), cat("quiescenceArr"), numProcesses, numTrials, samplingSize, **_fitOptions(fit, seed))
         _done(verbose, t0)
     cols = [byChr[c]["locations"].columns() for c in chrOrder]
     chrNum = np.concatenate([np.full(len(c[1]), i + 1, dtype=np.int64) for i, c in enumerate(cols)])
@@ -388,7 +443,7 @@ def mainFromArrays(results, stateInfo, outputDir, fileTag, numProcesses, pvalBoo
 
 
 def main(group1Name, group2Name, stateInfo, outputDir, fileTag, numProcesses, pvalBool, diagnosticBool, numTrials,
-         samplingSize, expFreqPath, roiWidth, verbose, backend=None):
+         samplingSize, expFreqPath, roiWidth, verbose, backend=None, fit="host", seed=None):
     tTotal = time()
     outputDirPath = Path(outputDir)
     numStates = getNumStates(stateInfo)
@@ -399,7 +454,7 @@ def main(group1Name, group2Name, stateInfo, outputDir, fileTag, numProcesses, pv
     empiricalRun = pvalBool and any(outputDirPath.glob("temp_nullExceed_*.npz"))
     if pvalBool and not empiricalRun:
         t0 = _stage(verbose, "Fitting distances")
-        params, _, _ = fitDistances(outputDirPath, numProcesses, numTrials, samplingSize)
+        params, _, _ = fitDistances(outputDirPath, numProcesses, numTrials, samplingSize, fit=fit, seed=seed)
         _done(verbose, t0)
     t0 = _stage(verbose, "Reading in files")
     locationArr, distanceArrReal, maxDiffArr, chrDict, empirical = _readInData(outputDirPath, numStates, backend)

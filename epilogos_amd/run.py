@@ -230,6 +230,10 @@ def _init_device_and_group(world, under_launcher):
               help="Paired mode with -n: draw every bin's null groups K times and report empirical p-values, "
                    "(1 + #{pooled null distances >= |distance|}) / (1 + K x non-quiescent bins), instead of fitting a distribution "
                    "(no fit: -t and -z are unused); one GPU only.  1: one draw and the fit")
+@click.option("--fit", "fit", type=click.Choice(["host", "gpu"]), default="host", show_default=True,
+              help="Paired mode with -n: where the [-t] generalised-normal fits of the null distances run.  host: scipy, on [-c] cores, "
+                   "sub-samples from OS entropy.  gpu: on the device, sub-samples seeded from [--null-seed]: two runs with the same seed "
+                   "write the same p-values")
 @click.option("--gpus", "gpus", type=int, default=1, show_default=True,
               help="GPUs of this node to split the genome over (0 = all visible); replaces the SLURM fan-out of the reference")
 @click.option("--cache-dir", "cacheDir", type=str, default=None,
@@ -262,7 +266,7 @@ def _init_device_and_group(world, under_launcher):
 def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2, outputDirectory, stateInfo, saliency,
          numProcesses, exitBool, diagnosticBool, numTrials, samplingSize, quiescentState, groupSize, version, partition,
          pvalBool, roiWidth, fileTag, expFreqMem, expCombMem, scoreMem, roiMem, nullSeed, nullDraws, gpus, cacheDir, columns, columnsA, columnsB, checkStates,
-         groupingsFile, chromhmm, metadata, chromsizes, segments, binWidth, stateNames, keepMatrices):
+         groupingsFile, chromhmm, metadata, chromsizes, segments, binWidth, stateNames, keepMatrices, fit="host"):
     """Information-theoretic navigation of multi-tissue functional genomic annotations -- MI355X scoring engine."""
     if version:
         print("Version:", __version__)
@@ -283,6 +287,13 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
     if nullDraws > 1 and (gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
         print("ERROR: [--null-draws] greater than 1 runs on one GPU: the exceedance counts of several ranks are not added up yet; "
               "use [--gpus 1]"); sys.exit()
+    # --fit gpu: the same, so that every command line without it gets today's messages
+    if fit == "gpu" and mode != "paired":
+        print("ERROR: [--fit gpu] is only valid in paired mode"); sys.exit()
+    if fit == "gpu" and not pvalBool:
+        print("ERROR: [--fit gpu] requires [-n, --null-distribution]: without it nothing is fitted"); sys.exit()
+    if fit == "gpu" and nullDraws > 1:
+        print("ERROR: [--fit gpu] cannot be combined with [--null-draws] greater than 1: empirical p-values need no fit"); sys.exit()
     # --groupings: as above, its own combinations and its file's errors before everything else -- nothing is read but that file
     groupings = None
     if groupingsFile is not None:
@@ -449,8 +460,12 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
         finally:
             driver.finish_writes()                               # one process: the score text was still being written under STEP 4
 
+    def fitOptions():
+        # nothing for --fit host: STEP 4 is called exactly as before.  nullSeed is the run's one seed by now, drawn or given
+        return dict(fit="gpu", seed=nullSeed) if fit == "gpu" else {}
+
     def step4_paired(results, outDir):
-        if pvalBool and max(numProcesses, 1) > 1 and nullDraws == 1:
+        if pvalBool and max(numProcesses, 1) > 1 and nullDraws == 1 and fit != "gpu":
             driver.finish_writes()                               # -n -c K forks a pool for the fits: not with writer threads running
         try:
             if rank == 0:
@@ -459,7 +474,7 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
                 t0 = time.perf_counter()
                 from .roiAndVisualPairwise import mainFromArrays as roiPairwise
                 roiPairwise(results, stateInfo, outDir, fileTag, max(numProcesses, 1), pvalBool, numTrials, samplingSize,
-                            outDir / storedExpPath.name, roiWidth if roiWidth else 125, False)
+                            outDir / storedExpPath.name, roiWidth if roiWidth else 125, False, **fitOptions())
                 if os.environ.get("EPILOGOS_TIMING"):
                     print("    [timing] %-34s %7.2f s" % ("STEP 4", time.perf_counter() - t0), flush=True)
         finally:

@@ -12,7 +12,8 @@ For each: the wall time from the start of the first child to the exit of the las
 at the end of the first grouping's STEP 1 -- imports, device init, the read of the file, its upload and that grouping's count
 pass (milliseconds) -- which is the fixed cost the later groupings do not pay again; and the [timing] lines of the run, summed
 by phase, which say where the rest went.  Output directories and the input go to a scratch directory that is removed at the end.
-usage: groupings_bench.py [--bins 1246253] [--columns 833] [--groupings 8] [--only single|paired] [--trials 101] [--workdir DIR]"""
+usage: groupings_bench.py [--bins 1246253] [--columns 833] [--groupings 8] [--only single|paired] [--trials 101] [--fit host|gpu]
+                          [--workdir DIR]"""
 import argparse
 import json
 import os
@@ -35,6 +36,7 @@ ap.add_argument("--columns", type=int, default=833)
 ap.add_argument("--groupings", type=int, default=8)
 ap.add_argument("--only", choices=["single", "paired"], default=None)
 ap.add_argument("--trials", type=int, default=101, help="-t of the paired commands (the fits of -n)")
+ap.add_argument("--fit", choices=["host", "gpu"], default=None, help="--fit of the paired commands (default: not passed, the host fit)")
 ap.add_argument("--workdir", type=str, default=None)
 ap.add_argument("--child-limit", type=int, default=900, help="seconds a child process may take")
 a = ap.parse_args()
@@ -94,7 +96,7 @@ def phases(lines):
 
 
 work = Path(tempfile.mkdtemp(prefix="groupings_bench_", dir=a.workdir))
-result = {"bins": R, "N": N, "S": S, "groupings": G, "input": ".epgm", "trials": a.trials}
+result = {"bins": R, "N": N, "S": S, "groupings": G, "input": ".epgm", "trials": a.trials, "fit": a.fit or "host"}
 try:
     ind = work / "in"
     ind.mkdir()
@@ -117,7 +119,8 @@ try:
             lines.append(["g%02d" % g] + [spec(c.tolist()) for c in groups])
         gfile = work / (mode + ".tsv")
         gfile.write_text("".join("\t".join(l) + "\n" for l in lines))
-        common = ["-i", str(ind), "-j", str(meta), "-s", "1"] + (["-m", "paired", "-n", "--null-seed", "1", "-t", str(a.trials)] if mode == "paired" else [])
+        common = ["-i", str(ind), "-j", str(meta), "-s", "1"] + (["-m", "paired", "-n", "--null-seed", "1", "-t", str(a.trials)] + (["--fit", a.fit] if a.fit else [])
+                                                       if mode == "paired" else [])
         walls = []
         for l in lines:
             cols = ["--columns", l[1]] if mode == "single" else ["--columns-a", l[1], "--columns-b", l[2]]
