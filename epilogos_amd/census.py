@@ -33,8 +33,8 @@ def state_headers(stateInfo, S):
 
 def read_names(metadata):
     """Biosample names: column 1 of the metadata file behind its header line, the way the preprocessing command reads it."""
-    from .stateByLine import _first_fields
-    return _first_fields(metadata, skip=1)
+    from .textBatches import first_fields
+    return first_fields(metadata, skip=1)
 
 
 def table_lines(entries, heads):

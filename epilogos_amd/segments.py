@@ -11,7 +11,6 @@ build_matrices_device the files -> {chromosome: (X int8 [R_c, ldx] on the device
 The parser on the device is strict (the grammar is written out in the header).  A file it refuses is named in one warning line
 and parsed on the host, which also takes '\\r\\n', blanks around fields, track / browser / # lines, more than four fields and
 labels that are names (--state-names); errors of content raise ValueError with file and line on either path."""
-import ctypes as C
 import fnmatch
 import os
 import re
@@ -20,7 +19,8 @@ from pathlib import Path
 import numpy as np
 
 from . import _abi, _io
-from .stateByLine import BIN_WIDTH, _align, _first_fields
+from .stateByLine import BIN_WIDTH
+from .textBatches import TextBatches, align, first_fields, mark, offsets_of, pointers, put_column, reread_on_host, set_timings
 
 NAME_BYTES = 80
 _LABEL = re.compile(r"^[A-Za-z]?([0-9]{1,3})(_.*)?$", re.S)
@@ -41,7 +41,7 @@ def find_segments_named(datadir, metadata):
     datadir = Path(datadir)
     names = sorted(n for n in os.listdir(datadir) if not n.startswith("."))
     files, found = [], []
-    for b in _first_fields(metadata, skip=1):
+    for b in first_fields(metadata, skip=1):
         hits = [n for n in names if fnmatch.fnmatchcase(n, "*{}*segments.bed*".format(b))]
         if len(hits) > 1:
             raise ValueError("biosample {} has more than one segment file: {} and {}".format(b, datadir / hits[0], datadir / hits[1]))
@@ -205,13 +205,11 @@ def build_matrices_device(files, chroms, width=BIN_WIDTH, sizes=None, state_name
     """files: one segment file per biosample, in column order; chroms: the chromosome table.
     -> {chromosome: (X int8 [R_c, ldx] on the current device with ldx = N rounded up to 16 and -1 in columns >= N, (lo, hi))} for
     the chromosomes the files hold, in table order.  The host inflates the files `_io.host_budget()` at a time; a batch of up to
-    64 texts is uploaded at once through two pinned slots, each text is parsed (epg_seg_parse), and for every chromosome the
+    64 texts is uploaded at once (textBatches.TextBatches), each text is parsed (epg_seg_parse), and for every chromosome the
     batch's columns are expanded (epg_seg_expand) and transposed into its resident matrix (epg_sbl_transpose).  R_c comes from
     the first file (one synchronisation); every matrix stays resident until the caller has written it.  `timings` (a dict)
     receives inflate_s, upload_ms, parse_ms, expand_ms and transpose_ms (HIP events, summed over the batches)."""
     import torch
-    from concurrent.futures import ThreadPoolExecutor
-    from time import perf_counter
     from . import engine
     engine.require_gpu()
     files = [Path(f) for f in files]
@@ -226,125 +224,64 @@ def build_matrices_device(files, chroms, width=BIN_WIDTH, sizes=None, state_name
     threads = max(1, int(threads or _io.host_budget()))
     batch = int(_abi.call("epg_sbl_constant", 3))
     dev = torch.device("cuda", torch.cuda.current_device())
-    main = torch.cuda.current_stream()
     names = torch.from_numpy(name_table(chroms)).to(dev) if nchrom else torch.zeros(1, dtype=torch.uint8, device=dev)
-    t_wait = 0.0
     ev = {k: [] for k in ("upload", "parse", "expand", "transpose")}
 
-    def mark():
-        e = torch.cuda.Event(enable_timing=True)
-        e.record(main)
-        return e
-
-    def inflate(k):
-        return _io.Text(files[k], 1)
-
     def host_file(k, line):
-        print("epilogos_amd: {}: line {} is not a strict segment line -- reading this file on the host (slow)".format(files[k], line), flush=True)
-        with _io.Text(files[k], 1) as tx:
-            return parse_host(tx.data, files[k], chroms, width, state_names)
+        return reread_on_host(files[k], line, "a strict segment line", lambda a: parse_host(a, files[k], chroms, width, state_names))
 
     infos = torch.zeros((N, 4), dtype=torch.int64, device=dev)
     runs = torch.zeros((N, max(nchrom, 1), 3), dtype=torch.int64, device=dev)
-    sizes_b, caps = [0] * N, [0] * N
+    caps = []                                                    # the lines of every file, counted on the host
     host_cols = {}                                               # file -> what parse_host gave
-    ref = X = cols = col_pitch = None                            # ref: {chromosome index: R_c} of the first file
-    ldx = _align(N, 16)
-    slots = []                                                   # per parity: [pinned, device text, event "the batch has left the device text"]
-    with ThreadPoolExecutor(max_workers=threads) as pool:
-        starts = list(range(0, N, batch))
-        futs = {0: [pool.submit(inflate, k) for k in range(0, min(batch, N))]}
-        try:
-            for bi, k0 in enumerate(starts):
-                nb = min(batch, N - k0)
-                t0 = perf_counter()
-                texts = [f.result() for f in futs.pop(bi)]
-                try:
-                    offs = np.zeros(nb + 1, dtype=np.int64)
-                    loff = np.zeros(nb + 1, dtype=np.int64)
-                    for j, tx in enumerate(texts):
-                        sizes_b[k0 + j] = len(tx.data)
-                        caps[k0 + j] = count_lines(tx.data)
-                        offs[j + 1] = offs[j] + _align(len(tx.data), 16)
-                        loff[j + 1] = loff[j] + _align(max(caps[k0 + j], 1), 16)
-                    total = int(offs[-1])
-                    s = bi % 2
-                    if len(slots) <= s:
-                        slots.append([None, None, None])
-                    pinned, dtext, done = slots[s]
-                    if done is not None:
-                        done.synchronize()
-                    if pinned is None or pinned.numel() < total:
-                        room = _align(total + total // 8, 4096)
-                        pinned = torch.empty(room, dtype=torch.uint8).pin_memory()
-                        dtext = torch.empty(room, dtype=torch.uint8, device=dev)
-                    host = pinned.numpy()
-
-                    def stage(j):
-                        host[offs[j]:offs[j] + sizes_b[k0 + j]] = texts[j].data
-                    list(pool.map(stage, range(nb)))
-                    if bi + 1 < len(starts):                     # the next batch inflates while this one is on the device
-                        k1 = starts[bi + 1]
-                        futs[bi + 1] = [pool.submit(inflate, k) for k in range(k1, min(k1 + batch, N))]
-                finally:
-                    for tx in texts:
-                        tx.close()
-                t_wait += perf_counter() - t0
-                wsb = max(int(_abi.call("epg_seg_ws_bytes", sizes_b[k0 + j], nchrom)) for j in range(nb))
-                ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-                first = torch.empty(int(loff[-1]), dtype=torch.int32, device=dev)
-                state = torch.empty(int(loff[-1]), dtype=torch.int8, device=dev)
-                e0 = mark()
-                dtext[:total].copy_(pinned[:total], non_blocking=True)
-                e1 = mark()
+    ref = X = cols = col_of = col_pitch = None                   # ref: {chromosome index: R_c} of the first file
+    ldx = align(N, 16)
+    with TextBatches(files, batch, threads, dev, lambda k, data: count_lines(data)) as batches:
+        info_of, runs_of = pointers(infos), pointers(runs)
+        for b in batches:
+            k0, nb, stream = b.k0, b.nb, engine._stream()
+            caps.extend(b.facts)
+            loff = offsets_of([max(n, 1) for n in b.facts])       # where every file's lines start in `first` and `state`
+            wsb = max(int(_abi.call("epg_seg_ws_bytes", n, nchrom)) for n in b.sizes)
+            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+            first = torch.empty(int(loff[-1]), dtype=torch.int32, device=dev)
+            state = torch.empty(int(loff[-1]), dtype=torch.int8, device=dev)
+            text_of, first_of, state_of = pointers(b.text, b.offsets[:-1]), pointers(first, loff[:-1]), pointers(state, loff[:-1])
+            for j in range(nb):
+                _abi.call("epg_seg_parse", text_of[j], b.sizes[j], engine._ptr(names), nchrom, int(width), first_of[j], state_of[j], caps[k0 + j],
+                          runs_of[k0 + j], info_of[k0 + j], engine._ptr(ws), wsb, stream)
+            e2 = mark()
+            b.release()
+            ev["upload"].append(b.upload), ev["parse"].append((b.upload[1], e2))
+            if ref is None:                                      # R_c, to allocate: the one synchronisation before the last
+                bad = int(infos[0, 3].item())
+                if bad >= 0:
+                    host_cols[0] = host_file(0, bad + 1)
+                    ref = {i: len(host_cols[0][c][0]) for i, c in enumerate(chroms) if c in host_cols[0]}
+                else:
+                    r0 = runs[0].cpu().numpy()
+                    ref = {i: int(r0[i, 2]) for i in range(nchrom) if r0[i, 1] > 0}
+                col_pitch = max(align(max(ref.values(), default=0), 16), 16)
+                need = sum(ref.values()) * ldx + batch * col_pitch
+                free = torch.cuda.mem_get_info(dev)[0]
+                if need > free:
+                    raise RuntimeError("the matrices of {} chromosomes and {} biosamples take {:.2f} GB of device memory, {:.2f} GB are free".format(
+                        len(ref), N, need / 1e9, free / 1e9))
+                X = {i: torch.full((R, ldx), -1, dtype=torch.int8, device=dev) for i, R in ref.items()}
+                cols = torch.empty((batch, col_pitch), dtype=torch.int8, device=dev)
+                col_of = pointers(cols)
+            for i, R in ref.items():
+                e3 = mark()
                 for j in range(nb):
-                    k = k0 + j
-                    _abi.call("epg_seg_parse", C.c_void_p(dtext.data_ptr() + int(offs[j])), sizes_b[k], engine._ptr(names), nchrom, int(width),
-                              C.c_void_p(first.data_ptr() + 4 * int(loff[j])), C.c_void_p(state.data_ptr() + int(loff[j])), caps[k],
-                              C.c_void_p(runs.data_ptr() + 24 * max(nchrom, 1) * k), C.c_void_p(infos.data_ptr() + 32 * k),
-                              engine._ptr(ws), wsb, engine._stream())
-                e2 = mark()
-                slots[s] = [pinned, dtext, e2]
-                ev["upload"].append((e0, e1)), ev["parse"].append((e1, e2))
-                if ref is None:                                  # R_c, to allocate: the one synchronisation before the last
-                    bad = int(infos[0, 3].item())
-                    if bad >= 0:
-                        host_cols[0] = host_file(0, bad + 1)
-                        ref = {i: len(host_cols[0][c][0]) for i, c in enumerate(chroms) if c in host_cols[0]}
-                    else:
-                        r0 = runs[0].cpu().numpy()
-                        ref = {i: int(r0[i, 2]) for i in range(nchrom) if r0[i, 1] > 0}
-                    col_pitch = max(_align(max(ref.values(), default=0), 16), 16)
-                    need = sum(ref.values()) * ldx + batch * col_pitch
-                    free = torch.cuda.mem_get_info(dev)[0]
-                    if need > free:
-                        raise RuntimeError("the matrices of {} chromosomes and {} biosamples take {:.2f} GB of device memory, {:.2f} GB are free".format(
-                            len(ref), N, need / 1e9, free / 1e9))
-                    X = {i: torch.full((R, ldx), -1, dtype=torch.int8, device=dev) for i, R in ref.items()}
-                    cols = torch.empty((batch, col_pitch), dtype=torch.int8, device=dev)
-                for i, R in ref.items():
-                    e3 = mark()
-                    for j in range(nb):
-                        _abi.call("epg_seg_expand", C.c_void_p(first.data_ptr() + 4 * int(loff[j])), C.c_void_p(state.data_ptr() + int(loff[j])),
-                                  C.c_void_p(runs.data_ptr() + 24 * max(nchrom, 1) * (k0 + j)), i, C.c_void_p(cols.data_ptr() + j * col_pitch), R,
-                                  engine._stream())
-                    e4 = mark()
-                    _abi.call("epg_sbl_transpose", engine._ptr(cols), nb, col_pitch, R, engine._ptr(X[i]), ldx, k0, engine._stream())
-                    e5 = mark()
-                    ev["expand"].append((e3, e4)), ev["transpose"].append((e4, e5))
-        finally:
-            for fs in futs.values():                             # an error on the way: give the inflated buffers back
-                for f in fs:
-                    try:
-                        f.result().close()
-                    except Exception:
-                        pass
+                    _abi.call("epg_seg_expand", first_of[j], state_of[j], runs_of[k0 + j], i, col_of[j], R, stream)
+                e4 = mark()
+                _abi.call("epg_sbl_transpose", engine._ptr(cols), nb, col_pitch, R, engine._ptr(X[i]), ldx, k0, stream)
+                e5 = mark()
+                ev["expand"].append((e3, e4)), ev["transpose"].append((e4, e5))
+        inflate_s = batches.inflate_s
     info = infos.cpu().numpy()                                   # the one synchronisation behind the batches
     run = runs.cpu().numpy()
-    if timings is not None:
-        timings["inflate_s"] = t_wait
-        for k, pairs in ev.items():
-            timings[k + "_ms"] = float(sum(a.elapsed_time(b) for a, b in pairs))
+    set_timings(timings, inflate_s, ev)
     rows = []
     for k in range(N):
         lines, _lo, _hi, bad = (int(v) for v in info[k])
@@ -362,9 +299,7 @@ def build_matrices_device(files, chroms, width=BIN_WIDTH, sizes=None, state_name
         if c not in held:
             continue
         for k, got in host_cols.items():
-            col = torch.empty(col_pitch, dtype=torch.int8, device=dev)
-            col[:held[c]].copy_(torch.from_numpy(got[c][0]))
-            _abi.call("epg_sbl_transpose", engine._ptr(col), 1, col_pitch, held[c], engine._ptr(X[i]), ldx, k, engine._stream())
+            put_column(X[i], k, got[c][0], col_pitch)
         lo, hi = torch.aminmax(X[i][:, :N])                      # every cell is a state of the grammar: the range as written is this + 1
         out[c] = (X[i], (int(lo) + 1, int(hi) + 1))
     torch.cuda.synchronize()

@@ -10,7 +10,6 @@ write_epgm / read_epgm_header / read_epgm   the file format (layout: include/epi
 
 The parser on the device is strict.  A file it refuses is named in one warning line and parsed on the host in numpy the way
 pandas would read it (blanks and '\\r' stripped); what that cannot read raises."""
-import ctypes as C
 import fnmatch
 import os
 import struct
@@ -19,6 +18,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _abi, _io
+from .textBatches import TextBatches, align, first_fields, mark, pointers, put_column, reread_on_host, set_timings
 
 BIN_WIDTH = 200                                                  # the script's awk: (NR-3)*200, (NR-2)*200
 MAGIC = b"EPGM1\0\0\0"
@@ -30,15 +30,6 @@ EXT = ".epgm"
 
 # ---- which files ---------------------------------------------------------------------------------------------------------------
 
-def _first_fields(path, skip=0):
-    """`cut -f1 FILE | tail -n +(skip+1)` inside `$( )`: the first tab-separated field of every line, split at blanks."""
-    out = []
-    with open(path, "r", newline="\n") as fh:
-        for line in fh.read().split("\n")[skip:]:
-            out.extend(line.split("\t")[0].split())
-    return out
-
-
 def iter_calls(datadir, metadata, chromsizes):
     """(chromosome, [files]) for EVERY chromosome of `chromsizes`, an empty list where the directory holds none of its files."""
     for chrom, files, _names in iter_calls_named(datadir, metadata, chromsizes):
@@ -49,8 +40,8 @@ def iter_calls_named(datadir, metadata, chromsizes):
     """iter_calls with the biosample of every file: (chromosome, [files], [biosample names])."""
     datadir = Path(datadir)
     names = sorted(n for n in os.listdir(datadir) if not n.startswith("."))          # (a glob's order; `*` does not match a leading dot)
-    biosamples = _first_fields(metadata, skip=1)
-    for chrom in _first_fields(chromsizes):
+    biosamples = first_fields(metadata, skip=1)
+    for chrom in first_fields(chromsizes):
         files, found = [], []
         for b in biosamples:
             hits = [n for n in names if fnmatch.fnmatchcase(n, "*{}*{}_*.txt*".format(b, chrom))]
@@ -108,20 +99,14 @@ def parse_lenient(a, path="<text>"):
 
 # ---- the files of a chromosome on the device -----------------------------------------------------------------------------------
 
-def _align(n, a):
-    return (int(n) + a - 1) // a * a
-
-
 def build_matrix_device(files, timings=None, threads=None):
     """files: the state-by-line files of ONE chromosome, one per biosample, in column order.
     -> (X int8 [R, ldx] on the current device with ldx = N rounded up to 16 and -1 in columns >= N, N, chrName, (lo, hi)).
-    The host inflates the files through the native reader, `_io.host_budget()` at a time; a batch of files is uploaded at once,
-    each is parsed into its column of the batch (epg_sbl_parse) and the batch is transposed into X (epg_sbl_transpose).  Batch
-    k + 1 is inflated while batch k is on the device.  `timings` (a dict) receives inflate_s (waiting for the
-    inflating threads and staging), upload_ms, parse_ms and transpose_ms (HIP events, summed over the batches)."""
+    The host inflates the files through the native reader, `_io.host_budget()` at a time; a batch of files is uploaded at once
+    (textBatches.TextBatches), each is parsed into its column of the batch (epg_sbl_parse) and the batch is transposed into X
+    (epg_sbl_transpose).  Batch k + 1 is inflated while batch k is on the device.  `timings` (a dict) receives inflate_s (waiting
+    for the inflating threads and staging), upload_ms, parse_ms and transpose_ms (HIP events, summed over the batches)."""
     import torch
-    from concurrent.futures import ThreadPoolExecutor
-    from time import perf_counter
     from . import engine
     engine.require_gpu()
     files = [Path(f) for f in files]
@@ -131,103 +116,45 @@ def build_matrix_device(files, timings=None, threads=None):
     threads = max(1, int(threads or _io.host_budget()))
     batch = int(_abi.call("epg_sbl_constant", 3))
     dev = torch.device("cuda", torch.cuda.current_device())
-    main = torch.cuda.current_stream()
-    t_wait = 0.0
     ev = {k: [] for k in ("upload", "parse", "transpose")}
 
-    def mark():
-        e = torch.cuda.Event(enable_timing=True)
-        e.record(main)
-        return e
-
-    def inflate(k):
-        return _io.Text(files[k], 1)
+    def inspect(k, data):                                        # -> (chromosome of the header, rows: of the first file only)
+        return header_chromosome(data), (count_rows_text(data) if k == 0 else None)
 
     infos = torch.zeros((N, 4), dtype=torch.int64, device=dev)
-    sizes, chroms = [0] * N, [None] * N
-    X = R = col_pitch = cols = None
-    slots = []                                                   # per parity: [pinned, device text, event "the batch has left the device buffers"]
-    with ThreadPoolExecutor(max_workers=threads) as pool:
-        starts = list(range(0, N, batch))
-        futs = {0: [pool.submit(inflate, k) for k in range(0, min(batch, N))]}
-        try:
-            for bi, k0 in enumerate(starts):
-                nb = min(batch, N - k0)
-                t0 = perf_counter()
-                texts = [f.result() for f in futs.pop(bi)]
-                try:
-                    offs = np.zeros(nb + 1, dtype=np.int64)
-                    for j, tx in enumerate(texts):
-                        sizes[k0 + j] = len(tx.data)
-                        chroms[k0 + j] = header_chromosome(tx.data)
-                        offs[j + 1] = offs[j] + _align(len(tx.data), 16)
-                    if R is None:
-                        R = count_rows_text(texts[0].data)
-                        col_pitch = max(_align(R, 16), 16)
-                        ldx = _align(N, 16)
-                        X = torch.full((R, ldx), -1, dtype=torch.int8, device=dev)
-                        cols = torch.empty((batch, col_pitch), dtype=torch.int8, device=dev)
-                    total = int(offs[-1])
-                    s = bi % 2
-                    if len(slots) <= s:
-                        slots.append([None, None, None])
-                    pinned, dtext, done = slots[s]
-                    if done is not None:
-                        done.synchronize()
-                    if pinned is None or pinned.numel() < total:
-                        cap = _align(total + total // 8, 4096)
-                        pinned = torch.empty(cap, dtype=torch.uint8).pin_memory()
-                        dtext = torch.empty(cap, dtype=torch.uint8, device=dev)
-                    host = pinned.numpy()
-
-                    def stage(j):
-                        host[offs[j]:offs[j] + sizes[k0 + j]] = texts[j].data
-                    list(pool.map(stage, range(nb)))
-                    if bi + 1 < len(starts):                     # the next batch inflates while this one is on the device
-                        k1 = starts[bi + 1]
-                        futs[bi + 1] = [pool.submit(inflate, k) for k in range(k1, min(k1 + batch, N))]
-                finally:
-                    for tx in texts:
-                        tx.close()
-                t_wait += perf_counter() - t0
-                wsb = max(int(_abi.call("epg_sbl_ws_bytes", sizes[k0 + j])) for j in range(nb))
-                ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-                e0 = mark()
-                dtext[:total].copy_(pinned[:total], non_blocking=True)
-                e1 = mark()
-                for j in range(nb):
-                    _abi.call("epg_sbl_parse", C.c_void_p(dtext.data_ptr() + int(offs[j])), sizes[k0 + j], C.c_void_p(cols.data_ptr() + j * col_pitch), R,
-                              C.c_void_p(infos.data_ptr() + 32 * (k0 + j)), engine._ptr(ws), wsb, engine._stream())
-                e2 = mark()
-                _abi.call("epg_sbl_transpose", engine._ptr(cols), nb, col_pitch, R, engine._ptr(X), X.shape[1], k0, engine._stream())
-                e3 = mark()
-                slots[s] = [pinned, dtext, e3]
-                ev["upload"].append((e0, e1)), ev["parse"].append((e1, e2)), ev["transpose"].append((e2, e3))
-        finally:
-            for fs in futs.values():                             # an error on the way: give the inflated buffers back
-                for f in fs:
-                    try:
-                        f.result().close()
-                    except Exception:
-                        pass
+    info_of = pointers(infos)
+    chroms = []
+    X = R = col_pitch = cols = col_of = None
+    with TextBatches(files, batch, threads, dev, inspect) as batches:
+        for b in batches:
+            chroms.extend(c for c, _rows in b.facts)
+            if R is None:
+                R = b.facts[0][1]
+                col_pitch = max(align(R, 16), 16)
+                X = torch.full((R, align(N, 16)), -1, dtype=torch.int8, device=dev)
+                cols = torch.empty((batch, col_pitch), dtype=torch.int8, device=dev)
+                col_of = pointers(cols)
+            wsb = max(int(_abi.call("epg_sbl_ws_bytes", n)) for n in b.sizes)
+            ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+            e1 = mark()                                          # (behind the first batch's fill of X, which is not the parser's time)
+            for j, text in enumerate(pointers(b.text, b.offsets[:-1])):
+                _abi.call("epg_sbl_parse", text, b.sizes[j], col_of[j], R, info_of[b.k0 + j], engine._ptr(ws), wsb, engine._stream())
+            e2 = mark()
+            _abi.call("epg_sbl_transpose", engine._ptr(cols), b.nb, col_pitch, R, engine._ptr(X), X.shape[1], b.k0, engine._stream())
+            e3 = mark()
+            b.release()
+            ev["upload"].append(b.upload), ev["parse"].append((e1, e2)), ev["transpose"].append((e2, e3))
+        inflate_s = batches.inflate_s
     info = infos.cpu().numpy()                                   # the one synchronisation
-    if timings is not None:
-        timings["inflate_s"] = t_wait
-        for k, pairs in ev.items():
-            timings[k + "_ms"] = float(sum(a.elapsed_time(b) for a, b in pairs))
+    set_timings(timings, inflate_s, ev)
     lo, hi = 128, 0
     for k in range(N):
         rows, flo, fhi, bad = (int(v) for v in info[k])
         if bad >= 0:
-            print("epilogos_amd: {}: line {} is not a plain state 1..127 -- reading this file on the host (slow)".format(files[k], bad + 1),
-                  flush=True)
-            with _io.Text(files[k], 1) as tx:
-                col, flo, fhi = parse_lenient(tx.data, files[k])
+            col, flo, fhi = reread_on_host(files[k], bad + 1, "a plain state 1..127", lambda a: parse_lenient(a, files[k]))
             rows = len(col)
             if rows == R and rows:
-                c = torch.empty(col_pitch, dtype=torch.int8, device=dev)
-                c[:rows].copy_(torch.from_numpy(col))
-                _abi.call("epg_sbl_transpose", engine._ptr(c), 1, col_pitch, R, engine._ptr(X), X.shape[1], k, engine._stream())
+                put_column(X, k, col, col_pitch)
         if rows != R:
             raise ValueError("{} holds {} bins, {} holds {}: the files of a chromosome must have the same number of lines".format(
                 files[0], R, files[k], rows))

@@ -1,13 +1,27 @@
-"""CPU-side checks of the drop-in boundary: the library builds, loads, and exports exactly what the header
-declares.  No compute calls (no GPU here)."""
-import ctypes
-import re
+"""CPU-side checks of the drop-in boundary: the library builds, loads, and exports exactly what every public header declares;
+every header of _abi.HEADERS is bound by its table, type for type.  No compute calls (no GPU here)."""
 import shutil
 import subprocess
 
 import pytest
 
 from epilogos_amd import _abi, build
+from tests.abi_headers import ctypes_of, header_prototypes
+
+# what the headers declare today, pinned: the exact names, or their number and prefix
+NAMES = {
+    "groups": ["epg_bin_hist_groups"],
+    "nulldraws": ["epg_null_dist_draws_parts", "epg_null_exceed", "epg_null_exceed_ws_bytes"],
+    "simsearch_pick": ["epg_simsearch_pick", "epg_simsearch_pick_ws_bytes", "epg_simsearch_rank", "epg_simsearch_rank_ws_bytes",
+                       "epg_simsearch_rolling_max", "epg_simsearch_rowscore"],
+    "census": ["epg_state_census"],
+    "concordance": ["epg_concordance", "epg_concordance_ws_bytes"],
+    "gennorm": ["epgf_gennorm_fit", "epgf_gennorm_nnlf", "epgf_gennorm_ws_bytes"],
+}
+# (at least, at most, prefix)
+COUNT_AND_PREFIX = {"scores_text": (2, None, "epgt_"), "statebyline": (4, 4, "epg_sbl_"), "segments": (4, 4, "epg_seg_")}
+# the source file with the header's entry points, where it is not epg_<key>.hip
+SOURCE = {"core": "epg_abi.hip", "nulldraws": "epg_null_exceed.hip"}
 
 
 @pytest.fixture(scope="module")
@@ -19,54 +33,64 @@ def lib():
     return _abi.load()
 
 
-def _header_prototypes():
-    """name -> (return type, [parameter declarations]) of every prototype in include/epilogos_amd.h."""
-    txt = re.sub(r"/\*.*?\*/", "", _abi.HEADER.read_text(), flags=re.S)
-    txt = re.sub(r'^\s*(#.*|extern "C" \{|\})\s*$', "", txt, flags=re.M)
-    protos = {}
-    for stmt in txt.split(";"):
-        m = re.match(r"\s*(.*?)\b(epg_[a-z0-9_]+)\s*\((.*)\)\s*$", stmt, flags=re.S)
-        if m:
-            args = " ".join(m.group(3).split())
-            protos[m.group(2)] = (" ".join(m.group(1).split()), [] if args in ("", "void") else [a.strip() for a in args.split(",")])
-    return protos
+def test_the_registry_is_the_list_of_public_headers():
+    assert list(_abi.HEADERS) == list(build.PUBLIC_HEADERS) and len(_abi.HEADERS) == 10
+    assert set(NAMES) | set(COUNT_AND_PREFIX) | {"core"} == set(_abi.HEADERS)
+    assert _abi.HEADERS["core"] == (_abi.HEADER, _abi.PROTOTYPES) and _abi.HEADER.name == "epilogos_amd.h"
+    assert _abi.header_symbols() == _abi.header_symbols("core")
+    assert _abi.ABI_VERSION == _abi.header_constant("core", "EPG_ABI_VERSION") == 2
+    with pytest.raises(RuntimeError):
+        _abi.header_constant("core", "EPG_NO_SUCH_CONSTANT")
 
 
-def _ctypes_of(decl):
-    """The ctypes types that bind a header type (a parameter declaration, with or without its name)."""
-    if "*" in decl:
-        return {ctypes.c_void_p, ctypes.c_char_p}
-    base = decl.replace("const ", "").split()[0]
-    return {"int64_t": {ctypes.c_int64}, "int32_t": {ctypes.c_int32, ctypes.c_int}, "int": {ctypes.c_int32, ctypes.c_int},
-            "uint64_t": {ctypes.c_uint64}}[base]
+def test_the_tables_are_pairwise_disjoint():
+    """A header of its own: no other header, and no other table, knows its entry points."""
+    keys = list(_abi.HEADERS)
+    for i, a in enumerate(keys):
+        for b in keys[i + 1:]:
+            assert not set(_abi.HEADERS[a].prototypes) & set(_abi.HEADERS[b].prototypes), (a, b)
+            assert not set(_abi.header_symbols(a)) & set(_abi.header_symbols(b)), (a, b)
 
 
-def test_header_and_binding_agree():
-    hdr = _abi.header_symbols()
-    assert hdr, "no prototypes parsed from include/epilogos_amd.h"
-    assert sorted(_abi.PROTOTYPES) == hdr
-    protos = _header_prototypes()
+@pytest.mark.parametrize("which", list(_abi.HEADERS))
+def test_header_and_binding_agree(which):
+    header = _abi.HEADERS[which]
+    hdr = _abi.header_symbols(which)
+    assert hdr, "no prototypes parsed from %s" % header.path
+    assert sorted(header.prototypes) == hdr
+    protos = header_prototypes(which)
     assert sorted(protos) == hdr
-    for name, (res, args) in _abi.PROTOTYPES.items():
+    if which in NAMES:
+        assert hdr == NAMES[which]
+    if which in COUNT_AND_PREFIX:
+        least, most, prefix = COUNT_AND_PREFIX[which]
+        assert len(hdr) >= least and (most is None or len(hdr) <= most) and all(n.startswith(prefix) for n in hdr)
+    for name, (res, args) in header.prototypes.items():
         ret, params = protos[name]
-        assert res in _ctypes_of(ret), "%s returns %s in the header, %s in _abi.PROTOTYPES" % (name, ret, res.__name__)
-        assert len(args) == len(params), "%s: %d parameters in the header, %d in _abi.PROTOTYPES" % (name, len(params), len(args))
+        assert res is ctypes_of(ret, returned=True), "%s returns %s in the header, %s in the binding" % (name, ret, res.__name__)
+        assert len(args) == len(params), "%s: %d parameters in the header, %d in the binding" % (name, len(params), len(args))
         for i, (a, p) in enumerate(zip(args, params)):
-            assert a in _ctypes_of(p), "%s: parameter %d is `%s` in the header, %s in _abi.PROTOTYPES" % (name, i, p, a.__name__)
+            assert a is ctypes_of(p), "%s: parameter %d is `%s` in the header, %s in the binding" % (name, i, p, a.__name__)
+    assert header.path in build.HEADERS and header.path.name == build.PUBLIC_HEADERS[which]
+    assert SOURCE.get(which, "epg_%s.hip" % which) in build.SOURCES
 
 
-def test_library_exports_every_header_symbol(lib):
-    for name in _abi.header_symbols():
-        assert hasattr(lib, name), "libepilogos_hip.so does not export " + name
+@pytest.mark.parametrize("which", list(_abi.HEADERS))
+def test_library_exports_every_header_symbol(lib, which):
+    import ctypes
+    fresh = ctypes.CDLL(str(_abi.lib_path()))                    # looked up by the plain name: a C++-mangled export would not be found
+    for name in _abi.header_symbols(which):
+        assert hasattr(lib, name) and hasattr(fresh, name), "libepilogos_hip.so does not export " + name
 
 
-def test_exports_are_c_abi(lib):
+@pytest.mark.parametrize("which", list(_abi.HEADERS))
+def test_exports_are_c_abi(lib, which):
     nm = shutil.which("nm")
     if nm is None:
         pytest.skip("nm not available")
     out = subprocess.run([nm, "-D", "--defined-only", str(_abi.lib_path())], capture_output=True, text=True).stdout
     exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-    for name in _abi.header_symbols():
+    for name in _abi.header_symbols(which):
         assert name in exported          # unmangled => extern "C"
 
 

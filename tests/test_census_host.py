@@ -1,62 +1,10 @@
-"""The state census, the host side (no GPU): include/epilogos_census.h against its binding and the library's exports, the entry
+"""The state census, the host side (no GPU; tests/test_abi_symbols.py holds include/epilogos_census.h against its binding): the entry
 point's argument checks (made before the first HIP call), the table's text from given arrays, and the command lines."""
 import ctypes
-import re
-import shutil
-import subprocess
 
 import numpy as np
 
 from epilogos_amd import _abi, census
-
-
-def _header_prototypes():
-    txt = re.sub(r"/\*.*?\*/", "", _abi.CENSUS_HEADER.read_text(), flags=re.S)
-    txt = re.sub(r'^\s*(#.*|extern "C" \{|\})\s*$', "", txt, flags=re.M)
-    protos = {}
-    for stmt in txt.split(";"):
-        m = re.match(r"\s*(.*?)\b(epg_[a-z0-9_]+)\s*\((.*)\)\s*$", stmt, flags=re.S)
-        if m:
-            args = " ".join(m.group(3).split())
-            protos[m.group(2)] = (" ".join(m.group(1).split()), [] if args in ("", "void") else [a.strip() for a in args.split(",")])
-    return protos
-
-
-def _ctypes_of(decl):
-    if "*" in decl:
-        return {ctypes.c_void_p, ctypes.c_char_p}
-    base = decl.replace("const ", "").split()[0]
-    return {"int64_t": {ctypes.c_int64}, "int32_t": {ctypes.c_int32, ctypes.c_int}, "int": {ctypes.c_int32, ctypes.c_int},
-            "uint64_t": {ctypes.c_uint64}}[base]
-
-
-def test_header_and_binding_agree():
-    hdr = _abi.census_header_symbols()
-    assert hdr == ["epg_state_census"] and sorted(_abi.CENSUS_PROTOTYPES) == hdr
-    # a header of its own: the main header, its binding table and its version do not know the entry point
-    assert not set(hdr) & set(_abi.PROTOTYPES) and not set(hdr) & set(_abi.header_symbols())
-    assert _abi.ABI_VERSION == 2
-    protos = _header_prototypes()
-    assert sorted(protos) == hdr
-    for name, (res, args) in _abi.CENSUS_PROTOTYPES.items():
-        ret, params = protos[name]
-        assert res in _ctypes_of(ret), name
-        assert len(args) == len(params), name
-        for i, (a, p) in enumerate(zip(args, params)):
-            assert a in _ctypes_of(p), "%s: parameter %d is `%s` in the header, %s in the binding" % (name, i, p, a.__name__)
-    from epilogos_amd import build
-    assert _abi.CENSUS_HEADER in build.HEADERS and "epg_census.hip" in build.SOURCES
-
-
-def test_library_exports_the_symbol_unmangled():
-    lib = ctypes.CDLL(str(_abi.lib_path()))
-    for name in _abi.census_header_symbols():
-        assert hasattr(lib, name), name
-    nm = shutil.which("nm")
-    if nm is not None:
-        out = subprocess.run([nm, "-D", "--defined-only", str(_abi.lib_path())], capture_output=True, text=True).stdout
-        exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-        assert set(_abi.census_header_symbols()) <= exported
 
 
 def test_argument_validation_without_gpu():

@@ -1,11 +1,9 @@
-"""The biosample concordance, the host side (no GPU): include/epilogos_concordance.h against its binding and the library's
-exports, the entry points' argument checks (made before the first HIP call), the two tables and the duplicate warning from
+"""The biosample concordance, the host side (no GPU; tests/test_abi_symbols.py holds include/epilogos_concordance.h against its
+binding): the entry points' argument checks (made before the first HIP call), the two tables and the duplicate warning from
 handmade matrices, the command lines, and `epilogos-prep --concordance` with the device stood in for by numpy."""
 import ctypes
 import io
 import re
-import shutil
-import subprocess
 
 import click
 import numpy as np
@@ -25,54 +23,6 @@ def restatement(x, S):
         agree[i] = ((x[:, i:i + 1] == x) & valid[:, i:i + 1]).sum(axis=0)
         both[i] = (valid[:, i:i + 1] & valid).sum(axis=0)
     return agree, both
-
-
-def _header_prototypes():
-    txt = re.sub(r"/\*.*?\*/", "", _abi.CONCORDANCE_HEADER.read_text(), flags=re.S)
-    txt = re.sub(r'^\s*(#.*|extern "C" \{|\})\s*$', "", txt, flags=re.M)
-    protos = {}
-    for stmt in txt.split(";"):
-        m = re.match(r"\s*(.*?)\b(epg_[a-z0-9_]+)\s*\((.*)\)\s*$", stmt, flags=re.S)
-        if m:
-            args = " ".join(m.group(3).split())
-            protos[m.group(2)] = (" ".join(m.group(1).split()), [] if args in ("", "void") else [a.strip() for a in args.split(",")])
-    return protos
-
-
-def _ctypes_of(decl):
-    if "*" in decl:
-        return {ctypes.c_void_p, ctypes.c_char_p}
-    base = decl.replace("const ", "").split()[0]
-    return {"int64_t": {ctypes.c_int64}, "int32_t": {ctypes.c_int32, ctypes.c_int}, "int": {ctypes.c_int32, ctypes.c_int}}[base]
-
-
-def test_header_and_binding_agree():
-    hdr = _abi.concordance_header_symbols()
-    assert hdr == ["epg_concordance", "epg_concordance_ws_bytes"] and sorted(_abi.CONCORDANCE_PROTOTYPES) == hdr
-    # a header of its own: the main header, its binding table and its version do not know the entry points
-    assert not set(hdr) & set(_abi.PROTOTYPES) and not set(hdr) & set(_abi.header_symbols())
-    assert _abi.ABI_VERSION == 2
-    protos = _header_prototypes()
-    assert sorted(protos) == hdr
-    for name, (res, args) in _abi.CONCORDANCE_PROTOTYPES.items():
-        ret, params = protos[name]
-        assert res in _ctypes_of(ret), name
-        assert len(args) == len(params), name
-        for i, (a, p) in enumerate(zip(args, params)):
-            assert a in _ctypes_of(p), "%s: parameter %d is `%s` in the header, %s in the binding" % (name, i, p, a.__name__)
-    from epilogos_amd import build
-    assert _abi.CONCORDANCE_HEADER in build.HEADERS and "epg_concordance.hip" in build.SOURCES
-
-
-def test_library_exports_the_symbols_unmangled():
-    lib = ctypes.CDLL(str(_abi.lib_path()))
-    for name in _abi.concordance_header_symbols():
-        assert hasattr(lib, name), name
-    nm = shutil.which("nm")
-    if nm is not None:
-        out = subprocess.run([nm, "-D", "--defined-only", str(_abi.lib_path())], capture_output=True, text=True).stdout
-        exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-        assert set(_abi.concordance_header_symbols()) <= exported
 
 
 def test_argument_validation_without_gpu():

@@ -1,11 +1,8 @@
 """The device fit of the paired null distribution, the host side (no GPU): the algorithm of include/epilogos_gennorm.h restated in
-numpy (tests/gennorm_ref.py) against scipy's own fit; the header against its binding and the library's exports; the entry points'
+numpy (tests/gennorm_ref.py) against scipy's own fit; what the header promises beyond its binding (tests/test_abi_symbols.py); the entry points'
 argument checks, made before the first HIP call, in the documented order; --fit on the command line and its way down to _fitParams;
 the seeding of the sub-samples.  scipy is the reference throughout."""
 import ctypes
-import re
-import shutil
-import subprocess
 import warnings
 
 import numpy as np
@@ -113,57 +110,16 @@ def test_the_median_pick_is_the_existing_rule():
             assert ref.median_pick(nnlf) == want == rv.medianTrial(nnlf)
 
 
-# ---- header, binding, library ----------------------------------------------------------------------------------------------------
-def _header_prototypes():
-    txt = re.sub(r"/\*.*?\*/", "", _abi.GENNORM_HEADER.read_text(), flags=re.S)
-    txt = re.sub(r'^\s*(#.*|extern "C" \{|\})\s*$', "", txt, flags=re.M)
-    protos = {}
-    for stmt in txt.split(";"):
-        m = re.match(r"\s*(.*?)\b(epgf_[a-z0-9_]+)\s*\((.*)\)\s*$", stmt, flags=re.S)
-        if m:
-            args = " ".join(m.group(3).split())
-            protos[m.group(2)] = (" ".join(m.group(1).split()), [a.strip() for a in args.split(",")])
-    return protos
-
-
-def _ctypes_of(decl):
-    if "*" in decl:
-        return {ctypes.c_void_p, ctypes.c_char_p}
-    base = decl.replace("const ", "").split()[0]
-    return {"int64_t": {ctypes.c_int64}, "int32_t": {ctypes.c_int32, ctypes.c_int}, "int": {ctypes.c_int32, ctypes.c_int}}[base]
-
-
-NAMES = ["epgf_gennorm_fit", "epgf_gennorm_nnlf", "epgf_gennorm_ws_bytes"]
-
-
-def test_header_and_binding_agree():
-    assert _abi.gennorm_header_symbols() == NAMES and sorted(_abi.GENNORM_PROTOTYPES) == NAMES
-    assert _abi.ABI_VERSION == 2
-    protos = _header_prototypes()
-    assert sorted(protos) == NAMES
-    for name, (res, args) in _abi.GENNORM_PROTOTYPES.items():
-        ret, params = protos[name]
-        assert res in _ctypes_of(ret), name
-        assert len(args) == len(params), name
-        for i, (a, p) in enumerate(zip(args, params)):
-            assert a in _ctypes_of(p), "%s: parameter %d is `%s` in the header, %s in the binding" % (name, i, p, a.__name__)
+# ---- the header ------------------------------------------------------------------------------------------------------------------
+def test_the_entry_points_take_a_stream_and_keep_their_prefix():
+    """(tests/test_abi_symbols.py holds the header against its binding and the library's exports.)"""
+    from tests.abi_headers import header_prototypes
+    protos = header_prototypes("gennorm")
     assert protos["epgf_gennorm_fit"][1][-1] == "void* stream" and protos["epgf_gennorm_nnlf"][1][-1] == "void* stream"
-    from epilogos_amd import build
-    assert _abi.GENNORM_HEADER in build.HEADERS and "epg_gennorm.hip" in build.SOURCES
     # the prefix keeps the entry points out of the table of tests/test_hip_abi_streams.py; tests/test_hip_gennorm_streams.py runs its procedure
     from tests.test_abi_streams_coverage import stream_prototypes
     assert not [n for n in stream_prototypes() if "gennorm" in n]
-    assert "epgf_" in _abi.GENNORM_HEADER.read_text().split("#ifndef")[0]
-
-
-def test_library_exports_the_symbols_unmangled():
-    lib = ctypes.CDLL(str(_abi.lib_path()))
-    for name in NAMES:
-        assert hasattr(lib, name), name
-    nm = shutil.which("nm")
-    if nm is not None:
-        out = subprocess.run([nm, "-D", "--defined-only", str(_abi.lib_path())], capture_output=True, text=True).stdout
-        assert set(NAMES) <= {line.split()[-1] for line in out.splitlines() if " T " in line}
+    assert "epgf_" in _abi.HEADERS["gennorm"].path.read_text().split("#ifndef")[0]
 
 
 def refusals(lib, x, idx, out, ws, M=5000, T=3, n=257, ws_bytes=1 << 30):

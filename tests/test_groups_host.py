@@ -1,9 +1,7 @@
-"""Column groups, the host side (no GPU): include/epilogos_groups.h against its binding and the library's exports, the entry
+"""Column groups, the host side (no GPU; tests/test_abi_symbols.py holds include/epilogos_groups.h against its binding): the entry
 point's argument checks (made before the first HIP call), and the membership bytes the engine builds for the kernel."""
 import ctypes
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,53 +9,8 @@ import pytest
 from epilogos_amd import _abi, engine
 
 
-def _header_prototypes():
-    txt = re.sub(r"/\*.*?\*/", "", _abi.GROUP_HEADER.read_text(), flags=re.S)
-    txt = re.sub(r'^\s*(#.*|extern "C" \{|\})\s*$', "", txt, flags=re.M)
-    protos = {}
-    for stmt in txt.split(";"):
-        m = re.match(r"\s*(.*?)\b(epg_[a-z0-9_]+)\s*\((.*)\)\s*$", stmt, flags=re.S)
-        if m:
-            args = " ".join(m.group(3).split())
-            protos[m.group(2)] = (" ".join(m.group(1).split()), [] if args in ("", "void") else [a.strip() for a in args.split(",")])
-    return protos
-
-
-def _ctypes_of(decl):
-    if "*" in decl:
-        return {ctypes.c_void_p, ctypes.c_char_p}
-    base = decl.replace("const ", "").split()[0]
-    return {"int64_t": {ctypes.c_int64}, "int32_t": {ctypes.c_int32, ctypes.c_int}, "int": {ctypes.c_int32, ctypes.c_int},
-            "uint64_t": {ctypes.c_uint64}}[base]
-
-
-def test_header_and_binding_agree():
-    hdr = _abi.group_header_symbols()
-    assert hdr == ["epg_bin_hist_groups"] and sorted(_abi.GROUP_PROTOTYPES) == hdr
-    # a header of its own: the main header, its binding table and its version do not know the entry point
-    assert not set(hdr) & set(_abi.PROTOTYPES) and not set(hdr) & set(_abi.header_symbols())
-    assert _abi.ABI_VERSION == 2
-    protos = _header_prototypes()
-    assert sorted(protos) == hdr
-    for name, (res, args) in _abi.GROUP_PROTOTYPES.items():
-        ret, params = protos[name]
-        assert res in _ctypes_of(ret), name
-        assert len(args) == len(params), name
-        for i, (a, p) in enumerate(zip(args, params)):
-            assert a in _ctypes_of(p), "%s: parameter %d is `%s` in the header, %s in the binding" % (name, i, p, a.__name__)
-    assert re.search(r"#define EPG_GROUPS_MAX %d\b" % engine.GROUPS_MAX, _abi.GROUP_HEADER.read_text())
-
-
-def test_library_exports_the_symbol_unmangled():
-    # a fresh handle, looked up by the plain name: a C++-mangled export would not be found under it
-    lib = ctypes.CDLL(str(_abi.lib_path()))
-    for name in _abi.group_header_symbols():
-        assert hasattr(lib, name), name
-    nm = shutil.which("nm")
-    if nm is not None:                                 # where binutils is installed, the dynamic symbol table says the same
-        out = subprocess.run([nm, "-D", "--defined-only", str(_abi.lib_path())], capture_output=True, text=True).stdout
-        exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-        assert set(_abi.group_header_symbols()) <= exported
+def test_the_headers_group_limit_is_the_engines():
+    assert re.search(r"#define EPG_GROUPS_MAX %d\b" % engine.GROUPS_MAX, _abi.HEADERS["groups"].path.read_text())
 
 
 def test_argument_validation_without_gpu():

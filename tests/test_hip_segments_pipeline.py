@@ -210,3 +210,35 @@ def test_epilogos_scores_both_directories_alike(tmp_path, tree, golden_built):
     a = run_epilogos(["-i", str(written[0].parent)] + args, tmp_path / "a")
     b = run_epilogos(["-i", str(by_lines[0].parent)] + args, tmp_path / "b")
     same_outputs(a, b, ["scores_t_matrix_chr1", "regionsOfInterest_"])
+
+
+def test_third_batch_reuses_a_slot_that_has_to_grow(tmp_path, capsys):
+    """build_matrices_device on two full batches and one file more: the third batch is the first to reuse a staging slot, and its
+    one file is larger than the whole first batch plus an eighth (runs of a chromosome outside the table, which the device grammar
+    skips), so slot 0 waits for its event and grows.  A file of the second batch has \\r\\n line ends and goes the host way."""
+    from epilogos_amd import _abi, segments as seg
+    batch = int(_abi.load().epg_sbl_constant(3))
+    n = 2 * batch + 1
+    table = [("chrP", 33), ("chrQ", 7)]
+    rng = np.random.default_rng(129)
+    per_file = [[(c, random_calls(rng, R)) for c, R in table] for _ in range(n)]
+    crlf = batch + 6                                             # a file of the second batch
+    texts = [segment_text(per, eol="\r\n" if k == crlf else "\n") for k, per in enumerate(per_file)]
+    first_batch = sum((len(t) + 15) // 16 * 16 for t in texts[:batch])
+    other = segment_text([("chrUn", np.arange(first_batch // 8) % 2 + 1)])        # one line of at least 17 bytes per bin
+    assert len(other) > first_batch + first_batch // 8 + 4096    # beyond what slot 0 was given for the first batch
+    texts[n - 1] = segment_text(per_file[n - 1][:1]) + other + segment_text(per_file[n - 1][1:])
+    files = []
+    for k, t in enumerate(texts):
+        files.append(tmp_path / ("B%03d_18_segments.bed" % k))
+        files[-1].write_bytes(t)
+    got = seg.build_matrices_device(files, [c for c, _R in table])
+    out = capsys.readouterr().out
+    assert out.count("on the host") == 1 and out.count(str(files[crlf])) == 1 and sum(str(f) in out for f in files) == 1
+    assert n == 129 and list(got) == [c for c, _R in table]
+    for i, (c, R) in enumerate(table):
+        want = np.stack([np.repeat(v, e - s) for s, e, v in (rle(per[i][1]) for per in per_file)], axis=1)
+        X, (lo, hi) = got[c]
+        x = X.cpu().numpy()
+        assert x.shape == (R, (n + 15) // 16 * 16) and np.array_equal(x[:, :n], (want - 1).astype(np.int8)) and (x[:, n:] == -1).all(), c
+        assert (lo, hi) == (want.min(), want.max()), c

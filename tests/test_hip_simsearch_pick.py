@@ -12,7 +12,7 @@ from tests import simsearch_pick_ref as ref
 from tests.abi_arena import Arena
 
 pytestmark = pytest.mark.gpu
-T = _abi.pick_header_constant("EPG_PICK_TILE")
+T = _abi.header_constant("simsearch_pick", "EPG_PICK_TILE")
 WINDOWS = [1, 2, 5, 24, 25, 124, 125]
 
 

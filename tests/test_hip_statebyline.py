@@ -318,6 +318,33 @@ def test_build_matrix_device_many_files_and_the_host_fallback(tmp_path, capsys):
     assert x.shape == (777, (n + 15) // 16 * 16) and np.array_equal(x[:, :n], (want - 1).astype(np.int8)) and (x[:, n:] == -1).all()
 
 
+def test_build_matrix_device_third_batch_reuses_a_slot_that_has_to_grow(tmp_path, capsys):
+    """Two full batches and one file more: the third batch is the first to reuse a staging slot.  Its one file is larger than the
+    whole first batch plus an eighth (a padded second header line), so slot 0 waits for its event and grows; it has \\r\\n line
+    ends as well, so its column is the host's.  R = 33 is no multiple of 16: the column pitch is 48."""
+    rng = np.random.default_rng(129)
+    batch, R = const(3), 33
+    n = 2 * batch + 1
+    vals = [mixed_values(rng, R) for _ in range(n)]
+    texts = [make_text(v, final_newline=k % 3 != 0) for k, v in enumerate(vals)]
+    first_batch = sum((len(t) + 15) // 16 * 16 for t in texts[:batch])
+    pad = first_batch + first_batch // 8 + 4096                  # beyond what slot 0 was given for the first batch
+    texts[n - 1] = make_text(vals[n - 1], head=HEAD[:-1] + b"x" * pad + b"\n").replace(b"\n", b"\r\n")
+    files = _write_calls(tmp_path / "calls", texts)
+    zipped = batch + 6                                           # a file of the second batch
+    with gzip.open(str(files[zipped]) + ".gz", "wb") as fh:
+        fh.write(texts[zipped])
+    files[zipped].unlink()
+    files[zipped] = Path(str(files[zipped]) + ".gz")
+    X, N, name, (lo, hi) = sbl.build_matrix_device(files)
+    out = capsys.readouterr().out
+    assert out.count(str(files[n - 1])) == 1 and sum(str(f) in out for f in files) == 1
+    want = np.stack(vals, axis=1)
+    assert N == n == 129 and name == "chr1" and (lo, hi) == (want.min(), want.max())
+    x = X.cpu().numpy()
+    assert x.shape == (R, (n + 15) // 16 * 16) and np.array_equal(x[:, :n], (want - 1).astype(np.int8)) and (x[:, n:] == -1).all()
+
+
 def test_build_matrix_device_refusals(tmp_path, capsys):
     rng = np.random.default_rng(9)
     texts = [make_text(mixed_values(rng, 100)) for _ in range(3)]

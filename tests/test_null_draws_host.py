@@ -1,9 +1,7 @@
-"""--null-draws K, the host side (no GPU): the seeds of the K draws, the command line's refusals, the binding of
-include/epilogos_nulldraws.h and its argument checks, and STEP 4 on exceedance counts -- empirical p-values
+"""--null-draws K, the host side (no GPU): the seeds of the K draws, the command line's refusals, the argument checks of
+include/epilogos_nulldraws.h (tests/test_abi_symbols.py holds it against its binding), and STEP 4 on exceedance counts -- empirical p-values
 (1 + e) / (1 + M), Benjamini-Hochberg of them, today's three files, no fit."""
-import ctypes
 import gzip
-import re
 import shutil
 
 import numpy as np
@@ -111,22 +109,6 @@ def lib():
             pytest.skip("hipcc not available and library not prebuilt")
         build.build_library()
     return _abi.load()
-
-
-def test_header_and_binding_agree():
-    hdr = _abi.nulldraws_header_symbols()
-    assert hdr == ["epg_null_dist_draws_parts", "epg_null_exceed", "epg_null_exceed_ws_bytes"]
-    assert sorted(_abi.NULLDRAWS_PROTOTYPES) == hdr
-    assert not set(hdr) & set(_abi.PROTOTYPES) and not set(hdr) & set(_abi.header_symbols())
-    txt = re.sub(r"/\*.*?\*/", "", _abi.NULLDRAWS_HEADER.read_text(), flags=re.S)
-    for name, (res, args) in _abi.NULLDRAWS_PROTOTYPES.items():
-        m = re.search(r"(\w+)\s+%s\s*\((.*?)\)\s*;" % name, txt, flags=re.S)
-        params = [p.strip() for p in " ".join(m.group(2).split()).split(",")]
-        assert len(params) == len(args), name
-        assert res is {"int": ctypes.c_int, "int64_t": ctypes.c_int64}[m.group(1)]
-        for p, a in zip(params, args):
-            want = ctypes.c_void_p if "*" in p else {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64}[p.replace("const ", "").split()[0]]
-            assert a is want, (name, p)
 
 
 def test_abi_version_is_unchanged(lib):

@@ -1,10 +1,8 @@
-"""The GPU scores-text reader, the host side (no GPU): the new header against its binding and the library's exports, the entry
-points' argument checks, chunk cutting, and similaritySearch_query.readGrid -- without a GPU, with the device step refusing
+"""The GPU scores-text reader, the host side (no GPU): the header's status constants (tests/test_abi_symbols.py holds it against
+its binding), the entry points' argument checks, chunk cutting, and similaritySearch_query.readGrid -- without a GPU, with the device step refusing
 the file, and with the device step's results put together into mm.readScores' arrays."""
 import ctypes
 import re
-import shutil
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -17,58 +15,15 @@ from epilogos_amd import similaritySearch_query as sq
 GOLD = np.load(Path(__file__).resolve().parent / "golden" / "simsearch.npz")
 
 
-# ---- header, binding, exports ---------------------------------------------------------------------------------------------
+# ---- the header ---------------------------------------------------------------------------------------------------------------
 
-def _header_prototypes():
-    txt = re.sub(r"/\*.*?\*/", "", _abi.TEXT_HEADER.read_text(), flags=re.S)
-    txt = re.sub(r'^\s*(#.*|extern "C" \{|\})\s*$', "", txt, flags=re.M)
-    protos = {}
-    for stmt in txt.split(";"):
-        m = re.match(r"\s*(.*?)\b(epgt_[a-z0-9_]+)\s*\((.*)\)\s*$", stmt, flags=re.S)
-        if m:
-            args = " ".join(m.group(3).split())
-            protos[m.group(2)] = (" ".join(m.group(1).split()), [] if args in ("", "void") else [a.strip() for a in args.split(",")])
-    return protos
-
-
-def _ctypes_of(decl):
-    if "*" in decl:
-        return {ctypes.c_void_p, ctypes.c_char_p}
-    base = decl.replace("const ", "").split()[0]
-    return {"int64_t": {ctypes.c_int64}, "int32_t": {ctypes.c_int32, ctypes.c_int}, "int": {ctypes.c_int32, ctypes.c_int},
-            "uint64_t": {ctypes.c_uint64}}[base]
-
-
-def test_header_and_binding_agree():
-    hdr = _abi.text_header_symbols()
-    assert len(hdr) >= 2 and sorted(_abi.TEXT_PROTOTYPES) == hdr
-    assert not set(hdr) & set(_abi.PROTOTYPES) and not any(n.startswith("epg_") for n in hdr)
-    protos = _header_prototypes()
-    assert sorted(protos) == hdr
-    for name, (res, args) in _abi.TEXT_PROTOTYPES.items():
-        ret, params = protos[name]
-        assert res in _ctypes_of(ret), name
-        assert len(args) == len(params), name
-        for i, (a, p) in enumerate(zip(args, params)):
-            assert a in _ctypes_of(p), "%s: parameter %d is `%s` in the header, %s in the binding" % (name, i, p, a.__name__)
-
-
-def test_library_exports_the_new_symbols_unmangled():
-    lib = _abi.load()
-    for name in _abi.text_header_symbols():
-        assert hasattr(lib, name)
-    # the status word's constants are the ones the host front reads
-    hdr = _abi.TEXT_HEADER.read_text()
+def test_the_headers_status_constants_are_the_host_fronts():
+    """(tests/test_abi_symbols.py holds the header against its binding and the library's exports.)"""
+    hdr = _abi.HEADERS["scores_text"].path.read_text()
     for code, _text in scoresText.REASONS.items():
         assert re.search(r"#define EPGT_REASON_[A-Z]+ %d\b" % code, hdr)
     assert len(re.findall(r"#define EPGT_REASON_", hdr)) == len(scoresText.REASONS)
     assert "#define EPGT_CLEAN INT64_MAX" in hdr and scoresText.CLEAN == 2 ** 63 - 1
-    nm = shutil.which("nm")
-    if nm is None:
-        pytest.skip("nm not available")
-    out = subprocess.run([nm, "-D", "--defined-only", str(_abi.lib_path())], capture_output=True, text=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-    assert set(_abi.text_header_symbols()) <= exported
 
 
 def test_argument_validation_without_gpu():

@@ -1,17 +1,14 @@
 """ChromHMM segment files, the host side (no GPU): which file is which biosample's, the rules across files, the lenient host
-parser on every form it takes and every error of content it raises (file:line), the new header against its binding and the
-library's exports, the entry points' argument checks, and the command line.  Expected columns are np.repeat over the runs."""
+parser on every form it takes and every error of content it raises (file:line), the header's constants, the entry points'
+argument checks, and the command line.  Expected columns are np.repeat over the runs."""
 import ctypes
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 from click.testing import CliRunner
 
 from epilogos_amd import _abi, preprocess, segments as seg, stateByLine as sbl
-from tests.test_statebyline_host import _ctypes_of
 
 
 # ---- which files ----------------------------------------------------------------------------------------------------------
@@ -162,50 +159,11 @@ def test_host_parser_raises_on_errors_of_content_with_file_and_line(what):
             assert "dir/some_segments.bed:%d:" % (at + shift) in str(e.value), (what, str(e.value))
 
 
-# ---- header, binding, exports ---------------------------------------------------------------------------------------------
-
-def _header_prototypes():
-    txt = re.sub(r"/\*.*?\*/", "", _abi.SEG_HEADER.read_text(), flags=re.S)
-    txt = re.sub(r'^\s*(#.*|extern "C" \{|\})\s*$', "", txt, flags=re.M)
-    protos = {}
-    for stmt in txt.split(";"):
-        m = re.match(r"\s*(.*?)\b(epg_[a-z0-9_]+)\s*\((.*)\)\s*$", stmt, flags=re.S)
-        if m:
-            args = " ".join(m.group(3).split())
-            protos[m.group(2)] = (" ".join(m.group(1).split()), [] if args in ("", "void") else [a.strip() for a in args.split(",")])
-    return protos
-
-
-def test_header_and_binding_agree():
-    hdr = _abi.seg_header_symbols()
-    assert len(hdr) == 4 and sorted(_abi.SEG_PROTOTYPES) == hdr
-    assert not set(hdr) & (set(_abi.PROTOTYPES) | set(_abi.SBL_PROTOTYPES)) and all(n.startswith("epg_seg_") for n in hdr)
-    protos = _header_prototypes()
-    assert sorted(protos) == hdr
-    for name, (res, args) in _abi.SEG_PROTOTYPES.items():
-        ret, params = protos[name]
-        assert res in _ctypes_of(ret), name
-        assert len(args) == len(params), name
-        for i, (a, p) in enumerate(zip(args, params)):
-            assert a in _ctypes_of(p), "%s: parameter %d is `%s` in the header, %s in the binding" % (name, i, p, a.__name__)
-    assert _abi.ABI_VERSION == 2                                 # a new header, not a new version of the old one
-
-
-def test_library_exports_the_new_symbols_unmangled():
-    lib = _abi.load()
-    for name in _abi.seg_header_symbols():
-        assert hasattr(lib, name)
-    nm = shutil.which("nm")
-    if nm is None:
-        pytest.skip("nm not available")
-    out = subprocess.run([nm, "-D", "--defined-only", str(_abi.lib_path())], capture_output=True, text=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-    assert set(_abi.seg_header_symbols()) <= exported
-
+# ---- the header's constants and the entry points' checks (tests/test_abi_symbols.py holds the header against its binding) ---
 
 def test_constants_and_argument_validation_without_gpu():
     lib = _abi.load()
-    hdr = _abi.SEG_HEADER.read_text()
+    hdr = _abi.HEADERS["segments"].path.read_text()
     which = {n: int(v) for n, v in re.findall(r"#define EPG_SEG_(THREAD_BYTES|BLOCK_BYTES|EXPAND_TILE_BINS|MAX_CHROMS) (\d+)", hdr)}
     assert sorted(which.values()) == [0, 1, 2, 3]
     tb, bb = lib.epg_seg_constant(which["THREAD_BYTES"]), lib.epg_seg_constant(which["BLOCK_BYTES"])

@@ -1,11 +1,8 @@
-"""`simsearch -b --step1 gpu`, the host side (no GPU): include/epilogos_simsearch_pick.h against its binding and the library's
-exports, the argument checks made before the first HIP call, cli()'s handling of --step1, the STEP 1 child of a --gpus N build, and
-similaritySearch_step1's orchestration -- shifts, masks, compaction, final order, coordinates -- against similaritySearch_max_mean
-with numpy restatements (tests/simsearch_pick_ref.py) in place of the device steps."""
+"""`simsearch -b --step1 gpu`, the host side (no GPU; tests/test_abi_symbols.py holds include/epilogos_simsearch_pick.h against
+its binding): the header's tile constants, the argument checks made before the first HIP call, cli()'s handling of --step1, the
+STEP 1 child of a --gpus N build, and similaritySearch_step1's orchestration -- shifts, masks, compaction, final order,
+coordinates -- against similaritySearch_max_mean with numpy restatements (tests/simsearch_pick_ref.py) in place of the device steps."""
 import ctypes
-import re
-import shutil
-import subprocess
 import sys
 from pathlib import Path
 
@@ -20,59 +17,14 @@ from tests import simsearch_pick_ref as ref
 
 ROOT = Path(__file__).resolve().parents[1]
 GOLD = np.load(ROOT / "tests" / "golden" / "simsearch.npz")
-SYMBOLS = ["epg_simsearch_pick", "epg_simsearch_pick_ws_bytes", "epg_simsearch_rank", "epg_simsearch_rank_ws_bytes",
-           "epg_simsearch_rolling_max", "epg_simsearch_rowscore"]
 
 
-# ---- header, binding, exports ------------------------------------------------------------------------------------------------------
+# ---- the header --------------------------------------------------------------------------------------------------------------------
 
-def _header_prototypes():
-    txt = re.sub(r"/\*.*?\*/", "", _abi.PICK_HEADER.read_text(), flags=re.S)
-    txt = re.sub(r'^\s*(#.*|extern "C" \{|\})\s*$', "", txt, flags=re.M)
-    protos = {}
-    for stmt in txt.split(";"):
-        m = re.match(r"\s*(.*?)\b(epg_[a-z0-9_]+)\s*\((.*)\)\s*$", stmt, flags=re.S)
-        if m:
-            args = " ".join(m.group(3).split())
-            protos[m.group(2)] = (" ".join(m.group(1).split()), [] if args in ("", "void") else [a.strip() for a in args.split(",")])
-    return protos
-
-
-def _ctypes_of(decl):
-    if "*" in decl:
-        return {ctypes.c_void_p, ctypes.c_char_p}
-    base = decl.replace("const ", "").split()[0]
-    return {"int64_t": {ctypes.c_int64}, "int32_t": {ctypes.c_int32, ctypes.c_int}, "int": {ctypes.c_int32, ctypes.c_int},
-            "uint64_t": {ctypes.c_uint64}}[base]
-
-
-def test_header_and_binding_agree():
-    hdr = _abi.pick_header_symbols()
-    assert hdr == SYMBOLS and sorted(_abi.PICK_PROTOTYPES) == hdr
-    # a header of its own: the main header, its binding table and its version do not know the entry points
-    assert not set(hdr) & set(_abi.PROTOTYPES) and not set(hdr) & set(_abi.header_symbols())
-    assert _abi.ABI_VERSION == 2
-    protos = _header_prototypes()
-    assert sorted(protos) == hdr
-    for name, (res, args) in _abi.PICK_PROTOTYPES.items():
-        ret, params = protos[name]
-        assert res in _ctypes_of(ret), name
-        assert len(args) == len(params), name
-        for i, (a, p) in enumerate(zip(args, params)):
-            assert a in _ctypes_of(p), "%s: parameter %d is `%s` in the header, %s in the binding" % (name, i, p, a.__name__)
-    T, maxW = _abi.pick_header_constant("EPG_PICK_TILE"), _abi.pick_header_constant("EPG_PICK_MAX_W")
+def test_a_tile_and_its_halos_fit_the_lds():
+    """(tests/test_abi_symbols.py holds the header against its binding and the library's exports.)"""
+    T, maxW = _abi.header_constant("simsearch_pick", "EPG_PICK_TILE"), _abi.header_constant("simsearch_pick", "EPG_PICK_MAX_W")
     assert T % 256 == 0 and 3 * 4 * (T + 2 * (maxW - 1)) <= 48 * 1024            # key, prefix and suffix of a tile and its halos
-
-
-def test_library_exports_the_symbols_unmangled():
-    lib = ctypes.CDLL(str(_abi.lib_path()))
-    for name in SYMBOLS:
-        assert hasattr(lib, name), name
-    nm = shutil.which("nm")
-    if nm is not None:
-        out = subprocess.run([nm, "-D", "--defined-only", str(_abi.lib_path())], capture_output=True, text=True).stdout
-        exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-        assert set(SYMBOLS) <= exported
 
 
 def test_argument_validation_without_gpu():

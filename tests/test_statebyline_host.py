@@ -1,11 +1,9 @@
-"""ChromHMM state-by-line preprocessing, the host side (no GPU): the new header against its binding and the library's exports,
-the entry points' argument checks, the script's file selection rule (stateByLine.find_calls), and the binary matrix file
+"""ChromHMM state-by-line preprocessing, the host side (no GPU): the header's constants (tests/test_abi_symbols.py holds it
+against its binding), the entry points' argument checks, the script's file selection rule (stateByLine.find_calls), and the binary matrix file
 (.epgm) read by helpers.readTable exactly as the equivalent text matrix is -- pinned to the reference's own matrix_chr1.txt
 (tests/golden/statebyline.npz) through a pure-numpy builder."""
 import ctypes
 import re
-import shutil
-import subprocess
 from pathlib import Path
 
 import numpy as np
@@ -16,56 +14,11 @@ from epilogos_amd import _abi, _io, helpers, stateByLine as sbl
 GOLD = np.load(Path(__file__).resolve().parent / "golden" / "statebyline.npz")
 
 
-# ---- header, binding, exports ---------------------------------------------------------------------------------------------
-
-def _header_prototypes():
-    txt = re.sub(r"/\*.*?\*/", "", _abi.SBL_HEADER.read_text(), flags=re.S)
-    txt = re.sub(r'^\s*(#.*|extern "C" \{|\})\s*$', "", txt, flags=re.M)
-    protos = {}
-    for stmt in txt.split(";"):
-        m = re.match(r"\s*(.*?)\b(epg_[a-z0-9_]+)\s*\((.*)\)\s*$", stmt, flags=re.S)
-        if m:
-            args = " ".join(m.group(3).split())
-            protos[m.group(2)] = (" ".join(m.group(1).split()), [] if args in ("", "void") else [a.strip() for a in args.split(",")])
-    return protos
-
-
-def _ctypes_of(decl):
-    if "*" in decl:
-        return {ctypes.c_void_p, ctypes.c_char_p}
-    base = decl.replace("const ", "").split()[0]
-    return {"int64_t": {ctypes.c_int64}, "int32_t": {ctypes.c_int32, ctypes.c_int}, "int": {ctypes.c_int32, ctypes.c_int}}[base]
-
-
-def test_header_and_binding_agree():
-    hdr = _abi.sbl_header_symbols()
-    assert len(hdr) == 4 and sorted(_abi.SBL_PROTOTYPES) == hdr
-    assert not set(hdr) & set(_abi.PROTOTYPES) and all(n.startswith("epg_sbl_") for n in hdr)
-    protos = _header_prototypes()
-    assert sorted(protos) == hdr
-    for name, (res, args) in _abi.SBL_PROTOTYPES.items():
-        ret, params = protos[name]
-        assert res in _ctypes_of(ret), name
-        assert len(args) == len(params), name
-        for i, (a, p) in enumerate(zip(args, params)):
-            assert a in _ctypes_of(p), "%s: parameter %d is `%s` in the header, %s in the binding" % (name, i, p, a.__name__)
-
-
-def test_library_exports_the_new_symbols_unmangled():
-    lib = _abi.load()
-    for name in _abi.sbl_header_symbols():
-        assert hasattr(lib, name)
-    nm = shutil.which("nm")
-    if nm is None:
-        pytest.skip("nm not available")
-    out = subprocess.run([nm, "-D", "--defined-only", str(_abi.lib_path())], capture_output=True, text=True).stdout
-    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
-    assert set(_abi.sbl_header_symbols()) <= exported
-
+# ---- the header's constants and the entry points' checks (tests/test_abi_symbols.py holds the header against its binding) ---
 
 def test_constants_and_argument_validation_without_gpu():
     lib = _abi.load()
-    hdr = _abi.SBL_HEADER.read_text()
+    hdr = _abi.HEADERS["statebyline"].path.read_text()
     which = {n: int(v) for n, v in re.findall(r"#define EPG_SBL_(THREAD_BYTES|BLOCK_BYTES|TILE_BINS|MAX_BATCH) (\d+)", hdr)}
     assert sorted(which.values()) == [0, 1, 2, 3]
     tb, bb = lib.epg_sbl_constant(which["THREAD_BYTES"]), lib.epg_sbl_constant(which["BLOCK_BYTES"])
