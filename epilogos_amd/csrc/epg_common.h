@@ -39,7 +39,8 @@ static inline const char* exp_env(const char*) { return nullptr; }
 // >= 1 and applied to a block count that is >= 1 (calls of no rows return before), and every capped kernel walks its tiles with a
 // gridDim stride, none assumes a minimum grid.  k_s3_score, k_s3_score_bl, k_s3_hist and the S3 contraction take one slice / task
 // per workgroup: their grids do not come from num_cus() and the switch does not change them.
-enum Force { FORCE_NULL_SEQ = 0, FORCE_S3_SCORE_BINS, FORCE_S3_CONTRACTION, FORCE_S3_HIST_LDS, FORCE_K1_BLOCKS_PER_CU, FORCE_CUS, FORCE_COUNT };
+enum Force { FORCE_NULL_SEQ = 0, FORCE_S3_SCORE_BINS, FORCE_S3_CONTRACTION, FORCE_S3_HIST_LDS, FORCE_K1_BLOCKS_PER_CU, FORCE_CUS,
+             FORCE_K1_PLAIN_LOADS, FORCE_COUNT };
 extern int g_force[FORCE_COUNT];
 
 #define EPG_HIP(expr)                                                                         \

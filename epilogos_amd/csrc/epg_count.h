@@ -225,6 +225,140 @@ __device__ __forceinline__ void tile_loop(const char* __restrict__ X, long R, in
         super_tile<S>(X, R, ldx, g, st, j, b, count, epilogue, finish);
 }
 
+// ---- The same words through LDS: a non-temporal LDS-DMA stream (k_bin_hist on the 15-, 18- and 25-state models, NG = 1..8) ----
+// load_groups asks for every 128-byte line twice (64-byte halves of 16 rows per instruction), which is why plain nt loads lose
+// (3.1-3.4 ms) and the launch reads at 5.3-5.4 TB/s in that shape.  global_load_lds_dwordx4 with per-lane SOURCE addresses fetches
+// the same 16 rows as 1 KiB pieces that run along the rows -- piece p = 64 i + lane of instruction i is chunk p % C of row p / C
+// (C = chunks per row), every line asked for once -- and takes nt: 7.0-7.1 TB/s for the bare stream against 5.3-5.4
+// (tools/ubench/dma_stream.hip, profiles/r07a_*; the ring's depth and the waves per CU make no difference there).
+// One slot of 16 rows per wave (16 x 16 C bytes, at most 16 KiB; 13.25 KiB at N = 833), lane-linear: chunk c of row r at 16 (r C + c).
+// The wave that fills the slot is the wave that reads it, so nothing but its own vmcnt orders the two (no barrier, no hand-off):
+//     read the slot into w[NG][8] (ds_read_b128, the lanes and the order of load_groups) | lgkmcnt(0): the slot is free |
+//     DMA of the NEXT half tile | count this one from registers | vmcnt(0): the next has landed | epilogue, finish (H stores)
+// -- one half tile ahead with the registers as the second buffer, and the wait stands BEFORE the H stores, so no load waits for
+// a store.  The reads are inline asm: the compiler puts vmcnt(0) before any LDS access it sees while a DMA is pending.
+// LDS budget of a workgroup: 4 slots = 1 KiB x C <= 64 KiB dynamic + bin_hist_body's static <= 6.6 KiB: two workgroups per CU
+// (grid_for_tiles) fit the 160 KiB at every width.
+// Needs X and ldx 16-byte aligned and 16 ldx < 2^32 (per-lane 32-bit offsets); the host takes load_groups otherwise.
+// Rows past R (the last super-tile) and lanes past the 16 C pieces ask for X's first chunk or for nothing: no byte outside
+// [X, X + R ldx) is requested.
+typedef u32 epg_ldsx4 __attribute__((ext_vector_type(4)));
+
+template <int NG>
+struct DmaHalfTile {
+    static constexpr int NI = 2 * NG;      // DMA instructions per half tile: pieces 64 i .. 64 i + 63, the last one or two partly or not used
+    u32 soff[NI];                          // this lane's piece of instruction i: byte offset from the half tile's first row
+    u64 rpack;                             // its row in the half tile, 4 bits per instruction
+    char* slot;                            // the wave's slot
+    u32 rd, rd_tail[2];                    // LDS addresses this lane reads: chunk j of row b; the clamped chunks of the last group
+    int npieces;                           // 16 C
+
+    __device__ __forceinline__ void init(char* ring, int wave, int lane, const RowGeom& g, long ldx) {
+        const int j = lane & 3, b = lane >> 2, C = g.chunks;
+        npieces = 16 * C;
+        slot = ring + wave * (256 * C);
+        rpack = 0;
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            const int p = 64 * i + lane;
+            int r = p / C;
+            const int c = p - r * C;
+            const bool used = r < 16;
+            r = used ? r : 0;
+            soff[i] = used ? (u32)r * (u32)ldx + 16u * (u32)c : 0u;
+            rpack |= (u64)r << (4 * i);
+        }
+        const u32 row = (u32)(uintptr_t)slot + 16u * (u32)(b * C);
+        rd = row + 16u * j;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int c = 4 * (NI - 2 + k) + j;
+            rd_tail[k] = row + 16u * (u32)(c < g.last ? c : g.last);
+        }
+    }
+
+    // request rows row0 .. row0 + 15 of X[R, ldx]
+    __device__ __forceinline__ void fill(const char* __restrict__ X, long R, long ldx, long row0, int lane) const {
+        const char* Xh = X + row0 * ldx;
+        const long left = R - row0;        // rows of the half tile that exist (wave-uniform, may be <= 0)
+        auto piece = [&](int i, const char* src) {
+            if (i < NI - 2 || 64 * i + lane < npieces)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                                 (__attribute__((address_space(3))) void*)(slot + 1024 * i), 16, 0, 2 /* nt */);
+        };
+        if (left >= 16) {                  // (two loops: one with a select per piece costs every half tile 7 VALU per piece)
+#pragma unroll
+            for (int i = 0; i < NI; ++i) piece(i, Xh + soff[i]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < NI; ++i) piece(i, (long)((rpack >> (4 * i)) & 15) < left ? Xh + soff[i] : X);
+        }
+    }
+
+    // every DMA this wave has issued has landed
+    static __device__ __forceinline__ void wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+    // the slot's words in load_groups' layout (load_slot<true>'s masks on the last group); on return the slot may be refilled
+    __device__ __forceinline__ void read(const RowGeom& g, int j, u32 (&w)[NG][8]) const {
+        epg_ldsx4 v[NI];
+        __builtin_amdgcn_sched_barrier(0);                                                           // (nothing between the reads and their wait)
+#pragma unroll
+        for (int i = 0; i < NI - 2; ++i) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v[i]) : "v"(rd), "n"(64 * i) : "memory");
+        asm volatile("ds_read_b128 %0, %1" : "=v"(v[NI - 2]) : "v"(rd_tail[0]) : "memory");
+        asm volatile("ds_read_b128 %0, %1" : "=v"(v[NI - 1]) : "v"(rd_tail[1]) : "memory");
+#pragma unroll
+        for (int i = 0; i < NI; ++i) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v[i])::"memory");   // (names every destination)
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) {
+            u32* o = &w[i >> 1][4 * (i & 1)];
+            o[0] = v[i].x; o[1] = v[i].y; o[2] = v[i].z; o[3] = v[i].w;
+            if (i >= NI - 2) {
+                const int c = 4 * i + j;
+                const u32 inv = c > g.last ? 0xffffffffu : 0u;
+                const bool is_last = c == g.last;
+#pragma unroll
+                for (int d = 0; d < 4; ++d) o[d] |= inv | (is_last ? g.tail[d] : 0u);
+            }
+        }
+    }
+};
+
+// tile_loop with DmaHalfTile as the source of the words: the same super-tiles per wave, the same epilogue / finish calls
+template <int S, int NG, int NW = 4, typename Epilogue, typename Finish>
+__device__ __forceinline__ void tile_loop_dma(const char* __restrict__ X, long R, int N, long ldx, char* ring, Epilogue&& epilogue, Finish&& finish) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int j = lane & 3, b = lane >> 2;
+    const RowGeom g = make_geom(N);
+    const long nsuper = (R + 31) >> 5, stride = (long)gridDim.x * NW;
+    long st = (long)blockIdx.x * NW + wave;
+    if (st >= nsuper) return;              // (wave-uniform; the callers' barriers come after the loop, every wave reaches them)
+    DmaHalfTile<NG> dma;
+    dma.init(ring, wave, lane, g, ldx);
+    dma.fill(X, R, ldx, st * 32, lane);
+    dma.wait();
+    for (; st < nsuper; st += stride) {
+#pragma unroll
+        for (int half = 0; half < 2; ++half) {
+            const long row = st * 32 + half * 16 + b;
+            u32 w[NG][8];
+            dma.read(g, j, w);
+            if (half == 0) dma.fill(X, R, ldx, st * 32 + 16, lane);
+            else if (st + stride < nsuper) dma.fill(X, R, ldx, (st + stride) * 32, lane);
+            u32 cnt[S];
+#pragma unroll
+            for (int s = 0; s < S; ++s) cnt[s] = 0;
+#pragma unroll
+            for (int t = 0; t < NG; ++t) count_group<S>(w[t], cnt);
+            dma.wait();
+            epilogue(half, row, row < R, cnt);
+        }
+        const long row0 = st * 32;
+        finish(st, row0, (int)(R - row0 < 32 ? R - row0 : 32));
+    }
+}
+
 // The same loop over SEVERAL matrices ("parts", epg_parts.h) in one launch, in super-tiles of 32 rows.  enter(part) tells the
 // caller which part the following epilogue / finish calls belong to.  Every part must have a width in the instantiation's range
 // (128 (NG - 1) < N <= 128 NG, or NG == 0).

@@ -104,12 +104,15 @@ __device__ __forceinline__ void bin_hist_body(int Sout_, u64* __restrict__ count
     }
 }
 
-template <int SC, int NG, bool FULL>
+// DMA: the state words come through the wave's LDS slot (tile_loop_dma, epg_count.h; 1 KiB x ceil(N / 16) of dynamic LDS)
+template <int SC, int NG, bool FULL, bool DMA = false>
 __global__ __launch_bounds__(256) void k_bin_hist(const char* __restrict__ X, long R, int N, long ldx, int Sout_,
                                                    u16* __restrict__ H, u64* __restrict__ counts) {
+    extern __shared__ __attribute__((aligned(16))) char s_ring[];
     bin_hist_body<SC, FULL, false>(Sout_, counts, N, nullptr, [&](auto&& enter, auto&& epilogue, auto&& finish) {
         enter(H);
-        tile_loop<SC, NG>(X, R, N, ldx, epilogue, finish);
+        if constexpr (DMA) tile_loop_dma<SC, NG>(X, R, N, ldx, s_ring, epilogue, finish);
+        else tile_loop<SC, NG>(X, R, N, ldx, epilogue, finish);
     });
 }
 
@@ -349,6 +352,12 @@ static void with_count_core(int S, int ng, F&& f) {
                                       [&](auto sc) { f(sc, std::integral_constant<int, 0>{}, std::false_type{}); });
 }
 
+// The LDS-DMA loads of k_bin_hist (DmaHalfTile, epg_count.h) want 16-byte aligned rows and 32-bit offsets inside a half tile;
+// epg_test_force(6, 1) keeps the plain loads for A/B runs and the tests (tools/kbench.py, tools/s1_ab.py)
+static bool dma_rows_ok(const char* X, long ldx) {
+    return !g_force[FORCE_K1_PLAIN_LOADS] && ((reinterpret_cast<uintptr_t>(X) | (uintptr_t)ldx) & 15) == 0 && ldx < (1L << 27);
+}
+
 // rows the fast kernel may touch: all of them unless its 16-byte last chunk could run past the allocation
 long fast_rows(long R, int N, long ldx) {
     const long chunks = (N + 15) / 16;
@@ -376,11 +385,24 @@ extern "C" int epg_bin_hist(const int8_t* X8, int64_t R, int32_t N, int64_t ldx,
     }
     const long Rf = fast_rows(R, N, ldx);
     if (Rf > 0) {
+        hipError_t dyn = hipSuccess;
         with_count_core(S, (N + 127) / 128, [&](auto SC, auto NG, auto MODEL) {
             // odd S stores uint16 by uint16 either way; with the row width as a run-time value that path measured 2.30 ms
             // against 2.64 ms for the compile-time one (15 M x 833, S = 15), so only even S takes the compile-time width
-            hipLaunchKernelGGL((k_bin_hist<SC, NG, MODEL && (SC & 1) == 0>), dim3(grid_for_tiles(Rf)), dim3(256), 0, st, X, Rf, N, ldx, S, H, cnt);
+            constexpr bool FULL = MODEL && (SC & 1) == 0;
+            if constexpr (MODEL && NG > 0) {
+                if (dma_rows_ok(X, ldx)) {
+                    static DynLds lds;
+                    const int ring = 1024 * ((N + 15) / 16);
+                    dyn = ensure_dyn_lds(lds, reinterpret_cast<const void*>(k_bin_hist<SC, NG, FULL, true>), 1024 * 8 * NG);
+                    if (dyn == hipSuccess)
+                        hipLaunchKernelGGL((k_bin_hist<SC, NG, FULL, true>), dim3(grid_for_tiles(Rf)), dim3(256), ring, st, X, Rf, N, ldx, S, H, cnt);
+                    return;
+                }
+            }
+            hipLaunchKernelGGL((k_bin_hist<SC, NG, FULL>), dim3(grid_for_tiles(Rf)), dim3(256), 0, st, X, Rf, N, ldx, S, H, cnt);
         });
+        if (dyn != hipSuccess) return fail(EPG_ERR_HIP, "bin_hist: the LDS ring was refused: %s", hipGetErrorString(dyn));
         EPG_LAUNCH_CHECK("k_bin_hist");
     }
     if (Rf < R) {

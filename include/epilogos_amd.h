@@ -277,7 +277,9 @@ int epg_simsearch_slices(const int32_t* X, int64_t R, int32_t S, int32_t blockSi
  * the count; epg_device_cus() reports it while it is set): with 1 a few thousand rows give every wave many tiles, so that the state
  * the kernels carry from one tile to the next -- prefetched tiles, packed running counts and their flush, the cursor through
  * several parts, re-used LDS staging areas -- runs at test sizes (tests/test_hip_persistent_loops.py); same results for every
- * value.  value 0 = the library decides (the default). */
+ * value, 6 = the count pass of epg_bin_hist reads its rows with plain loads (1) where it would stream them through LDS by
+ * non-temporal DMA (the 15-, 18- and 25-state models on rows of up to 1024 columns, 16-byte aligned X and ldx; same integers,
+ * tests/test_hip_count_dma.py).  value 0 = the library decides (the default). */
 int epg_test_force(int32_t which, int32_t value);
 
 #ifdef __cplusplus

@@ -50,6 +50,7 @@ for rnd in range(a.rounds + 1):
     for cfg in a.configs:
         v, bpc = [int(t) for t in cfg.split(":")]
         lib.epg_test_force(4, bpc)
+        lib.epg_test_force(6, v)                    # variant 1: the count pass with its plain loads, 0: its LDS-DMA stream
         if "hist" in a.what:
             counts.zero_()
             t = timed(lambda: engine.bin_hist(X, N, S, counts=counts, H=H))
