@@ -114,6 +114,19 @@ assert list(_TABLES) == list(_build.PUBLIC_HEADERS)
 HEADERS = {which: Header(_build.ROOT / "include" / name, _TABLES[which]) for which, name in _build.PUBLIC_HEADERS.items()}
 HEADER, PROTOTYPES = HEADERS["core"]
 
+# package-internal entry points (build.INTERNAL_HEADERS): exported by the same library and bound by load() like the public ones, but
+# declared under csrc/ and outside the registry above, whose ten headers and their names the binding tests pin.  csrc/epg_pvals.h
+# says what promotes a header from here to HEADERS.
+_INTERNAL_TABLES = {
+    "pvals": {                                            # p-values and Benjamini-Hochberg of paired mode with -n
+        "epgf_gennorm_pvals": (C.c_int, [_p, _i64, _p, _p, _p, _p]),
+        "epgf_bh_ws_bytes": (_i64, [_i64]),
+        "epgf_bh_adjust": (C.c_int, [_p, _i64, _p, _p, _p, _i64, _p]),
+    },
+}
+assert list(_INTERNAL_TABLES) == list(_build.INTERNAL_HEADERS)
+INTERNAL = {which: Header(_build.CSRC / name, _INTERNAL_TABLES[which]) for which, name in _build.INTERNAL_HEADERS.items()}
+
 _lib = None
 
 
@@ -160,7 +173,7 @@ def load():
         raise EpilogosHipError(-3, "%s is missing: build it with `python -m epilogos_amd.build` "
                                    "(there is no CPU fallback)" % path)
     lib = C.CDLL(str(path))
-    for header in HEADERS.values():
+    for header in [*HEADERS.values(), *INTERNAL.values()]:
         for name, (res, args) in header.prototypes.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
             fn.restype = res

@@ -581,6 +581,38 @@ def gennorm_nnlf(x, params, ws=None):
     return out
 
 
+def gennorm_pvals(x, params):
+    """Two-sided p-value of every x under gennorm(beta, loc, scale) (epgf_gennorm_pvals, csrc/epg_pvals.h): params float64 [3] on
+    the device, e.g. a row of gennorm_fit's.  -> (p float64 [M], flags int32 [2] = (NaN p-values, iterations stopped at the cap)).
+    Current stream, no synchronisation."""
+    M = _check_gennorm_x(x)
+    if params.dtype != torch.float64 or params.numel() != 3 or not params.is_cuda or not params.is_contiguous():
+        raise ValueError("params must be a contiguous float64 CUDA tensor of 3 elements (beta, loc, scale)")
+    p = torch.empty(M, dtype=torch.float64, device=x.device)
+    flags = torch.empty(2, dtype=torch.int32, device=x.device)
+    _abi.call("epgf_gennorm_pvals", _ptr(x), M, _ptr(params), _ptr(p), _ptr(flags), _stream())
+    return p, flags
+
+
+def bh_ws_bytes(M):
+    return max(int(_abi.call("epgf_bh_ws_bytes", M)), 256)
+
+
+def bh_adjust(p, ws=None):
+    """Benjamini-Hochberg adjusted p-values (epgf_bh_adjust), the bits of roiAndVisualPairwise.benjaminiHochberg: p float64 [M] ->
+    (adj float64 [M], flags int32 [1] = the number of p that are NaN or negative; adj means nothing when it is not 0).  The
+    workspace is sized and owned here unless `ws` (uint8, at least bh_ws_bytes(M)) is handed in.  Current stream, no synchronisation."""
+    if p.dtype != torch.float64 or p.dim() != 1 or not p.is_cuda or not p.is_contiguous() or p.numel() < 1:
+        raise ValueError("p must be a non-empty contiguous 1-D float64 CUDA tensor")
+    M = p.numel()
+    adj = torch.empty(M, dtype=torch.float64, device=p.device)
+    flags = torch.empty(1, dtype=torch.int32, device=p.device)
+    if ws is None:
+        ws = torch.empty(bh_ws_bytes(M), dtype=torch.uint8, device=p.device)
+    _abi.call("epgf_bh_adjust", _ptr(p), M, _ptr(adj), _ptr(flags), _ptr(ws), ws.numel(), _stream())
+    return adj, flags
+
+
 def select_columns(X, cols):
     """The columns `cols` (0-based int64) of a state matrix as a matrix of its own: int8 [R, padded_width(len(cols))], padding
     bytes 0xFF.  What the grouped count pass does not serve (S3 needs the states themselves; models of 32 .. 127 states) runs

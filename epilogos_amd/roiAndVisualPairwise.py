@@ -360,18 +360,61 @@ def _fitParams(distanceArrNull, quiescenceArr, numProcesses, numTrials, sampling
     return tuple(results[medianTrial([r[1] for r in results])][0])
 
 
+def _pvalOptions(pvals):
+    """What STEP 4 passes on beyond what it always passed: nothing for the host's p-value stage."""
+    return {} if pvals == "host" else dict(pvals=pvals)
+
+
+def _pvalsGpu(distanceArrReal, params, empirical):
+    """The pvals="gpu" branch of _finish (csrc/epg_pvals.h): one upload of the distances and the three parameters, the p-value kernel
+    and the Benjamini-Hochberg adjustment back to back on the device, one download of p, the adjusted p and the flag words.
+    empirical given (--null-draws K > 1): the p-values are the host's and only the adjustment runs on the device.
+    -> (pvals, mhPvals), or None when a flag word is not zero: a p-value that is NaN (a NaN distance, unusable parameters) or
+    negative, or an iteration that stopped at its cap."""
+    import torch
+    from . import engine
+    engine.require_gpu()
+    if empirical is not None:
+        pvals = np.ascontiguousarray(empirical, dtype=np.float64)
+        p, pflags = torch.from_numpy(pvals).cuda(), None
+    else:
+        x = torch.from_numpy(np.ascontiguousarray(distanceArrReal, dtype=np.float32)).cuda()
+        theta = torch.from_numpy(np.array([params[0], params[-2], params[-1]], dtype=np.float64)).cuda()
+        p, pflags = engine.gennorm_pvals(x, theta)
+    adj, bflags = engine.bh_adjust(p)
+    flags = (bflags if pflags is None else torch.cat([pflags, bflags])).cpu().numpy()
+    if flags.any():
+        return None
+    return (pvals if empirical is not None else p.cpu().numpy()), adj.cpu().numpy()
+
+
 def _finish(params, locationArr, distanceArrReal, maxDiffArr, chrDict, stateInfo, outputDirPath, fileTag, pvalBool, roiWidth,
-            expFreqPath, verbose, empirical=None):
+            expFreqPath, verbose, empirical=None, pvals="host"):
     """Everything of main() after the inputs are in memory (reference :72-169 without the figures).  empirical: the bins'
-    empirical p-values (empiricalPVals); they take the place of the fitted distribution's and `params` is not used."""
+    empirical p-values (empiricalPVals); they take the place of the fitted distribution's and `params` is not used.
+    pvals="gpu": the p-values and their Benjamini-Hochberg adjustment on the device (_pvalsGpu), both under the first of the two
+    stage labels; a non-zero flag sends the whole stage back to the host functions."""
+    if pvals not in ("host", "gpu"):
+        raise ValueError("pvals must be 'host' or 'gpu', not {!r}".format(pvals))
+    onDevice = pvals == "gpu"                        # (below, `pvals` is the array of p-values, as it always was)
     stateNameList = getStateNames(stateInfo)
     roiPath = outputDirPath / "regionsOfInterest_{}.txt".format(fileTag)
     if pvalBool:
         t0 = _stage(verbose, "Calculating p-vals")
-        pvals = empirical if empirical is not None else calculatePVals(distanceArrReal, params[0], params[-2], params[-1])
+        device = None
+        if onDevice and len(distanceArrReal):
+            device = _pvalsGpu(distanceArrReal, params, empirical)
+            if device is None:
+                print("WARNING: a p-value is not a number or negative, or an iteration met its cap; computing the p-values on the host instead",
+                      flush=True)
+        if device is not None:
+            pvals, mhPvals = device
+        else:
+            pvals = empirical if empirical is not None else calculatePVals(distanceArrReal, params[0], params[-2], params[-1])
         _done(verbose, t0)
         t0 = _stage(verbose, "Benjamini-Hochberg procedure")
-        mhPvals = benjaminiHochberg(pvals)
+        if device is None:
+            mhPvals = benjaminiHochberg(pvals)
         _done(verbose, t0)
         t0 = _stage(verbose, "Writing metrics")
         writeMetrics(locationArr, chrDict, maxDiffArr, stateNameList, distanceArrReal, outputDirPath, fileTag, True,
@@ -407,7 +450,7 @@ def _is_location_sorted(chrNum, starts, ends):
 
 
 def mainFromArrays(results, stateInfo, outputDir, fileTag, numProcesses, pvalBool, numTrials, samplingSize, expFreqPath,
-                   roiWidth, verbose, fit="host", seed=None):
+                   roiWidth, verbose, fit="host", seed=None, pvals="host"):
     """main() on the arrays driver.run_paired_groups hands back ({stem: dict(chrName, locations, nullDistances,
     quiescenceArr, distances, maxDiff)}) instead of the temp_*.npz / pairwiseDelta text round trip."""
     outputDirPath = Path(outputDir)
@@ -439,11 +482,11 @@ def mainFromArrays(results, stateInfo, outputDir, fileTag, numProcesses, pvalBoo
         dist, maxdiff = dist[order], maxdiff[order]
         empirical = empirical[order] if empirical is not None else None
     _finish(params, locationArr, dist, maxdiff, chrDict, stateInfo, outputDirPath, fileTag, pvalBool, roiWidth, expFreqPath, verbose,
-            empirical=empirical)
+            empirical=empirical, **_pvalOptions(pvals))
 
 
 def main(group1Name, group2Name, stateInfo, outputDir, fileTag, numProcesses, pvalBool, diagnosticBool, numTrials,
-         samplingSize, expFreqPath, roiWidth, verbose, backend=None, fit="host", seed=None):
+         samplingSize, expFreqPath, roiWidth, verbose, backend=None, fit="host", seed=None, pvals="host"):
     tTotal = time()
     outputDirPath = Path(outputDir)
     numStates = getNumStates(stateInfo)
@@ -462,7 +505,7 @@ def main(group1Name, group2Name, stateInfo, outputDir, fileTag, numProcesses, pv
     if empiricalRun and empirical is None:
         raise ValueError("temp_nullExceed_*.npz is missing for some of the pairwiseDelta files in {}".format(outputDirPath))
     _finish(params, locationArr, distanceArrReal, maxDiffArr, chrDict, stateInfo, outputDirPath, fileTag, pvalBool, roiWidth,
-            expFreqPath, verbose, empirical=empirical if empiricalRun else None)
+            expFreqPath, verbose, empirical=empirical if empiricalRun else None, **_pvalOptions(pvals))
     if verbose: print("Total Time:", time() - tTotal, flush=True)
 
 

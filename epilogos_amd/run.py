@@ -234,6 +234,10 @@ def _init_device_and_group(world, under_launcher):
               help="Paired mode with -n: where the [-t] generalised-normal fits of the null distances run.  host: scipy, on [-c] cores, "
                    "sub-samples from OS entropy.  gpu: on the device, sub-samples seeded from [--null-seed]: two runs with the same seed "
                    "write the same p-values")
+@click.option("--pvals", "pvals", type=click.Choice(["host", "gpu"]), default="host", show_default=True,
+              help="Paired mode with -n: where the p-values of the bins and their Benjamini-Hochberg adjustment are computed.  host: scipy "
+                   "and numpy.  gpu: on the device (with [--null-draws] greater than 1 the adjustment only); the adjusted values are the "
+                   "host's bit for bit, the p-values agree to about 1e-13")
 @click.option("--gpus", "gpus", type=int, default=1, show_default=True,
               help="GPUs of this node to split the genome over (0 = all visible); replaces the SLURM fan-out of the reference")
 @click.option("--cache-dir", "cacheDir", type=str, default=None,
@@ -266,7 +270,7 @@ def _init_device_and_group(world, under_launcher):
 def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2, outputDirectory, stateInfo, saliency,
          numProcesses, exitBool, diagnosticBool, numTrials, samplingSize, quiescentState, groupSize, version, partition,
          pvalBool, roiWidth, fileTag, expFreqMem, expCombMem, scoreMem, roiMem, nullSeed, nullDraws, gpus, cacheDir, columns, columnsA, columnsB, checkStates,
-         groupingsFile, chromhmm, metadata, chromsizes, segments, binWidth, stateNames, keepMatrices, fit="host"):
+         groupingsFile, chromhmm, metadata, chromsizes, segments, binWidth, stateNames, keepMatrices, fit="host", pvals="host"):
     """Information-theoretic navigation of multi-tissue functional genomic annotations -- MI355X scoring engine."""
     if version:
         print("Version:", __version__)
@@ -294,6 +298,11 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
         print("ERROR: [--fit gpu] requires [-n, --null-distribution]: without it nothing is fitted"); sys.exit()
     if fit == "gpu" and nullDraws > 1:
         print("ERROR: [--fit gpu] cannot be combined with [--null-draws] greater than 1: empirical p-values need no fit"); sys.exit()
+    # --pvals gpu: the same
+    if pvals == "gpu" and mode != "paired":
+        print("ERROR: [--pvals gpu] is only valid in paired mode"); sys.exit()
+    if pvals == "gpu" and not pvalBool:
+        print("ERROR: [--pvals gpu] requires [-n, --null-distribution]: without it no p-value is computed"); sys.exit()
     # --groupings: as above, its own combinations and its file's errors before everything else -- nothing is read but that file
     groupings = None
     if groupingsFile is not None:
@@ -464,6 +473,10 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
         # nothing for --fit host: STEP 4 is called exactly as before.  nullSeed is the run's one seed by now, drawn or given
         return dict(fit="gpu", seed=nullSeed) if fit == "gpu" else {}
 
+    def pvalOptions():
+        # nothing for --pvals host, as above
+        return dict(pvals="gpu") if pvals == "gpu" else {}
+
     def step4_paired(results, outDir):
         if pvalBool and max(numProcesses, 1) > 1 and nullDraws == 1 and fit != "gpu":
             driver.finish_writes()                               # -n -c K forks a pool for the fits: not with writer threads running
@@ -474,7 +487,7 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
                 t0 = time.perf_counter()
                 from .roiAndVisualPairwise import mainFromArrays as roiPairwise
                 roiPairwise(results, stateInfo, outDir, fileTag, max(numProcesses, 1), pvalBool, numTrials, samplingSize,
-                            outDir / storedExpPath.name, roiWidth if roiWidth else 125, False, **fitOptions())
+                            outDir / storedExpPath.name, roiWidth if roiWidth else 125, False, **fitOptions(), **pvalOptions())
                 if os.environ.get("EPILOGOS_TIMING"):
                     print("    [timing] %-34s %7.2f s" % ("STEP 4", time.perf_counter() - t0), flush=True)
         finally:

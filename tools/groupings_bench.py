@@ -13,7 +13,7 @@ at the end of the first grouping's STEP 1 -- imports, device init, the read of t
 pass (milliseconds) -- which is the fixed cost the later groupings do not pay again; and the [timing] lines of the run, summed
 by phase, which say where the rest went.  Output directories and the input go to a scratch directory that is removed at the end.
 usage: groupings_bench.py [--bins 1246253] [--columns 833] [--groupings 8] [--only single|paired] [--trials 101] [--fit host|gpu]
-                          [--workdir DIR]"""
+                          [--pvals host|gpu] [--workdir DIR]"""
 import argparse
 import json
 import os
@@ -37,6 +37,7 @@ ap.add_argument("--groupings", type=int, default=8)
 ap.add_argument("--only", choices=["single", "paired"], default=None)
 ap.add_argument("--trials", type=int, default=101, help="-t of the paired commands (the fits of -n)")
 ap.add_argument("--fit", choices=["host", "gpu"], default=None, help="--fit of the paired commands (default: not passed, the host fit)")
+ap.add_argument("--pvals", choices=["host", "gpu"], default=None, help="--pvals of the paired commands (default: not passed, the host stage)")
 ap.add_argument("--workdir", type=str, default=None)
 ap.add_argument("--child-limit", type=int, default=900, help="seconds a child process may take")
 a = ap.parse_args()
@@ -119,7 +120,7 @@ try:
             lines.append(["g%02d" % g] + [spec(c.tolist()) for c in groups])
         gfile = work / (mode + ".tsv")
         gfile.write_text("".join("\t".join(l) + "\n" for l in lines))
-        common = ["-i", str(ind), "-j", str(meta), "-s", "1"] + (["-m", "paired", "-n", "--null-seed", "1", "-t", str(a.trials)] + (["--fit", a.fit] if a.fit else [])
+        common = ["-i", str(ind), "-j", str(meta), "-s", "1"] + (["-m", "paired", "-n", "--null-seed", "1", "-t", str(a.trials)] + (["--fit", a.fit] if a.fit else []) + (["--pvals", a.pvals] if a.pvals else [])
                                                        if mode == "paired" else [])
         walls = []
         for l in lines:
