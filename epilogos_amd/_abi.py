@@ -116,16 +116,27 @@ HEADER, PROTOTYPES = HEADERS["core"]
 
 # package-internal entry points (build.INTERNAL_HEADERS): exported by the same library and bound by load() like the public ones, but
 # declared under csrc/ and outside the registry above, whose ten headers and their names the binding tests pin.  csrc/epg_pvals.h
-# says what promotes a header from here to HEADERS.
+# says what promotes a header from here to HEADERS.  The device text writer's table ("textout", csrc/epg_textout.h, prefix epgw_) is
+# package-internal in the same way and bound through WRITER (build.WRITER_HEADERS): INTERNAL stays the p-value stage's alone, as
+# tests/test_pvals_host.py pins it.
 _INTERNAL_TABLES = {
     "pvals": {                                            # p-values and Benjamini-Hochberg of paired mode with -n
         "epgf_gennorm_pvals": (C.c_int, [_p, _i64, _p, _p, _p, _p]),
         "epgf_bh_ws_bytes": (_i64, [_i64]),
         "epgf_bh_adjust": (C.c_int, [_p, _i64, _p, _p, _p, _i64, _p]),
     },
+    "textout": {                                          # the device text writer: score text and its BGZF compression
+        "epgw_text_bytes_max": (_i64, [_i64, _i32, _i64]),
+        "epgw_format_ws_bytes": (_i64, [_i64]),
+        "epgw_format_scores": (C.c_int, [_p, _i64, _i32, _i64, _p, _p, _p, _i64, _p, _p, _p, _i64, _p]),
+        "epgw_bgzf_bytes_max": (_i64, [_i64, _i32]),
+        "epgw_bgzf_ws_bytes": (_i64, [_i64]),
+        "epgw_bgzf_compress": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _i64, _p]),
+    },
 }
-assert list(_INTERNAL_TABLES) == list(_build.INTERNAL_HEADERS)
+assert list(_INTERNAL_TABLES) == [*_build.INTERNAL_HEADERS, *_build.WRITER_HEADERS]
 INTERNAL = {which: Header(_build.CSRC / name, _INTERNAL_TABLES[which]) for which, name in _build.INTERNAL_HEADERS.items()}
+WRITER = {which: Header(_build.CSRC / name, _INTERNAL_TABLES[which]) for which, name in _build.WRITER_HEADERS.items()}
 
 _lib = None
 
@@ -173,7 +184,7 @@ def load():
         raise EpilogosHipError(-3, "%s is missing: build it with `python -m epilogos_amd.build` "
                                    "(there is no CPU fallback)" % path)
     lib = C.CDLL(str(path))
-    for header in [*HEADERS.values(), *INTERNAL.values()]:
+    for header in [*HEADERS.values(), *INTERNAL.values(), *WRITER.values()]:
         for name, (res, args) in header.prototypes.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
             fn.restype = res

@@ -5,6 +5,7 @@ library or a GPU is missing -- there is no CPU fallback.  `set_for_testing` exis
 can exercise the host logic (file naming, partitioning, the gloo collective path) with an oracle-backed stand-in;
 nothing in the package ever installs one.
 """
+import collections
 import os
 
 import numpy as np
@@ -352,6 +353,18 @@ class _HipSession:
             self._count(self._pending)
             self._pending, self._pending_rows = [], 0
 
+    downloaded = collections.Counter()   # name -> score arrays copied to the host by any session of this process (the writer tests count them)
+
+    def device_text(self, locations, scores):
+        """--writer gpu: the BGZF bytes (host uint8 array, no end-of-file block) of the score file of device scores [R, S] with
+        `locations`, or None when the device refused a value (engine.scores_text_bgzf)."""
+        got = self.eng.scores_text_bgzf(locations, scores)
+        return None if got is None else got[0][:got[1]].cpu().numpy()
+
+    def release_text(self):
+        """--writer gpu, after the last part: the writer's reusable text, workspace and output buffers go back."""
+        self.eng.release_text_buffers()
+
     def drop_part(self, pid):
         self._flush()
         self.parts[pid] = None
@@ -630,12 +643,19 @@ class _HipSingleSession(_HipSession):
         """Device tensor of a part scored by launch() (bench.py: the scores stay in HBM)."""
         return self._early[pid]
 
-    def scores(self, pid):
+    def scores(self, pid, text=None):
+        """Host array of part `pid`'s scores.  text (the part's _io.Locations; --writer gpu): -> (the array, its score file's BGZF
+        bytes from the device or None when the device refused a value) -- the array still comes down, STEP 4 reads it."""
         self.check()
         if pid in self._early:
             self.parts[pid] = None
-            return self._early.pop(pid).cpu().numpy()
-        return self.scores_device(pid).cpu().numpy()
+            dev = self._early.pop(pid)
+        else:
+            dev = self.scores_device(pid)
+        self.downloaded["scores"] += 1
+        if text is None:
+            return dev.cpu().numpy()
+        return dev.cpu().numpy(), self.device_text(text, dev)
 
 
 class _Pair:
@@ -928,7 +948,7 @@ class _HipPairedSession(_HipSession):
     def _s1_widths(self):
         return [self.NA, self.NB] + ([self.groupSize] if self.groupSize != -1 else [])
 
-    def results(self, pid):
+    def results(self, pid, text=None):
         """Host arrays of part `pid`.  A part launch() did not score is scored with EVERY part still held (see _results); the
         parts are then downloaded one by one as the driver asks for them."""
         self.check()
@@ -936,8 +956,18 @@ class _HipPairedSession(_HipSession):
             self._early.update(self._results([p for p, part in enumerate(self.parts) if part is not None]))
             self._settle()
         r = self._early.pop(pid)
-        out = {"delta": r["delta"].cpu().numpy(), "null": r["null"].cpu().numpy(), "quies": r["quies"].cpu().numpy().astype(bool),
+        out = {"null": r["null"].cpu().numpy(), "quies": r["quies"].cpu().numpy().astype(bool),
                "rdist": r["rdist"].cpu().numpy(), "mdiff": r["mdiff"].cpu().numpy()}
+        # --writer gpu (text = the part's _io.Locations): the deltas become their file's BGZF bytes where they sit and are not
+        # downloaded -- STEP 4 works from rdist and mdiff -- unless the device refused a value: then they come down for the host writer
+        out["delta_text"] = None if text is None else self.device_text(text, r["delta"])
+        if out["delta_text"] is None:
+            self.downloaded["delta"] += 1
+            out["delta"] = r["delta"].cpu().numpy()
+        else:
+            out["delta"] = None
+        if text is None:
+            del out["delta_text"]
         if "exceed" in r:                                # (--null-draws K > 1 only)
             out["exceed"] = r["exceed"].cpu().numpy()
         return out

@@ -327,10 +327,34 @@ def _clean_parts(outputDir, kind, fileTag):
             p.unlink()
 
 
-def _assemble_text(outputDir, kind, final_name, fileTag, fi, owners, rows_fi):
+BGZF_EOF = bytes([0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0])
+
+
+def write_bgzf(path, pieces, eof=True):
+    """--writer gpu: the ONE place a device-written file is put together.  pieces: BGZF streams WITHOUT an end-of-file block, in row
+    order -- byte blobs (what the device compressed) or paths of part files (removed once copied).  eof: the file is complete and
+    gets its one end-of-file block; a part file of a range border (eof=False) gets none, because it will be a piece itself.  A file
+    without rows is that block alone."""
+    with open(path, "wb") as out:
+        for piece in pieces:
+            if isinstance(piece, (str, os.PathLike)):
+                with open(piece, "rb") as src:
+                    shutil.copyfileobj(src, out)
+                os.unlink(piece)
+            else:
+                out.write(memoryview(piece))
+        if eof:
+            out.write(BGZF_EOF)
+
+
+def _assemble_text(outputDir, kind, final_name, fileTag, fi, owners, rows_fi, writer="host"):
     """Rank 0: a file cut by range borders is the concatenation of its parts' gzip members, in row order, by the exact
-    names the plan gives; a file with one owner was written under its final name already."""
+    names the plan gives; a file with one owner was written under its final name already.  writer="gpu": the parts are BGZF
+    without end-of-file blocks and write_bgzf completes the file."""
     if len(owners) == 1 and owners[0] == (0, rows_fi):
+        return
+    if writer == "gpu":
+        write_bgzf(outputDir / final_name, [outputDir / _part_name(kind, fileTag, fi, lo) for lo, _hi in owners])
         return
     with open(outputDir / final_name, "wb") as out:
         for lo, _hi in owners:
@@ -495,6 +519,14 @@ def finish_writes():
 # ---- STEP 1-3, written once for both modes.  Every rank runs the same collectives (barrier, all-reduce, send / recv) in the
 # same order, so the sequence lives in _run_groups alone; a mode object supplies only what differs between the modes: its
 # inputs and session, how a parsed file becomes a session part, its per-part outputs and rank 0's per-file result.
+class _DeviceText:
+    """--writer gpu: what a part hands the writer pool -- blob, the file's BGZF bytes from the device (no end-of-file block), or
+    None with `array`, the float32 scores downloaded for the host writer, when the device refused a value."""
+
+    def __init__(self, blob, array):
+        self.blob, self.array = blob, array
+
+
 class _Single:
     """One group: a part is one file's rows; scores_* text; rank 0's result per file is (chrName, scores, Locations)."""
     kind, census, upload_note = "scores", "single", ""
@@ -533,10 +565,14 @@ class _Single:
         _check_columns_fit(self.columns, n, self.groups[0][part[0]])
         return sess.add_device(X, n, columns=self.columns)
 
-    def part_out(self, sess, pid):
-        """-> (the array written as text, [the arrays rank 0 collects]) of a part."""
-        sc = sess.scores(pid)
-        return sc, [sc]
+    def part_out(self, sess, pid, loc=None):
+        """-> (the array written as text, [the arrays rank 0 collects]) of a part.  loc (the part's Locations; --writer gpu): the
+        first is a _DeviceText."""
+        if loc is None:
+            sc = sess.scores(pid)
+            return sc, [sc]
+        sc, blob = sess.scores(pid, text=loc)
+        return _DeviceText(blob, sc), [sc]
 
     def result(self, temp, chrName, loc, arrays):
         """Rank 0: a file's entry of the results from its parts' arrays (arrays[i] = array i of every part, in row order)."""
@@ -590,14 +626,14 @@ class _Paired:
         # session draws the null groups right behind the count pass (on its second stream)
         return sess.add_staged(XA, nA, XB, nB, shuffle_key(fi, lo))
 
-    def part_out(self, sess, pid):
-        res = sess.results(pid)
+    def part_out(self, sess, pid, loc=None):
+        res = sess.results(pid) if loc is None else sess.results(pid, text=loc)
         arrays = [np.asarray(res["null"], dtype=np.float32), np.asarray(res["quies"], dtype=np.bool_),
                   np.asarray(res["rdist"], dtype=np.float32), np.asarray(res["mdiff"], dtype=np.int32)]
         if self.draws > 1:
             arrays.append(np.asarray(res["exceed"], dtype=np.int64))
             self.pool = int(sess.null_pool)
-        return res["delta"], arrays
+        return (res["delta"] if loc is None else _DeviceText(res["delta_text"], res["delta"])), arrays
 
     def result(self, temp, chrName, loc, arrays):
         null, quies, dist, mdiff = (_cat(a, np.zeros(0, dtype=t)).astype(t) for a, t in zip(arrays, (np.float32, bool, np.float32, np.int32)))
@@ -714,7 +750,7 @@ def _state_verdict(d, sess, mode, jobs):
     raise StateCheckFailed(1)
 
 
-def _run_groups(mode, outputDir, fileTag, backend, defer_writes, store=None):
+def _run_groups(mode, outputDir, fileTag, backend, defer_writes, store=None, writer="host"):
     """STEP 1-3 of either mode over the bin-range partition -> (exp_freq, results of rank 0 by file stem, else None).
     store (a _ResidentStore, run_groupings): the partition is the store's -- planned by the run's first grouping -- and STEP 1
     takes its parts from the store's replayable source (_ResidentStore.parts), which keeps the uploaded matrices for the groupings
@@ -735,15 +771,18 @@ def _run_groups(mode, outputDir, fileTag, backend, defer_writes, store=None):
         plan = store.plan
     sess = mode.open(be)
     try:
-        return _run_session(mode, sess, d, tm, plan, outputDir, fileTag, defer_writes, store)
+        return _run_session(mode, sess, d, tm, plan, outputDir, fileTag, defer_writes, store, writer)
     finally:
         if store is not None:
             store.uploads = int(getattr(sess, "n_uploads", 0))
             sess.close()                               # histograms, null groups and results go before the next grouping's session opens
 
 
-def _run_session(mode, sess, d, tm, plan, outputDir, fileTag, defer_writes, store):
-    """_run_groups, from the open session on."""
+def _run_session(mode, sess, d, tm, plan, outputDir, fileTag, defer_writes, store, text_writer="host"):
+    """_run_groups, from the open session on.  text_writer="gpu": a part's text is formatted and compressed on the device, the
+    writer pool's job is a plain file write (write_bgzf); a part whose scores the device refuses goes through the host writer."""
+    if text_writer not in ("host", "gpu"):
+        raise ValueError("writer must be 'host' or 'gpu'")
     files = mode.groups[0]
     layout, rows, my_parts, owner = plan
     if mode.check_states:
@@ -802,11 +841,21 @@ def _run_session(mode, sess, d, tm, plan, outputDir, fileTag, defer_writes, stor
     writer = ThreadPoolExecutor(max_workers=nwriters)
     try:
         for k, (fi, lo, hi) in enumerate(my_parts):
-            text, arrays = mode.part_out(sess, pids[k])
+            text, arrays = mode.part_out(sess, pids[k]) if text_writer == "host" else mode.part_out(sess, pids[k], locs[k])
             whole = lo == 0 and hi == rows[fi]
             name = "{}_{}_{}.txt.gz".format(mode.kind, fileTag, fileStem(files[fi])) if whole else _part_name(mode.kind, fileTag, fi, lo)
+            if isinstance(text, _DeviceText) and text.blob is not None:
+                jobs.append(writer.submit(write_bgzf, outputDir / name, [text.blob], whole))
+                payloads.append(arrays + [np.asarray(locs[k].blob), np.asarray(locs[k].offsets)])
+                continue
+            if isinstance(text, _DeviceText):
+                print("WARNING: [--writer gpu] {} holds a value the device does not format (not finite, or 2^31 and above): this file is "
+                      "written by the host writer".format(name), flush=True)
+                text = text.array
             jobs.append(writer.submit(writeScores, text, outputDir / name, locs[k], None, wthreads))
             payloads.append(arrays + [np.asarray(locs[k].blob), np.asarray(locs[k].offsets)])
+        if text_writer == "gpu":
+            sess.release_text()
         tm.lap("scores (kernels + download)")
     except BaseException:
         writer.shutdown(wait=True)
@@ -827,8 +876,10 @@ def _run_session(mode, sess, d, tm, plan, outputDir, fileTag, defer_writes, stor
             stem = fileStem(f)
             final = "{}_{}_{}.txt.gz".format(mode.kind, fileTag, stem)
             owners = sorted((lo, hi) for parts in plans for (pf, lo, hi) in parts if pf == fi)
-            _assemble_text(outputDir, mode.kind, final, fileTag, fi, owners, rows[fi])
-            if not owners:                             # an empty input file still gets its (empty) output
+            _assemble_text(outputDir, mode.kind, final, fileTag, fi, owners, rows[fi], text_writer)
+            if not owners and text_writer == "gpu":
+                write_bgzf(outputDir / final, [])
+            elif not owners:                           # an empty input file still gets its (empty) output
                 writeScores(np.zeros((0, mode.S), dtype=np.float32), outputDir / final,
                             _io.Locations(np.zeros(0, dtype=np.uint8), np.zeros(1, dtype=np.int64)))
             parts = [got[(fi, lo)] for lo, _ in owners]
@@ -940,7 +991,7 @@ class _ResidentStore:
 
 def run_groupings(files, groupings, numStates, saliency, outputDir, fileTag, quiescentState=None, groupSize=-1, nullSeed=None,
                   verbose=False, backend=None, device=None, keep_temps=True, defer_writes=False, nullDraws=1, checkStates=False,
-                  resident=None, flat=False):
+                  resident=None, flat=False, writer="host"):
     """Many groupings of the biosample columns of ONE set of files in one run: every file is parsed and uploaded once, its matrix
     stays on the device (_ResidentStore: unless the admission rule refuses it), and every grouping runs STEP 1-3 from the resident
     matrices with a session of its own.  groupings: [(name, cols)] -- each what run_single_group(columns=cols) computes -- or
@@ -958,7 +1009,9 @@ def run_groupings(files, groupings, numStates, saliency, outputDir, fileTag, qui
     seeded with them: no reader starts, nothing is parsed or uploaded, every grouping's info says uploads == parsed_files == 0, and
     checkStates censuses them where they are.  They are read, never written.
     flat (one grouping): its outputs go to outputDir itself -- a plain run, --columns or --columns-a/-b over resident matrices is
-    a one-grouping run of this function; a single-mode grouping whose columns are None is the whole matrix."""
+    a one-grouping run of this function; a single-mode grouping whose columns are None is the whole matrix.
+    writer ("host" or "gpu", here and in the run_* functions below): where the score text of every part is formatted and compressed
+    (write_bgzf; the command line's --writer)."""
     files = [Path(f) for f in files]
     groupings = [tuple(g) for g in groupings]
     if not groupings:
@@ -987,7 +1040,7 @@ def run_groupings(files, groupings, numStates, saliency, outputDir, fileTag, qui
             else:
                 mode = _Single(files, numStates, saliency, keep_temps, g[1])
             mode.check_states = bool(checkStates) and k == 0
-            q, results = _run_groups(mode, out, fileTag, backend, defer_writes, store)
+            q, results = _run_groups(mode, out, fileTag, backend, defer_writes, store, writer)
             if k == 0 and len(groupings) > 1:
                 # what did not fit is said once, by rank 0, for all ranks (a collective: every rank is here after its first grouping)
                 kept, refused = (int(v) for v in d.all_reduce_counts(np.array([len(store.kept), len(store.refused)], dtype=np.int64)))
@@ -1003,7 +1056,7 @@ def run_groupings(files, groupings, numStates, saliency, outputDir, fileTag, qui
 
 
 def run_single_group(files, numStates, saliency, outputDir, fileTag, verbose=False, backend=None, device=None,
-                     keep_temp_scores=True, defer_writes=False, columns=None, checkStates=False):
+                     keep_temp_scores=True, defer_writes=False, columns=None, checkStates=False, writer="host"):
     """STEP 1-3 for a single group over `files` (one per chromosome).  Returns (exp_freq float32, results) where results
     (rank 0 only, else None) maps file stem -> (chrName, float32 scores [R, S], _io.Locations) for an in-process STEP 4.
     keep_temp_scores writes the reference's temp_scores_{tag}_{stem}.npz (scores.py:166-169) for a STEP 4 run
@@ -1011,11 +1064,12 @@ def run_single_group(files, numStates, saliency, outputDir, fileTag, verbose=Fal
     biosample columns): the group is these columns of the files; the outputs are those of files cut to them beforehand."""
     mode = _Single([Path(f) for f in files], numStates, saliency, keep_temp_scores, columns)
     mode.check_states = bool(checkStates)
-    return _run_groups(mode, outputDir, fileTag, backend, defer_writes)
+    return _run_groups(mode, outputDir, fileTag, backend, defer_writes, writer=writer)
 
 
 def run_paired_groups(files1, files2, numStates, saliency, outputDir, fileTag, quiescentState, groupSize, nullSeed,
-                      verbose=False, backend=None, device=None, keep_temps=True, defer_writes=False, nullDraws=1, checkStates=False):
+                      verbose=False, backend=None, device=None, keep_temps=True, defer_writes=False, nullDraws=1, checkStates=False,
+                      writer="host"):
     """STEP 1-3 of paired mode (reference run.py:205-221,258-279 + scores.py:172-256) over the bin-range partition.
     Background counts are taken over the column concatenation [A|B] (helpers.py:173) -- from the two groups' own
     histograms, each group is uploaded once -- all-reduced once; each rank then scores A, B and the two shuffled null
@@ -1030,15 +1084,16 @@ def run_paired_groups(files1, files2, numStates, saliency, outputDir, fileTag, q
     mode = _Paired([Path(f) for f in files1], [Path(f) for f in files2], numStates, saliency, quiescentState, groupSize, nullSeed,
                    keep_temps, nullDraws)
     mode.check_states = bool(checkStates)
-    return _run_groups(mode, outputDir, fileTag, backend, defer_writes)
+    return _run_groups(mode, outputDir, fileTag, backend, defer_writes, writer=writer)
 
 
 def run_paired_columns(files, colsA, colsB, numStates, saliency, outputDir, fileTag, quiescentState, groupSize, nullSeed,
-                       verbose=False, backend=None, device=None, keep_temps=True, defer_writes=False, nullDraws=1, checkStates=False):
+                       verbose=False, backend=None, device=None, keep_temps=True, defer_writes=False, nullDraws=1, checkStates=False,
+                      writer="host"):
     """run_paired_groups for two groups that are column groups (0-based indices) of ONE set of files: every file is parsed and
     uploaded once and feeds both groups.  The partition, the hand-over between ranks and the all-reduce are run_paired_groups':
     they move histograms and row ranges.  Outputs are those of run_paired_groups on files cut to the groups beforehand."""
     mode = _PairedColumns([Path(f) for f in files], colsA, colsB, numStates, saliency, quiescentState, groupSize, nullSeed, keep_temps,
                           nullDraws)
     mode.check_states = bool(checkStates)
-    return _run_groups(mode, outputDir, fileTag, backend, defer_writes)
+    return _run_groups(mode, outputDir, fileTag, backend, defer_writes, writer=writer)

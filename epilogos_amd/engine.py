@@ -613,6 +613,106 @@ def bh_adjust(p, ws=None):
     return adj, flags
 
 
+# ---- the device text writer (csrc/epg_textout.h): epilogos --writer gpu
+BGZF_EOF = bytes([0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0])
+_text_bufs = {}                     # (device, name) -> uint8 tensor: ONE reusable set per device, grown when a part needs more
+
+
+def _text_buf(device, name, nbytes):
+    key = (str(device), name)
+    t = _text_bufs.get(key)
+    if t is None or t.numel() < nbytes:
+        _text_bufs.pop(key, None)
+        t = None                                             # (the smaller buffer goes before the larger one is asked for)
+        t = _text_bufs[key] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
+    return t
+
+
+def release_text_buffers():
+    """Give the text writer's reusable buffers back (a session does when it closes)."""
+    _text_bufs.clear()
+
+
+def _check_scores_2d(scores):
+    if scores.dtype != torch.float32 or scores.dim() != 2 or not scores.is_cuda or scores.shape[1] < 1:
+        raise ValueError("scores must be a float32 [R, S] CUDA tensor")
+    if scores.shape[0] and ((scores.shape[0] > 1 and scores.stride(0) < scores.shape[1]) or (scores.shape[1] > 1 and scores.stride(1) != 1)):
+        raise ValueError("scores must have unit column stride and a row stride of at least S")
+    return int(scores.shape[0]), int(scores.shape[1]), int(scores.stride(0)) if scores.shape[0] > 1 else int(scores.shape[1])
+
+
+def format_scores(scores, loc, loc_off, text=None, ws=None):
+    """The text epgio_write_scores formats for float32 scores [R, S] (any row stride) and the rows' locations (loc uint8 blob, loc_off
+    int64 [R + 1], both on the device), byte for byte (epgw_format_scores).  -> (text uint8, row_off int64 [R + 1], flags int32 [1]):
+    the text is text[:row_off[R]]; nothing may be used when flags[0] != 0 (a value that is not finite or not below 2^31 in
+    magnitude).  text / ws: buffers to use (None: allocated at their bounds).  Current stream, no synchronisation."""
+    R, S, ld = _check_scores_2d(scores)
+    if loc.dtype != torch.uint8 or loc_off.dtype != torch.int64 or loc_off.numel() != R + 1 or not loc.is_contiguous() or not loc_off.is_contiguous():
+        raise ValueError("loc must be a contiguous uint8 blob and loc_off contiguous int64 [R + 1]")
+    dev = scores.device
+    if text is None:
+        text = torch.empty(max(int(_abi.call("epgw_text_bytes_max", R, S, loc.numel())), 256), dtype=torch.uint8, device=dev)
+    if ws is None:
+        ws = torch.empty(max(int(_abi.call("epgw_format_ws_bytes", R)), 256), dtype=torch.uint8, device=dev)
+    row_off = torch.empty(R + 1, dtype=torch.int64, device=dev)
+    flags = torch.empty(1, dtype=torch.int32, device=dev)
+    _abi.call("epgw_format_scores", _ptr(scores) if R else None, R, S, ld, _ptr(loc) if R else None, _ptr(loc_off) if R else None, _ptr(text),
+              text.numel(), _ptr(row_off), _ptr(flags), _ptr(ws), ws.numel(), _stream())
+    return text, row_off, flags
+
+
+def bgzf_compress(text, n, row_off=None, eof=True, out=None, ws=None):
+    """text[:n] (uint8, device) as BGZF (epgw_bgzf_compress): blocks of at most 65 280 text bytes, each its own gzip member, the
+    28-byte end-of-file block behind them when `eof`.  row_off (int64 [R + 1], format_scores') lets the compressor match rows against
+    the row above; without it only literals are coded.  -> (out uint8, n_out int64 [1], flags int32 [1]): the stream is
+    out[:n_out].  Current stream, no synchronisation."""
+    n = int(n)
+    if text.dtype != torch.uint8 or not text.is_cuda or not text.is_contiguous() or text.numel() < n:
+        raise ValueError("text must be a contiguous uint8 CUDA tensor of at least n bytes")
+    R = 0 if row_off is None else row_off.numel() - 1
+    if row_off is not None and (row_off.dtype != torch.int64 or not row_off.is_contiguous()):
+        raise ValueError("row_off must be contiguous int64")
+    dev = text.device
+    if out is None:
+        out = torch.empty(max(int(_abi.call("epgw_bgzf_bytes_max", n, int(bool(eof)))), 256), dtype=torch.uint8, device=dev)
+    if ws is None:
+        ws = torch.empty(max(int(_abi.call("epgw_bgzf_ws_bytes", n)), 256), dtype=torch.uint8, device=dev)
+    n_out = torch.empty(1, dtype=torch.int64, device=dev)
+    flags = torch.empty(1, dtype=torch.int32, device=dev)
+    _abi.call("epgw_bgzf_compress", _ptr(text), n, _ptr(row_off) if R else None, R, int(bool(eof)), _ptr(out), out.numel(), _ptr(n_out),
+              _ptr(flags), _ptr(ws), ws.numel(), _stream())
+    return out, n_out, flags
+
+
+def scores_text_bgzf(locations, scores_device, eof=False):
+    """A part's score file on the device: the text of format_scores for `locations` (a _io.Locations, uploaded here) and the float32
+    [R, S] scores where they sit, compressed by bgzf_compress -> (uint8 device tensor, n_bytes): the file's bytes are the first
+    n_bytes (without the end-of-file block unless `eof`: driver.finish_bgzf appends the one a finished file carries).  None when a
+    flag is set -- a value the device does not format -- and nothing may be used: the caller writes that file on the host.
+    Synchronises twice: the text's size comes back between the two kernels' calls (the synchronisation csrc/epg_textout.h
+    documents), the stream's size after them.  The buffers are one reusable set per device (release_text_buffers)."""
+    R, S, _ld = _check_scores_2d(scores_device)
+    if len(locations) != R:
+        raise ValueError("locations and scores disagree on the number of rows")
+    dev = scores_device.device
+    blob = np.ascontiguousarray(locations.blob, dtype=np.uint8)
+    off = np.ascontiguousarray(locations.offsets, dtype=np.int64)
+    loc = torch.from_numpy(blob).to(dev) if blob.size else torch.zeros(1, dtype=torch.uint8, device=dev)
+    loc_off = torch.from_numpy(off).to(dev)
+    text = _text_buf(dev, "text", _abi.call("epgw_text_bytes_max", R, S, int(off[-1] - off[0]) if R else 0))
+    ws = _text_buf(dev, "ws", max(_abi.call("epgw_format_ws_bytes", R), _abi.call("epgw_bgzf_ws_bytes", text.numel())))
+    text, row_off, flags = format_scores(scores_device, loc, loc_off, text=text, ws=ws)
+    n, flag = (int(v) for v in torch.stack([row_off[R], flags[0].to(torch.int64)]).cpu())
+    if flag:
+        return None
+    out = _text_buf(dev, "out", _abi.call("epgw_bgzf_bytes_max", n, int(bool(eof))))
+    out, n_out, flags = bgzf_compress(text, n, row_off, eof=eof, out=out, ws=ws)
+    n_bytes, flag = (int(v) for v in torch.stack([n_out[0], flags[0].to(torch.int64)]).cpu())
+    if flag:
+        raise EpilogosHipError(-3, "the BGZF stream did not fit its own bound")
+    return out, n_bytes
+
+
 def select_columns(X, cols):
     """The columns `cols` (0-based int64) of a state matrix as a matrix of its own: int8 [R, padded_width(len(cols))], padding
     bytes 0xFF.  What the grouped count pass does not serve (S3 needs the states themselves; models of 32 .. 127 states) runs

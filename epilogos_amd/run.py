@@ -238,6 +238,10 @@ def _init_device_and_group(world, under_launcher):
               help="Paired mode with -n: where the p-values of the bins and their Benjamini-Hochberg adjustment are computed.  host: scipy "
                    "and numpy.  gpu: on the device (with [--null-draws] greater than 1 the adjustment only); the adjusted values are the "
                    "host's bit for bit, the p-values agree to about 1e-13")
+@click.option("--writer", "writer", type=click.Choice(["host", "gpu"]), default="host", show_default=True,
+              help="Where scores_*.txt.gz (single mode) and pairwiseDelta_*.txt.gz (paired mode) are formatted and compressed.  host: the "
+                   "native writer threads (EPILOGOS_GZIP_LEVEL and EPILOGOS_BGZF are its settings).  gpu: on the device, always as BGZF; "
+                   "only compressed bytes come back, and paired mode downloads no deltas.  The decompressed bytes are the same")
 @click.option("--gpus", "gpus", type=int, default=1, show_default=True,
               help="GPUs of this node to split the genome over (0 = all visible); replaces the SLURM fan-out of the reference")
 @click.option("--cache-dir", "cacheDir", type=str, default=None,
@@ -270,7 +274,7 @@ def _init_device_and_group(world, under_launcher):
 def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2, outputDirectory, stateInfo, saliency,
          numProcesses, exitBool, diagnosticBool, numTrials, samplingSize, quiescentState, groupSize, version, partition,
          pvalBool, roiWidth, fileTag, expFreqMem, expCombMem, scoreMem, roiMem, nullSeed, nullDraws, gpus, cacheDir, columns, columnsA, columnsB, checkStates,
-         groupingsFile, chromhmm, metadata, chromsizes, segments, binWidth, stateNames, keepMatrices, fit="host", pvals="host"):
+         groupingsFile, chromhmm, metadata, chromsizes, segments, binWidth, stateNames, keepMatrices, fit="host", pvals="host", writer="host"):
     """Information-theoretic navigation of multi-tissue functional genomic annotations -- MI355X scoring engine."""
     if version:
         print("Version:", __version__)
@@ -477,6 +481,10 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
         # nothing for --pvals host, as above
         return dict(pvals="gpu") if pvals == "gpu" else {}
 
+    def writerOptions():
+        # nothing for --writer host, as above: the drivers are called exactly as before
+        return dict(writer="gpu") if writer == "gpu" else {}
+
     def step4_paired(results, outDir):
         if pvalBool and max(numProcesses, 1) > 1 and nullDraws == 1 and fit != "gpu":
             driver.finish_writes()                               # -n -c K forks a pool for the fits: not with writer threads running
@@ -520,7 +528,8 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
             say("\nSTEP 1-3: background counts over [A|B] -> all-reduce -> scores, null groups, deltas (%d GPU(s))" % world)
         runs = driver.run_groupings(files, groupings, numStates, saliency, outputDirPath, fileTag, quiescentState, groupSize, nullSeed,
                                     verbose=False, device=device, keep_temps=False, defer_writes=True, nullDraws=nullDraws,
-                                    checkStates=checkStates, **({} if resident is None else {"resident": resident, "flat": flat}))
+                                    checkStates=checkStates, **({} if resident is None else {"resident": resident, "flat": flat}),
+                                    **writerOptions())
         resident = None                                          # (the store's from here on: gone with the run)
         try:
             for k, g in enumerate(groupings):
@@ -537,7 +546,7 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
         say("\nSTEP 1-3: background counts -> all-reduce -> scores (bin-range partition over %d GPU(s))" % world)
         try:
             _, results = run_single_group(files, numStates, saliency, outputDirPath, fileTag, verbose=False, device=device,
-                                          keep_temp_scores=False, defer_writes=True, columns=cols, checkStates=checkStates)
+                                          keep_temp_scores=False, defer_writes=True, columns=cols, checkStates=checkStates, **writerOptions())
         finally:
             driver.abort_early_readers()                         # (nothing to do once the stage driver has taken them over)
         step4_single(results, outputDirPath)
@@ -548,11 +557,11 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
             if pairedColumns:
                 _, results = run_paired_columns(files, colsA, colsB, numStates, saliency, outputDirPath, fileTag, quiescentState,
                                                 groupSize, nullSeed, verbose=False, device=device, keep_temps=False, defer_writes=True,
-                                                nullDraws=nullDraws, checkStates=checkStates)
+                                                nullDraws=nullDraws, checkStates=checkStates, **writerOptions())
             else:
                 _, results = run_paired_groups(files, files2, numStates, saliency, outputDirPath, fileTag, quiescentState, groupSize,
                                                nullSeed, verbose=False, device=device, keep_temps=False, defer_writes=True,
-                                               nullDraws=nullDraws, checkStates=checkStates)
+                                               nullDraws=nullDraws, checkStates=checkStates, **writerOptions())
         finally:
             driver.abort_early_readers()
         step4_paired(results, outputDirPath)
