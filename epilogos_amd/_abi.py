@@ -118,7 +118,8 @@ HEADER, PROTOTYPES = HEADERS["core"]
 # declared under csrc/ and outside the registry above, whose ten headers and their names the binding tests pin.  csrc/epg_pvals.h
 # says what promotes a header from here to HEADERS.  The device text writer's table ("textout", csrc/epg_textout.h, prefix epgw_) is
 # package-internal in the same way and bound through WRITER (build.WRITER_HEADERS): INTERNAL stays the p-value stage's alone, as
-# tests/test_pvals_host.py pins it.
+# tests/test_pvals_host.py pins it.  The device BGZF reader's table ("bgzf_inflate", csrc/epg_bgzf_inflate.h, prefix epgz_) is bound
+# through READER (build.READER_HEADERS) for the same reason: tests/test_writer_host.py pins WRITER to the text writer alone.
 _INTERNAL_TABLES = {
     "pvals": {                                            # p-values and Benjamini-Hochberg of paired mode with -n
         "epgf_gennorm_pvals": (C.c_int, [_p, _i64, _p, _p, _p, _p]),
@@ -133,10 +134,17 @@ _INTERNAL_TABLES = {
         "epgw_bgzf_ws_bytes": (_i64, [_i64]),
         "epgw_bgzf_compress": (C.c_int, [_p, _i64, _p, _i64, _i32, _p, _i64, _p, _p, _p, _i64, _p]),
     },
+    "bgzf_inflate": {                                     # the device BGZF reader: members inflated, the text's newline index
+        "epgz_inflate_lds_bytes": (_i64, []),
+        "epgz_bgzf_inflate": (C.c_int, [_p, _i64, _p, _i64, _p, _i64, _p, _p, _p]),
+        "epgz_newline_segments": (_i64, [_i64, _i64]),
+        "epgz_newline_index": (C.c_int, [_p, _i64, _i64, _p, _p, _p]),
+    },
 }
-assert list(_INTERNAL_TABLES) == [*_build.INTERNAL_HEADERS, *_build.WRITER_HEADERS]
+assert list(_INTERNAL_TABLES) == [*_build.INTERNAL_HEADERS, *_build.WRITER_HEADERS, *_build.READER_HEADERS]
 INTERNAL = {which: Header(_build.CSRC / name, _INTERNAL_TABLES[which]) for which, name in _build.INTERNAL_HEADERS.items()}
 WRITER = {which: Header(_build.CSRC / name, _INTERNAL_TABLES[which]) for which, name in _build.WRITER_HEADERS.items()}
+READER = {which: Header(_build.CSRC / name, _INTERNAL_TABLES[which]) for which, name in _build.READER_HEADERS.items()}
 
 _lib = None
 
@@ -184,7 +192,7 @@ def load():
         raise EpilogosHipError(-3, "%s is missing: build it with `python -m epilogos_amd.build` "
                                    "(there is no CPU fallback)" % path)
     lib = C.CDLL(str(path))
-    for header in [*HEADERS.values(), *INTERNAL.values(), *WRITER.values()]:
+    for header in [*HEADERS.values(), *INTERNAL.values(), *WRITER.values(), *READER.values()]:
         for name, (res, args) in header.prototypes.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
             fn.restype = res

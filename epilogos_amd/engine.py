@@ -713,6 +713,42 @@ def scores_text_bgzf(locations, scores_device, eof=False):
     return out, n_bytes
 
 
+# ---- the device BGZF reader (csrc/epg_bgzf_inflate.h): simsearch --inflate gpu
+def bgzf_inflate(comp, table, out=None, status=None, flags=None):
+    """The members of a BGZF stream inflated on the device (epgz_bgzf_inflate): comp uint8 (device) holds the compressed bytes, table
+    int64 [M, 5] (device; bgzfIndex.members' rows: payload offset in comp, payload bytes, text offset in out, ISIZE, CRC-32) says
+    where every member lies and goes.  -> (out uint8, status int32 [M], flags int32 [1]): status[m] is 0 or the reason member m was
+    given up (then its bytes of out are zeros), flags[0] the number of members with a reason.  out: the buffer to fill (None: one
+    of max(text offset + ISIZE) bytes, which costs a synchronisation).  Current stream, no synchronisation otherwise."""
+    if comp.dtype != torch.uint8 or not comp.is_cuda or not comp.is_contiguous():
+        raise ValueError("comp must be a contiguous uint8 CUDA tensor")
+    if table.dtype != torch.int64 or not table.is_cuda or not table.is_contiguous() or table.dim() != 2 or table.shape[1] != 5:
+        raise ValueError("table must be a contiguous int64 [M, 5] CUDA tensor")
+    M, dev = int(table.shape[0]), comp.device
+    if out is None:
+        out = torch.empty(max(int((table[:, 2] + table[:, 3]).max()) if M else 0, 16), dtype=torch.uint8, device=dev)
+    if status is None:
+        status = torch.empty(max(M, 1), dtype=torch.int32, device=dev)[:M]
+    if flags is None:
+        flags = torch.empty(1, dtype=torch.int32, device=dev)
+    _abi.call("epgz_bgzf_inflate", _ptr(comp) if comp.numel() else None, comp.numel(), _ptr(table) if M else None, M, _ptr(out), out.numel(),
+              _ptr(status) if M else None, _ptr(flags), _stream())
+    return out, status, flags
+
+
+def newline_index(text, seg_bytes, n=None):
+    """Per segment of seg_bytes bytes (a multiple of 16) of text[:n] (uint8, device, 16-byte aligned): the number of newlines in it and
+    the offset of the last one, -1 when there is none (epgz_newline_index) -> (count int64 [segments], last int64 [segments]).
+    Current stream, no synchronisation."""
+    n = text.numel() if n is None else int(n)
+    if text.dtype != torch.uint8 or not text.is_cuda or not text.is_contiguous() or text.numel() < n:
+        raise ValueError("text must be a contiguous uint8 CUDA tensor of at least n bytes")
+    nseg = int(_abi.call("epgz_newline_segments", n, int(seg_bytes)))
+    both = torch.empty((2, nseg), dtype=torch.int64, device=text.device)
+    _abi.call("epgz_newline_index", _ptr(text) if n else None, n, int(seg_bytes), _ptr(both[0]) if n else None, _ptr(both[1]) if n else None, _stream())
+    return both[0], both[1]
+
+
 def select_columns(X, cols):
     """The columns `cols` (0-based int64) of a state matrix as a matrix of its own: int8 [R, padded_width(len(cols))], padding
     bytes 0xFF.  What the grouped count pass does not serve (S3 needs the states themselves; models of 32 .. 127 states) runs

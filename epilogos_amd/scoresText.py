@@ -6,7 +6,12 @@ on the current stream: chunk k + 1 is staged and uploaded while chunk k parses. 
 the rows of a chunk are counted on the host (its newlines), so every chunk knows its row offset in the final tensors, and the
 status word is shared by all chunks.  The parser is strict: a file that is not of its grammar raises NotStrict with the first
 offending row and the caller reads it with pandas instead (similaritySearch_query.readGrid), as helpers.readTable does for
-state matrices.  Python does no per-row work: chromosome names are read from the text at the rows where they change."""
+state matrices.  Python does no per-row work: chromosome names are read from the text at the rows where they change.
+
+read_scores_device(path, inflate="gpu") (`simsearch --inflate gpu`) inflates a BGZF file on the device instead
+(csrc/epg_bgzf_inflate.h): bgzfIndex.members gives the member table, the COMPRESSED bytes are uploaded through the two page-locked
+buffers in groups of whole members and inflated into one device text buffer, the newline index of the text (engine.newline_index)
+lets the host cut the chunks and count their rows without the text, and the parser runs on slices of the device text."""
 import ctypes as C
 
 import numpy as np
@@ -82,14 +87,204 @@ def _name_at(a, pos):
         step *= 8
 
 
-def read_scores_device(path, chunk_bytes=CHUNK_BYTES, timings=None):
+class _DeviceText:
+    """The device text as _name_at reads it: a slice is a small download."""
+
+    def __init__(self, text, n):
+        self.text, self.n = text, n
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, s):
+        return self.text[s.start:min(s.stop, self.n)].cpu().numpy()
+
+
+def cut_chunks_indexed(n, chunk_bytes, seg_bytes, count, last):
+    """cut_chunks without the text, from its newline index (engine.newline_index: per segment of seg_bytes bytes the number of
+    newlines and the offset of the last one, -1 for none) -> ([(first byte, end)], rows of every chunk).  The rule is cut_chunks':
+    a chunk ends behind a newline within chunk_bytes of its start -- the last one of the whole segments that end there, so up to a
+    segment earlier than cut_chunks would --, a row longer than that runs on to a newline (the last one of the first segment that
+    has one), the text's end closes the last chunk and counts as a row when no newline stands there."""
+    n, chunk_bytes, seg_bytes = int(n), max(1, int(chunk_bytes)), int(seg_bytes)
+    count, last = np.asarray(count, dtype=np.int64), np.asarray(last, dtype=np.int64)
+    newest = np.maximum.accumulate(last) if len(last) else last                # the last newline at or before each segment's end
+    before = np.concatenate(([0], np.cumsum(count))).astype(np.int64)
+    total = int(before[-1]) + (1 if n and (not len(newest) or int(newest[-1]) != n - 1) else 0)
+    chunks, rows, lo, done = [], [], 0, 0
+    while lo < n:
+        lim = lo + chunk_bytes
+        if lim >= n:
+            hi = n
+        else:
+            s = lim // seg_bytes - 1                                          # the last whole segment that ends at or before lim
+            e = int(newest[s]) if s >= 0 else -1
+            if e < lo:                                                         # a row longer than the chunk
+                s = int(np.searchsorted(newest, lo, side="left"))
+                e = int(newest[s]) if s < len(newest) else n - 1
+            hi = e + 1
+        r = total - done if hi == n else int(before[(hi - 1) // seg_bytes + 1]) - done
+        chunks.append((lo, hi))
+        rows.append(r)
+        lo, done = hi, done + r
+    return chunks, rows
+
+
+GROUP_BYTES = 32 << 20
+INFLATE_CHOICES = ("host", "gpu")
+
+
+def _read_scores_inflated(path, chunk_bytes, timings):
+    """read_scores_device's result with the file inflated on the device (csrc/epg_bgzf_inflate.h), None when the host has to do it:
+    the file is not BGZF all the way (plain gzip, text: nothing is said), or the device gave up a member (one warning line)."""
+    import mmap
+    import torch
+    from time import perf_counter
+    from . import bgzfIndex, engine
+    t_all = perf_counter()
+    got = bgzfIndex.members(path)
+    if got is None or got[1] == 0:
+        return None
+    table, total = got
+    M = len(table)
+    if timings is not None:
+        timings["index_s"] = perf_counter() - t_all
+    chunk_bytes = min(int(chunk_bytes), 0x7fff0000 // 2)
+    seg_bytes = max(16, min(4096, chunk_bytes // 4 // 16 * 16))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    ends = table[:, 0] + table[:, 1] + bgzfIndex.TRAILER                       # the file offset behind every member
+    groups, m0 = [], 0
+    while m0 < M:                                                              # whole members, about GROUP_BYTES of the file each
+        b0 = int(table[m0, 0]) - bgzfIndex.HEADER
+        m1 = max(m0 + 1, int(np.searchsorted(ends, b0 + GROUP_BYTES, side="right")))
+        groups.append((m0, m1, b0, int(ends[m1 - 1])))
+        m0 = m1
+    with open(path, "rb") as f, mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as mm:
+        a = np.frombuffer(mm, dtype=np.uint8)
+        try:
+            comp_bytes = len(a)
+            cap = max(b1 - b0 for _m0, _m1, b0, b1 in groups)
+            dcomp = torch.empty(comp_bytes, dtype=torch.uint8, device=dev)
+            dtable = torch.from_numpy(table).to(dev)
+            text = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+            mstatus = torch.empty(M, dtype=torch.int32, device=dev)
+            flags = torch.zeros(len(groups), dtype=torch.int32, device=dev)
+            pinned = [torch.empty(cap, dtype=torch.uint8).pin_memory() for _ in range(min(2, len(groups)))]
+            copied = [torch.cuda.Event() for _ in pinned]
+            main, copy = torch.cuda.current_stream(), torch.cuda.Stream()
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+            copy.wait_stream(main)
+            ev[0].record(main)
+            for k, (m0, m1, b0, b1) in enumerate(groups):
+                s, nb = k % 2, b1 - b0
+                if k >= 2:
+                    copied[s].synchronize()                      # the pinned buffer's last upload has left it
+                pinned[s].numpy()[:nb] = a[b0:b1]
+                with torch.cuda.stream(copy):
+                    dcomp[b0:b1].copy_(pinned[s][:nb], non_blocking=True)
+                    copied[s].record(copy)
+                main.wait_event(copied[s])
+                _abi.call("epgz_bgzf_inflate", engine._ptr(dcomp), comp_bytes, engine._ptr(dtable[m0:m1]), m1 - m0, engine._ptr(text), total,
+                          engine._ptr(mstatus[m0:m1]), engine._ptr(flags[k:k + 1]), engine._stream())
+            ev[1].record(main)
+            count, last = engine.newline_index(text, seg_bytes, total)
+            ev[2].record(main)
+            count, last, bad = count.cpu().numpy(), last.cpu().numpy(), int(flags.sum().cpu())      # the one synchronisation
+        finally:
+            del a
+    if timings is not None:
+        timings["inflate_s"] = perf_counter() - t_all
+        timings["upload_inflate_ms"] = ev[0].elapsed_time(ev[1])
+        timings["newline_index_ms"] = ev[1].elapsed_time(ev[2])
+    if bad:
+        st = mstatus.cpu().numpy()
+        k = int(np.flatnonzero(st)[0])
+        print("WARNING: [--inflate gpu] %s: member %d (%s); inflating on the host instead"
+              % (path, k, MEMBER_REASONS.get(int(st[k]), "reason %d" % int(st[k]))), flush=True)
+        return None
+    t0 = perf_counter()
+    has = np.flatnonzero(last >= 0)
+    head = text[:int(last[has[0]]) + 1 if len(has) else total].cpu().numpy()  # the first row (and what follows it in its segment)
+    F = first_row_fields(head)
+    if F < 4:
+        raise NotStrict(REASONS[1], 0, 1)
+    chunks, rows = cut_chunks_indexed(total, chunk_bytes, seg_bytes, count, last)
+    row0 = np.concatenate(([0], np.cumsum(rows))).astype(np.int64)
+    R, S = int(row0[-1]), F - 3
+    if timings is not None:
+        timings["count_s"] = perf_counter() - t0
+    x = torch.empty((R, S), dtype=torch.int32, device=dev)
+    start = torch.empty(R, dtype=torch.int64, device=dev)
+    end = torch.empty(R, dtype=torch.int64, device=dev)
+    chrom_at = torch.empty(R, dtype=torch.int32, device=dev)
+    status = torch.tensor([CLEAN, 0], dtype=torch.int64, device=dev)
+    wsb = _abi.call("epgt_scores_ws_bytes", max(hi - lo for lo, hi in chunks))
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev0.record(main)
+    for k, (lo, hi) in enumerate(chunks):                                      # slices of the device text: no second upload
+        _abi.call("epgt_scores_parse", engine._ptr(text[lo:hi]), hi - lo, F, int(rows[k]), int(row0[k]), engine._ptr(x), engine._ptr(start),
+                  engine._ptr(end), engine._ptr(chrom_at), engine._ptr(ws), wsb, engine._ptr(status), engine._stream())
+    ev1.record(main)
+    word, _found = status.cpu().tolist()
+    if timings is not None:
+        timings["upload_parse_ms"] = ev0.elapsed_time(ev1)
+    if word != CLEAN:
+        raise NotStrict(REASONS.get(word & 15, "reason %d" % (word & 15)), word >> 4, word & 15)
+    t0 = perf_counter()
+    runs = _runs_of(_DeviceText(text, total), chrom_at, chunks, row0, R)
+    start, end = start.cpu().numpy(), end.cpu().numpy()
+    if timings is not None:
+        timings["coords_s"] = perf_counter() - t0
+    return x, start, end, [tuple(r) for r in runs]
+
+
+# enum Reason of csrc/epg_bgzf_inflate_block.h
+MEMBER_REASONS = {1: "its table row is refused", 2: "block type 3", 3: "a stored block's LEN and NLEN disagree", 4: "an over-subscribed code",
+                  5: "an incomplete code", 6: "a repeat with no length before it", 7: "a run of code lengths past their number",
+                  8: "literal/length symbol 286 or 287", 9: "distance symbol 30 or 31", 10: "a distance before the member's first byte",
+                  11: "output beyond ISIZE", 12: "bits past the payload", 13: "CRC-32 mismatch", 14: "fewer bytes than ISIZE",
+                  15: "bits that are no code", 16: "a bad dynamic block header", 17: "the stream ends before the payload"}
+
+
+def _runs_of(a, chrom_at, chunks, row0, R):
+    """[[chromosome, row0, row1]] from the rows where the parser saw the name change: the names are read from the text `a` there."""
+    import torch
+    at = torch.nonzero(chrom_at >= 0).reshape(-1)
+    pos = chrom_at[at].cpu().numpy().astype(np.int64)
+    at = at.cpu().numpy()
+    pos += np.asarray([c[0] for c in chunks], dtype=np.int64)[np.searchsorted(row0, at, side="right") - 1]
+    runs = []
+    for r, p in zip(at.tolist(), pos.tolist()):                  # one turn per change of chromosome (and per chunk)
+        name = _name_at(a, p)
+        if runs and runs[-1][0] == name:                         # a chunk's first row carries on the chromosome before it
+            continue
+        if name.lower() in NOT_TEXT:
+            raise NotStrict("a chromosome name pandas does not keep as text (%s)" % name, r)
+        if runs:
+            runs[-1][2] = r
+        runs.append([name, r, R])
+    return runs
+
+
+def read_scores_device(path, chunk_bytes=CHUNK_BYTES, timings=None, inflate="host"):
     """-> (x int32 [R, S] device tensor, start int64 [R], end int64 [R] host arrays, runs [(chromosome, row0, row1)]); raises
     NotStrict.  `timings` (a dict) receives inflate_s (the file to text), count_s (chunk cutting and row counts), upload_parse_ms (HIP events
-    around all chunks) and coords_s."""
+    around all chunks) and coords_s.
+    inflate "gpu": a BGZF file is inflated on the device (_read_scores_inflated: the compressed bytes are uploaded, the text never
+    exists on the host); timings then also receives index_s, upload_inflate_ms and newline_index_ms, and inflate_s is the device
+    path's wall time up to its synchronisation.  Any other file, and a file of which the device gives up a member, is read as
+    with "host"."""
     import torch
     from time import perf_counter
     from . import engine
     engine.require_gpu()
+    if inflate not in INFLATE_CHOICES:
+        raise ValueError("inflate must be one of %s, not %r" % (", ".join(INFLATE_CHOICES), inflate))
+    if inflate == "gpu":
+        got = _read_scores_inflated(path, chunk_bytes, timings)
+        if got is not None:
+            return got
     chunk_bytes = min(int(chunk_bytes), 0x7fff0000 // 2)
     threads = _io.host_budget()
     t0 = perf_counter()

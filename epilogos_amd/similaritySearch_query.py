@@ -56,16 +56,16 @@ def windowFirstBin(table, chrom, start, end, windowBP, windowBins):
     return row0 + b
 
 
-def readGrid(scoresPath):
+def readGrid(scoresPath, inflate="host"):
     """(coords object [R, 3]: chromosome, start, end; genome int64 [R, S]: the scores x 1e5), host arrays with the values of
     mm.readScores(scoresPath)'s inputArr[:, :3] and third result.  With a GPU the file is parsed there as text; a file the strict
     parser refuses gets one warning line and is read by mm.readScores, so that it behaves as it always did (to_grid's ValueError
-    for values off the grid included)."""
+    for values off the grid included).  inflate "gpu" (--inflate gpu): a BGZF file is inflated on the device too."""
     import torch
     from . import scoresText
     if torch.cuda.is_available() and _abi.lib_path().exists():
         try:
-            x, start, end, runs = scoresText.read_scores_device(scoresPath)
+            x, start, end, runs = scoresText.read_scores_device(scoresPath, **({"inflate": inflate} if inflate != "host" else {}))
         except scoresText.NotStrict as e:
             print("            Warning: %s is not a plain \"%%.5f\" scores file (row %d: %s); reading it with pandas"
                   % (scoresPath, e.row, e.reason), flush=True)
@@ -127,14 +127,14 @@ def recsText(indices, reducedCoords, nblk):
     return "".join("{}\t{}\t{}\n".format(reducedCoords[i, 0], reducedCoords[i, 1], reducedCoords[i + nblk - 1, 2]) for i in keep)
 
 
-def liveQuery(query, scoresPath, outputDir, windowBP, nDesiredMatches):
+def liveQuery(query, scoresPath, outputDir, windowBP, nDesiredMatches, inflate="host"):
     """One similarity_search_region_{chr}_{start}_{end}_recs.bed per query region, named by the window that was searched."""
     from .similaritySearch_run import generateRegionArr, windowParameters
     print("\n\n\n        Reading in data...", flush=True); readTime = time()
     queryArr = generateRegionArr(query)
     windowBP, windowBins, blockSize = windowParameters(scoresPath, windowBP)
     nblk = windowBins // blockSize
-    coords, genome = readGrid(scoresPath)
+    coords, genome = readGrid(scoresPath, **({"inflate": inflate} if inflate != "host" else {}))
     table = chromosomeTable(coords[:, 0], coords[:, 1], coords[:, 2])
     print("            Time:", format(time() - readTime, '.0f'), "seconds\n", flush=True)
     print("        Querying regions...", flush=True)

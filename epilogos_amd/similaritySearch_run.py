@@ -27,6 +27,7 @@ import pandas as pd
 from .helpers import splitGpusOption
 
 STEP1_CHOICES = ("host", "gpu")
+INFLATE_CHOICES = ("host", "gpu")
 
 BLOCK_SIZES_200 = {5000: 1, 10000: 2, 25000: 5, 50000: 10, 75000: 15, 100000: 20}
 BLOCK_SIZES_20 = {500: 1, 1000: 2, 2500: 5, 5000: 10, 7500: 15, 10000: 20}
@@ -73,13 +74,16 @@ def generateRegionArr(query):
                      + "or path to bed file containing query regions)")
 
 
-def buildSimSearch(scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatches, filterState, filterScore, gpus=1, step1="host"):
+def buildSimSearch(scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatches, filterState, filterScore, gpus=1, step1="host", inflate="host"):
     """STEP 1-3.  gpus > 1: STEP 2 as that many child processes, one per GPU (runChildren); nJobs (-j) is ignored either way.
     step1 "gpu": STEP 1 on the GPU (similaritySearch_step1), in this process with one GPU, as one child process (step1Job) with
-    more: this process then stays GPU-free."""
+    more: this process then stays GPU-free.  inflate "gpu" (with step1 "gpu" only): STEP 1 inflates a BGZF scores file on the device."""
     from . import similaritySearch_calc, similaritySearch_max_mean, similaritySearch_write
     if step1 not in STEP1_CHOICES:
         raise ValueError("step1 must be one of %s, not %r" % (", ".join(STEP1_CHOICES), step1))
+    if inflate not in INFLATE_CHOICES or (inflate == "gpu" and step1 != "gpu"):
+        raise ValueError("inflate must be one of %s (gpu only with step1 gpu), not %r" % (", ".join(INFLATE_CHOICES), inflate))
+    more = {"inflate": inflate} if inflate != "host" else {}                  # `host` adds nothing to any call
     print("\n\n\n        Building Similarity Search Results...", flush=True)
     windowBP, windowBins, blockSize = windowParameters(scoresPath, windowBP)
     if gpus > 1:
@@ -91,10 +95,10 @@ def buildSimSearch(scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatch
     if step1 == "host":
         similaritySearch_max_mean.main(outputDir, scoresPath, windowBins, blockSize, windowBP, filterState, filterScore)
     elif gpus > 1:
-        runChildren([step1Job(outputDir, scoresPath, windowBins, blockSize, windowBP, filterState, filterScore, nCores)], step="STEP 1")
+        runChildren([step1Job(outputDir, scoresPath, windowBins, blockSize, windowBP, filterState, filterScore, nCores, **more)], step="STEP 1")
     else:
         from . import similaritySearch_step1
-        similaritySearch_step1.main(outputDir, scoresPath, windowBins, blockSize, windowBP, filterState, filterScore)
+        similaritySearch_step1.main(outputDir, scoresPath, windowBins, blockSize, windowBP, filterState, filterScore, **more)
     print("\n        STEP 2: Similarity Search Calculation", flush=True)
     if gpus > 1:
         for stale in Path(outputDir).glob("simsearch_indices_*.npy"):     # an earlier build's: STEP 3 would merge them in
@@ -142,7 +146,7 @@ def childJobs(outputDir, windowBins, blockSize, nCores, nDesiredMatches, gpus):
     return jobs
 
 
-def step1Job(outputDir, scoresPath, windowBins, blockSize, windowBP, filterState, filterScore, nCores):
+def step1Job(outputDir, scoresPath, windowBins, blockSize, windowBP, filterState, filterScore, nCores, inflate="host"):
     """(argv, env) of the STEP 1 child of a `--gpus N --step1 gpu` build: `python -m epilogos_amd.similaritySearch_step1` on GPU
     LOCAL_RANK = 0, with the whole host thread budget (it runs alone, before STEP 2's children)."""
     from ._io import node_cores
@@ -154,6 +158,8 @@ def step1Job(outputDir, scoresPath, windowBins, blockSize, windowBP, filterState
     env["PYTHONPATH"] = root + (os.pathsep + env["PYTHONPATH"] if env.get("PYTHONPATH") else "")
     argv = [sys.executable, "-m", "epilogos_amd.similaritySearch_step1", str(Path(outputDir).resolve()), str(Path(scoresPath).resolve()),
             str(windowBins), str(blockSize), str(windowBP), str(filterState), str(filterScore)]
+    if inflate != "host":
+        argv += ["--inflate", inflate]
     return argv, env
 
 
@@ -285,6 +291,11 @@ def main(buildBool, scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatc
     step1 = (click.get_current_context().obj or {}).get("step1")      # cli()'s --step1: None when not given
     if step1 is not None and query != "":
         raise click.UsageError("--step1 applies to -b only: query mode builds no index")
+    inflate = (click.get_current_context().obj or {}).get("inflate")  # cli()'s --inflate: None when not given
+    if inflate is not None and query != "" and scoresPath is None:
+        raise click.UsageError("--inflate applies to -q with -s (and to -b --step1 gpu): -q -m reads no scores file")
+    if inflate is not None and buildBool and step1 != "gpu":
+        raise click.UsageError("--inflate applies to -b only with --step1 gpu: the host's STEP 1 reads the scores file with pandas")
     if query != "" and simSearchPath is None and scoresPath is None:
         raise click.UsageError("-q needs either -m simsearch.bed.gz (look the region up in a built index) or -s scores.txt.gz "
                                "(search the region live on the GPU)")
@@ -295,12 +306,14 @@ def main(buildBool, scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatc
         raise NotADirectoryError("Given path is not a directory: {}".format(str(outputDir)))
     if buildBool:
         buildSimSearch(scoresPath, outputDir, windowBP, nJobs, nCores, nDesiredMatches, filterState, filterScore,
-                       gpus=1 if gpus is None else gpus, step1="host" if step1 is None else step1)
+                       gpus=1 if gpus is None else gpus, step1="host" if step1 is None else step1,
+                       **({"inflate": inflate} if inflate not in (None, "host") else {}))
     elif simSearchPath is not None:
         querySimSearch(query, simSearchPath, outputDir)
     else:
         from . import similaritySearch_query
-        similaritySearch_query.liveQuery(query, scoresPath, outputDir, windowBP, nDesiredMatches)
+        similaritySearch_query.liveQuery(query, scoresPath, outputDir, windowBP, nDesiredMatches,
+                                         **({"inflate": inflate} if inflate not in (None, "host") else {}))
 
 
 def resolveGpus(value):
@@ -311,36 +324,49 @@ def resolveGpus(value):
     return run._visible_gpus() if n == 0 else n
 
 
-def splitStep1Option(argv):
-    """`--step1 V` / `--step1=V`, anywhere in an argument list -> (V as written, the last one given; None when there is none; ""
-    for a trailing `--step1`) and the list without them (splitGpusOption's rule)."""
+def splitOption(argv, name):
+    """`name V` / `name=V`, anywhere in an argument list -> (V as written, the last one given; None when there is none; "" for a
+    trailing `name`) and the list without them (splitGpusOption's rule)."""
     value, out, skip = None, [], False
     for a in argv:
         if skip:
             value, skip = a, False
-        elif a == "--step1":
+        elif a == name:
             value, skip = "", True
-        elif a.startswith("--step1="):
-            value = a[len("--step1="):]
+        elif a.startswith(name + "="):
+            value = a[len(name) + 1:]
         else:
             out.append(a)
     return value, out
 
 
+def splitStep1Option(argv):
+    """splitOption for `--step1`."""
+    return splitOption(argv, "--step1")
+
+
+def splitInflateOption(argv):
+    """splitOption for `--inflate`."""
+    return splitOption(argv, "--inflate")
+
+
 def cli(argv=None):
-    """`python -m epilogos_amd.similaritySearch_run`: main with `--gpus N` / `--gpus=N` and `--step1 {host,gpu}` taken out of the
-    arguments first (main's click options stay the reference's); the values reach main through click's ctx.obj."""
+    """`python -m epilogos_amd.similaritySearch_run`: main with `--gpus N` / `--gpus=N`, `--step1 {host,gpu}` and `--inflate {host,gpu}`
+    taken out of the arguments first (main's click options stay the reference's); the values reach main through click's ctx.obj."""
     argv = sys.argv[1:] if argv is None else list(argv)
     value, rest = splitGpusOption(argv)
     step1, rest = splitStep1Option(rest)
+    inflate, rest = splitInflateOption(rest)
     try:
         gpus = None if value is None else resolveGpus(value)
         if step1 is not None and step1 not in STEP1_CHOICES:
             raise click.UsageError("--step1 takes one of %s, not %r" % (", ".join(STEP1_CHOICES), step1))
+        if inflate is not None and inflate not in INFLATE_CHOICES:
+            raise click.UsageError("--inflate takes one of %s, not %r" % (", ".join(INFLATE_CHOICES), inflate))
     except click.UsageError as e:
         e.show()
         sys.exit(e.exit_code)
-    main.main(args=rest, prog_name="python -m epilogos_amd.similaritySearch_run", obj={"gpus": gpus, "step1": step1})
+    main.main(args=rest, prog_name="python -m epilogos_amd.similaritySearch_run", obj={"gpus": gpus, "step1": step1, "inflate": inflate})
 
 
 if __name__ == "__main__":

@@ -38,12 +38,12 @@ SLICE_BATCH = 256
 
 # ---- the device steps ----------------------------------------------------------------------------------------------------------
 
-def readDevice(scoresPath, timings=None):
+def readDevice(scoresPath, timings=None, inflate="host"):
     """-> (x int32 [G, S] device tensor, start int64 [G], end int64 [G] host arrays, runs [(chromosome, row0, row1)]); raises
-    scoresText.NotStrict."""
+    scoresText.NotStrict.  inflate "gpu" (--inflate gpu): a BGZF file is inflated on the device too."""
     from . import engine, scoresText
     engine.require_gpu()
-    return scoresText.read_scores_device(scoresPath, timings=timings)
+    return scoresText.read_scores_device(scoresPath, timings=timings, **({"inflate": inflate} if inflate != "host" else {}))
 
 
 def rowScores(x):
@@ -249,12 +249,12 @@ class _Writer(threading.Thread):
         return self.seconds
 
 
-def main(outputDir, scoresPath, windowBins, blockSize, windowBP, filterState, filterScore, timings=None):
+def main(outputDir, scoresPath, windowBins, blockSize, windowBP, filterState, filterScore, timings=None, inflate="host"):
     from . import scoresText
     outputDir = Path(outputDir)
     t = time()
     try:
-        x, start, end, runs = readDevice(scoresPath, timings)
+        x, start, end, runs = readDevice(scoresPath, timings, **({"inflate": inflate} if inflate != "host" else {}))
     except scoresText.NotStrict as e:
         print("            Warning: %s is not a plain \"%%.5f\" scores file (row %d: %s); reading it with pandas"
               % (scoresPath, e.row, e.reason), flush=True)
@@ -288,5 +288,6 @@ if __name__ == "__main__":
         if torch.cuda.is_available():            # (without one, require_gpu says so)
             local = int(os.environ["LOCAL_RANK"])
             torch.cuda.set_device(local % torch.cuda.device_count() if os.environ.get("EPILOGOS_DIST_BACKEND") else local)
+    extra = {"inflate": sys.argv[9]} if len(sys.argv) > 9 and sys.argv[8] == "--inflate" else {}      # (step1Job appends it for `gpu` alone)
     main(Path(sys.argv[1]), Path(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), int(sys.argv[5]), int(sys.argv[6]),
-         float(sys.argv[7]))
+         float(sys.argv[7]), **extra)
