@@ -146,6 +146,19 @@ INTERNAL = {which: Header(_build.CSRC / name, _INTERNAL_TABLES[which]) for which
 WRITER = {which: Header(_build.CSRC / name, _INTERNAL_TABLES[which]) for which, name in _build.WRITER_HEADERS.items()}
 READER = {which: Header(_build.CSRC / name, _INTERNAL_TABLES[which]) for which, name in _build.READER_HEADERS.items()}
 
+# the device metrics writer's table ("metrics_text", csrc/epg_metrics_text.h, prefix epgm_), bound through METRICS
+# (build.METRICS_HEADERS).  A table dictionary of its own: tests/test_inflate_host.py pins the keys of _INTERNAL_TABLES to the three
+# registries above
+_METRICS_TABLES = {
+    "metrics_text": {                                     # pairwiseMetrics rows formatted on the device
+        "epgm_text_bytes_max": (_i64, [_i64, _i64, _i64, _i32]),
+        "epgm_format_ws_bytes": (_i64, [_i64]),
+        "epgm_format_metrics": (C.c_int, [_p, _p, _i32, _i64, _p, _p, _p, _p, _p, _i32, _i64, _p, _p, _p, _p, _i64, _p, _i64, _p, _p, _p, _i64, _p]),
+    },
+}
+assert list(_METRICS_TABLES) == list(_build.METRICS_HEADERS)
+METRICS = {which: Header(_build.CSRC / name, _METRICS_TABLES[which]) for which, name in _build.METRICS_HEADERS.items()}
+
 _lib = None
 
 
@@ -155,12 +168,17 @@ def header_symbols(which="core"):
     return sorted(set(re.findall(r"\b(epg[tf]?_[a-z0-9_]+)\s*\(", txt)))
 
 
+def header_constant_of(header, name):
+    """The value of `#define name <integer>` of a Header of any registry."""
+    m = re.search(r"^#define\s+%s\s+(\d+)" % re.escape(name), header.path.read_text(), flags=re.M)
+    if m is None:
+        raise RuntimeError("%s not found in %s" % (name, header.path))
+    return int(m.group(1))
+
+
 def header_constant(which, name):
     """The value of `#define name <integer>` of the header `which` of HEADERS."""
-    m = re.search(r"^#define\s+%s\s+(\d+)" % re.escape(name), HEADERS[which].path.read_text(), flags=re.M)
-    if m is None:
-        raise RuntimeError("%s not found in %s" % (name, HEADERS[which].path))
-    return int(m.group(1))
+    return header_constant_of(HEADERS[which], name)
 
 
 def pick_header_constant(name):
@@ -192,7 +210,7 @@ def load():
         raise EpilogosHipError(-3, "%s is missing: build it with `python -m epilogos_amd.build` "
                                    "(there is no CPU fallback)" % path)
     lib = C.CDLL(str(path))
-    for header in [*HEADERS.values(), *INTERNAL.values(), *WRITER.values(), *READER.values()]:
+    for header in [*HEADERS.values(), *INTERNAL.values(), *WRITER.values(), *READER.values(), *METRICS.values()]:
         for name, (res, args) in header.prototypes.items():
             fn = getattr(lib, name)  # AttributeError if the symbol is missing: fail loudly
             fn.restype = res

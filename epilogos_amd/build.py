@@ -10,7 +10,7 @@ CSRC = PKG / "csrc"
 LIB_DIR = PKG / "_lib"
 LIB_PATH = LIB_DIR / "libepilogos_hip.so"
 SOURCES = ["epg_abi.hip", "epg_s1.hip", "epg_s2.hip", "epg_s3.hip", "epg_s3_transpose.hip", "epg_s3_gemm.hip", "epg_s3_lanes.hip", "epg_null.hip", "epg_wide.hip", "epg_simsearch.hip",
-           "epg_simsearch_prep.hip", "epg_scores_text.hip", "epg_groups.hip", "epg_null_exceed.hip", "epg_statebyline.hip", "epg_segments.hip", "epg_simsearch_pick.hip", "epg_census.hip", "epg_concordance.hip", "epg_gennorm.hip", "epg_pvals.hip", "epg_textout.hip", "epg_bgzf_inflate.hip"]
+           "epg_simsearch_prep.hip", "epg_scores_text.hip", "epg_groups.hip", "epg_null_exceed.hip", "epg_statebyline.hip", "epg_segments.hip", "epg_simsearch_pick.hip", "epg_census.hip", "epg_concordance.hip", "epg_gennorm.hip", "epg_pvals.hip", "epg_textout.hip", "epg_bgzf_inflate.hip", "epg_metrics_text.hip"]
 # the public headers under include/, each bound by the table of the same key in _abi.HEADERS
 PUBLIC_HEADERS = {"core": "epilogos_amd.h", "scores_text": "epilogos_scores_text.h", "groups": "epilogos_groups.h", "nulldraws": "epilogos_nulldraws.h",
                   "statebyline": "epilogos_statebyline.h", "segments": "epilogos_segments.h", "simsearch_pick": "epilogos_simsearch_pick.h",
@@ -24,8 +24,11 @@ WRITER_HEADERS = {"textout": "epg_textout.h"}
 # the device BGZF reader's entry points (epgz_): package-internal in the same way, bound by _abi.READER.  Again a registry of its own:
 # tests/test_writer_host.py pins WRITER_HEADERS to the text writer's header alone
 READER_HEADERS = {"bgzf_inflate": "epg_bgzf_inflate.h"}
-HEADERS = [CSRC / "epg_common.h", CSRC / "epg_count.h", CSRC / "epg_paircount.h", CSRC / "epg_parts.h", CSRC / "epg_pairdist.h", CSRC / "epg_text_scan.h", CSRC / "epg_fmt_f5.h", CSRC / "epg_bgzf_block.h", CSRC / "epg_bgzf_inflate_block.h",
-           *[ROOT / "include" / name for name in PUBLIC_HEADERS.values()], *[CSRC / name for name in INTERNAL_HEADERS.values()], *[CSRC / name for name in WRITER_HEADERS.values()], *[CSRC / name for name in READER_HEADERS.values()]]
+# the device metrics writer's entry points (epgm_): package-internal in the same way, bound by _abi.METRICS.  Once more a registry of
+# its own: tests/test_inflate_host.py pins READER_HEADERS to the reader's header alone, and the three registries above to their order
+METRICS_HEADERS = {"metrics_text": "epg_metrics_text.h"}
+HEADERS = [CSRC / "epg_common.h", CSRC / "epg_count.h", CSRC / "epg_paircount.h", CSRC / "epg_parts.h", CSRC / "epg_pairdist.h", CSRC / "epg_text_scan.h", CSRC / "epg_fmt_f5.h", CSRC / "epg_fmt_e5.h", CSRC / "epg_bgzf_block.h", CSRC / "epg_bgzf_inflate_block.h",
+           *[ROOT / "include" / name for name in PUBLIC_HEADERS.values()], *[CSRC / name for name in INTERNAL_HEADERS.values()], *[CSRC / name for name in WRITER_HEADERS.values()], *[CSRC / name for name in READER_HEADERS.values()], *[CSRC / name for name in METRICS_HEADERS.values()]]
 ARCH = "gfx950"
 
 

@@ -4,7 +4,7 @@
 //   * k_tw_lengths   a thread per row: the row's length from its location bytes and its values' digit counts (epg_fmt_f5.h: integer
 //                    arithmetic only), refused values and bad locations OR-ed into the flag word; the tile's sum by the workgroup
 //                    scan of epg_text_scan.h;
-//   * k_tw_tile_offsets  one workgroup: the exclusive scan of the tiles' sums, the text's size into row_off[R];
+//   * k_text_tile_offsets (epg_text_scan.h)  one workgroup: the exclusive scan of the tiles' sums, the text's size into row_off[R];
 //   * k_tw_write     a workgroup per TW_ROWS rows, a thread per row: the rows' offsets (the tile's offset + the workgroup scan of
 //                    their lengths) into row_off, then the text.  The rows' text is put together in LDS, a window of TW_WIN bytes
 //                    of the text at a time (a tile of 256 rows of an 18-state model is ~46 KB: two windows; a thread skips the
@@ -57,26 +57,6 @@ __global__ __launch_bounds__(TW_ROWS) void k_tw_lengths(const float* __restrict_
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
 }
 
-// one workgroup: the tiles' sums become, in place, the text offsets of the tiles' first rows; row_off[R] = the size of the text
-__global__ __launch_bounds__(1024) void k_tw_tile_offsets(u64* __restrict__ tile_sum, long ntiles, long R, long long* __restrict__ row_off) {
-    __shared__ u64 s_sum[1024];
-    const int tid = threadIdx.x;
-    const long chunk = (ntiles + 1023) / 1024;
-    const long lo = tid * chunk < ntiles ? tid * chunk : ntiles, hi = lo + chunk < ntiles ? lo + chunk : ntiles;
-    u64 sum = 0;
-    for (long b = lo; b < hi; ++b) sum += tile_sum[b];
-    s_sum[tid] = sum;
-    __syncthreads();
-    u64 run = 0;
-    for (int k = 0; k < tid; ++k) run += s_sum[k];
-    for (long b = lo; b < hi; ++b) {
-        const u64 own = tile_sum[b];
-        tile_sum[b] = run;
-        run += own;
-    }
-    if (tid == 1023) row_off[R] = (long long)run;
-}
-
 __global__ __launch_bounds__(TW_ROWS) void k_tw_write(const float* __restrict__ scores, long R, int S, long ld, const char* __restrict__ loc,
                                                       const long long* __restrict__ loc_off, const u32* __restrict__ lens, const u64* __restrict__ tile_off,
                                                       long long* __restrict__ row_off, char* __restrict__ text, long long text_cap, int* __restrict__ flags) {
@@ -91,7 +71,7 @@ __global__ __launch_bounds__(TW_ROWS) void k_tw_write(const float* __restrict__ 
     const long long T0 = (long long)tile_off[blockIdx.x], T1 = T0 + tile_len;
     const long long rs = T0 + before, re = rs + len;
     if (r < r1) row_off[r] = rs;
-    if (row_off[R] > text_cap) {                             // (written by k_tw_tile_offsets, before this kernel)
+    if (row_off[R] > text_cap) {                             // (written by k_text_tile_offsets, before this kernel)
         if (blockIdx.x == 0 && tid == 0) atomicOr(flags, 2);
         return;
     }
@@ -320,8 +300,8 @@ extern "C" int epgw_format_scores(const float* scores, int64_t R, int32_t S, int
         hipLaunchKernelGGL(k_tw_lengths, dim3((unsigned)L.ntiles), dim3(TW_ROWS), 0, st, scores, (long)R, (int)S, (long)ld, loff, lens, tiles, flags);
         EPG_LAUNCH_CHECK("k_tw_lengths");
     }
-    hipLaunchKernelGGL(k_tw_tile_offsets, dim3(1), dim3(1024), 0, st, tiles, (long)L.ntiles, (long)R, roff);
-    EPG_LAUNCH_CHECK("k_tw_tile_offsets");
+    hipLaunchKernelGGL(k_text_tile_offsets<1024>, dim3(1), dim3(1024), 0, st, tiles, (long)L.ntiles, (long)R, roff);
+    EPG_LAUNCH_CHECK("k_text_tile_offsets");
     if (L.ntiles) {
         hipLaunchKernelGGL(k_tw_write, dim3((unsigned)L.ntiles), dim3(TW_ROWS), 0, st, scores, (long)R, (int)S, (long)ld, loc, loff, (const u32*)lens,
                            (const u64*)tiles, roff, text, (long long)text_cap, flags);

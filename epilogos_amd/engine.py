@@ -713,6 +713,101 @@ def scores_text_bgzf(locations, scores_device, eof=False):
     return out, n_bytes
 
 
+# ---- the device metrics writer (csrc/epg_metrics_text.h): epilogos --metrics gpu
+METRICS_CHUNK_TEXT_BYTES = 256 << 20    # a chunk of rows is formatted into at most this much text (its bound, not its size): with the
+#                                         compressed stream's bound and the row arrays a chunk's buffers stay under 1 GiB
+
+
+def _name_table(names, device):
+    """A list of names as the blob and the int64 offsets the kernels read -> (blob uint8 device, off int64 device, bytes, longest)."""
+    from . import _io
+    blob, off = _io._string_table(names)                     # (the host writer's own tables; the blob ends in one spare byte)
+    return torch.from_numpy(blob).to(device), torch.from_numpy(off).to(device), int(off[-1]), int(np.diff(off).max()) if len(off) > 1 else 0
+
+
+def format_metrics(chrom, chrom_off, chrom_bytes, chrom_idx, start, end, names, names_off, names_bytes, maxdiff, dist, pvals=None, mh=None,
+                   text=None, ws=None, chrom_max=None, name_max=None):
+    """The rows epgio_write_metrics formats, byte for byte (epgm_format_metrics): chrom / names are the two name tables (uint8 blob of
+    chrom_bytes / names_bytes bytes and int64 offsets, on the device), chrom_idx int32 [R], start / end int64 [R], maxdiff int32 [R]
+    (1-based), dist float32 [R] and, both or neither, pvals / mh float64 [R] -- all contiguous, on one device.  -> (text uint8,
+    row_off int64 [R + 1], flags int32 [1]): the text is text[:row_off[R]]; nothing may be used when flags[0] != 0 (the EPGM_FLAG_*
+    bits of the header).  text / ws: buffers to use (None: allocated at their bounds, for names of at most chrom_max / name_max
+    bytes, by default the header's EPGM_NAME_MAX).  Current stream, no synchronisation."""
+    R = int(dist.numel())
+    rows = [(chrom_idx, torch.int32), (start, torch.int64), (end, torch.int64), (maxdiff, torch.int32), (dist, torch.float32)]
+    if (pvals is None) != (mh is None):
+        raise ValueError("pvals and mh go together")
+    if pvals is not None:
+        rows += [(pvals, torch.float64), (mh, torch.float64)]
+    for t, dt in rows:
+        if t.dtype != dt or t.dim() != 1 or t.numel() != R or not t.is_cuda or not t.is_contiguous():
+            raise ValueError("the row arrays must be contiguous 1-D CUDA tensors of R elements: chrom_idx and maxdiff int32, start and end "
+                             "int64, dist float32, pvals and mh float64")
+    for blob, off in ((chrom, chrom_off), (names, names_off)):
+        if blob.dtype != torch.uint8 or off.dtype != torch.int64 or not blob.is_cuda or not off.is_cuda or not blob.is_contiguous() or not off.is_contiguous() or off.numel() < 1:
+            raise ValueError("a name table is a contiguous uint8 blob and contiguous int64 offsets [n + 1], on the device")
+    dev = dist.device
+    if text is None:
+        limit = _abi.header_constant_of(_abi.METRICS["metrics_text"], "EPGM_NAME_MAX")
+        bound = _abi.call("epgm_text_bytes_max", R, limit if chrom_max is None else int(chrom_max), limit if name_max is None else int(name_max),
+                          int(pvals is not None))
+        text = torch.empty(max(int(bound), 256), dtype=torch.uint8, device=dev)
+    if ws is None:
+        ws = torch.empty(max(int(_abi.call("epgm_format_ws_bytes", R)), 256), dtype=torch.uint8, device=dev)
+    row_off = torch.empty(R + 1, dtype=torch.int64, device=dev)
+    flags = torch.empty(1, dtype=torch.int32, device=dev)
+    p = (lambda t: _ptr(t) if R else None)
+    _abi.call("epgm_format_metrics", p(chrom), p(chrom_off), chrom_off.numel() - 1, int(chrom_bytes), p(chrom_idx), p(start), p(end), p(names),
+              p(names_off), names_off.numel() - 1, int(names_bytes), p(maxdiff), p(dist), p(pvals) if pvals is not None else None,
+              p(mh) if mh is not None else None, R, _ptr(text), text.numel(), _ptr(row_off), _ptr(flags), _ptr(ws), ws.numel(), _stream())
+    return text, row_off, flags
+
+
+def metrics_text_bgzf(chromNames, chrom_idx, start, end, stateNames, maxdiff, dist, pvals=None, mh=None, device=None):
+    """pairwiseMetrics_*.txt.gz on the device: the rows of format_metrics, compressed by bgzf_compress, chunk of rows after chunk of rows
+    -> a list of uint8 host arrays, the file's bytes without the end-of-file block (driver.write_bgzf appends the one a finished file
+    carries); None when a flag is set -- a value or an index the device does not format -- and nothing may be used: the caller writes
+    the file on the host.  The two name lists and the row arrays are host arrays (uploaded here, a chunk at a time); pvals and mh may be
+    float64 device tensors instead (--pvals gpu leaves them there: no second upload).  Rows per chunk: as many as keep the bound of
+    the chunk's text under METRICS_CHUNK_TEXT_BYTES.  Synchronises twice per chunk, as scores_text_bgzf does, and reuses its
+    per-device buffers (release_text_buffers)."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    R = len(dist)
+    chrom, chrom_off, chrom_bytes, chrom_max = _name_table(chromNames, dev)
+    names, names_off, names_bytes, name_max = _name_table(stateNames, dev)
+    limit = _abi.header_constant_of(_abi.METRICS["metrics_text"], "EPGM_NAME_MAX")
+    if chrom_max > limit or name_max > limit:
+        return None
+    with_p = pvals is not None
+    per_row = max(int(_abi.call("epgm_text_bytes_max", 1, chrom_max, name_max, int(with_p))), 1)
+    step = max(METRICS_CHUNK_TEXT_BYTES // per_row, 1)
+
+    def up(a, lo, hi, dtype):
+        if torch.is_tensor(a):
+            return a[lo:hi].contiguous()
+        return torch.from_numpy(np.ascontiguousarray(a[lo:hi], dtype=dtype)).to(dev)
+    pieces = []
+    for lo in range(0, R, step):
+        hi = min(R, lo + step)
+        n_rows = hi - lo
+        text = _text_buf(dev, "text", per_row * n_rows)
+        ws = _text_buf(dev, "ws", max(_abi.call("epgm_format_ws_bytes", n_rows), _abi.call("epgw_bgzf_ws_bytes", text.numel())))
+        text, row_off, flags = format_metrics(chrom, chrom_off, chrom_bytes, up(chrom_idx, lo, hi, np.int32), up(start, lo, hi, np.int64),
+                                              up(end, lo, hi, np.int64), names, names_off, names_bytes, up(maxdiff, lo, hi, np.int32),
+                                              up(dist, lo, hi, np.float32), up(pvals, lo, hi, np.float64) if with_p else None,
+                                              up(mh, lo, hi, np.float64) if with_p else None, text=text, ws=ws)
+        n, flag = (int(v) for v in torch.stack([row_off[n_rows], flags[0].to(torch.int64)]).cpu())
+        if flag:
+            return None
+        out = _text_buf(dev, "out", _abi.call("epgw_bgzf_bytes_max", n, 0))
+        out, n_out, flags = bgzf_compress(text, n, row_off, eof=False, out=out, ws=ws)
+        n_bytes, flag = (int(v) for v in torch.stack([n_out[0], flags[0].to(torch.int64)]).cpu())
+        if flag:
+            raise EpilogosHipError(-3, "the BGZF stream did not fit its own bound")
+        pieces.append(out[:n_bytes].cpu().numpy())
+    return pieces
+
+
 # ---- the device BGZF reader (csrc/epg_bgzf_inflate.h): simsearch --inflate gpu
 def bgzf_inflate(comp, table, out=None, status=None, flags=None):
     """The members of a BGZF stream inflated on the device (epgz_bgzf_inflate): comp uint8 (device) holds the compressed bytes, table

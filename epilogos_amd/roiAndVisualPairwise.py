@@ -32,7 +32,7 @@ import scipy.stats as st
 from . import _io
 from . import backend as _backend
 from .helpers import getNumStates, strToBool
-from .roiSingle import findSign, getStateNames, maxMean, orderChromosomes
+from .roiSingle import _maxMeanOn, _roiOptions, findSign, getStateNames, maxMean, orderChromosomes
 
 
 def benjaminiHochberg(pvals):
@@ -206,6 +206,45 @@ def writeMetrics(locationArr, chrDict, maxDiffArr, nameArr, distanceArrReal, out
                       mhPvals if pvalBool else None)
 
 
+METRICS_DEVICE_REFUSED = ("WARNING: [--metrics gpu] the device does not format this file (a p-value outside [0, 1] or not a number, a distance "
+                          "that is not finite, a state or a chromosome outside its table, a negative coordinate); writing it with the host writer instead")
+
+
+def writeMetricsDevice(locationArr, chrDict, maxDiffArr, nameArr, distanceArrReal, outputDirPath, fileTag, pvalBool, pvals=(), mhPvals=(),
+                       devicePvals=None):
+    """writeMetrics with the rows formatted and compressed on the device (engine.metrics_text_bgzf, csrc/epg_metrics_text.h): the same
+    decompressed bytes, always as BGZF with one end-of-file block, whatever EPILOGOS_BGZF and EPILOGOS_GZIP_LEVEL say.  devicePvals:
+    (p, adjusted p) as float64 device tensors in the rows' order, when the p-value stage left them there (--pvals gpu): they are
+    formatted where they sit.  -> False, and nothing is written, when the device refuses the file (a flag of the kernel)."""
+    from . import driver, engine
+    engine.require_gpu()
+    outputDirPath.mkdir(parents=True, exist_ok=True)
+    numbers = sorted(chrDict)
+    index = np.zeros(max(numbers) + 1 if numbers else 1, dtype=np.int32)
+    index[numbers] = np.arange(len(numbers), dtype=np.int32)
+    p, mh = (None, None) if not pvalBool else (devicePvals if devicePvals is not None else (pvals, mhPvals))
+    pieces = engine.metrics_text_bgzf([chrDict[n] for n in numbers], index[locationArr[:, 0]] if len(locationArr) else np.zeros(0, dtype=np.int32),
+                                      locationArr[:, 1], locationArr[:, 2], list(nameArr), maxDiffArr, distanceArrReal, p, mh)
+    if pieces is None:
+        return False
+    driver.write_bgzf(outputDirPath / "pairwiseMetrics_{}.txt.gz".format(fileTag), pieces)
+    return True
+
+
+def _writeMetricsOn(metrics, devicePvals=None):
+    """The metrics writer of `metrics` ("host" or "gpu"): writeMetrics, or writeMetricsDevice with writeMetrics behind its refusal."""
+    if metrics == "host":
+        return writeMetrics
+    if metrics != "gpu":
+        raise ValueError("metrics must be 'host' or 'gpu', not {!r}".format(metrics))
+
+    def write(*args, **kwargs):
+        if not writeMetricsDevice(*args, devicePvals=devicePvals, **kwargs):
+            print(METRICS_DEVICE_REFUSED, flush=True)
+            writeMetrics(*args, **kwargs)
+    return write
+
+
 def _stars_p(p):
     return "***" if p <= 0.01 else ("**" if p <= 0.05 else ("*" if p <= 0.1 else "."))
 
@@ -225,12 +264,14 @@ def createSignificantLociTxt(filePath, locationArr, chrDict, distanceArr, maxDif
                 findSign(score), p, mh, _stars_p(mh)))
 
 
-def _regions(locationArr, distanceArr, roiWidth):
+def _regions(locationArr, distanceArr, roiWidth, roi="host"):
     """Top-100 maxmean windows over |distance| and, per window, the index of its most different bin
-    (reference :682-689 / :755-762 with helpers.generateROIIndicesArr :277-296)."""
+    (reference :682-689 / :755-762 with helpers.generateROIIndicesArr :277-296).  roi="gpu": searched on the device
+    (roiSingle.maxMeanDevice), the same windows."""
     W = int(roiWidth)
     absd = np.abs(distanceArr)
-    chrom, w_start, w_end, _, centre = maxMean(locationArr[:, 0], locationArr[:, 1], locationArr[:, 2], absd, W, 100)
+    search = maxMean if roi == "host" else _maxMeanOn(roi)
+    chrom, w_start, w_end, _, centre = search(locationArr[:, 0], locationArr[:, 1], locationArr[:, 2], absd, W, 100)
     maxIndices = np.zeros(len(centre), dtype=np.int64)
     for k, c in enumerate(centre):
         lo = int(c) - W // 2
@@ -239,11 +280,11 @@ def _regions(locationArr, distanceArr, roiWidth):
     return chrom, w_start, w_end, maxIndices
 
 
-def createROITxt(filePath, locationArr, chrDict, distanceArr, maxDiffArr, nameArr, pvals, mhPvals, roiWidth):
+def createROITxt(filePath, locationArr, chrDict, distanceArr, maxDiffArr, nameArr, pvals, mhPvals, roiWidth, roi="host"):
     """Regions whose most different bin is significant, best first, cut at the first non-significant one
     (reference :646-723)."""
     with open(filePath, "w") as out:
-        chrom, w_start, w_end, maxIndices = _regions(locationArr, distanceArr, roiWidth)
+        chrom, w_start, w_end, maxIndices = _regions(locationArr, distanceArr, roiWidth, **_roiOptions(roi))
         nonSig = np.where(mhPvals[maxIndices] > 0.1)[0]
         n = int(nonSig.min()) if len(nonSig) else len(maxIndices)
         for k in range(n):
@@ -255,10 +296,10 @@ def createROITxt(filePath, locationArr, chrDict, distanceArr, maxDiffArr, nameAr
                 findSign(score), p, mh, _stars_p(mh)))
 
 
-def createROINoSignificance(filePath, locationArr, chrDict, distanceArr, maxDiffArr, nameArr, zScores, roiWidth):
+def createROINoSignificance(filePath, locationArr, chrDict, distanceArr, maxDiffArr, nameArr, zScores, roiWidth, roi="host"):
     """Top-100 regions with the z-score of their most different bin (reference :726-778)."""
     with open(filePath, "w") as out:
-        chrom, w_start, w_end, maxIndices = _regions(locationArr, distanceArr, roiWidth)
+        chrom, w_start, w_end, maxIndices = _regions(locationArr, distanceArr, roiWidth, **_roiOptions(roi))
         for k in range(len(maxIndices)):
             i = maxIndices[k]
             score = float(np.float32(distanceArr[i]))
@@ -365,12 +406,18 @@ def _pvalOptions(pvals):
     return {} if pvals == "host" else dict(pvals=pvals)
 
 
-def _pvalsGpu(distanceArrReal, params, empirical):
+def _metricsOptions(metrics):
+    """As _pvalOptions: nothing for the host's metrics writer."""
+    return {} if metrics == "host" else dict(metrics=metrics)
+
+
+def _pvalsGpu(distanceArrReal, params, empirical, keep=None):
     """The pvals="gpu" branch of _finish (csrc/epg_pvals.h): one upload of the distances and the three parameters, the p-value kernel
     and the Benjamini-Hochberg adjustment back to back on the device, one download of p, the adjusted p and the flag words.
     empirical given (--null-draws K > 1): the p-values are the host's and only the adjustment runs on the device.
     -> (pvals, mhPvals), or None when a flag word is not zero: a p-value that is NaN (a NaN distance, unusable parameters) or
-    negative, or an iteration that stopped at its cap."""
+    negative, or an iteration that stopped at its cap.  keep: a list that gets (p, adjusted p) as they sit on the device, for the
+    metrics writer of --metrics gpu."""
     import torch
     from . import engine
     engine.require_gpu()
@@ -385,15 +432,19 @@ def _pvalsGpu(distanceArrReal, params, empirical):
     flags = (bflags if pflags is None else torch.cat([pflags, bflags])).cpu().numpy()
     if flags.any():
         return None
+    if keep is not None:
+        keep.append((p, adj))
     return (pvals if empirical is not None else p.cpu().numpy()), adj.cpu().numpy()
 
 
 def _finish(params, locationArr, distanceArrReal, maxDiffArr, chrDict, stateInfo, outputDirPath, fileTag, pvalBool, roiWidth,
-            expFreqPath, verbose, empirical=None, pvals="host"):
+            expFreqPath, verbose, empirical=None, pvals="host", roi="host", metrics="host"):
     """Everything of main() after the inputs are in memory (reference :72-169 without the figures).  empirical: the bins'
     empirical p-values (empiricalPVals); they take the place of the fitted distribution's and `params` is not used.
     pvals="gpu": the p-values and their Benjamini-Hochberg adjustment on the device (_pvalsGpu), both under the first of the two
-    stage labels; a non-zero flag sends the whole stage back to the host functions."""
+    stage labels; a non-zero flag sends the whole stage back to the host functions.  roi="gpu": the region search on the device
+    (roiSingle.maxMeanDevice).  metrics="gpu": pairwiseMetrics formatted and compressed on the device (writeMetricsDevice), from the
+    device's own p-values when pvals="gpu" left them there."""
     if pvals not in ("host", "gpu"):
         raise ValueError("pvals must be 'host' or 'gpu', not {!r}".format(pvals))
     onDevice = pvals == "gpu"                        # (below, `pvals` is the array of p-values, as it always was)
@@ -401,9 +452,9 @@ def _finish(params, locationArr, distanceArrReal, maxDiffArr, chrDict, stateInfo
     roiPath = outputDirPath / "regionsOfInterest_{}.txt".format(fileTag)
     if pvalBool:
         t0 = _stage(verbose, "Calculating p-vals")
-        device = None
+        device, kept = None, []
         if onDevice and len(distanceArrReal):
-            device = _pvalsGpu(distanceArrReal, params, empirical)
+            device = _pvalsGpu(distanceArrReal, params, empirical, **(dict(keep=kept) if metrics == "gpu" else {}))
             if device is None:
                 print("WARNING: a p-value is not a number or negative, or an iteration met its cap; computing the p-values on the host instead",
                       flush=True)
@@ -417,11 +468,12 @@ def _finish(params, locationArr, distanceArrReal, maxDiffArr, chrDict, stateInfo
             mhPvals = benjaminiHochberg(pvals)
         _done(verbose, t0)
         t0 = _stage(verbose, "Writing metrics")
-        writeMetrics(locationArr, chrDict, maxDiffArr, stateNameList, distanceArrReal, outputDirPath, fileTag, True,
-                     pvals=pvals, mhPvals=mhPvals)
+        _writeMetricsOn(metrics, kept[0] if kept else None)(locationArr, chrDict, maxDiffArr, stateNameList, distanceArrReal, outputDirPath, fileTag, True,
+                                                           pvals=pvals, mhPvals=mhPvals)
+        del kept
         _done(verbose, t0)
         t0 = _stage(verbose, "Regions of interest txt")
-        createROITxt(roiPath, locationArr, chrDict, distanceArrReal, maxDiffArr, stateNameList, pvals, mhPvals, roiWidth)
+        createROITxt(roiPath, locationArr, chrDict, distanceArrReal, maxDiffArr, stateNameList, pvals, mhPvals, roiWidth, **_roiOptions(roi))
         _done(verbose, t0)
         t0 = _stage(verbose, "Significant loci txt")
         createSignificantLociTxt(outputDirPath / "significantLoci_{}.txt.gz".format(fileTag), locationArr, chrDict,
@@ -432,10 +484,10 @@ def _finish(params, locationArr, distanceArrReal, maxDiffArr, chrDict, stateInfo
         zScores = np.abs(st.zscore(distanceArrReal))
         _done(verbose, t0)
         t0 = _stage(verbose, "Writing metrics")
-        writeMetrics(locationArr, chrDict, maxDiffArr, stateNameList, distanceArrReal, outputDirPath, fileTag, False)
+        _writeMetricsOn(metrics)(locationArr, chrDict, maxDiffArr, stateNameList, distanceArrReal, outputDirPath, fileTag, False)
         _done(verbose, t0)
         t0 = _stage(verbose, "Regions of interest txt")
-        createROINoSignificance(roiPath, locationArr, chrDict, distanceArrReal, maxDiffArr, stateNameList, zScores, roiWidth)
+        createROINoSignificance(roiPath, locationArr, chrDict, distanceArrReal, maxDiffArr, stateNameList, zScores, roiWidth, **_roiOptions(roi))
         _done(verbose, t0)
     remove(Path(expFreqPath))
 
@@ -450,7 +502,7 @@ def _is_location_sorted(chrNum, starts, ends):
 
 
 def mainFromArrays(results, stateInfo, outputDir, fileTag, numProcesses, pvalBool, numTrials, samplingSize, expFreqPath,
-                   roiWidth, verbose, fit="host", seed=None, pvals="host"):
+                   roiWidth, verbose, fit="host", seed=None, pvals="host", roi="host", metrics="host"):
     """main() on the arrays driver.run_paired_groups hands back ({stem: dict(chrName, locations, nullDistances,
     quiescenceArr, distances, maxDiff)}) instead of the temp_*.npz / pairwiseDelta text round trip."""
     outputDirPath = Path(outputDir)
@@ -482,11 +534,11 @@ def mainFromArrays(results, stateInfo, outputDir, fileTag, numProcesses, pvalBoo
         dist, maxdiff = dist[order], maxdiff[order]
         empirical = empirical[order] if empirical is not None else None
     _finish(params, locationArr, dist, maxdiff, chrDict, stateInfo, outputDirPath, fileTag, pvalBool, roiWidth, expFreqPath, verbose,
-            empirical=empirical, **_pvalOptions(pvals))
+            empirical=empirical, **_pvalOptions(pvals), **_roiOptions(roi), **_metricsOptions(metrics))
 
 
 def main(group1Name, group2Name, stateInfo, outputDir, fileTag, numProcesses, pvalBool, diagnosticBool, numTrials,
-         samplingSize, expFreqPath, roiWidth, verbose, backend=None, fit="host", seed=None, pvals="host"):
+         samplingSize, expFreqPath, roiWidth, verbose, backend=None, fit="host", seed=None, pvals="host", roi="host", metrics="host"):
     tTotal = time()
     outputDirPath = Path(outputDir)
     numStates = getNumStates(stateInfo)
@@ -505,7 +557,8 @@ def main(group1Name, group2Name, stateInfo, outputDir, fileTag, numProcesses, pv
     if empiricalRun and empirical is None:
         raise ValueError("temp_nullExceed_*.npz is missing for some of the pairwiseDelta files in {}".format(outputDirPath))
     _finish(params, locationArr, distanceArrReal, maxDiffArr, chrDict, stateInfo, outputDirPath, fileTag, pvalBool, roiWidth,
-            expFreqPath, verbose, empirical=empirical if empiricalRun else None, **_pvalOptions(pvals))
+            expFreqPath, verbose, empirical=empirical if empiricalRun else None, **_pvalOptions(pvals), **_roiOptions(roi),
+            **_metricsOptions(metrics))
     if verbose: print("Total Time:", time() - tTotal, flush=True)
 
 

@@ -5,7 +5,9 @@ the reference's vendored filter_regions (filter_regions.py:375-448 through helpe
 regionsOfInterest_{fileTag}.txt; then removes the temporaries and exp_freq like the reference (quirk Q4).
 
 The selection is a sequential greedy pick on a 1-D vector: it stays on the host.  Rolling max / mean use the same pandas
-primitive the reference calls, so that ties between windows that share their maximum are broken by bit-identical means."""
+primitive the reference calls, so that ties between windows that share their maximum are broken by bit-identical means.
+roi="gpu" (`epilogos --roi gpu`): rolling maximum, rank and pick run on the device instead (maxMeanDevice), the same windows in
+the same order; the rolling mean, the validity mask and the text stay here."""
 from os import remove
 from pathlib import Path
 from sys import argv
@@ -72,22 +74,28 @@ def greedyWalk(sc, rmean, rmax, W, maxRegions, _first_candidates=None):
     return np.array(sorted(chosen), dtype=np.int64)        # back to genomic order
 
 
-def maxMean(chrom, start, end, score, roiWidth, maxRegions, _first_candidates=None):
-    """Top `maxRegions` non-overlapping windows of `roiWidth` bins by (rolling max, rolling mean, centre score).
-    Restates filter_regions.Filter.maxmean (:375-448) + helpers.maxMean (:253-274) on plain arrays.
-    Returns (chromosome, window start, window end, score = rolling max, original centre index), best first."""
+def _windows(start, end, score, roiWidth):
+    """What maxMean and maxMeanDevice share: the rows that have both shifted coordinates, their window coordinates and scores."""
     W, h = int(roiWidth), int(roiWidth) // 2
     R = len(score)
-    score = np.asarray(score, dtype=np.float64)
     # window coordinates: Start of the bin h to the left, End of the bin h (odd W) / h-1 (even W) to the right
     e_off = h if W % 2 else h - 1
     lo, hi = h, R - e_off                      # rows that have both shifted coordinates (Series.shift + dropna)
     if hi <= lo:
-        return [np.array([])] * 5
+        return None
     orig = np.arange(lo, hi)
-    w_start = np.asarray(start)[orig - h]
-    w_end = np.asarray(end)[orig + e_off]
-    sc = score[lo:hi]
+    return orig, np.asarray(start)[orig - h], np.asarray(end)[orig + e_off], score[lo:hi]
+
+
+def maxMean(chrom, start, end, score, roiWidth, maxRegions, _first_candidates=None):
+    """Top `maxRegions` non-overlapping windows of `roiWidth` bins by (rolling max, rolling mean, centre score).
+    Restates filter_regions.Filter.maxmean (:375-448) + helpers.maxMean (:253-274) on plain arrays.
+    Returns (chromosome, window start, window end, score = rolling max, original centre index), best first."""
+    W = int(roiWidth)
+    win = _windows(start, end, np.asarray(score, dtype=np.float64), W)
+    if win is None:
+        return [np.array([])] * 5
+    orig, w_start, w_end, sc = win
     # the rolling MEAN stays pandas' own (an online add/remove sum with compensation: its last bits depend on the whole history,
     # and they break ties); the rolling MAX is exact in any implementation -- the native one is pandas' deque, threaded
     rmean = pd.Series(sc).rolling(W, center=True).mean().to_numpy()
@@ -104,6 +112,53 @@ def maxMean(chrom, start, end, score, roiWidth, maxRegions, _first_candidates=No
     return (np.asarray(chrom)[orig[final]], w_start[final], w_end[final], rmax[final], orig[final])
 
 
+ROI_DEVICE_REFUSED = "WARNING: [--roi gpu] {}; searching the regions on the host instead"
+
+
+def maxMeanDevice(chrom, start, end, score, roiWidth, maxRegions):
+    """maxMean with the rolling maximum, the compaction of the kept windows, the rank and the greedy pick on the device
+    (similaritySearch_step1.pickTop: the entry points of include/epilogos_simsearch_pick.h): the same five arrays, the same windows
+    in the same order.  pandas' rolling mean stays on the host (its last bits break ties and depend on the whole history), and so
+    does the mask of the windows that span two chromosomes; the float64 scores, the means and the mask are uploaded.
+    -> None, after one WARNING line, when the device path does not cover the call: a window above EPG_PICK_MAX_W bins, or a score
+    that is not finite (the rank's key image has no NaN)."""
+    import torch
+    from . import _abi, engine, similaritySearch_step1 as step1
+    W = int(roiWidth)
+    score = np.asarray(score, dtype=np.float64)
+    limit = _abi.pick_header_constant("EPG_PICK_MAX_W")
+    if W > limit:
+        print(ROI_DEVICE_REFUSED.format("a region of {} bins is wider than the device pick's {}".format(W, limit)), flush=True)
+        return None
+    if not np.isfinite(score).all():
+        print(ROI_DEVICE_REFUSED.format("a score is not finite"), flush=True)
+        return None
+    win = _windows(start, end, score, W)
+    if win is None:
+        return [np.array([])] * 5
+    orig, w_start, w_end, sc = win
+    rmean = pd.Series(sc).rolling(W, center=True).mean().to_numpy()
+    valid = ~np.isnan(rmean)                   # incomplete edge windows (the scores are finite)
+    valid &= ~(np.asarray(w_start, dtype=np.int64) >= np.asarray(w_end, dtype=np.int64))   # windows spanning two chromosomes
+    device = step1.deviceOf()
+    at, top = step1.pickTop(torch.from_numpy(np.ascontiguousarray(sc)).to(device), torch.from_numpy(rmean).to(device),
+                            torch.from_numpy(valid).to(device), W, maxRegions)
+    return (np.asarray(chrom)[orig[at]], w_start[at], w_end[at], top, orig[at])
+
+
+def _maxMeanOn(roi):
+    """The region search of `roi` ("host" or "gpu"): maxMean, or maxMeanDevice with maxMean behind its refusals."""
+    if roi == "host":
+        return maxMean
+    if roi != "gpu":
+        raise ValueError("roi must be 'host' or 'gpu', not {!r}".format(roi))
+
+    def search(chrom, start, end, score, roiWidth, maxRegions):
+        found = maxMeanDevice(chrom, start, end, score, roiWidth, maxRegions)
+        return found if found is not None else maxMean(chrom, start, end, score, roiWidth, maxRegions)
+    return search
+
+
 def readInData(outputDirPath):
     """All temp_scores_*.npz in chromosome order (reference roiSingle.py:43-76); removes them afterwards."""
     chunks = {}
@@ -118,9 +173,9 @@ def readInData(outputDirPath):
     return locationArr, scoreArr
 
 
-def createTopScoresTxt(filePath, locationArr, scoreArr, nameArr, roiWidth):
+def createTopScoresTxt(filePath, locationArr, scoreArr, nameArr, roiWidth, roi="host"):
     """regionsOfInterest*.txt: chromosome, start, end, largest-scoring state, |sum of scores|, sign
-    (reference roiSingle.py:95-142)."""
+    (reference roiSingle.py:95-142).  roi="gpu": the windows are searched on the device (maxMeanDevice), the same file."""
     W = int(roiWidth)
     # scoreArr: one [R, S] array, or the per-chromosome arrays in genomic order (a whole genome's scores are 1.1 GB: they are
     # not concatenated, only their row sums are)
@@ -134,7 +189,7 @@ def createTopScoresTxt(filePath, locationArr, scoreArr, nameArr, roiWidth):
 
     # locationArr: the reference's [R, 3] object array, or (chromosome, start, end) columns
     c0, c1, c2 = locationArr if isinstance(locationArr, tuple) else (locationArr[:, 0], locationArr[:, 1], locationArr[:, 2])
-    chrom, w_start, w_end, sc, centre = maxMean(c0, c1, c2, total, W, 100)
+    chrom, w_start, w_end, sc, centre = _maxMeanOn(roi)(c0, c1, c2, total, W, 100)
     S = parts[0].shape[1]
     lines = []
     for k in range(len(centre)):
@@ -150,7 +205,12 @@ def createTopScoresTxt(filePath, locationArr, scoreArr, nameArr, roiWidth):
         outFile.write("".join(lines))
 
 
-def mainFromArrays(results, outputDir, stateInfo, fileTag, expFreqPath, roiWidth, verbose):
+def _roiOptions(roi):
+    """What is passed on beyond what was always passed: nothing for the host's region search."""
+    return {} if roi == "host" else dict(roi=roi)
+
+
+def mainFromArrays(results, outputDir, stateInfo, fileTag, expFreqPath, roiWidth, verbose, roi="host"):
     """main() on the arrays driver.run_single_group hands back -- {stem: (chrName, scoreArr, _io.Locations)} -- instead
     of temp_scores_*.npz files: same output file, no 170 B/bin round trip through compressed pickles."""
     byChr = {v[0]: v for v in results.values()}
@@ -160,7 +220,7 @@ def mainFromArrays(results, outputDir, stateInfo, fileTag, expFreqPath, roiWidth
     locationArr = tuple(np.concatenate([c[k] for c in cols]) for k in range(3))
     if not verbose: print("    Regions of interest txt\t", end="", flush=True)
     createTopScoresTxt(Path(outputDir) / "regionsOfInterest_{}.txt".format(fileTag), locationArr, scoreArr,
-                       getStateNames(stateInfo), roiWidth)
+                       getStateNames(stateInfo), roiWidth, **_roiOptions(roi))
     if not verbose: print("\t[Done]", flush=True)
     remove(Path(expFreqPath))
 

@@ -242,6 +242,14 @@ def _init_device_and_group(world, under_launcher):
               help="Where scores_*.txt.gz (single mode) and pairwiseDelta_*.txt.gz (paired mode) are formatted and compressed.  host: the "
                    "native writer threads (EPILOGOS_GZIP_LEVEL and EPILOGOS_BGZF are its settings).  gpu: on the device, always as BGZF; "
                    "only compressed bytes come back, and paired mode downloads no deltas.  The decompressed bytes are the same")
+@click.option("--roi", "roi", type=click.Choice(["host", "gpu"]), default="host", show_default=True,
+              help="Where STEP 4 searches the regions of interest.  host: sort and greedy walk in numpy.  gpu: rolling maximum, rank and "
+                   "pick of the windows on the device; regionsOfInterest_*.txt is the same file.  A region above 1024 bins [-w] is "
+                   "searched on the host")
+@click.option("--metrics", "metrics", type=click.Choice(["host", "gpu"]), default="host", show_default=True,
+              help="Paired mode: where pairwiseMetrics_*.txt.gz is formatted and compressed.  host: the native writer threads "
+                   "(EPILOGOS_GZIP_LEVEL and EPILOGOS_BGZF are its settings).  gpu: on the device, always as BGZF, from the device's own "
+                   "p-values with [--pvals gpu].  The decompressed bytes are the same")
 @click.option("--gpus", "gpus", type=int, default=1, show_default=True,
               help="GPUs of this node to split the genome over (0 = all visible); replaces the SLURM fan-out of the reference")
 @click.option("--cache-dir", "cacheDir", type=str, default=None,
@@ -274,7 +282,8 @@ def _init_device_and_group(world, under_launcher):
 def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2, outputDirectory, stateInfo, saliency,
          numProcesses, exitBool, diagnosticBool, numTrials, samplingSize, quiescentState, groupSize, version, partition,
          pvalBool, roiWidth, fileTag, expFreqMem, expCombMem, scoreMem, roiMem, nullSeed, nullDraws, gpus, cacheDir, columns, columnsA, columnsB, checkStates,
-         groupingsFile, chromhmm, metadata, chromsizes, segments, binWidth, stateNames, keepMatrices, fit="host", pvals="host", writer="host"):
+         groupingsFile, chromhmm, metadata, chromsizes, segments, binWidth, stateNames, keepMatrices, fit="host", pvals="host", writer="host",
+         roi="host", metrics="host"):
     """Information-theoretic navigation of multi-tissue functional genomic annotations -- MI355X scoring engine."""
     if version:
         print("Version:", __version__)
@@ -307,6 +316,9 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
         print("ERROR: [--pvals gpu] is only valid in paired mode"); sys.exit()
     if pvals == "gpu" and not pvalBool:
         print("ERROR: [--pvals gpu] requires [-n, --null-distribution]: without it no p-value is computed"); sys.exit()
+    # --metrics gpu: the same; single mode writes no such file (--roi gpu is valid in both modes)
+    if metrics == "gpu" and mode != "paired":
+        print("ERROR: [--metrics gpu] is only valid in paired mode"); sys.exit()
     # --groupings: as above, its own combinations and its file's errors before everything else -- nothing is read but that file
     groupings = None
     if groupingsFile is not None:
@@ -467,7 +479,7 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
                 import time
                 t0 = time.perf_counter()
                 from .roiSingle import mainFromArrays as roiSingle
-                roiSingle(results, outDir, stateInfo, fileTag, outDir / storedExpPath.name, roiWidth if roiWidth else 50, False)
+                roiSingle(results, outDir, stateInfo, fileTag, outDir / storedExpPath.name, roiWidth if roiWidth else 50, False, **roiOptions())
                 if os.environ.get("EPILOGOS_TIMING"):
                     print("    [timing] %-34s %7.2f s" % ("STEP 4", time.perf_counter() - t0), flush=True)
         finally:
@@ -480,6 +492,10 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
     def pvalOptions():
         # nothing for --pvals host, as above
         return dict(pvals="gpu") if pvals == "gpu" else {}
+
+    def roiOptions():
+        # nothing for --roi host and --metrics host, as above
+        return {**(dict(roi="gpu") if roi == "gpu" else {}), **(dict(metrics="gpu") if metrics == "gpu" else {})}
 
     def writerOptions():
         # nothing for --writer host, as above: the drivers are called exactly as before
@@ -495,7 +511,7 @@ def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2
                 t0 = time.perf_counter()
                 from .roiAndVisualPairwise import mainFromArrays as roiPairwise
                 roiPairwise(results, stateInfo, outDir, fileTag, max(numProcesses, 1), pvalBool, numTrials, samplingSize,
-                            outDir / storedExpPath.name, roiWidth if roiWidth else 125, False, **fitOptions(), **pvalOptions())
+                            outDir / storedExpPath.name, roiWidth if roiWidth else 125, False, **fitOptions(), **pvalOptions(), **roiOptions())
                 if os.environ.get("EPILOGOS_TIMING"):
                     print("    [timing] %-34s %7.2f s" % ("STEP 4", time.perf_counter() - t0), flush=True)
         finally:

@@ -17,7 +17,7 @@ equal integer sums mostly have different float sums.
 A file the strict reader refuses (scoresText.NotStrict) gets the warning line similaritySearch_query.readGrid prints and is built by
 similaritySearch_max_mean.main.  Without a GPU or the library the module raises, as the engine does.
 
-The device steps are module-level functions (readDevice, rowScores, rollingMax, rankWindows, pickWindows, slices, reduce): a host
+The device steps are module-level functions (readDevice, rowScores, rollingMax, rankWindows, pickWindows, slices, reduce, deviceOf): a host
 test puts numpy restatements in their place, on CPU tensors.  `python -m epilogos_amd.similaritySearch_step1 outputDir scoresPath
 windowBins blockSize windowBP filterState filterScore` is the child of a `--gpus N` build: one fresh process on LOCAL_RANK."""
 import ctypes as C
@@ -120,6 +120,14 @@ def reduce(x, blockSize):
     return g.cpu().numpy().astype(np.int64)
 
 
+def deviceOf():
+    """The device STEP 4's region search uploads its three vectors to (roiSingle.maxMeanDevice); raises without a GPU or the library."""
+    import torch
+    from . import engine
+    engine.require_gpu()
+    return torch.device("cuda", torch.cuda.current_device())
+
+
 # ---- plumbing ------------------------------------------------------------------------------------------------------------------
 
 def rollingMean(sc, W, timings=None):
@@ -166,6 +174,42 @@ def coordsOf(start, end, runs):
     return coords
 
 
+def pickTop(sc, rmean, valid, W, maxRegions, clock=None, timings=None):
+    """The device part of roiSingle.maxMean, shared by pickRegions and by STEP 4's `--roi gpu` (roiSingle.maxMeanDevice): sc and rmean
+    float64 [m] (the centre scores and pandas' rolling means of the rows that have both shifted coordinates), valid bool [m] (False
+    where a window spans two chromosomes), all on one device -> (at, rmax): the picked windows' indices into sc, best first, and their
+    rolling maxima, as host arrays.  Rolling maximum, compaction of the kept windows, rank and greedy pick run through the
+    module-level steps, the pick in the compacted index space as the host's does; the final best-first order of the few picked
+    windows is the host's lexsort."""
+    import torch
+    tick = clock.tick if clock is not None else (lambda name: None)
+    none = np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.float64)
+    rmax = rollingMax(sc, W)
+    tick("rolling_max")
+    ok = ~torch.isnan(rmax)                                # incomplete edge windows
+    ok &= valid                                            # windows spanning two chromosomes
+    keep = torch.nonzero(ok).reshape(-1)
+    sc_c, rmax_c, rmean_c = sc[keep], rmax[keep], rmean[keep]
+    tick("compact")
+    if not keep.numel():
+        return none
+    rank = rankWindows(rmax_c, rmean_c, sc_c)
+    tick("rank")
+    chosen, launches = pickWindows(rank, W, maxRegions)
+    tick("pick")
+    if timings is not None:
+        timings.update(pick_launches=launches, windows=int(keep.numel()), picked=int(len(chosen)))
+    if not len(chosen):
+        return none
+    ch = torch.from_numpy(chosen).to(sc.device)
+    # best first, as maxMean's last sort: by (rolling max, rolling mean), windows that tie on both in genomic order
+    top = rmax_c[ch].cpu().numpy()
+    final = np.lexsort((-rmean_c[ch].cpu().numpy(), -top))
+    at = keep[ch].cpu().numpy()[final]
+    tick("final_order")
+    return at, top[final]
+
+
 def pickRegions(x, start, end, windowBins, timings=None):
     """roiSingle.maxMean with maxRegions = G // windowBins on the device grid -> the centre rows (int64, best first) and the
     window coordinates (start of the bin h to the left, end of the bin h / h - 1 to the right)."""
@@ -184,28 +228,11 @@ def pickRegions(x, start, end, windowBins, timings=None):
     sc = score[lo:hi]
     rmean = rollingMean(sc, W, timings)
     clock.tick("rolling_mean")
-    rmax = rollingMax(sc, W)
-    clock.tick("rolling_max")
     w_start, w_end = start[lo - h:hi - h], end[lo + e_off:hi + e_off]
-    ok = ~torch.isnan(rmax)                                # incomplete edge windows
-    ok &= torch.from_numpy(np.asarray(w_start < w_end)).to(x.device)       # windows spanning two chromosomes
-    keep = torch.nonzero(ok).reshape(-1)
-    sc_c, rmax_c, rmean_c = sc[keep], rmax[keep], rmean[keep]
-    clock.tick("compact")
-    rank = rankWindows(rmax_c, rmean_c, sc_c)
-    clock.tick("rank")
-    chosen, launches = pickWindows(rank, W, maxRegions)
-    clock.tick("pick")
-    if timings is not None:
-        timings.update(pick_launches=launches, windows=int(keep.numel()), picked=int(len(chosen)))
-    if not len(chosen):
+    at, _top = pickTop(sc, rmean, torch.from_numpy(np.asarray(w_start < w_end)).to(x.device), W, maxRegions, clock, timings)
+    if not len(at):
         return none, none, none
-    ch = torch.from_numpy(chosen).to(x.device)
-    # best first, as maxMean's last sort: by (rolling max, rolling mean), windows that tie on both in genomic order
-    final = np.lexsort((-rmean_c[ch].cpu().numpy(), -rmax_c[ch].cpu().numpy()))
-    at = keep[ch].cpu().numpy()[final]                     # index into rows lo .. hi
-    clock.tick("final_order")
-    return lo + at, np.asarray(w_start)[at], np.asarray(w_end)[at]
+    return lo + at, np.asarray(w_start)[at], np.asarray(w_end)[at]                # (at: index into rows lo .. hi)
 
 
 def selectRegions(x, start, end, runs, windowBins, blockSize, filterState, filterScore, timings=None):
