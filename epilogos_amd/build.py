@@ -27,7 +27,7 @@ READER_HEADERS = {"bgzf_inflate": "epg_bgzf_inflate.h"}
 # the device metrics writer's entry points (epgm_): package-internal in the same way, bound by _abi.METRICS.  Once more a registry of
 # its own: tests/test_inflate_host.py pins READER_HEADERS to the reader's header alone, and the three registries above to their order
 METRICS_HEADERS = {"metrics_text": "epg_metrics_text.h"}
-HEADERS = [CSRC / "epg_common.h", CSRC / "epg_count.h", CSRC / "epg_paircount.h", CSRC / "epg_parts.h", CSRC / "epg_pairdist.h", CSRC / "epg_text_scan.h", CSRC / "epg_fmt_f5.h", CSRC / "epg_fmt_e5.h", CSRC / "epg_bgzf_block.h", CSRC / "epg_bgzf_inflate_block.h",
+HEADERS = [CSRC / "epg_common.h", CSRC / "epg_count.h", CSRC / "epg_paircount.h", CSRC / "epg_parts.h", CSRC / "epg_pairdist.h", CSRC / "epg_text_scan.h", CSRC / "epg_text_rows.h", CSRC / "epg_fmt_f5.h", CSRC / "epg_fmt_e5.h", CSRC / "epg_bgzf_block.h", CSRC / "epg_bgzf_inflate_block.h",
            *[ROOT / "include" / name for name in PUBLIC_HEADERS.values()], *[CSRC / name for name in INTERNAL_HEADERS.values()], *[CSRC / name for name in WRITER_HEADERS.values()], *[CSRC / name for name in READER_HEADERS.values()], *[CSRC / name for name in METRICS_HEADERS.values()]]
 ARCH = "gfx950"
 

@@ -3,14 +3,16 @@
 //   * k_bgzf_inflate   a workgroup of ONE wave per member.  The phases are in epg_bgzf_inflate_block.h, which also says how a match is
 //                      ordered behind the bytes it reads: the member's text is put together in LDS (a window of 64 KB, shifted so that
 //                      16-byte chunks of LDS are 16-byte chunks of `out`), the payload comes through a 4 KB ring, lane 0 decodes
-//                      into tokens, all lanes copy them, all lanes take the CRC-32, and the window goes out in 16-byte stores once
-//                      the trailer agrees (zeros when it does not).  LDS: ~75 KB, so two workgroups -- two waves -- per CU.
+//                      into tokens, all lanes copy them, all lanes take the CRC-32, and the window goes out by st_store_span
+//                      (epg_text_scan.h) once the trailer agrees (zeros when it does not).  LDS: ~75 KB, so two workgroups -- two
+//                      waves -- per CU.
 //   * k_newline_index  a wave per segment, four per workgroup: 16 bytes per lane and turn, newlines counted four at a time in a
 //                      word, the wave's sum and maximum by shuffles.
 // Nothing synchronises.
 #include "epg_common.h"
 #include "epg_bgzf_inflate.h"
 #include "epg_bgzf_inflate_block.h"
+#include "epg_text_scan.h"
 
 namespace epg {
 
@@ -65,20 +67,8 @@ __global__ __launch_bounds__(BI_T) void k_bgzf_inflate(const unsigned char* __re
     }
     __syncthreads();
     const bool good = sh.status == epgbi::BI_OK;             // a member that was given up leaves zeros: two identical calls, identical bytes
-    const u32 a = sh.a, size = (u32)isize;
-    const unsigned char* bytes = reinterpret_cast<const unsigned char*>(sh.win4);
-    const uint4* chunks = reinterpret_cast<const uint4*>(sh.win4);
-    unsigned char* base = dst - a;
-    const int nchunks = (int)((a + size + 15u) >> 4);
-    for (int c = t; c < nchunks; c += BI_T) {
-        const u32 lo = 16u * c;
-        if (lo >= a && lo + 16u <= a + size) {
-            *reinterpret_cast<uint4*>(base + lo) = good ? chunks[c] : make_uint4(0, 0, 0, 0);
-        } else {
-            for (u32 j = 0; j < 16; ++j)
-                if (lo + j >= a && lo + j < a + size) base[lo + j] = good ? bytes[lo + j] : (unsigned char)0;
-        }
-    }
+    const u32 a = sh.a;
+    st_store_span(reinterpret_cast<const uint4*>(sh.win4), dst - a, a, (u32)isize, t, BI_T, !good);
 }
 
 constexpr int NL_WAVES = 4;

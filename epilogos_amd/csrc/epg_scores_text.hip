@@ -3,11 +3,11 @@
 // grid value is its digits: nothing is rounded.  The parser is strict and reports, never guesses: the first row that is not of
 // the grammar goes into the status word and the caller reads the file with the general reader instead.
 //
-//   k_st_index<false>  one workgroup per segment of ST_SEG bytes: the number of delimiters ('\t', '\n') of the segment.  A text
-//                      whose last byte is not '\n' (the end of a file without a final newline) has a virtual '\n' at position
-//                      nbytes, so positions 0 .. nbytes are indexed.
-//   k_st_scan          one workgroup: exclusive scan of the segment counts in place, the total D behind them; the number of whole
-//                      rows found (D / F) and, when the text holds more rows than the caller counted, the status.
+//   k_st_index<false>  st_text_index of epg_text_scan.h over tabs and newlines: one workgroup per segment of ST_SEG bytes, the
+//                      number of delimiters ('\t', '\n') of the segment.  A text whose last byte is not '\n' (the end of a file
+//                      without a final newline) has a virtual '\n' at position nbytes, so positions 0 .. nbytes are indexed.
+//   k_st_scan          one workgroup: exclusive scan of the segment counts in place (st_scan_segments), the total D behind them; the
+//                      number of whole rows found (D / F) and, when the text holds more rows than the caller counted, the status.
 //   k_st_index<true>   the same pass again: delim[i] = position of the i-th delimiter.
 //   k_st_parse         one thread per field: field k of row r lies between delimiters r * F + k - 1 and r * F + k.  The row shape
 //                      is checked field by field -- delimiter r * F + k must be '\t', or '\n' for k = F - 1 --, so the first
@@ -22,7 +22,7 @@
 // Nothing here reads outside text[0, nbytes) or writes outside rows row0 .. row0 + rows - 1 of the outputs, whatever the text
 // holds: positions come from the index of THIS text, and every field's thread is bounded by G <= rows * F and by D.
 #include "epg_common.h"
-#include "epg_text_scan.h"                                       // st_block_scan
+#include "epg_text_scan.h"
 #include "epilogos_scores_text.h"
 
 namespace epg {
@@ -34,47 +34,11 @@ static constexpr int ST_LDS_TEXT = 16384;            // bytes of text a parse wo
 static constexpr int ST_MAX_SCORE_LEN = 24;
 static constexpr int ST_MAX_FIELDS = 1 << 20;
 
-__device__ __forceinline__ bool st_is_delim(u32 c) { return c == '\t' || c == '\n'; }
-
-// bit j = position p0 + j is a delimiter, for the 16 positions from p0 (positions beyond nbytes are none)
-__device__ __forceinline__ u32 st_delim_mask(const char* __restrict__ text, long n, long p0) {
-    u32 m = 0;
-    if (p0 + 16 <= n) {
-        const uint4 v = ld16(text + p0);
-        const u32 w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-            if (st_is_delim((w[j >> 2] >> (8 * (j & 3))) & 0xffu)) m |= 1u << j;
-    } else {
-        for (int j = 0; j < 16; ++j) {
-            const long p = p0 + j;
-            if (p < n) {
-                if (st_is_delim((unsigned char)text[p])) m |= 1u << j;
-            } else if (p == n && n > 0 && text[n - 1] != '\n') {
-                m |= 1u << j;                                    // the virtual newline of a text that ends inside its last row
-            }
-        }
-    }
-    return m;
-}
-
 template <bool FILL>
 __global__ __launch_bounds__(ST_THREADS) void k_st_index(const char* __restrict__ text, long n, u32* __restrict__ seg,
                                                          u32* __restrict__ delim) {
     __shared__ u32 part[ST_THREADS / 64];
-    const long p0 = (long)blockIdx.x * ST_SEG + (long)threadIdx.x * 16;
-    u32 m = p0 <= n ? st_delim_mask(text, n, p0) : 0;
-    u32 total;
-    const u32 off = st_block_scan<ST_THREADS / 64>(__popc(m), part, &total);
-    if (!FILL) {
-        if (threadIdx.x == 0) seg[blockIdx.x] = total;
-    } else {
-        u32 at = seg[blockIdx.x] + off;
-        while (m) {
-            delim[at++] = (u32)(p0 + __ffs(m) - 1);
-            m &= m - 1;
-        }
-    }
+    st_text_index<FILL, ST_THREADS / 64>(text, n, seg, delim, 0xffffffffu, part, StIsTabOrNewline{});
 }
 
 __device__ __forceinline__ void st_report(unsigned long long* status, long row, int reason) {
@@ -86,15 +50,7 @@ __device__ __forceinline__ void st_report(unsigned long long* status, long row, 
 __global__ __launch_bounds__(ST_SCAN_THREADS) void k_st_scan(u32* __restrict__ seg, int nseg, int F, long rows, long row0,
                                                              long long* __restrict__ status) {
     __shared__ u32 part[ST_SCAN_THREADS / 64];
-    u32 carry = 0;
-    for (int i0 = 0; i0 < nseg; i0 += ST_SCAN_THREADS) {
-        const int i = i0 + (int)threadIdx.x;
-        const u32 v = i < nseg ? seg[i] : 0;
-        u32 total;
-        const u32 off = st_block_scan<ST_SCAN_THREADS / 64>(v, part, &total);
-        if (i < nseg) seg[i] = carry + off;
-        carry += total;
-    }
+    const u32 carry = st_scan_segments<ST_SCAN_THREADS / 64>(seg, nseg, part);
     if (threadIdx.x == 0) {
         seg[nseg] = carry;
         status[1] = (long long)(carry / (u32)F);

@@ -2,12 +2,14 @@
 // first bin and the state of every line and the run of lines of every chromosome of a table, and a chromosome's run -> its column
 // of int8 states.  The columns go into the matrix with k_sbl_transpose (epg_statebyline.hip).
 //
-// The parser is the index / scan / fill split of epg_scores_text.hip with lines for fields, and a second scan over the lines:
+// The parser is the index / scan / fill split of epg_scores_text.hip with lines for fields (st_text_index and st_scan_segments of
+// epg_text_scan.h), and a second scan over the lines:
 //
-//   k_seg_index<false>  one workgroup per segment of SEG_BLOCK bytes: the number of newlines of the segment.  A text whose last
-//                       byte is not '\n' has a virtual '\n' at position nbytes, so positions 0 .. nbytes are looked at.
-//   k_seg_scan          one workgroup: exclusive scan of the segment counts in place, the number of lines behind them; info, runs
-//                       and the per-chromosome words initialised.
+//   k_seg_index<false>  st_text_index over newlines: one workgroup per segment of SEG_BLOCK bytes, the number of newlines of the
+//                       segment.  A text whose last byte is not '\n' has a virtual '\n' at position nbytes, so positions
+//                       0 .. nbytes are looked at.
+//   k_seg_scan          one workgroup: exclusive scan of the segment counts in place (st_scan_segments), the number of lines behind
+//                       them; info, runs and the per-chromosome words initialised.
 //   k_seg_index<true>   the same pass again: nl[i] = position of the i-th newline.
 //   k_seg_parse         one thread per line.  The text of a workgroup's 256 lines is one contiguous span, staged in LDS the way
 //                       k_st_parse stages its fields (and read from global memory when a workgroup meets lines that long).  A
@@ -59,60 +61,20 @@ static constexpr int SEG_MIN_LINE = 8;
 
 static inline int64_t seg_lines(int64_t nbytes) { return nbytes / SEG_MIN_LINE + 2; }
 
-// bit j = position p0 + j ends a line, for the 16 positions from p0 (positions beyond nbytes end none)
-__device__ __forceinline__ u32 seg_newline_mask(const char* __restrict__ text, long n, long p0) {
-    u32 m = 0;
-    if (p0 + 16 <= n) {
-        const uint4 v = ld16(text + p0);
-        const u32 w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-            if (((w[j >> 2] >> (8 * (j & 3))) & 0xffu) == '\n') m |= 1u << j;
-    } else {
-        for (int j = 0; j < 16; ++j) {
-            const long p = p0 + j;
-            if (p < n) {
-                if (text[p] == '\n') m |= 1u << j;
-            } else if (p == n && n > 0 && text[n - 1] != '\n') {
-                m |= 1u << j;                                    // the virtual newline of a text that ends inside its last line
-            }
-        }
-    }
-    return m;
-}
+static_assert(SEG_THREAD_BYTES == 16, "st_text_index gives a thread 16 bytes of text");
 
 template <bool FILL>
 __global__ __launch_bounds__(SEG_THREADS) void k_seg_index(const char* __restrict__ text, long n, u32* __restrict__ seg,
                                                            u32* __restrict__ nl, u32 lmax) {
     __shared__ u32 part[SEG_THREADS / 64];
-    const long p0 = (long)blockIdx.x * SEG_BLOCK + (long)threadIdx.x * SEG_THREAD_BYTES;
-    u32 m = p0 <= n ? seg_newline_mask(text, n, p0) : 0;
-    u32 total;
-    const u32 off = st_block_scan<SEG_THREADS / 64>(__popc(m), part, &total);
-    if (!FILL) {
-        if (threadIdx.x == 0) seg[blockIdx.x] = total;
-    } else {
-        u32 at = seg[blockIdx.x] + off;
-        while (m && at < lmax) {
-            nl[at++] = (u32)(p0 + __ffs(m) - 1);
-            m &= m - 1;
-        }
-    }
+    st_text_index<FILL, SEG_THREADS / 64>(text, n, seg, nl, lmax, part, StIsNewline{});
 }
 
 // seg[0 .. nseg): counts -> exclusive offsets; seg[nseg] = the number of lines; the outputs initialised
 __global__ __launch_bounds__(SEG_SCAN_THREADS) void k_seg_scan(u32* __restrict__ seg, int nseg, long long* __restrict__ runs,
                                                                u32* __restrict__ cfirst, int nchrom, long long* __restrict__ info) {
     __shared__ u32 part[SEG_SCAN_THREADS / 64];
-    u32 carry = 0;
-    for (int i0 = 0; i0 < nseg; i0 += SEG_SCAN_THREADS) {
-        const int i = i0 + (int)threadIdx.x;
-        const u32 v = i < nseg ? seg[i] : 0;
-        u32 total;
-        const u32 off = st_block_scan<SEG_SCAN_THREADS / 64>(v, part, &total);
-        if (i < nseg) seg[i] = carry + off;
-        carry += total;
-    }
+    const u32 carry = st_scan_segments<SEG_SCAN_THREADS / 64>(seg, nseg, part);
     for (int c = threadIdx.x; c < nchrom; c += SEG_SCAN_THREADS) {
         cfirst[c] = 0xffffffffu;
         runs[3 * c] = runs[3 * c + 1] = runs[3 * c + 2] = 0;

@@ -6,7 +6,8 @@
 //
 //   k_sbl_count  one workgroup per segment of SBL_SEG bytes: the number of newlines of the segment.  A text whose last byte is not
 //                '\n' has a virtual '\n' at position nbytes, so positions 0 .. nbytes are looked at.
-//   k_sbl_scan   one workgroup: exclusive scan of the segment counts in place, the total behind them; info[] initialised.
+//   k_sbl_scan   one workgroup: exclusive scan of the segment counts in place (st_scan_segments of epg_text_scan.h); info[]
+//                initialised from the total.
 //   k_sbl_parse  the same walk again.  A thread holds 16 bytes of text and the 4 before them; the newline at byte j of its 16 ends
 //                line (newlines before it), and the line's 1 .. 3 digits are the bytes before j up to the previous newline: all inside
 //                the thread's 20-byte window.  The lines of a workgroup are consecutive bins, so their states are staged in LDS
@@ -36,7 +37,8 @@ static constexpr int SBL_TILE_BINS = 256;
 static constexpr int SBL_MAX_BATCH = 64;
 
 // The thread's window: w[] holds text[p0 - 4, p0 + 16) as 5 little-endian words (0 outside the text, '\n' at position n of a text
-// that ends inside its last line).  -> bit j = position p0 + j ends a line.
+// that ends inside its last line).  -> bit j = position p0 + j ends a line.  Not st_byte_mask of epg_text_scan.h: the parse needs the
+// four bytes before the thread's 16 in registers as well.
 __device__ __forceinline__ u32 sbl_window(const char* __restrict__ text, long n, long p0, u32 w[5]) {
     if (p0 >= 4 && p0 + 16 <= n) {
         __builtin_memcpy(&w[0], text + p0 - 4, 4);
@@ -73,15 +75,7 @@ __global__ __launch_bounds__(SBL_THREADS) void k_sbl_count(const char* __restric
 // seg[0 .. nseg): counts -> exclusive offsets; info initialised from the number of lines
 __global__ __launch_bounds__(SBL_SCAN_THREADS) void k_sbl_scan(u32* __restrict__ seg, int nseg, long long* __restrict__ info) {
     __shared__ u32 part[SBL_SCAN_THREADS / 64];
-    u32 carry = 0;
-    for (int i0 = 0; i0 < nseg; i0 += SBL_SCAN_THREADS) {
-        const int i = i0 + (int)threadIdx.x;
-        const u32 v = i < nseg ? seg[i] : 0;
-        u32 total;
-        const u32 off = st_block_scan<SBL_SCAN_THREADS / 64>(v, part, &total);
-        if (i < nseg) seg[i] = carry + off;
-        carry += total;
-    }
+    const u32 carry = st_scan_segments<SBL_SCAN_THREADS / 64>(seg, nseg, part);
     if (threadIdx.x == 0) {
         const long long rows = carry >= 2 ? (long long)carry - 2 : 0;
         info[0] = rows;

@@ -1,46 +1,48 @@
 // The device text writer (epg_textout.h): score text and its BGZF compression.  gfx950 only.
 //
-// Format, three launches on the caller's stream:
-//   * k_tw_lengths   a thread per row: the row's length from its location bytes and its values' digit counts (epg_fmt_f5.h: integer
-//                    arithmetic only), refused values and bad locations OR-ed into the flag word; the tile's sum by the workgroup
-//                    scan of epg_text_scan.h;
-//   * k_text_tile_offsets (epg_text_scan.h)  one workgroup: the exclusive scan of the tiles' sums, the text's size into row_off[R];
-//   * k_tw_write     a workgroup per TW_ROWS rows, a thread per row: the rows' offsets (the tile's offset + the workgroup scan of
-//                    their lengths) into row_off, then the text.  The rows' text is put together in LDS, a window of TW_WIN bytes
-//                    of the text at a time (a tile of 256 rows of an 18-state model is ~46 KB: two windows; a thread skips the
-//                    fields that lie outside the window), and every window goes out in 16-byte stores, aligned in the text: only the
-//                    up to 15 bytes at a tile's two ends, which share their 16 bytes with the neighbouring tile, are stored byte by
-//                    byte.  LDS: TW_WIN = 32 KB.
+// Format: the row writer of epg_text_rows.h (three launches on the caller's stream: lengths, tile offsets, write) with the score row as
+// its policy, TwRows: the location's bytes, then S times a tab and a "%.5f" value (epg_fmt_f5.h: integer arithmetic only).  Refused
+// values and bad locations are OR-ed into the flag word.  A tile of 256 rows of an 18-state model is ~46 KB, two windows: the policy
+// skips the values that lie in front of a window without formatting them and stops at the first one behind it.
 // Compress, three launches (the phases are in epg_bgzf_block.h, which also says what is matched):
 //   * k_bgzf_plan    a workgroup per block of 65 280 text bytes: histogram walk + CRC-32, one thread builds the code and the block
 //                    header, second walk for the threads' bit counts, workgroup scan (epg_text_scan.h), the block's record (size,
 //                    code, header bits, bit offsets: 2.3 KB) into the workspace.  LDS: ~9 KB.
-//   * k_bgzf_offsets one workgroup: the exclusive scan of the blocks' sizes, the stream's size into n_out.
+//   * k_bgzf_offsets one workgroup: the exclusive scan of the blocks' sizes (st_scan_chunks of epg_text_scan.h), the stream's size
+//                    into n_out.
 //   * k_bgzf_emit    a workgroup per block (and one for the end-of-file block): the member is put together in 64 KB of zeroed LDS
 //                    -- header, DEFLATE bits by atomic OR at the recorded bit offsets (third walk) or the stored bytes, CRC-32 and
-//                    ISIZE -- shifted so that 16-byte chunks of LDS are 16-byte chunks of `out`, and stored as the text is.
-//                    LDS: 64 KB + 1 KB, two workgroups per CU.
+//                    ISIZE -- shifted so that 16-byte chunks of LDS are 16-byte chunks of `out`, and stored by st_store_span
+//                    (epg_text_scan.h).  LDS: 64 KB + 1 KB, two workgroups per CU.
 // Nothing synchronises: the text's size reaches epgw_bgzf_compress as the host value n, see the header.
 #include "epg_common.h"
 #include "epg_textout.h"
-#include "epg_text_scan.h"
+#include "epg_text_rows.h"
 #include "epg_fmt_f5.h"
 #include "epg_bgzf_block.h"
 
 namespace epg {
 
-constexpr int TW_ROWS = 256;
-constexpr int TW_WIN = 32768;
+// the score row: its location and S values
+struct TwRow {
+    long long lo0, llen;                                     // the location's bytes in the blob, without their newline
+};
 
-__global__ __launch_bounds__(TW_ROWS) void k_tw_lengths(const float* __restrict__ scores, long R, int S, long ld, const long long* __restrict__ loc_off,
-                                                        u32* __restrict__ lens, u64* __restrict__ tile_sum, int* __restrict__ flags) {
-    __shared__ u32 s_part[TW_ROWS / 64];
-    const long r = (long)blockIdx.x * TW_ROWS + threadIdx.x;
-    u32 len = 0;
-    if (r < R) {
-        long long L = loc_off[r + 1] - loc_off[r] - 1;
-        int bad = 0;
+struct TwRows {
+    const float* scores;
+    long R;
+    int S;
+    long ld;
+    const char* loc;
+    const long long* loc_off;
+    using Row = TwRow;
+    static constexpr int FLAG_CAP = 2;
+
+    __device__ __forceinline__ u32 load(long r, TwRow& w, int& bad) const {
+        w.lo0 = loc_off[r];
+        long long L = loc_off[r + 1] - w.lo0 - 1;
         if (L < 0 || L > (1 << 20)) { L = 0; bad = 2; }      // (a location of a megabyte is no location: the tile's sum stays 32 bits)
+        w.llen = L;
         const float* row = scores + r * ld;
         for (int s = 0; s < S; ++s) {
             const u32 bits = __float_as_uint(row[s]);
@@ -48,81 +50,26 @@ __global__ __launch_bounds__(TW_ROWS) void k_tw_lengths(const float* __restrict_
             if (!epgfmt::f5_scale(bits, &q)) bad |= 1;
             L += 1 + epgfmt::f5_len(bits, q);
         }
-        len = (u32)(L + 1);
-        lens[r] = len;
-        if (bad) atomicOr(flags, bad);
+        return (u32)(L + 1);
     }
-    u32 total;
-    st_block_scan<TW_ROWS / 64>(len, s_part, &total);
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
-}
 
-__global__ __launch_bounds__(TW_ROWS) void k_tw_write(const float* __restrict__ scores, long R, int S, long ld, const char* __restrict__ loc,
-                                                      const long long* __restrict__ loc_off, const u32* __restrict__ lens, const u64* __restrict__ tile_off,
-                                                      long long* __restrict__ row_off, char* __restrict__ text, long long text_cap, int* __restrict__ flags) {
-    __shared__ uint4 s_win4[TW_WIN / 16];
-    __shared__ u32 s_part[TW_ROWS / 64];
-    char* win = reinterpret_cast<char*>(s_win4);
-    const int tid = threadIdx.x;
-    const long r0 = (long)blockIdx.x * TW_ROWS, r1 = r0 + TW_ROWS < R ? r0 + TW_ROWS : R, r = r0 + tid;
-    const u32 len = r < r1 ? lens[r] : 0u;
-    u32 tile_len;
-    const u32 before = st_block_scan<TW_ROWS / 64>(len, s_part, &tile_len);
-    const long long T0 = (long long)tile_off[blockIdx.x], T1 = T0 + tile_len;
-    const long long rs = T0 + before, re = rs + len;
-    if (r < r1) row_off[r] = rs;
-    if (row_off[R] > text_cap) {                             // (written by k_text_tile_offsets, before this kernel)
-        if (blockIdx.x == 0 && tid == 0) atomicOr(flags, 2);
-        return;
-    }
-    long long lo0 = 0, llen = 0;
-    if (r < r1) {
-        lo0 = loc_off[r];
-        llen = loc_off[r + 1] - lo0 - 1;
-        if (llen < 0 || llen > (1 << 20)) llen = 0;
-    }
-    for (long long w0 = T0 & ~15ll; w0 < T1; w0 += TW_WIN) {
-        const long long w1 = w0 + TW_WIN;
-        if (r < r1 && rs < w1 && re > w0) {
-            auto put = [&](long long at, char c) {
-                const long long k = at - w0;
-                if (k >= 0 && k < TW_WIN) win[k] = c;
-            };
-            long long i0 = w0 - rs, i1 = w1 - rs;
-            if (i0 < 0) i0 = 0;
-            if (i1 > llen) i1 = llen;
-            for (long long i = i0; i < i1; ++i) win[rs + i - w0] = loc[lo0 + i];
-            long long pos = rs + llen;
-            const float* row = scores + r * ld;
-            for (int s = 0; s < S && pos < w1; ++s) {
-                const u32 bits = __float_as_uint(row[s]);
-                uint64_t q;
-                epgfmt::f5_scale(bits, &q);
-                const int L = 1 + epgfmt::f5_len(bits, q);
-                if (pos + L > w0) {
-                    put(pos, '\t');
-                    const long long at = pos + 1;
-                    epgfmt::f5_emit(bits, q, [&](int i, char c) { put(at + i, c); });
-                }
-                pos += L;
-            }
-            put(re - 1, '\n');
-        }
-        __syncthreads();
-        const long long lo = w0 > T0 ? w0 : T0, hi = w1 < T1 ? w1 : T1;
-        for (int c = tid; c < TW_WIN / 16; c += TW_ROWS) {
-            const long long g = w0 + 16ll * c;
-            if (g >= hi || g + 16 <= lo) continue;
-            if (g >= lo && g + 16 <= hi) {
-                *reinterpret_cast<uint4*>(text + g) = s_win4[c];
+    __device__ __forceinline__ void emit(long r, const TwRow& w, TextSink& sink) const {
+        sink.bytes(loc + w.lo0, w.llen);
+        const float* row = scores + r * ld;
+        for (int s = 0; s < S && !sink.past(); ++s) {
+            const u32 bits = __float_as_uint(row[s]);
+            uint64_t q;
+            epgfmt::f5_scale(bits, &q);
+            const int L = 1 + epgfmt::f5_len(bits, q);
+            if (sink.in_front(L)) {
+                sink.skip(L);
             } else {
-                for (int j = 0; j < 16; ++j)
-                    if (g + j >= lo && g + j < hi) text[g + j] = win[16 * c + j];
+                sink.put('\t');
+                sink.skip(epgfmt::f5_emit(bits, q, sink.at()));
             }
         }
-        __syncthreads();
     }
-}
+};
 
 // ---- BGZF ----------------------------------------------------------------------------------------------------------------------------
 using epgbg::BG_T;
@@ -162,21 +109,10 @@ __global__ __launch_bounds__(BG_T) void k_bgzf_plan(const unsigned char* __restr
 
 __global__ __launch_bounds__(BG_SCAN_THREADS) void k_bgzf_offsets(const epgbg::Rec* __restrict__ recs, long nblocks, int eof, long long* __restrict__ blk_off,
                                                                   long long* __restrict__ n_out) {
-    __shared__ long long s_sum[BG_SCAN_THREADS];
-    const int tid = threadIdx.x;
-    const long chunk = (nblocks + BG_SCAN_THREADS - 1) / BG_SCAN_THREADS;
-    const long lo = tid * chunk < nblocks ? tid * chunk : nblocks, hi = lo + chunk < nblocks ? lo + chunk : nblocks;
-    long long sum = 0;
-    for (long b = lo; b < hi; ++b) sum += recs[b].size;
-    s_sum[tid] = sum;
-    __syncthreads();
-    long long run = 0;
-    for (int k = 0; k < tid; ++k) run += s_sum[k];
-    for (long b = lo; b < hi; ++b) {
-        blk_off[b] = run;
-        run += recs[b].size;
-    }
-    if (tid == BG_SCAN_THREADS - 1) {
+    __shared__ u64 s_sum[BG_SCAN_THREADS];
+    const long long run = (long long)st_scan_chunks<BG_SCAN_THREADS>(nblocks, s_sum, [&](long b) { return (u64)recs[b].size; },
+                                                                     [&](long b, u64 x) { blk_off[b] = (long long)x; });
+    if (threadIdx.x == BG_SCAN_THREADS - 1) {
         blk_off[nblocks] = run;
         n_out[0] = run + (eof ? 28 : 0);
     }
@@ -227,30 +163,10 @@ __global__ __launch_bounds__(BG_T) void k_bgzf_emit(const unsigned char* __restr
         epgbg::emit_tokens(words, a, rec, s_code, s_len, text, rw, B0, B1, t);
     }
     __syncthreads();
-    unsigned char* base = out + (at - a);
-    for (int c = t; c < nchunks; c += BG_T) {
-        const u32 lo = 16u * c;
-        if (lo >= a && lo + 16u <= a + size) {
-            *reinterpret_cast<uint4*>(base + lo) = s_stage4[c];
-        } else {
-            for (u32 j = 0; j < 16; ++j)
-                if (lo + j >= a && lo + j < a + size) base[lo + j] = bytes[lo + j];
-        }
-    }
+    st_store_span(s_stage4, out + (at - a), a, size, t, BG_T);
 }
 
 // ---- entry points ----------------------------------------------------------------------------------------------------------------
-struct TwLayout {
-    int64_t lens, tiles, total, ntiles;
-};
-
-static void tw_layout(int64_t R, TwLayout& L) {
-    L.ntiles = (R + TW_ROWS - 1) / TW_ROWS;
-    L.lens = 0;
-    L.tiles = align_up((R > 0 ? R : 1) * 4, 256);
-    L.total = L.tiles + align_up((L.ntiles > 0 ? L.ntiles : 1) * 8, 256);
-}
-
 static int64_t bg_blocks(int64_t n) { return (n + BG_TEXT - 1) / BG_TEXT; }
 static int64_t bg_recs_at(int64_t nblocks) { return align_up((nblocks + 1) * 8, 256); }
 
@@ -267,9 +183,7 @@ extern "C" int64_t epgw_format_ws_bytes(int64_t R) {
         fail(EPG_ERR_INVALID_ARG, "format_ws_bytes: bad shape R=%lld", (long long)R);
         return -1;
     }
-    TwLayout L;
-    tw_layout(R, L);
-    return L.total;
+    return text_rows_ws_bytes(R);
 }
 
 extern "C" int epgw_format_scores(const float* scores, int64_t R, int32_t S, int64_t ld, const char* loc, const int64_t* loc_off, char* text,
@@ -279,35 +193,9 @@ extern "C" int epgw_format_scores(const float* scores, int64_t R, int32_t S, int
     if (R > 0 && !scores) return fail(EPG_ERR_INVALID_ARG, "format_scores: scores is NULL");
     if (R > 0 && !loc) return fail(EPG_ERR_INVALID_ARG, "format_scores: loc is NULL");
     if (R > 0 && !loc_off) return fail(EPG_ERR_INVALID_ARG, "format_scores: loc_off is NULL");
-    if (!text) return fail(EPG_ERR_INVALID_ARG, "format_scores: text is NULL");
-    if (!row_off) return fail(EPG_ERR_INVALID_ARG, "format_scores: row_off is NULL");
-    if (!flags) return fail(EPG_ERR_INVALID_ARG, "format_scores: flags is NULL");
-    if (!ws) return fail(EPG_ERR_INVALID_ARG, "format_scores: ws is NULL");
-    if (reinterpret_cast<uintptr_t>(text) & 255) return fail(EPG_ERR_INVALID_ARG, "format_scores: text is not 256-byte aligned");
-    if (reinterpret_cast<uintptr_t>(ws) & 255) return fail(EPG_ERR_INVALID_ARG, "format_scores: ws is not 256-byte aligned");
-    if (text_cap < 0) return fail(EPG_ERR_INVALID_ARG, "format_scores: text_cap=%lld < 0", (long long)text_cap);
-    TwLayout L;
-    tw_layout(R, L);
-    if (ws_bytes < L.total) return fail(EPG_ERR_WORKSPACE, "format_scores: workspace %lld < %lld bytes", (long long)ws_bytes, (long long)L.total);
-    hipStream_t st = (hipStream_t)stream;
-    char* base = static_cast<char*>(ws);
-    u32* lens = reinterpret_cast<u32*>(base + L.lens);
-    u64* tiles = reinterpret_cast<u64*>(base + L.tiles);
-    long long* roff = reinterpret_cast<long long*>(row_off);
-    const long long* loff = reinterpret_cast<const long long*>(loc_off);
-    EPG_HIP(hipMemsetAsync(flags, 0, sizeof(int32_t), st));
-    if (L.ntiles) {
-        hipLaunchKernelGGL(k_tw_lengths, dim3((unsigned)L.ntiles), dim3(TW_ROWS), 0, st, scores, (long)R, (int)S, (long)ld, loff, lens, tiles, flags);
-        EPG_LAUNCH_CHECK("k_tw_lengths");
-    }
-    hipLaunchKernelGGL(k_text_tile_offsets<1024>, dim3(1), dim3(1024), 0, st, tiles, (long)L.ntiles, (long)R, roff);
-    EPG_LAUNCH_CHECK("k_text_tile_offsets");
-    if (L.ntiles) {
-        hipLaunchKernelGGL(k_tw_write, dim3((unsigned)L.ntiles), dim3(TW_ROWS), 0, st, scores, (long)R, (int)S, (long)ld, loc, loff, (const u32*)lens,
-                           (const u64*)tiles, roff, text, (long long)text_cap, flags);
-        EPG_LAUNCH_CHECK("k_tw_write");
-    }
-    return EPG_OK;
+    if (const int rc = text_rows_check_out("format_scores", text, text_cap, row_off, flags, ws, ws_bytes, text_rows_ws_bytes(R))) return rc;
+    const TwRows p = {scores, (long)R, (int)S, (long)ld, loc, reinterpret_cast<const long long*>(loc_off)};
+    return text_rows_launch(p, R, text, text_cap, row_off, flags, ws, (hipStream_t)stream, "k_tw_lengths", "k_tw_write");
 }
 
 extern "C" int64_t epgw_bgzf_bytes_max(int64_t n, int32_t eof) {

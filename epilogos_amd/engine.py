@@ -684,6 +684,21 @@ def bgzf_compress(text, n, row_off=None, eof=True, out=None, ws=None):
     return out, n_out, flags
 
 
+def _compress_formatted(text, row_off, flags, rows, ws, eof):
+    """What format_scores / format_metrics just left in (text, row_off, flags) for `rows` rows, compressed by bgzf_compress into the
+    device's "out" buffer -> (out, n_bytes); None when a format flag is set.  Synchronises twice: the text's size comes back between
+    the two kernels' calls (the synchronisation csrc/epg_textout.h documents), the stream's size after them."""
+    n, flag = (int(v) for v in torch.stack([row_off[rows], flags[0].to(torch.int64)]).cpu())
+    if flag:
+        return None
+    out = _text_buf(text.device, "out", _abi.call("epgw_bgzf_bytes_max", n, int(bool(eof))))
+    out, n_out, flags = bgzf_compress(text, n, row_off, eof=eof, out=out, ws=ws)
+    n_bytes, flag = (int(v) for v in torch.stack([n_out[0], flags[0].to(torch.int64)]).cpu())
+    if flag:
+        raise EpilogosHipError(-3, "the BGZF stream did not fit its own bound")
+    return out, n_bytes
+
+
 def scores_text_bgzf(locations, scores_device, eof=False):
     """A part's score file on the device: the text of format_scores for `locations` (a _io.Locations, uploaded here) and the float32
     [R, S] scores where they sit, compressed by bgzf_compress -> (uint8 device tensor, n_bytes): the file's bytes are the first
@@ -702,15 +717,7 @@ def scores_text_bgzf(locations, scores_device, eof=False):
     text = _text_buf(dev, "text", _abi.call("epgw_text_bytes_max", R, S, int(off[-1] - off[0]) if R else 0))
     ws = _text_buf(dev, "ws", max(_abi.call("epgw_format_ws_bytes", R), _abi.call("epgw_bgzf_ws_bytes", text.numel())))
     text, row_off, flags = format_scores(scores_device, loc, loc_off, text=text, ws=ws)
-    n, flag = (int(v) for v in torch.stack([row_off[R], flags[0].to(torch.int64)]).cpu())
-    if flag:
-        return None
-    out = _text_buf(dev, "out", _abi.call("epgw_bgzf_bytes_max", n, int(bool(eof))))
-    out, n_out, flags = bgzf_compress(text, n, row_off, eof=eof, out=out, ws=ws)
-    n_bytes, flag = (int(v) for v in torch.stack([n_out[0], flags[0].to(torch.int64)]).cpu())
-    if flag:
-        raise EpilogosHipError(-3, "the BGZF stream did not fit its own bound")
-    return out, n_bytes
+    return _compress_formatted(text, row_off, flags, R, ws, eof)
 
 
 # ---- the device metrics writer (csrc/epg_metrics_text.h): epilogos --metrics gpu
@@ -796,15 +803,10 @@ def metrics_text_bgzf(chromNames, chrom_idx, start, end, stateNames, maxdiff, di
                                               up(end, lo, hi, np.int64), names, names_off, names_bytes, up(maxdiff, lo, hi, np.int32),
                                               up(dist, lo, hi, np.float32), up(pvals, lo, hi, np.float64) if with_p else None,
                                               up(mh, lo, hi, np.float64) if with_p else None, text=text, ws=ws)
-        n, flag = (int(v) for v in torch.stack([row_off[n_rows], flags[0].to(torch.int64)]).cpu())
-        if flag:
+        done = _compress_formatted(text, row_off, flags, n_rows, ws, False)
+        if done is None:
             return None
-        out = _text_buf(dev, "out", _abi.call("epgw_bgzf_bytes_max", n, 0))
-        out, n_out, flags = bgzf_compress(text, n, row_off, eof=False, out=out, ws=ws)
-        n_bytes, flag = (int(v) for v in torch.stack([n_out[0], flags[0].to(torch.int64)]).cpu())
-        if flag:
-            raise EpilogosHipError(-3, "the BGZF stream did not fit its own bound")
-        pieces.append(out[:n_bytes].cpu().numpy())
+        pieces.append(done[0][:done[1]].cpu().numpy())
     return pieces
 
 

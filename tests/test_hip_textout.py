@@ -119,6 +119,24 @@ def test_the_text_is_the_host_writer_s(eng, inputs, name, pad):
     assert (ends == 10).all() and want.count(b"\n") == x.shape[0]
 
 
+def test_a_row_that_crosses_two_window_boundaries(eng, tmp_path):
+    """Three rows, S = 2; the middle row's location is 70 000 bytes long, so the row begins in one 32 KB window of the text, fills the
+    next completely and ends in a third: the only way a single row's bytes are split between windows."""
+    rows = [b"chr1\t0\t200\n", b"c" + b"A" * 70000 + b"\t200\t400\n", b"chr1\t400\t600\n"]
+    off = np.zeros(4, dtype=np.int64)
+    np.cumsum([len(x) for x in rows], out=off[1:])
+    loc = _io.Locations(np.frombuffer(b"".join(rows), dtype=np.uint8).copy(), off)
+    x = np.array([[0.25, -1.5], [3.125, -0.00001], [12345.678, 0.0]], dtype=np.float32)
+    want = host_text(tmp_path, loc, x)
+    assert want.count(b"\n") == 3 and want.startswith(b"chr1\t0\t200\t0.25000\t-1.50000\nc" + b"A" * 70000 + b"\t200\t400\t3.12500\t")
+    text, row_off, flag = device_text(eng, loc, x)
+    o = row_off.cpu().numpy()
+    assert flag == 0 and o[0] == 0 and o[-1] == len(want)
+    assert o[1] < 32768 and o[2] > 65536 + 16                   # the middle row: from inside the first window into the third
+    assert text[:len(want)].cpu().numpy().tobytes() == want
+    assert (np.frombuffer(want, dtype=np.uint8)[o[1:] - 1] == 10).all()
+
+
 def test_every_edge_value_alone(eng, tmp_path):
     """(R, S) = (1, 1) holds one value: each edge value in turn, and as a column, so that every one of them is formatted."""
     e = edge_values()
