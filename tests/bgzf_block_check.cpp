@@ -4,6 +4,9 @@
 //       -o bgzf_block_check && ./bgzf_block_check
 // Every case must round-trip through zlib's inflate (which checks each member's CRC-32 and ISIZE), every member must be at most
 // 65 536 bytes with BSIZE = its size - 1, and the cases with repeated rows must come out below their zeroth-order entropy.
+// The hostile families of tests/bgzf_hostile.py are built here again from the same recipes (deep alphabets that need the 15-bit and
+// the 7-bit cut, a ladder of every match length and of both ends of every distance symbol, one-byte, long and empty rows, rows across
+// block borders); for the two deep alphabets the code's depth is asserted on the builder's own state.
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -27,12 +30,15 @@ static uint32_t rnd() {
     return (uint32_t)(g_state >> 11);
 }
 
+static int g_max_len, g_max_cllen;                                             // over the blocks of the last compress(): the deepest codes
+
 static std::vector<unsigned char> compress(const std::vector<unsigned char>& text, const std::vector<long long>* rows, bool eof, long long* stored_blocks) {
     const long long n = (long long)text.size();
     const long long nb = (n + BG_TEXT - 1) / BG_TEXT;
     const Rows rw = make_rows(rows ? rows->data() : nullptr, rows ? (long long)rows->size() - 1 : 0, n);
     std::vector<Rec> recs((size_t)nb);
     *stored_blocks = 0;
+    g_max_len = g_max_cllen = 0;
     for (long long b = 0; b < nb; ++b) {
         const long long B0 = b * BG_TEXT, B1 = B0 + BG_TEXT < n ? B0 + BG_TEXT : n;
         static Shared sh;
@@ -42,6 +48,8 @@ static std::vector<unsigned char> compress(const std::vector<unsigned char>& tex
         for (int t = 0; t < BG_T; ++t) plan_hist(sh, text.data(), rw, B0, B1, t);
         sh.hist[256] += 1;
         build_block_code(sh);
+        for (int i = 0; i < BG_NSYM; ++i) g_max_len = sh.len[i] > g_max_len ? sh.len[i] : g_max_len;
+        for (int i = 0; i < 19; ++i) g_max_cllen = sh.cllen[i] > g_max_cllen ? sh.cllen[i] : g_max_cllen;
         u32 total = 0;
         for (int t = 0; t < BG_T; ++t) {
             rec.tbits[t] = sh.hdr_bits + total;
@@ -150,6 +158,132 @@ static int check(const char* what, const std::vector<unsigned char>& text, const
     return 0;
 }
 
+// ---- the hostile families (tests/bgzf_hostile.py) ------------------------------------------------------------------------------------
+static const unsigned char ALPHA[17] = "0123456789.-\tchr";
+static unsigned char letter() { return ALPHA[rnd() % 16]; }
+static unsigned char other(unsigned char c) {                                  // a letter that is not c
+    int k = 0;
+    while (k < 16 && ALPHA[k] != c) ++k;
+    return ALPHA[(k + 1 + (int)(rnd() % 15)) % 16];
+}
+static void end_row(const std::vector<unsigned char>& text, std::vector<long long>& rows) { rows.push_back((long long)text.size()); }
+
+static void ladder_lengths(std::vector<unsigned char>& text, std::vector<long long>& rows) {
+    text.clear();
+    rows.assign(1, 0);
+    for (int k = 0; k < 300; ++k) text.push_back(letter());
+    end_row(text, rows);
+    for (int r = 0; r < 255; ++r) {                                            // 222 and 223 again: the first block's border takes their rows
+        const int L = r < 253 ? 6 + r : 222 + (r - 253);
+        for (int k = 0; k < 300; ++k) {
+            const unsigned char up = text[text.size() - 300];
+            text.push_back(k < L ? up : other(up));
+        }
+        end_row(text, rows);
+    }
+}
+static void ladder_distances(std::vector<unsigned char>& text, std::vector<long long>& rows) {
+    std::vector<int> ds = {1, 2, 3, 4};
+    for (int sym = 4; sym < 30; ++sym) {
+        const int nb = sym / 2 - 1, lo = 1 + ((2 + (sym & 1)) << nb);
+        ds.push_back(lo);
+        ds.push_back(lo + (1 << nb) - 1);
+    }
+    ds.push_back(32769);
+    ds.push_back(40000);
+    text.clear();
+    rows.assign(1, 0);
+    for (int d : ds) {
+        for (int k = 0; k < d; ++k) text.push_back(text.size() >= 40 ? other(text[text.size() - 40]) : letter());
+        end_row(text, rows);
+        for (int k = 0; k < 40; ++k) text.push_back(text[text.size() - (size_t)d]);
+        end_row(text, rows);
+    }
+}
+static void shuffle(std::vector<unsigned char>& t) {
+    for (size_t i = t.size(); i > 1; --i) {
+        const size_t j = rnd() % i;
+        const unsigned char x = t[i - 1];
+        t[i - 1] = t[j];
+        t[j] = x;
+    }
+}
+static void chain(std::vector<unsigned char>& text) {
+    text.clear();
+    long long a = 1, b = 2;
+    for (int k = 0; k < 21; ++k) {
+        text.insert(text.end(), (size_t)a, (unsigned char)k);
+        const long long c = a + b;
+        a = b;
+        b = c;
+    }
+    shuffle(text);
+}
+static void dyadic(std::vector<unsigned char>& text) {
+    const int per[16] = {0, 0, 0, 0, 6, 12, 5, 16, 5, 7, 1, 16, 0, 1, 1, 153};
+    text.clear();
+    int v = 0;
+    for (int L = 4; L <= 15; ++L)
+        for (int c = 0; c < per[L]; ++c) text.insert(text.end(), (size_t)1 << (15 - L), (unsigned char)v++);
+    shuffle(text);
+}
+static void one_byte_rows(std::vector<unsigned char>& text, std::vector<long long>& rows) {
+    text.clear();
+    rows.assign(1, 0);
+    for (int r = 0; r < 70000; ++r) {
+        text.push_back(r > 0 && rnd() % 3 < 2 ? text.back() : letter());
+        end_row(text, rows);
+    }
+}
+static void long_rows(std::vector<unsigned char>& text, std::vector<long long>& rows) {
+    text.clear();
+    rows.assign(1, 0);
+    std::vector<unsigned char> a(50000), b(32768);
+    for (auto& c : a) c = letter();
+    for (auto& c : b) c = letter();
+    for (int r = 0; r < 8; ++r) {
+        const std::vector<unsigned char>& row = r < 3 ? a : b;
+        text.insert(text.end(), row.begin(), row.end());
+        end_row(text, rows);
+    }
+}
+static void empty_rows(std::vector<unsigned char>& text, std::vector<long long>& rows) {
+    text.clear();
+    rows.assign(1, 0);
+    for (int r = 0; r < 3000; ++r) {
+        if (r % 4 == 1) {
+            const std::vector<unsigned char> up(text.end() - 57, text.end());
+            text.insert(text.end(), up.begin(), up.end());
+        } else if (r % 4 != 2)
+            for (int k = 0; k < 57; ++k) text.push_back(letter());
+        end_row(text, rows);
+    }
+}
+static void border(int pad, std::vector<unsigned char>& text, std::vector<long long>& rows) {
+    text.clear();
+    rows.assign(1, 0);
+    std::vector<unsigned char> row(300);
+    for (auto& c : row) c = letter();
+    if (pad) {
+        for (int k = 0; k < pad; ++k) text.push_back(letter());
+        end_row(text, rows);
+    }
+    for (int r = 0; r < 652; ++r) {
+        text.insert(text.end(), row.begin(), row.end());
+        end_row(text, rows);
+    }
+}
+
+// a deep alphabet: one block, not stored, the literal/length code exactly 15 bits deep, the code-length code want_cl (0: any)
+static int check_deep(const char* what, const std::vector<unsigned char>& text, int want_cl) {
+    if (check(what, text, nullptr, 0, false)) return 1;
+    if (text.size() > (size_t)BG_TEXT || g_max_len != 15 || (want_cl && g_max_cllen != want_cl)) {
+        printf("%s: deepest code %d bits (wanted 15), code-length code %d (wanted %d)\n", what, g_max_len, g_max_cllen, want_cl);
+        return 1;
+    }
+    return 0;
+}
+
 int main() {
     std::vector<unsigned char> text;
     std::vector<long long> rows;
@@ -179,6 +313,24 @@ int main() {
     }
     text.assign(200000, 'a');
     bad |= check("one byte repeated, no rows", text, nullptr, 0, false);
+    chain(text);
+    bad |= check_deep("chain: Fibonacci weights", text, 0);
+    dyadic(text);
+    bad |= check_deep("dyadic: 15 bits, nothing to cut", text, 7);
+    ladder_lengths(text, rows);
+    bad |= check("ladder of lengths 6 .. 258", text, &rows, 0, false);
+    ladder_distances(text, rows);
+    bad |= check("ladder of distances", text, &rows, 0, false);
+    one_byte_rows(text, rows);
+    bad |= check("70000 rows of one byte", text, &rows, 0, false);
+    long_rows(text, rows);
+    bad |= check("rows of 50000 and 32768 bytes", text, &rows, 0, false);
+    empty_rows(text, rows);
+    bad |= check("every fourth row empty", text, &rows, 0, false);
+    for (int pad : {0, 180, 179}) {
+        border(pad, text, rows);
+        bad |= check("equal rows across block borders", text, &rows, 0, true);
+    }
     printf(bad ? "bgzf_block_check: FAILED\n" : "bgzf_block_check: ok\n");
     return bad;
 }

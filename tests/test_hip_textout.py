@@ -285,14 +285,15 @@ def test_size_conditions(streams):
 
 def s_compress(abi, want, off, eof, n_out):
     sp = Spec(18)
-    R = len(off) - 1
+    R = 0 if off is None else len(off) - 1                                      # (None: no row offsets, the pointer is NULL)
     sp.inp("text", np.frombuffer(want, dtype=U8), mis=3)
-    sp.inp("row_off", off, mis=8)
+    if off is not None:
+        sp.inp("row_off", off, mis=8)
     sp.out("out", U8, n_out)                                                    # exactly the stream: a byte beyond it lands in the guard
     sp.out("n_out", I64, 1, mis=8)
     sp.out("flags", I32, 1, mis=4)
     sp.ws("ws", abi.call("epgw_bgzf_ws_bytes", len(want)))
-    sp.call = lambda abi, P, st: abi.call("epgw_bgzf_compress", P["text"], len(want), P["row_off"], R, int(eof), P["out"], n_out, P["n_out"], P["flags"],
+    sp.call = lambda abi, P, st: abi.call("epgw_bgzf_compress", P["text"], len(want), P.get("row_off"), R, int(eof), P["out"], n_out, P["n_out"], P["flags"],
                                           P["ws"], sp.nbytes("ws"), st)
 
     def verify(o):
