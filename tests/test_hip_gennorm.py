@@ -4,7 +4,11 @@ The negative log-likelihood is held against scipy's on float64 within tests/genn
 fit of the same sub-sample with the one-sided condition of tests/test_gennorm_host.py (scipy's nnlf at the device's parameters is
 at most scipy's nnlf at scipy's parameters plus fmin's ftol), on samples and sub-samples for which the numpy restatement of the
 algorithm satisfies it (tests/test_gennorm_host.py runs the restatement on FIT_CASES without a GPU).  Two points have no maximum likelihood
-(beta grows without bound): scipy's fmin stops at its cap there and so does the kernel, flag 1; every other case must converge."""
+(beta grows without bound): scipy's fmin stops at its cap there and so does the kernel, flag 1; every other case must converge.
+
+The later turns of the kernels' loops have cases of their own, each with its arithmetic asserted from constants restated beside it: the
+fit's sweeps of 1024 groups of four values (n = 4101, 8195 and the command's default 100000), the nnlf pass's second and later chunk of a
+workgroup on the one-CU grid of tests/grid_cap.py, its second and third tile of 256 parameter sets."""
 import ctypes as C
 
 import numpy as np
@@ -13,6 +17,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from tests import gennorm_ref as ref
+from tests.grid_cap import capped_and_not, cdiv
 from tests.test_gennorm_host import no_worse_than_scipy, refusals, scipy_nnlf
 
 pytestmark = pytest.mark.gpu
@@ -32,14 +37,42 @@ FIT_CASES = [
     ("signedsq", 3000, 3, False, 0, 0),
     ("rounded", 257, 101, False, 0, 0),
     ("signedsq", 2, 1, False, 1, 0),
+    # sweeps beyond the first: a thread of the fit's workgroup takes group tid, tid + 1024, ... of four values (sweeps_of below).
+    # 4097: 1024 groups and a tail of one, the last one-sweep shape; 4101: the smallest n with a tail at which thread 0 takes a second
+    # group; 8195: two whole sweeps and a tail of three; 100000: the command's default -z, 25 sweeps (thread 0) and 24 (the others)
+    ("signedsq", 4097, 3, True, 0, 3),
+    ("rounded", 4097, 1, False, 0, 0),
+    ("gennorm06", 4101, 3, True, 0, 0),
+    ("gennorm2", 4101, 1, False, 0, 0),
+    ("gennorm2", 8195, 3, True, 0, 0),
+    ("signedsq", 8195, 1, False, 0, 0),
+    ("signedsq", 100000, 2, True, 0, 2),
+    ("gennorm06", 100000, 1, False, 0, 0),
 ]
+# the size of the sample a case draws from: M0, and more for the sizes that M0 does not hold twice over
+M0_OF = {8195: 20000, 100000: 120000}
 IDS = ["%s-n%d-T%d-%s" % (f, n, T, "idx" if i else "all") for f, n, T, i, _flag, _seed in FIT_CASES]
 
 
 def case_inputs(family, n, T, with_idx, seed=0):
     """-> (x float32 [M], idx int32 [T, n] or None)"""
-    x = ref.sample(family, M0)
-    return (x, ref.sub_samples(M0, T, n, seed)) if with_idx else (x[:n].copy(), None)
+    M = M0_OF.get(n, M0)
+    assert M >= n
+    x = ref.sample(family, M)
+    return (x, ref.sub_samples(M, T, n, seed)) if with_idx else (x[:n].copy(), None)
+
+
+GN_THREADS, GN_GROUP = 1024, 4               # k_gennorm_fit: threads of a trial's workgroup, floats of a group (epg_gennorm.hip)
+
+
+def sweeps_of(n):
+    """(groups, tail, turns of the gather / gn_block_sum loop that thread 0 runs, turns of the workgroup's last thread)."""
+    groups = n // GN_GROUP
+    return groups, n % GN_GROUP, -(-groups // GN_THREADS), groups // GN_THREADS
+
+
+def case_of(family, n, T, with_idx):
+    return FIT_CASES.index(next(c for c in FIT_CASES if c[:4] == (family, n, T, with_idx)))
 
 
 @pytest.fixture(scope="module")
@@ -151,6 +184,67 @@ def test_nnlf_does_not_depend_on_T_or_the_call(abi):
         assert np.array_equal(bits(raw_nnlf(abi, x, p[t:t + 1])), bits(whole[t:t + 1])), t
 
 
+# ---- nnlf: a workgroup's second and later chunks, the second and third tile of parameter sets ---------------------------------------
+GN_CHUNK, GN_TT, GN_GRID_PER_CU = 1024, 256, 8   # epg_gennorm.hip: values per chunk, sets per LDS tile (and per finish workgroup), workgroups per CU
+
+
+def nnlf_chunks_per_workgroup(M, cus):
+    """(fewest, most) chunks that a workgroup of k_gennorm_nnlf_partial walks with c += gridDim.x on a device of `cus` CUs."""
+    chunks = cdiv(M, GN_CHUNK)
+    grid = min(chunks, GN_GRID_PER_CU * cus)
+    return chunks // grid, cdiv(chunks, grid)
+
+
+def hold_nnlf_against_scipy(x, p, got):
+    """Every valid set of p within ref.nnlf_bound of scipy, every other one +inf -> the largest |device - scipy| / bound."""
+    worst = 0.0
+    for t in range(len(p)):
+        if not (p[t, 0] > 0 and p[t, 2] > 0) or np.isnan(p[t]).any():
+            assert got[t] == np.inf, (t, p[t], got[t])
+            continue
+        want, bound = scipy_nnlf(p[t], x), ref.nnlf_bound(p[t], x)
+        worst = max(worst, abs(got[t] - want) / bound)
+        assert abs(got[t] - want) <= bound, "set %d %s: %.17g, scipy %.17g, bound %.3g" % (t, p[t], got[t], want, bound)
+    return worst
+
+
+@pytest.mark.parametrize("M", [9217, 70001])
+def test_nnlf_chunk_turns_on_the_one_cu_grid(abi, M):
+    """c += gridDim.x: 8 workgroups on the one-CU grid.  9217 values are 10 chunks, two workgroups take two and six take one; 70001
+    are 69 chunks, eight or nine per workgroup.  The sums are added per chunk, in chunk order: the grid must not change a bit."""
+    assert nnlf_chunks_per_workgroup(M, 1) == {9217: (1, 2), 70001: (8, 9)}[M]
+    if M == 70001:
+        assert nnlf_chunks_per_workgroup(M, 1)[0] >= 3
+    assert nnlf_chunks_per_workgroup(M, abi.call("epg_device_cus")) == (1, 1)            # what every other test of this module runs
+    x = ref.sample("signedsq", M)
+    sets = nnlf_params(x, 8)
+    sets[3] = INVALID[M % len(INVALID)]
+    got = capped_and_not(abi, lambda: {"nnlf": raw_nnlf(abi, x, sets)})["nnlf"]
+    print("M=%d on one CU: largest |device - scipy| / bound = %.3g" % (M, hold_nnlf_against_scipy(x, sets, got)))
+
+
+@pytest.mark.parametrize("T", [256, 257, 600])
+@pytest.mark.parametrize("M", [1023, 9217])
+def test_nnlf_tiles_of_parameter_sets(abi, M, T):
+    """t0 += GN_TT in k_gennorm_nnlf_partial, and 256 sets per workgroup of k_gennorm_nnlf_finish: one whole tile, a second tile of one
+    set, three tiles with a ragged last; 9217 values: the tiles inside the second and later chunk too."""
+    tiles = cdiv(T, GN_TT)
+    assert tiles == {256: 1, 257: 2, 600: 3}[T] and (T % GN_TT != 0) == (T != 256)
+    x = ref.sample("signedsq", M)
+    sets = nnlf_params(x, T)
+    # invalid sets: the last of the first tile, then one in every later tile that holds a valid set beside it (the second tile of
+    # T = 257 is ONE set: it stays valid, so that its value is held against scipy)
+    planted = [t for t in (GN_TT - 1, GN_TT + 1, 2 * GN_TT + 3) if t < T]
+    assert [t // GN_TT for t in planted] == list(range(tiles if T != GN_TT + 1 else 1))
+    for j, t in enumerate(planted):
+        sets[t] = INVALID[(M + T + j) % len(INVALID)]
+    got = raw_nnlf(abi, x, sets)
+    assert (got[planted] == np.inf).all()
+    print("M=%d T=%d: largest |device - scipy| / bound = %.3g" % (M, T, hold_nnlf_against_scipy(x, sets, got)))
+    for t in sorted({0, GN_TT - 2, GN_TT - 1, GN_TT, GN_TT + 1, 2 * GN_TT - 1, 2 * GN_TT, T - 1} & set(range(T))):
+        assert np.array_equal(bits(raw_nnlf(abi, x, sets[t:t + 1])), bits(got[t:t + 1])), t
+
+
 # ---- fit -------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("k", range(len(FIT_CASES)), ids=IDS)
 def test_fit_against_scipy(abi, k):
@@ -172,15 +266,35 @@ def test_fit_against_scipy(abi, k):
         no_worse_than_scipy(params[t], s, "%s n=%d trial %d" % (family, n, t))
 
 
+def test_the_later_sweep_cases_sweep_more_than_once():
+    """The arithmetic of the cases beyond one sweep, from the constants restated above (no GPU work)."""
+    assert sweeps_of(3000) == (750, 0, 1, 0)                                            # the largest of the earlier cases: one turn
+    assert sweeps_of(4097) == (1024, 1, 1, 1)                                           # every thread one whole turn, thread 0 the tail
+    assert sweeps_of(4101) == (1025, 1, 2, 1)                                           # thread 0 alone takes a second group
+    assert sweeps_of(8195) == (2048, 3, 2, 2)
+    assert sweeps_of(100000) == (25000, 0, 25, 24)
+    for n in (4097, 4101, 8195, 100000):
+        assert {c[3] for c in FIT_CASES if c[1] == n} == {True, False}, n               # each size with idx and without
+
+
 def test_a_trial_has_the_same_bits_alone_and_in_a_batch_of_101(abi):
     x, idx, params, fval, info = fitted(abi, 0)
     assert len(idx) == 101
     for t in (0, 50, 100):
         p1, f1, i1 = raw_fit(abi, x, idx[t:t + 1], 1, idx.shape[1])
         assert np.array_equal(bits(p1), bits(params[t:t + 1])) and np.array_equal(bits(f1), bits(fval[t:t + 1])) and np.array_equal(i1, info[t:t + 1]), t
+    # ... and a trial of two sweeps and a tail in a batch of 3: the slices of the workspace are 8256 floats apart, not n
+    x, idx, params, fval, info = fitted(abi, case_of("gennorm2", 8195, 3, True))
+    assert len(idx) == 3 and sweeps_of(idx.shape[1])[2:] == (2, 2)
+    for t in (0, 1, 2):
+        p1, f1, i1 = raw_fit(abi, x, idx[t:t + 1], 1, idx.shape[1])
+        assert np.array_equal(bits(p1), bits(params[t:t + 1])) and np.array_equal(bits(f1), bits(fval[t:t + 1])) and np.array_equal(i1, info[t:t + 1]), t
 
 
-@pytest.mark.parametrize("k", [0, 3, 7], ids=[IDS[0], IDS[3], IDS[7]])
+_TWICE = [0, 3, 7, case_of("gennorm06", 4101, 3, True), case_of("signedsq", 100000, 2, True)]
+
+
+@pytest.mark.parametrize("k", _TWICE, ids=[IDS[k] for k in _TWICE])
 def test_two_identical_calls_give_identical_bits(abi, k):
     family, n, T, _with_idx, _flag, _seed = FIT_CASES[k]
     x, idx, params, fval, info = fitted(abi, k)

@@ -8,7 +8,11 @@ below loc relative plus 1e-300, above loc absolute.  p == 1 at x == loc and p ==
 
 epgf_bh_adjust against roiAndVisualPairwise.benjaminiHochberg BIT FOR BIT: ten sizes around the tile and the wave, six kinds of
 input; its flag; two calls, the same bits; argument validation of both entry points in the documented order on device memory.
-The host references are computed once per module."""
+The host references are computed once per module.
+
+The later turns of the kernels' loops: k_gennorm_pvals on the one-CU grid of tests/grid_cap.py (nine grid-stride turns over 70001 values,
+NaN counts carried from turn to turn, byte for byte the device's own grid) and k_bh_carry with two and three tiles per thread (2^21 + 1
+and 4 196 357 values); each case restates the kernel's constants and asserts its own turn count."""
 import ctypes
 
 import numpy as np
@@ -18,6 +22,7 @@ torch = pytest.importorskip("torch")
 
 from epilogos_amd import roiAndVisualPairwise as rv
 from tests import pvals_ref as ref
+from tests.grid_cap import capped_and_not, cdiv
 from tests.test_pvals_host import host_pvals
 
 pytestmark = pytest.mark.gpu
@@ -74,6 +79,63 @@ def test_pvals_flags(eng, host):
     for bad in ((0.0, 0.0, 1.0), (-1.0, 0.0, 1.0), (1.0, 0.0, 0.0), (np.nan, 0.0, 1.0), (1.0, np.nan, 1.0), (1.0, 0.0, np.nan)):
         p, flags = device_pvals(eng, x, bad)
         assert list(flags) == [1025, 0] and np.isnan(p).all(), bad
+
+
+# ---- the grid-stride turns of k_gennorm_pvals: the one-CU grid ------------------------------------------------------------------------
+PV_THREADS, PV_BLOCKS_PER_CU = 256, 32                       # epg_pvals.hip: a workgroup, workgroups per compute unit
+M_TURNS = 70001
+
+
+def pvals_turns(M, cus):
+    """(threads of the grid, the most turns of a thread's loop) on a device of `cus` compute units."""
+    threads = min(cdiv(M, PV_THREADS), PV_BLOCKS_PER_CU * cus) * PV_THREADS
+    return threads, cdiv(M, threads)
+
+
+@pytest.mark.parametrize("params", ref.PARAMS, ids=["beta%g" % p[0] for p in ref.PARAMS])
+def test_pvals_grid_stride_turns_on_the_one_cu_grid(eng, host, params):
+    """70001 values on 8192 threads: nine turns, the last one ragged.  scipy with the bounds of test_pvals_against_scipy (the inputs
+    are that test's), and the device's own grid, where a thread has one turn, byte for byte."""
+    assert pvals_turns(M_TURNS, 1) == (8192, 9) and M_TURNS % 8192 != 0
+    assert pvals_turns(M_TURNS, eng._abi.call("epg_device_cus"))[1] == 1
+    x, want = host[params, M_TURNS]
+
+    def fn():
+        p, flags = device_pvals(eng, x, params)
+        return {"p": p, "flags": flags}
+    out = capped_and_not(eng._abi, fn)
+    p = out["p"]
+    assert p.dtype == np.float64 and p.shape == (M_TURNS,) and list(out["flags"]) == [0, 0]
+    rel, ab = ref.differences(p, want, x, params[1])
+    print("beta %g on one CU: relative below loc %.3g (bound %.3g), absolute above loc %.3g (bound %.3g)"
+          % (params[0], rel, ref.FACTOR * ref.REL_BELOW, ab, ref.FACTOR * ref.ABS_ABOVE))
+    xd = x.astype(np.float64)
+    assert (p[xd == params[1]] == 1.0).all() and (p[np.isinf(xd)] == 0.0).all()
+    assert rel <= ref.FACTOR * ref.REL_BELOW
+    assert ab <= ref.FACTOR * ref.ABS_ABOVE
+
+
+def test_pvals_flags_are_carried_across_turns(eng, host):
+    """A thread's NaN count lives in a register from turn to turn: thread 700 of the one-CU grid meets NaN in its turns 0 and 1,
+    thread 5 in its last turn only, thread 8191 in turn 3, the last value of all (thread 4464, turn 8) is one too."""
+    params = ref.PARAMS[0]
+    x, _want = host[params, M_TURNS]
+    stride, turns = pvals_turns(M_TURNS, 1)
+    assert (stride, turns) == (8192, 9)
+    planted = [700, 700 + stride, 5 + 8 * stride, 3 * stride + stride - 1, M_TURNS - 1]
+    assert len(set(planted)) == 5 and max(planted) == M_TURNS - 1 and np.isfinite(x[planted]).all()
+    assert sorted(i % stride for i in planted) == [5, 700, 700, 4464, 8191]
+    y = x.copy()
+    y[planted] = np.nan
+    base, flags = device_pvals(eng, x, params)
+    assert list(flags) == [0, 0]
+
+    def fn():
+        p, flags = device_pvals(eng, y, params)
+        return {"p": p, "flags": flags}
+    out = capped_and_not(eng._abi, fn)
+    assert list(out["flags"]) == [len(planted), 0] and np.isnan(out["p"][planted]).all()
+    assert np.array_equal(np.delete(out["p"], planted).view(np.uint64), np.delete(base, planted).view(np.uint64))
 
 
 def test_pvals_from_a_device_fit_s_row(eng):
@@ -141,6 +203,51 @@ def test_bh_flags(eng):
     q[9] = np.inf                                                               # +inf is a p >= +0.0: adjusted to 1, like the host's
     got, flags = device_bh(eng, q)
     assert list(flags) == [0] and np.array_equal(got.view(np.uint64), rv.benjaminiHochberg(q).view(np.uint64))
+
+
+# ---- k_bh_carry with more than one tile per thread ---------------------------------------------------------------------------------
+BH_TILE, BH_CARRY_THREADS = 2048, 1024                       # epg_pvals.hip: sorted values per tile, threads of the ONE carry workgroup
+BH_BIG = (2097152, 2097153, 4196357)
+BH_BIG_KINDS = ("uniform", "rounded", "descending", "above_one")
+
+
+def bh_carry_shape(M):
+    """(tiles, tiles per carry thread, threads that own a tile, tiles of the last of them)."""
+    tiles = cdiv(M, BH_TILE)
+    chunk = cdiv(tiles, BH_CARRY_THREADS)
+    return tiles, chunk, cdiv(tiles, chunk), tiles - (cdiv(tiles, chunk) - 1) * chunk
+
+
+def test_bh_big_sizes_give_a_carry_thread_more_than_one_tile():
+    assert bh_carry_shape(max(BH_SIZES)) == (35, 1, 35, 1)                      # the largest size of the test above
+    assert bh_carry_shape(2097152) == (1024, 1, 1024, 1)                        # the last shape of one tile per thread
+    assert bh_carry_shape(2097153) == (1025, 2, 513, 1)                         # threads 513 .. 1023 own nothing, thread 512 one tile of ONE value
+    assert bh_carry_shape(4196357) == (2050, 3, 684, 1)                         # thread 683 is ragged, the last tile too
+    assert 4196357 % BH_TILE == 5
+
+
+@pytest.mark.parametrize("kind", BH_BIG_KINDS)
+@pytest.mark.parametrize("M", BH_BIG)
+def test_bh_with_chunks_of_tiles_is_the_host_s_bit_for_bit(eng, M, kind):
+    """("descending": every minimum comes from the far right, a wrong carry between two chunks shows in nearly every value.)"""
+    assert bh_carry_shape(M)[1] == {2097152: 1, 2097153: 2, 4196357: 3}[M]
+    p = bh_input(kind, M)
+    want = rv.benjaminiHochberg(p)
+    got, flags = device_bh(eng, p)
+    assert list(flags) == [0]
+    differ = got.view(np.uint64) != want.view(np.uint64)
+    assert not differ.any(), "%s M=%d: %d of %d values differ, the first at %d" % (kind, M, int(differ.sum()), M, int(np.argmax(differ)))
+
+
+def test_bh_flags_with_chunks_of_tiles(eng):
+    M = BH_BIG[-1]
+    assert bh_carry_shape(M)[1] == 3
+    p = bh_input("uniform", M)
+    planted = {3: np.nan, 700 * BH_TILE: -0.0, 1030 * BH_TILE + 7: np.nan, 2049 * BH_TILE: -np.inf, M - 1: -0.25}
+    assert len({i // BH_TILE for i in planted}) == 4 and max(planted) < M        # (tiles of the input; sorted, they all go behind +inf)
+    for i, v in planted.items():
+        p[i] = v
+    assert list(device_bh(eng, p)[1]) == [len(planted)]
 
 
 def test_engine_checks_its_arguments(eng):

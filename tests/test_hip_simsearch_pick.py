@@ -1,7 +1,8 @@
 """The kernels of `simsearch -b --step1 gpu` (include/epilogos_simsearch_pick.h) against tests/simsearch_pick_ref.py, exact equality
 everywhere: the centre scores, the rolling maximum, the rank and the pick at the smallest shapes where they can go wrong (around the
 window, around the pick tile T, several tiles), and one call of each inside the guarded arena of tests/abi_arena.py.  No grid of
-these kernels is sized by the compute-unit count, so there is no one-CU case."""
+these kernels is sized by the compute-unit count, so there is no one-CU case.  Two loops take a second turn only beyond those shapes and
+have cases of their own: k_compact_offsets beyond 256 tiles, the halo load of k_pick_sweep beyond W = 257."""
 import ctypes
 
 import numpy as np
@@ -167,6 +168,39 @@ def test_a_plateau_costs_a_sweep_per_tile_not_one_per_window(W):
     assert np.array_equal(got, np.arange(0, n, W))
     assert launches <= -(-n // T) == 4
     assert W > 125 or launches * 10 <= n // W
+
+
+PK_THREADS = 256                                                 # epg_simsearch_pick.hip: the workgroup of the pick kernels
+
+
+@pytest.mark.parametrize("n,W", [(PK_THREADS * T + 1, 125), (2 * PK_THREADS * T + T + 5, 25)])
+def test_pick_with_more_tiles_than_the_offsets_workgroup_has_threads(n, W):
+    """k_compact_offsets scans the tiles' counts in turns of 256 with a carry: 256 tiles and ONE position in the second turn; three
+    turns, the last of two tiles, the very last ragged.  (A genome of 15 M bins is 29 turns.)"""
+    tiles = -(-n // T)
+    assert (-(-tiles // PK_THREADS), tiles - (-(-tiles // PK_THREADS) - 1) * PK_THREADS, n % T) == {125: (2, 1, 1), 25: (3, 2, 5)}[W]
+    assert -(-(3 * T + 7) // T) <= PK_THREADS                    # the largest of the sizes above: one turn
+    rank = ref.pattern("random", n, W, T, seed=W)
+    rank[np.nonzero(rank == 0)[0][0]], rank[n - 1] = rank[n - 1], 0          # the best window is the last: the last tile holds a pick
+    full = ref.pick(rank, W, n)
+    assert full[-1] == n - 1 and full[0] < T
+    got, launches = _pick(rank, W, n)
+    assert np.array_equal(got, full) and launches >= 1
+    cap = len(full) // 2                                          # ... and with the threshold on the ranks
+    assert np.array_equal(_pick(rank, W, cap)[0], ref.pick(rank, W, cap))
+
+
+@pytest.mark.parametrize("W", [300, 1024])
+def test_pick_with_a_halo_wider_than_the_workgroup(W):
+    """k_pick_sweep loads the two halos of W - 1 states with j += 256: a second turn beyond W = 257, four at the largest window."""
+    assert -(-(W - 1) // PK_THREADS) == {300: 2, 1024: 4}[W] and max(WINDOWS) - 1 <= PK_THREADS
+    assert W <= _abi.header_constant("simsearch_pick", "EPG_PICK_MAX_W")
+    n = 3 * T + 7
+    for name in ("random", "reversed", "saw_window", "best_last_of_tile"):
+        rank = ref.pattern(name, n, W, T, seed=W)
+        for cap in (3, n):
+            got, _launches = _pick(rank, W, cap)
+            assert np.array_equal(got, ref.pick(rank, W, cap)), (W, name, cap)
 
 
 def test_pick_of_nothing():
