@@ -157,8 +157,9 @@ def _aligned_rows(T, lo, hi):
     """Rows [lo, hi) of a resident part as the kernels want them: the score entry points take 16-byte aligned bases
     (epg_s1.hip check_score_from_hist_args, epg_null.hip, epg_s2.hip), and a row slice of an [R, S] uint16 array starts at
     lo * S * 2 bytes -- a view only when that is a multiple of 16, else a copy of just these rows."""
+    from . import engine
     t = T[lo:hi]
-    if t.data_ptr() % 16 == 0 and t.untyped_storage().nbytes() <= 4 * max(t.numel() * t.element_size(), 1):
+    if engine.aligned16(t) and t.untyped_storage().nbytes() <= 4 * max(t.numel() * t.element_size(), 1):
         return t
     # a copy of just these rows: a misaligned slice -- or one that would keep alive an allocation several times its size (the
     # histograms of a whole batch of parts come from ONE allocation, engine.hist_rows_alloc: a rank that hands most of a batch

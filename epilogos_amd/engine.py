@@ -22,12 +22,97 @@ def require_gpu():
     _abi.load()
 
 
-def _ptr(t):
+def ptr(t):
+    """The unchecked address of a tensor (None: NULL) -- for the batch readers' launch-bound loops ("One binding per
+    entry point") and for tests; every wrapper below hands its arguments to _arg / _mat instead."""
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+def stream(s=None):
+    """The hipStream_t of the torch stream s (None: the current one)."""
+    return C.c_void_p((torch.cuda.current_stream() if s is None else s).cuda_stream)
+
+
+_ptr, _stream = ptr, stream
+
+
+def aligned16(t):
+    return t.data_ptr() % 16 == 0
+
+
+# ---- the binding helpers: every wrapper's tensors go through _arg / _mat, its scratch through _scratch, its part tables through
+# _parts / _ints.  They read tensor metadata only: no synchronisation, no device read, no launch (a captured graph never sees them).
+def _on_device(where, t, dtype, dev):
+    """What _arg and _mat ask of every tensor: on a CUDA device, the one of the call's other tensors, of the dtype the header names."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError("engine.%s must be a tensor on a CUDA device" % where)
+    if dev is not None and t.device != dev:
+        raise ValueError("engine.%s is on %s, the call's other tensors on %s" % (where, t.device, dev))
+    if t.dtype != dtype:
+        raise ValueError("engine.%s must be %s, not %s" % (where, dtype, t.dtype))
+
+
+def _arg(where, t, dtype, need, dev=None, null=False):
+    """THE argument check, for a vector or flat buffer the kernel reads or writes `need` elements of: -> its address (NULL for None
+    where `null` says the header documents one, and for a tensor without elements -- `need` is then 0).  where: "wrapper: argument";
+    dev: the device of the call's other tensors.  A row slice H[a:b] is contiguous."""
+    if t is None:
+        if null:
+            return None
+        raise ValueError("engine.%s is required (the kernel takes no NULL pointer there)" % where)
+    _on_device(where, t, dtype, dev)
+    if not t.is_contiguous():
+        raise ValueError("engine.%s must be contiguous (shape %s has strides %s)" % (where, tuple(t.shape), t.stride()))
+    if t.numel() < need:                                         # (numel() again below: a tensor without elements has no address)
+        raise ValueError("engine.%s holds %d elements, the kernel touches %d" % (where, t.numel(), need))
+    return C.c_void_p(t.data_ptr()) if t.numel() else None
+
+
+def _mat(where, t, dtype, width, dev=None):
+    """_arg for a matrix the kernel takes with a row pitch (state matrices, format_scores' scores), of which it touches `width`
+    columns: 2-D, unit column stride, a row stride of at least its width -> (address, rows, row pitch)."""
+    _on_device(where, t, dtype, dev)
+    if t.dim() != 2:
+        raise ValueError("engine.%s must be 2-D" % where)
+    R, W = t.shape
+    if width > W:
+        raise ValueError("engine.%s has rows of %d elements, the kernel touches %d" % (where, W, width))
+    ld = t.stride(0)
+    if R and ((W > 1 and t.stride(1) != 1) or (R > 1 and ld < W)):       # (a matrix without rows may have any strides)
+        raise ValueError("engine.%s must have unit column stride and a row stride of at least its width (shape %s has strides %s)"
+                         % (where, tuple(t.shape), t.stride()))
+    return C.c_void_p(t.data_ptr()), R, max(ld, W)
+
+
+def _scratch_bytes(entry, *dims, floor=256):
+    """What the size query `entry` (a *_ws_bytes / *_bytes_max entry point; None: nothing to ask) answers for dims, at least `floor`."""
+    return max(int(_abi.call(entry, *dims)) if entry else 0, floor)
+
+
+def _scratch(where, ws, dev, entry, *dims):
+    """THE scratch of a call: the caller's `ws` when given (a uint8 CUDA buffer; whether it is large enough is the library's
+    EPG_ERR_WORKSPACE to say), else a fresh one of _scratch_bytes(entry, *dims) -> (buffer, address, bytes)."""
+    if ws is None:
+        ws = torch.empty(_scratch_bytes(entry, *dims), dtype=torch.uint8, device=dev)
+    return ws, _arg(where, ws, torch.uint8, 0, dev), ws.numel()
+
+
+def _ptr_array(ts):
+    return (C.c_void_p * len(ts))(*[t.data_ptr() if t is not None and t.numel() else None for t in ts])
+
+
+def _parts(where, ts, dtype, needs, dev):
+    """_ptr_array of a multi-part call's tensors, each through _arg (entries may be None, and empty where their part has no rows)."""
+    if len(ts) != len(needs):
+        raise ValueError("engine.%s lists %d tensors for %d parts" % (where, len(ts), len(needs)))
+    for t, need in zip(ts, needs):
+        _arg(where, t, dtype, need, dev, null=True)
+    return _ptr_array(ts)
+
+
+def _ints(ctype, values):
+    """The host array of a multi-part call's row counts, widths, pitches or keys."""
+    return (ctype * len(values))(*[int(v) for v in values])
 
 
 def padded_width(N):
@@ -350,43 +435,36 @@ def states_to_device(x, device="cuda"):
     return torch.from_numpy(host).to(device)
 
 
-def _check_states(X, N):
-    if X.dtype != torch.int8 or X.dim() != 2 or not X.is_cuda or X.stride(1) != 1:
-        raise ValueError("state matrix must be a 2-D int8 CUDA tensor with unit column stride")
-    if N > X.shape[1]:
-        raise ValueError("N exceeds the row width")
-    return X.shape[0], X.stride(0)
-
-
 def zeros_counts(n, dtype=torch.int64, device="cuda"):
     return torch.zeros(n, dtype=dtype, device=device)
 
 
 def bin_hist(X, N, S, want_hist=True, counts=None, want_counts=True, H=None):
     """K1: per-bin histograms H uint16 [R, S] (as int16 storage) and/or counts[S] += column sums."""
-    R, ldx = _check_states(X, N)
+    pX, R, ldx = _mat("bin_hist: X", X, torch.int8, N)
+    dev = X.device
     if H is None and want_hist:
-        H = torch.empty((R, S), dtype=torch.int16, device=X.device)
+        H = torch.empty((R, S), dtype=torch.int16, device=dev)
     if want_counts and counts is None:
-        counts = zeros_counts(S, device=X.device)
-    _abi.call("epg_bin_hist", _ptr(X), R, N, ldx, S, _ptr(H), _ptr(counts) if want_counts else None, _stream())
+        counts = zeros_counts(S, device=dev)
+    _abi.call("epg_bin_hist", pX, R, N, ldx, S, _arg("bin_hist: H", H, torch.int16, R * S, dev, null=True),
+              _arg("bin_hist: counts", counts, torch.int64, S, dev, null=True) if want_counts else None, _stream())
     return H, counts
 
 
 def bin_hist_s2(X, N, S, counts2=None, H=None, counts=None):
     """K1 with the S2 pair counts of the same bins folded into the launch (epg_bin_hist_s2): -> (H, counts2 int64 [S*S]);
     counts (int64 [S], optional) also gets the state counts."""
-    R, ldx = _check_states(X, N)
+    pX, R, ldx = _mat("bin_hist_s2: X", X, torch.int8, N)
+    dev = X.device
     if H is None:
-        H = torch.empty((R, S), dtype=torch.int16, device=X.device)
+        H = torch.empty((R, S), dtype=torch.int16, device=dev)
     if counts2 is None:
-        counts2 = zeros_counts(S * S, device=X.device)
-    _abi.call("epg_bin_hist_s2", _ptr(X), R, N, ldx, S, _ptr(H), _ptr(counts), _ptr(counts2), _stream())
+        counts2 = zeros_counts(S * S, device=dev)
+    _abi.call("epg_bin_hist_s2", pX, R, N, ldx, S, _arg("bin_hist_s2: H", H, torch.int16, R * S, dev),
+              _arg("bin_hist_s2: counts", counts, torch.int64, S, dev, null=True),
+              _arg("bin_hist_s2: counts2", counts2, torch.int64, S * S, dev), _stream())
     return H, counts2
-
-
-def _ptr_array(ts):
-    return (C.c_void_p * len(ts))(*[t.data_ptr() if t is not None and t.numel() else None for t in ts])
 
 
 def hist_rows_flat(rows, S, device, dtype=torch.int16):
@@ -414,12 +492,15 @@ def bin_hist_parts(Xs, Ns, S, counts=None, want_hist=True, Hs=None):
     n = len(Xs)
     if n == 0:
         return [], counts
-    shapes = [_check_states(X, N) if X.shape[0] else (0, max(N, 1)) for X, N in zip(Xs, Ns)]
     dev = Xs[0].device
+    shapes = [_mat("bin_hist_parts: Xs", X, torch.int8, N, dev)[1:] if X.shape[0] else (0, max(N, 1)) for X, N in zip(Xs, Ns)]
+    rows = [r for r, _l in shapes]
     if Hs is None and want_hist:
-        Hs = hist_rows_alloc([r for r, _l in shapes], S, dev)
-    _abi.call("epg_bin_hist_parts", n, _ptr_array(Xs), (C.c_int64 * n)(*[r for r, _l in shapes]), (C.c_int32 * n)(*[int(N or 1) for N in Ns]),
-              (C.c_int64 * n)(*[l for _r, l in shapes]), S, _ptr_array(Hs) if Hs is not None else None, _ptr(counts), _stream())
+        Hs = hist_rows_alloc(rows, S, dev)
+    _abi.call("epg_bin_hist_parts", n, _ptr_array(Xs), _ints(C.c_int64, rows), _ints(C.c_int32, [N or 1 for N in Ns]),
+              _ints(C.c_int64, [l for _r, l in shapes]),
+              S, _parts("bin_hist_parts: Hs", Hs, torch.int16, [r * S for r in rows], dev) if Hs is not None else None,
+              _arg("bin_hist_parts: counts", counts, torch.int64, S, dev, null=True), _stream())
     return Hs, counts
 
 
@@ -465,14 +546,14 @@ def bin_hist_groups(X, N, S, groups, counts=None, want_hist=True):
     """The count pass for column groups of ONE matrix (epg_bin_hist_groups): X is read once, every group gets per-bin
     histograms of its own columns.  groups: 1 .. GROUPS_MAX int64 arrays of 0-based columns.  -> ([H_g uint16 [R, S] as int16
     storage] or None, counts int64 [G, S]; counts is added to when given)."""
-    R, ldx = _check_states(X, N)
-    G = len(groups)
-    member = group_members(X.device, N, groups)
-    Hs = hist_rows_alloc([R] * G, S, X.device) if want_hist else None
+    pX, R, ldx = _mat("bin_hist_groups: X", X, torch.int8, N)
+    G, dev = len(groups), X.device
+    member = group_members(dev, N, groups)
+    Hs = hist_rows_alloc([R] * G, S, dev) if want_hist else None
     if counts is None:
-        counts = zeros_counts(G * S, device=X.device)
-    _abi.call("epg_bin_hist_groups", _ptr(X), R, N, ldx, S, G, _ptr(member), _ptr_array(Hs) if Hs is not None else None, _ptr(counts),
-              _stream())
+        counts = zeros_counts(G * S, device=dev)
+    _abi.call("epg_bin_hist_groups", pX, R, N, ldx, S, G, _arg("bin_hist_groups: member", member, torch.uint8, N, dev),
+              _ptr_array(Hs) if Hs is not None else None, _arg("bin_hist_groups: counts", counts, torch.int64, G * S, dev), _stream())
     return Hs, counts.view(G, S)
 
 
@@ -485,23 +566,25 @@ def state_census(X, N, S, census=None, other=None, first_bad=None, want_other=Tr
     0xFF, S .. 31 and the bytes 32 .. 254 that the count kernels would alias), first_bad = the smallest row * N + column of such a
     byte, FIRST_BAD_NONE when there is none.  Tensors given are added to (first_bad: minimised); want_other / want_first_bad
     False pass NULL and return None in their place."""
-    R, ldx = _check_states(X, N)
+    pX, R, ldx = _mat("state_census: X", X, torch.int8, N)
+    dev = X.device
     if census is None:
-        census = torch.zeros((N, S), dtype=torch.int64, device=X.device)
+        census = torch.zeros((N, S), dtype=torch.int64, device=dev)
     if other is None and want_other:
-        other = torch.zeros(N, dtype=torch.int64, device=X.device)
+        other = torch.zeros(N, dtype=torch.int64, device=dev)
     if first_bad is None and want_first_bad:
-        first_bad = torch.full((1,), FIRST_BAD_NONE, dtype=torch.int64, device=X.device)
-    for name, t, n in (("census", census, N * S), ("other", other, N), ("first_bad", first_bad, 1)):
-        if t is not None and (t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous() or t.numel() != n):
-            raise ValueError("%s must be a contiguous int64 CUDA tensor of %d elements" % (name, n))
+        first_bad = torch.full((1,), FIRST_BAD_NONE, dtype=torch.int64, device=dev)
+    ptrs = [_arg("state_census: " + name, t, torch.int64, n, dev, null=null)
+            for name, t, n, null in (("census", census, N * S, False), ("other", other, N, True), ("first_bad", first_bad, 1, True))]
+    if census.numel() != N * S:                                  # (it is returned as [N, S])
+        raise ValueError("engine.state_census: census must hold %d elements" % (N * S))
     if N > 0:                                                    # (an empty census tensor has no address to hand over)
-        _abi.call("epg_state_census", _ptr(X), R, N, max(ldx, 1), S, _ptr(census), _ptr(other), _ptr(first_bad), _stream())
+        _abi.call("epg_state_census", pX, R, N, max(ldx, 1), S, *ptrs, _stream())
     return census.view(N, S), other, first_bad
 
 
 def concordance_ws_bytes(R, N, S):
-    return max(int(_abi.call("epg_concordance_ws_bytes", R, N, S)), 256)
+    return _scratch_bytes("epg_concordance_ws_bytes", R, N, S)
 
 
 def concordance(X, N, S, agree=None, both=None, want_both=True, ws=None):
@@ -510,31 +593,33 @@ def concordance(X, N, S, agree=None, both=None, want_both=True, ws=None):
     is compared, as in state_census); both triangles and the diagonal, agree[i, i] == both[i, i] == the valid bins of column i.
     Tensors given are added to; want_both False passes NULL and returns None in its place.  The workspace is sized and owned
     here unless `ws` (uint8, at least concordance_ws_bytes(R, N, S)) is handed in."""
-    R, ldx = _check_states(X, N)
+    pX, R, ldx = _mat("concordance: X", X, torch.int8, N)
+    dev = X.device
     if N < 1:
         raise ValueError("concordance needs at least one biosample column")
     if agree is None:
-        agree = torch.zeros((N, N), dtype=torch.int64, device=X.device)
+        agree = torch.zeros((N, N), dtype=torch.int64, device=dev)
     if both is None and want_both:
-        both = torch.zeros((N, N), dtype=torch.int64, device=X.device)
-    for name, t in (("agree", agree), ("both", both)):
-        if t is not None and (t.dtype != torch.int64 or not t.is_cuda or not t.is_contiguous() or t.numel() != N * N):
-            raise ValueError("%s must be a contiguous int64 CUDA tensor of %d elements" % (name, N * N))
+        both = torch.zeros((N, N), dtype=torch.int64, device=dev)
+    ptrs = [_arg("concordance: " + name, t, torch.int64, N * N, dev, null=null) for name, t, null in (("agree", agree, False), ("both", both, True))]
+    if agree.numel() != N * N or (both is not None and both.numel() != N * N):    # (they are returned as [N, N])
+        raise ValueError("engine.concordance: agree and both must hold %d elements" % (N * N))
     if R > 0:
-        if ws is None:
-            ws = torch.empty(concordance_ws_bytes(R, N, S), dtype=torch.uint8, device=X.device)
-        _abi.call("epg_concordance", _ptr(X), R, N, ldx, S, _ptr(agree), _ptr(both), _ptr(ws), ws.numel(), _stream())
+        _ws, pws, nws = _scratch("concordance: ws", ws, dev, "epg_concordance_ws_bytes", R, N, S)
+        _abi.call("epg_concordance", pX, R, N, ldx, S, *ptrs, pws, nws, _stream())
     return agree.view(N, N), (both.view(N, N) if both is not None else None)
 
 
 def gennorm_ws_bytes(M, T, n=0):
-    return max(int(_abi.call("epgf_gennorm_ws_bytes", M, T, n)), 256)
+    return _scratch_bytes("epgf_gennorm_ws_bytes", M, T, n)
 
 
-def _check_gennorm_x(x):
-    if x.dtype != torch.float32 or x.dim() != 1 or not x.is_cuda or not x.is_contiguous() or x.numel() < 1:
-        raise ValueError("x must be a non-empty contiguous 1-D float32 CUDA tensor")
-    return x.numel()
+def _vector(where, x, dtype):
+    """_arg for a non-empty 1-D input whose length is the call's size -> (address, length)."""
+    p = _arg(where, x, dtype, 1)
+    if x.dim() != 1:
+        raise ValueError("engine.%s must be 1-D" % where)
+    return p, x.numel()
 
 
 def gennorm_fit(x, idx=None, n=None, ws=None):
@@ -542,42 +627,41 @@ def gennorm_fit(x, idx=None, n=None, ws=None):
     x[idx[t]] (idx: int32 [T, n], every index in 0 .. M-1, checked here); idx None: one trial on all of x.
     -> (params float64 [T, 3] = (beta, loc, scale), fval float64 [T], info int32 [T, 2] = (evaluations, flag)); flag 0 converged,
     1 stopped at the cap, 2 degenerate sample (params NaN).  Current stream, no synchronisation beyond the index check's."""
-    M = _check_gennorm_x(x)
+    px, M = _vector("gennorm_fit: x", x, torch.float32)
+    dev = x.device
     if idx is None:
-        T, n = 1, M if n is None else int(n)
+        T, n, pidx = 1, M if n is None else int(n), None
     else:
-        if idx.dtype != torch.int32 or idx.dim() != 2 or not idx.is_cuda or not idx.is_contiguous():
-            raise ValueError("idx must be a contiguous 2-D int32 CUDA tensor [T, n]")
+        pidx = _arg("gennorm_fit: idx", idx, torch.int32, 1, dev)
+        if idx.dim() != 2:
+            raise ValueError("engine.gennorm_fit: idx must be 2-D [T, n]")
         T = idx.shape[0]
         if n is not None and int(n) != idx.shape[1]:
             raise ValueError("n=%d is not the row length %d of idx" % (n, idx.shape[1]))
         n = idx.shape[1]
-        if T < 1 or n < 1:
-            raise ValueError("idx must hold at least one trial of at least two indices")
         lo, hi = torch.aminmax(idx)
         if int(lo) < 0 or int(hi) >= M:
             raise ValueError("idx holds an index outside 0 .. %d" % (M - 1))
-    params = torch.empty((T, 3), dtype=torch.float64, device=x.device)
-    fval = torch.empty(T, dtype=torch.float64, device=x.device)
-    info = torch.empty((T, 2), dtype=torch.int32, device=x.device)
-    if ws is None:
-        ws = torch.empty(gennorm_ws_bytes(M, T, n), dtype=torch.uint8, device=x.device)
-    _abi.call("epgf_gennorm_fit", _ptr(x), M, _ptr(idx), T, n, _ptr(params), _ptr(fval), _ptr(info), _ptr(ws), ws.numel(), _stream())
+    params = torch.empty((T, 3), dtype=torch.float64, device=dev)
+    fval = torch.empty(T, dtype=torch.float64, device=dev)
+    info = torch.empty((T, 2), dtype=torch.int32, device=dev)
+    _ws, pws, nws = _scratch("gennorm_fit: ws", ws, dev, "epgf_gennorm_ws_bytes", M, T, n)
+    _abi.call("epgf_gennorm_fit", px, M, pidx, T, n, _ptr(params), _ptr(fval), _ptr(info), pws, nws, _stream())
     return params, fval, info
 
 
 def gennorm_nnlf(x, params, ws=None):
     """Negative log-likelihood of ALL of x under each of the T parameter sets (epgf_gennorm_nnlf): params float64 [T, 3] ->
     float64 [T]; +inf for a set with beta <= 0, scale <= 0 or a NaN.  One pass over x."""
-    M = _check_gennorm_x(x)
-    if params.dtype != torch.float64 or params.dim() != 2 or params.shape[1] != 3 or not params.is_cuda or not params.is_contiguous() \
-            or params.shape[0] < 1:
-        raise ValueError("params must be a contiguous float64 CUDA tensor [T, 3]")
+    px, M = _vector("gennorm_nnlf: x", x, torch.float32)
+    dev = x.device
+    pparams = _arg("gennorm_nnlf: params", params, torch.float64, 3, dev)
+    if params.dim() != 2 or params.shape[1] != 3:
+        raise ValueError("engine.gennorm_nnlf: params must be [T, 3]")
     T = params.shape[0]
-    out = torch.empty(T, dtype=torch.float64, device=x.device)
-    if ws is None:
-        ws = torch.empty(gennorm_ws_bytes(M, T, 0), dtype=torch.uint8, device=x.device)
-    _abi.call("epgf_gennorm_nnlf", _ptr(x), M, _ptr(params), T, _ptr(out), _ptr(ws), ws.numel(), _stream())
+    out = torch.empty(T, dtype=torch.float64, device=dev)
+    _ws, pws, nws = _scratch("gennorm_nnlf: ws", ws, dev, "epgf_gennorm_ws_bytes", M, T, 0)
+    _abi.call("epgf_gennorm_nnlf", px, M, pparams, T, _ptr(out), pws, nws, _stream())
     return out
 
 
@@ -585,31 +669,31 @@ def gennorm_pvals(x, params):
     """Two-sided p-value of every x under gennorm(beta, loc, scale) (epgf_gennorm_pvals, csrc/epg_pvals.h): params float64 [3] on
     the device, e.g. a row of gennorm_fit's.  -> (p float64 [M], flags int32 [2] = (NaN p-values, iterations stopped at the cap)).
     Current stream, no synchronisation."""
-    M = _check_gennorm_x(x)
-    if params.dtype != torch.float64 or params.numel() != 3 or not params.is_cuda or not params.is_contiguous():
-        raise ValueError("params must be a contiguous float64 CUDA tensor of 3 elements (beta, loc, scale)")
-    p = torch.empty(M, dtype=torch.float64, device=x.device)
-    flags = torch.empty(2, dtype=torch.int32, device=x.device)
-    _abi.call("epgf_gennorm_pvals", _ptr(x), M, _ptr(params), _ptr(p), _ptr(flags), _stream())
+    px, M = _vector("gennorm_pvals: x", x, torch.float32)
+    dev = x.device
+    pparams = _arg("gennorm_pvals: params", params, torch.float64, 3, dev)
+    if params.numel() != 3:
+        raise ValueError("engine.gennorm_pvals: params must hold 3 elements (beta, loc, scale)")
+    p = torch.empty(M, dtype=torch.float64, device=dev)
+    flags = torch.empty(2, dtype=torch.int32, device=dev)
+    _abi.call("epgf_gennorm_pvals", px, M, pparams, _ptr(p), _ptr(flags), _stream())
     return p, flags
 
 
 def bh_ws_bytes(M):
-    return max(int(_abi.call("epgf_bh_ws_bytes", M)), 256)
+    return _scratch_bytes("epgf_bh_ws_bytes", M)
 
 
 def bh_adjust(p, ws=None):
     """Benjamini-Hochberg adjusted p-values (epgf_bh_adjust), the bits of roiAndVisualPairwise.benjaminiHochberg: p float64 [M] ->
     (adj float64 [M], flags int32 [1] = the number of p that are NaN or negative; adj means nothing when it is not 0).  The
     workspace is sized and owned here unless `ws` (uint8, at least bh_ws_bytes(M)) is handed in.  Current stream, no synchronisation."""
-    if p.dtype != torch.float64 or p.dim() != 1 or not p.is_cuda or not p.is_contiguous() or p.numel() < 1:
-        raise ValueError("p must be a non-empty contiguous 1-D float64 CUDA tensor")
-    M = p.numel()
-    adj = torch.empty(M, dtype=torch.float64, device=p.device)
-    flags = torch.empty(1, dtype=torch.int32, device=p.device)
-    if ws is None:
-        ws = torch.empty(bh_ws_bytes(M), dtype=torch.uint8, device=p.device)
-    _abi.call("epgf_bh_adjust", _ptr(p), M, _ptr(adj), _ptr(flags), _ptr(ws), ws.numel(), _stream())
+    pp, M = _vector("bh_adjust: p", p, torch.float64)
+    dev = p.device
+    adj = torch.empty(M, dtype=torch.float64, device=dev)
+    flags = torch.empty(1, dtype=torch.int32, device=dev)
+    _ws, pws, nws = _scratch("bh_adjust: ws", ws, dev, "epgf_bh_ws_bytes", M)
+    _abi.call("epgf_bh_adjust", pp, M, _ptr(adj), _ptr(flags), pws, nws, _stream())
     return adj, flags
 
 
@@ -633,31 +717,23 @@ def release_text_buffers():
     _text_bufs.clear()
 
 
-def _check_scores_2d(scores):
-    if scores.dtype != torch.float32 or scores.dim() != 2 or not scores.is_cuda or scores.shape[1] < 1:
-        raise ValueError("scores must be a float32 [R, S] CUDA tensor")
-    if scores.shape[0] and ((scores.shape[0] > 1 and scores.stride(0) < scores.shape[1]) or (scores.shape[1] > 1 and scores.stride(1) != 1)):
-        raise ValueError("scores must have unit column stride and a row stride of at least S")
-    return int(scores.shape[0]), int(scores.shape[1]), int(scores.stride(0)) if scores.shape[0] > 1 else int(scores.shape[1])
-
-
 def format_scores(scores, loc, loc_off, text=None, ws=None):
     """The text epgio_write_scores formats for float32 scores [R, S] (any row stride) and the rows' locations (loc uint8 blob, loc_off
     int64 [R + 1], both on the device), byte for byte (epgw_format_scores).  -> (text uint8, row_off int64 [R + 1], flags int32 [1]):
     the text is text[:row_off[R]]; nothing may be used when flags[0] != 0 (a value that is not finite or not below 2^31 in
     magnitude).  text / ws: buffers to use (None: allocated at their bounds).  Current stream, no synchronisation."""
-    R, S, ld = _check_scores_2d(scores)
-    if loc.dtype != torch.uint8 or loc_off.dtype != torch.int64 or loc_off.numel() != R + 1 or not loc.is_contiguous() or not loc_off.is_contiguous():
-        raise ValueError("loc must be a contiguous uint8 blob and loc_off contiguous int64 [R + 1]")
-    dev = scores.device
-    if text is None:
-        text = torch.empty(max(int(_abi.call("epgw_text_bytes_max", R, S, loc.numel())), 256), dtype=torch.uint8, device=dev)
-    if ws is None:
-        ws = torch.empty(max(int(_abi.call("epgw_format_ws_bytes", R)), 256), dtype=torch.uint8, device=dev)
+    pscores, R, ld = _mat("format_scores: scores", scores, torch.float32, 1)
+    S, dev = int(scores.shape[1]), scores.device
+    ploc = _arg("format_scores: loc", loc, torch.uint8, 0, dev)
+    ploc_off = _arg("format_scores: loc_off", loc_off, torch.int64, R + 1, dev)
+    if loc_off.numel() != R + 1:
+        raise ValueError("engine.format_scores: loc_off must hold R + 1 = %d elements" % (R + 1))
+    text, ptext, ntext = _scratch("format_scores: text", text, dev, "epgw_text_bytes_max", R, S, loc.numel())
+    _ws, pws, nws = _scratch("format_scores: ws", ws, dev, "epgw_format_ws_bytes", R)
     row_off = torch.empty(R + 1, dtype=torch.int64, device=dev)
     flags = torch.empty(1, dtype=torch.int32, device=dev)
-    _abi.call("epgw_format_scores", _ptr(scores) if R else None, R, S, ld, _ptr(loc) if R else None, _ptr(loc_off) if R else None, _ptr(text),
-              text.numel(), _ptr(row_off), _ptr(flags), _ptr(ws), ws.numel(), _stream())
+    _abi.call("epgw_format_scores", pscores if R else None, R, S, ld if R > 1 else S, ploc if R else None, ploc_off if R else None, ptext, ntext,
+              _ptr(row_off), _ptr(flags), pws, nws, _stream())
     return text, row_off, flags
 
 
@@ -667,20 +743,15 @@ def bgzf_compress(text, n, row_off=None, eof=True, out=None, ws=None):
     the row above; without it only literals are coded.  -> (out uint8, n_out int64 [1], flags int32 [1]): the stream is
     out[:n_out].  Current stream, no synchronisation."""
     n = int(n)
-    if text.dtype != torch.uint8 or not text.is_cuda or not text.is_contiguous() or text.numel() < n:
-        raise ValueError("text must be a contiguous uint8 CUDA tensor of at least n bytes")
-    R = 0 if row_off is None else row_off.numel() - 1
-    if row_off is not None and (row_off.dtype != torch.int64 or not row_off.is_contiguous()):
-        raise ValueError("row_off must be contiguous int64")
+    ptext = _arg("bgzf_compress: text", text, torch.uint8, n)
     dev = text.device
-    if out is None:
-        out = torch.empty(max(int(_abi.call("epgw_bgzf_bytes_max", n, int(bool(eof)))), 256), dtype=torch.uint8, device=dev)
-    if ws is None:
-        ws = torch.empty(max(int(_abi.call("epgw_bgzf_ws_bytes", n)), 256), dtype=torch.uint8, device=dev)
+    R = 0 if row_off is None else row_off.numel() - 1
+    prow_off = _arg("bgzf_compress: row_off", row_off, torch.int64, 0, dev, null=True)
+    out, pout, nout = _scratch("bgzf_compress: out", out, dev, "epgw_bgzf_bytes_max", n, int(bool(eof)))
+    _ws, pws, nws = _scratch("bgzf_compress: ws", ws, dev, "epgw_bgzf_ws_bytes", n)
     n_out = torch.empty(1, dtype=torch.int64, device=dev)
     flags = torch.empty(1, dtype=torch.int32, device=dev)
-    _abi.call("epgw_bgzf_compress", _ptr(text), n, _ptr(row_off) if R else None, R, int(bool(eof)), _ptr(out), out.numel(), _ptr(n_out),
-              _ptr(flags), _ptr(ws), ws.numel(), _stream())
+    _abi.call("epgw_bgzf_compress", ptext, n, prow_off if R else None, R, int(bool(eof)), pout, nout, _ptr(n_out), _ptr(flags), pws, nws, _stream())
     return out, n_out, flags
 
 
@@ -691,7 +762,7 @@ def _compress_formatted(text, row_off, flags, rows, ws, eof):
     n, flag = (int(v) for v in torch.stack([row_off[rows], flags[0].to(torch.int64)]).cpu())
     if flag:
         return None
-    out = _text_buf(text.device, "out", _abi.call("epgw_bgzf_bytes_max", n, int(bool(eof))))
+    out = _text_buf(text.device, "out", _scratch_bytes("epgw_bgzf_bytes_max", n, int(bool(eof))))
     out, n_out, flags = bgzf_compress(text, n, row_off, eof=eof, out=out, ws=ws)
     n_bytes, flag = (int(v) for v in torch.stack([n_out[0], flags[0].to(torch.int64)]).cpu())
     if flag:
@@ -706,7 +777,8 @@ def scores_text_bgzf(locations, scores_device, eof=False):
     flag is set -- a value the device does not format -- and nothing may be used: the caller writes that file on the host.
     Synchronises twice: the text's size comes back between the two kernels' calls (the synchronisation csrc/epg_textout.h
     documents), the stream's size after them.  The buffers are one reusable set per device (release_text_buffers)."""
-    R, S, _ld = _check_scores_2d(scores_device)
+    _p, R, _ld = _mat("scores_text_bgzf: scores_device", scores_device, torch.float32, 1)
+    S = int(scores_device.shape[1])
     if len(locations) != R:
         raise ValueError("locations and scores disagree on the number of rows")
     dev = scores_device.device
@@ -714,8 +786,8 @@ def scores_text_bgzf(locations, scores_device, eof=False):
     off = np.ascontiguousarray(locations.offsets, dtype=np.int64)
     loc = torch.from_numpy(blob).to(dev) if blob.size else torch.zeros(1, dtype=torch.uint8, device=dev)
     loc_off = torch.from_numpy(off).to(dev)
-    text = _text_buf(dev, "text", _abi.call("epgw_text_bytes_max", R, S, int(off[-1] - off[0]) if R else 0))
-    ws = _text_buf(dev, "ws", max(_abi.call("epgw_format_ws_bytes", R), _abi.call("epgw_bgzf_ws_bytes", text.numel())))
+    text = _text_buf(dev, "text", _scratch_bytes("epgw_text_bytes_max", R, S, int(off[-1] - off[0]) if R else 0))
+    ws = _text_buf(dev, "ws", max(_scratch_bytes("epgw_format_ws_bytes", R), _scratch_bytes("epgw_bgzf_ws_bytes", text.numel())))
     text, row_off, flags = format_scores(scores_device, loc, loc_off, text=text, ws=ws)
     return _compress_formatted(text, row_off, flags, R, ws, eof)
 
@@ -740,33 +812,28 @@ def format_metrics(chrom, chrom_off, chrom_bytes, chrom_idx, start, end, names, 
     row_off int64 [R + 1], flags int32 [1]): the text is text[:row_off[R]]; nothing may be used when flags[0] != 0 (the EPGM_FLAG_*
     bits of the header).  text / ws: buffers to use (None: allocated at their bounds, for names of at most chrom_max / name_max
     bytes, by default the header's EPGM_NAME_MAX).  Current stream, no synchronisation."""
-    R = int(dist.numel())
-    rows = [(chrom_idx, torch.int32), (start, torch.int64), (end, torch.int64), (maxdiff, torch.int32), (dist, torch.float32)]
     if (pvals is None) != (mh is None):
         raise ValueError("pvals and mh go together")
-    if pvals is not None:
-        rows += [(pvals, torch.float64), (mh, torch.float64)]
-    for t, dt in rows:
-        if t.dtype != dt or t.dim() != 1 or t.numel() != R or not t.is_cuda or not t.is_contiguous():
-            raise ValueError("the row arrays must be contiguous 1-D CUDA tensors of R elements: chrom_idx and maxdiff int32, start and end "
-                             "int64, dist float32, pvals and mh float64")
-    for blob, off in ((chrom, chrom_off), (names, names_off)):
-        if blob.dtype != torch.uint8 or off.dtype != torch.int64 or not blob.is_cuda or not off.is_cuda or not blob.is_contiguous() or not off.is_contiguous() or off.numel() < 1:
-            raise ValueError("a name table is a contiguous uint8 blob and contiguous int64 offsets [n + 1], on the device")
+    pdist, R = _arg("format_metrics: dist", dist, torch.float32, 0), int(dist.numel())
     dev = dist.device
+    def arg(name, t, dtype, need, null=False):                   # (checked whatever R is; the kernel gets NULL when there are no rows)
+        p = _arg("format_metrics: " + name, t, dtype, need, dev, null)
+        return p if R else None
+    row = lambda name, t, dtype, null=False: arg(name, t, dtype, R, null)
+    tab = lambda name, t, dtype: arg(name, t, dtype, int(dtype == torch.int64))
     if text is None:
         limit = _abi.header_constant_of(_abi.METRICS["metrics_text"], "EPGM_NAME_MAX")
-        bound = _abi.call("epgm_text_bytes_max", R, limit if chrom_max is None else int(chrom_max), limit if name_max is None else int(name_max),
-                          int(pvals is not None))
-        text = torch.empty(max(int(bound), 256), dtype=torch.uint8, device=dev)
-    if ws is None:
-        ws = torch.empty(max(int(_abi.call("epgm_format_ws_bytes", R)), 256), dtype=torch.uint8, device=dev)
+        text = torch.empty(_scratch_bytes("epgm_text_bytes_max", R, limit if chrom_max is None else int(chrom_max),
+                                          limit if name_max is None else int(name_max), int(pvals is not None)), dtype=torch.uint8, device=dev)
+    text, ptext, ntext = _scratch("format_metrics: text", text, dev, None)
+    _ws, pws, nws = _scratch("format_metrics: ws", ws, dev, "epgm_format_ws_bytes", R)
     row_off = torch.empty(R + 1, dtype=torch.int64, device=dev)
     flags = torch.empty(1, dtype=torch.int32, device=dev)
-    p = (lambda t: _ptr(t) if R else None)
-    _abi.call("epgm_format_metrics", p(chrom), p(chrom_off), chrom_off.numel() - 1, int(chrom_bytes), p(chrom_idx), p(start), p(end), p(names),
-              p(names_off), names_off.numel() - 1, int(names_bytes), p(maxdiff), p(dist), p(pvals) if pvals is not None else None,
-              p(mh) if mh is not None else None, R, _ptr(text), text.numel(), _ptr(row_off), _ptr(flags), _ptr(ws), ws.numel(), _stream())
+    _abi.call("epgm_format_metrics", tab("chrom", chrom, torch.uint8), tab("chrom_off", chrom_off, torch.int64), chrom_off.numel() - 1,
+              int(chrom_bytes), row("chrom_idx", chrom_idx, torch.int32), row("start", start, torch.int64), row("end", end, torch.int64),
+              tab("names", names, torch.uint8), tab("names_off", names_off, torch.int64), names_off.numel() - 1, int(names_bytes),
+              row("maxdiff", maxdiff, torch.int32), pdist if R else None, row("pvals", pvals, torch.float64, True), row("mh", mh, torch.float64, True),
+              R, ptext, ntext, _ptr(row_off), _ptr(flags), pws, nws, _stream())
     return text, row_off, flags
 
 
@@ -786,7 +853,7 @@ def metrics_text_bgzf(chromNames, chrom_idx, start, end, stateNames, maxdiff, di
     if chrom_max > limit or name_max > limit:
         return None
     with_p = pvals is not None
-    per_row = max(int(_abi.call("epgm_text_bytes_max", 1, chrom_max, name_max, int(with_p))), 1)
+    per_row = _scratch_bytes("epgm_text_bytes_max", 1, chrom_max, name_max, int(with_p), floor=1)
     step = max(METRICS_CHUNK_TEXT_BYTES // per_row, 1)
 
     def up(a, lo, hi, dtype):
@@ -798,7 +865,7 @@ def metrics_text_bgzf(chromNames, chrom_idx, start, end, stateNames, maxdiff, di
         hi = min(R, lo + step)
         n_rows = hi - lo
         text = _text_buf(dev, "text", per_row * n_rows)
-        ws = _text_buf(dev, "ws", max(_abi.call("epgm_format_ws_bytes", n_rows), _abi.call("epgw_bgzf_ws_bytes", text.numel())))
+        ws = _text_buf(dev, "ws", max(_scratch_bytes("epgm_format_ws_bytes", n_rows), _scratch_bytes("epgw_bgzf_ws_bytes", text.numel())))
         text, row_off, flags = format_metrics(chrom, chrom_off, chrom_bytes, up(chrom_idx, lo, hi, np.int32), up(start, lo, hi, np.int64),
                                               up(end, lo, hi, np.int64), names, names_off, names_bytes, up(maxdiff, lo, hi, np.int32),
                                               up(dist, lo, hi, np.float32), up(pvals, lo, hi, np.float64) if with_p else None,
@@ -817,19 +884,19 @@ def bgzf_inflate(comp, table, out=None, status=None, flags=None):
     where every member lies and goes.  -> (out uint8, status int32 [M], flags int32 [1]): status[m] is 0 or the reason member m was
     given up (then its bytes of out are zeros), flags[0] the number of members with a reason.  out: the buffer to fill (None: one
     of max(text offset + ISIZE) bytes, which costs a synchronisation).  Current stream, no synchronisation otherwise."""
-    if comp.dtype != torch.uint8 or not comp.is_cuda or not comp.is_contiguous():
-        raise ValueError("comp must be a contiguous uint8 CUDA tensor")
-    if table.dtype != torch.int64 or not table.is_cuda or not table.is_contiguous() or table.dim() != 2 or table.shape[1] != 5:
-        raise ValueError("table must be a contiguous int64 [M, 5] CUDA tensor")
-    M, dev = int(table.shape[0]), comp.device
+    pcomp, dev = _arg("bgzf_inflate: comp", comp, torch.uint8, 0), comp.device
+    ptable = _arg("bgzf_inflate: table", table, torch.int64, 0, dev)
+    if table.dim() != 2 or table.shape[1] != 5:
+        raise ValueError("engine.bgzf_inflate: table must be [M, 5]")
+    M = int(table.shape[0])
     if out is None:
         out = torch.empty(max(int((table[:, 2] + table[:, 3]).max()) if M else 0, 16), dtype=torch.uint8, device=dev)
     if status is None:
         status = torch.empty(max(M, 1), dtype=torch.int32, device=dev)[:M]
     if flags is None:
         flags = torch.empty(1, dtype=torch.int32, device=dev)
-    _abi.call("epgz_bgzf_inflate", _ptr(comp) if comp.numel() else None, comp.numel(), _ptr(table) if M else None, M, _ptr(out), out.numel(),
-              _ptr(status) if M else None, _ptr(flags), _stream())
+    _abi.call("epgz_bgzf_inflate", pcomp, comp.numel(), ptable, M, _arg("bgzf_inflate: out", out, torch.uint8, 0, dev), out.numel(),
+              _arg("bgzf_inflate: status", status, torch.int32, M, dev), _arg("bgzf_inflate: flags", flags, torch.int32, 1, dev), _stream())
     return out, status, flags
 
 
@@ -837,12 +904,10 @@ def newline_index(text, seg_bytes, n=None):
     """Per segment of seg_bytes bytes (a multiple of 16) of text[:n] (uint8, device, 16-byte aligned): the number of newlines in it and
     the offset of the last one, -1 when there is none (epgz_newline_index) -> (count int64 [segments], last int64 [segments]).
     Current stream, no synchronisation."""
+    ptext = _arg("newline_index: text", text, torch.uint8, 0 if n is None else int(n))
     n = text.numel() if n is None else int(n)
-    if text.dtype != torch.uint8 or not text.is_cuda or not text.is_contiguous() or text.numel() < n:
-        raise ValueError("text must be a contiguous uint8 CUDA tensor of at least n bytes")
-    nseg = int(_abi.call("epgz_newline_segments", n, int(seg_bytes)))
-    both = torch.empty((2, nseg), dtype=torch.int64, device=text.device)
-    _abi.call("epgz_newline_index", _ptr(text) if n else None, n, int(seg_bytes), _ptr(both[0]) if n else None, _ptr(both[1]) if n else None, _stream())
+    both = torch.empty((2, _scratch_bytes("epgz_newline_segments", n, int(seg_bytes), floor=0)), dtype=torch.int64, device=text.device)
+    _abi.call("epgz_newline_index", ptext if n else None, n, int(seg_bytes), _ptr(both[0]) if n else None, _ptr(both[1]) if n else None, _stream())
     return both[0], both[1]
 
 
@@ -858,6 +923,12 @@ def select_columns(X, cols):
     return out
 
 
+def _rows(where, H, S, dev=None, dtype=torch.int16):
+    """_arg for a [R, S] array whose row count is the call's R (a histogram, as a rule) -> (address, R)."""
+    R = H.shape[0] if isinstance(H, torch.Tensor) and H.dim() else 0
+    return _arg(where, H, dtype, R * S, dev), R
+
+
 def null_hist_from_binhist_parts(HAs, HBs, n_cols, S, ga, gb, seed, row0s, stream=None):
     """epg_null_hist_from_binhist for several parts in one launch (bit-identical to a call per part); outputs from ONE allocation
     per group.  -> (list of OA, list of OB)."""
@@ -866,10 +937,11 @@ def null_hist_from_binhist_parts(HAs, HBs, n_cols, S, ga, gb, seed, row0s, strea
         return [], []
     rows = [h.shape[0] for h in HAs]
     dev = HAs[0].device
+    need = [r * S for r in rows]
+    pA, pB = _parts("null_hist_from_binhist_parts: HAs", HAs, torch.int16, need, dev), _parts("null_hist_from_binhist_parts: HBs", HBs, torch.int16, need, dev)
     OAs, OBs = hist_rows_alloc(rows, S, dev), hist_rows_alloc(rows, S, dev)
-    _abi.call("epg_null_hist_from_binhist_parts", n, _ptr_array(HAs), _ptr_array(HBs), (C.c_int64 * n)(*rows), S, n_cols, ga, gb, seed,
-              (C.c_int64 * n)(*[int(r) for r in row0s]), _ptr_array(OAs), _ptr_array(OBs),
-              _stream() if stream is None else C.c_void_p(stream.cuda_stream))
+    _abi.call("epg_null_hist_from_binhist_parts", n, pA, pB, _ints(C.c_int64, rows), S, n_cols, ga, gb, seed, _ints(C.c_int64, row0s),
+              _ptr_array(OAs), _ptr_array(OBs), _stream(stream))
     return OAs, OBs
 
 
@@ -882,28 +954,32 @@ def null_dist_draws_parts(HAs, HBs, row0s, S, NA, NB, ga, gb, TnA, TnB, seeds, m
     seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
     K = int(seeds.size)
     rows = [h.shape[0] for h in HAs]
+    dev = HAs[0].device if n else None
     if outs is None:
-        dev = HAs[0].device if n else "cuda"
-        outs = [torch.empty((K, r), dtype=torch.float32, device=dev) for r in rows]
-    _abi.call("epg_null_dist_draws_parts", n, _ptr_array(HAs), _ptr_array(HBs), (C.c_int64 * n)(*rows),
-              (C.c_int64 * n)(*[int(r) for r in row0s]), _ptr_array(masks) if masks is not None else None, S, NA, NB, ga, gb, _ptr(TnA),
-              _ptr(TnB), seeds.ctypes.data_as(C.c_void_p), K, _ptr_array(outs), _stream())
+        outs = [torch.empty((K, r), dtype=torch.float32, device=dev or "cuda") for r in rows]
+    w, need = "null_dist_draws_parts: ", [r * S for r in rows]
+    _abi.call("epg_null_dist_draws_parts", n, _parts(w + "HAs", HAs, torch.int16, need, dev), _parts(w + "HBs", HBs, torch.int16, need, dev),
+              _ints(C.c_int64, rows), _ints(C.c_int64, row0s), _parts(w + "masks", masks, torch.uint8, rows, dev) if masks is not None else None,
+              S, NA, NB, ga, gb, _arg(w + "TnA", TnA, torch.float32, (ga + 1) * S, dev), _arg(w + "TnB", TnB, torch.float32, (gb + 1) * S, dev),
+              seeds.ctypes.data_as(C.c_void_p), K, _parts(w + "outs", outs, torch.float32, [K * r for r in rows], dev), _stream())
     return outs
 
 
 def null_exceed_ws_bytes(n):
-    return _abi.check(_abi.load().epg_null_exceed_ws_bytes(int(n)))
+    return _scratch_bytes("epg_null_exceed_ws_bytes", int(n))
 
 
 def null_exceed(null, d, exceed, ws=None):
     """exceed[b] += #{x in null : x is not NaN and |x| >= |d[b]|} (epg_null_exceed): null float32 [n] (any shape, contiguous), d
     float32 [R], exceed int64 [R], accumulated into.  ws: uint8 workspace of null_exceed_ws_bytes(n) bytes (None: allocated)."""
+    pnull, dev = _arg("null_exceed: null", null, torch.float32, 0), null.device
+    pd = _arg("null_exceed: d", d, torch.float32, 0, dev)
     n, R = null.numel(), d.numel()
+    pexceed = _arg("null_exceed: exceed", exceed, torch.int64, R, dev)
     if n == 0 or R == 0:
         return exceed
-    if ws is None:
-        ws = torch.empty(null_exceed_ws_bytes(n), dtype=torch.uint8, device=null.device)
-    _abi.call("epg_null_exceed", _ptr(null), n, _ptr(d), R, _ptr(exceed), _ptr(ws), ws.numel(), _stream())
+    _ws, pws, nws = _scratch("null_exceed: ws", ws, dev, "epg_null_exceed_ws_bytes", n)
+    _abi.call("epg_null_exceed", pnull, n, pd, R, pexceed, pws, nws, _stream())
     return exceed
 
 
@@ -912,186 +988,194 @@ def pair_count_null_parts(XAs, XBs, NA, NB, S, seed, row0s, counts=None):
     (epg_pair_count_null_parts).  -> (HAs, HBs, OAs, OBs) lists of [R_p, S] histograms (real groups, null groups).  Raises
     EpilogosHipError(-2) for shapes outside the fused kernel's: bin_hist_parts + null_hist_from_binhist_parts give the same."""
     n = len(XAs)
-    sa = [_check_states(X, NA) if X.shape[0] else (0, padded_width(NA)) for X in XAs]
-    sb = [_check_states(X, NB) if X.shape[0] else (0, padded_width(NB)) for X in XBs]
+    dev = XAs[0].device
+    sa = [_mat("pair_count_null_parts: XAs", X, torch.int8, NA, dev)[1:] if X.shape[0] else (0, padded_width(NA)) for X in XAs]
+    sb = [_mat("pair_count_null_parts: XBs", X, torch.int8, NB, dev)[1:] if X.shape[0] else (0, padded_width(NB)) for X in XBs]
     rows = [r for r, _l in sa]
     if rows != [r for r, _l in sb]:
         raise ValueError("paired inputs must have the same number of bins")
-    dev = XAs[0].device
     H = hist_rows_alloc(rows + rows, S, dev)
     O = hist_rows_alloc(rows + rows, S, dev)
-    _abi.call("epg_pair_count_null_parts", n, _ptr_array(XAs), _ptr_array(XBs), (C.c_int64 * n)(*rows), NA, NB,
-              (C.c_int64 * n)(*[l for _r, l in sa]), (C.c_int64 * n)(*[l for _r, l in sb]), S, _ptr_array(H[:n]), _ptr_array(H[n:]),
-              _ptr(counts), seed, (C.c_int64 * n)(*[int(r) for r in row0s]), _ptr_array(O[:n]), _ptr_array(O[n:]), _stream())
+    _abi.call("epg_pair_count_null_parts", n, _ptr_array(XAs), _ptr_array(XBs), _ints(C.c_int64, rows), NA, NB,
+              _ints(C.c_int64, [l for _r, l in sa]), _ints(C.c_int64, [l for _r, l in sb]), S, _ptr_array(H[:n]), _ptr_array(H[n:]),
+              _arg("pair_count_null_parts: counts", counts, torch.int64, S, dev, null=True), seed, _ints(C.c_int64, row0s), _ptr_array(O[:n]),
+              _ptr_array(O[n:]), _stream())
     return H[:n], H[n:], O[:n], O[n:]
 
 
 def hist_s2_from_binhist(H, S, counts=None):
+    pH, R = _rows("hist_s2_from_binhist: H", H, S)
     if counts is None:
         counts = zeros_counts(S * S, device=H.device)
-    _abi.call("epg_hist_s2_from_binhist", _ptr(H), H.shape[0], S, _ptr(counts), _stream())
+    _abi.call("epg_hist_s2_from_binhist", pH, R, S, _arg("hist_s2_from_binhist: counts", counts, torch.int64, S * S, H.device), _stream())
     return counts
 
 
 def hist_s2_from_binhist_pair(HA, HB, S, counts=None):
     """S2 counts of the column concatenation [A|B] from the two groups' histograms (helpers.py:173)."""
+    pHA, R = _rows("hist_s2_from_binhist_pair: HA", HA, S)
+    pHB = _arg("hist_s2_from_binhist_pair: HB", HB, torch.int16, R * S, HA.device)
     if HA.shape != HB.shape:
         raise ValueError("paired histograms must have the same shape")
     if counts is None:
         counts = zeros_counts(S * S, device=HA.device)
-    _abi.call("epg_hist_s2_from_binhist_pair", _ptr(HA), _ptr(HB), HA.shape[0], S, _ptr(counts), _stream())
+    _abi.call("epg_hist_s2_from_binhist_pair", pHA, pHB, R, S, _arg("hist_s2_from_binhist_pair: counts", counts, torch.int64, S * S, HA.device),
+              _stream())
     return counts
 
 
 def hist_s3_ws_bytes(R, N, S):
-    return max(int(_abi.call("epg_ws_bytes", 3, R, N, S)), 256)
+    return _scratch_bytes("epg_ws_bytes", 3, R, N, S)
 
 
 def hist_s3(X, N, S, counts=None, use_workspace=True, ws=None):
     """counts int32 [N*N*S*S] += biosample-pair state co-occurrences.  With a workspace (room for the transposed matrix)
     the matrix-core kernel runs; without one the ABI falls back to the LDS-counter kernel (same integers).  `ws`: a
     caller-owned workspace of at least hist_s3_ws_bytes(R, N, S) bytes (a session reuses one for all its parts)."""
-    R, ldx = _check_states(X, N)
+    pX, R, ldx = _mat("hist_s3: X", X, torch.int8, N)
+    dev = X.device
     if counts is None:
-        counts = zeros_counts(N * N * S * S, dtype=torch.int32, device=X.device)
-    if use_workspace:
-        if ws is None:
-            ws = torch.empty(hist_s3_ws_bytes(R, N, S), dtype=torch.uint8, device=X.device)
-        _abi.call("epg_hist_s3", _ptr(X), R, N, ldx, S, _ptr(counts), _ptr(ws), ws.numel(), _stream())
-    else:
-        _abi.call("epg_hist_s3", _ptr(X), R, N, ldx, S, _ptr(counts), None, 0, _stream())
+        counts = zeros_counts(N * N * S * S, dtype=torch.int32, device=dev)
+    pws, nws = _scratch("hist_s3: ws", ws, dev, "epg_ws_bytes", 3, R, N, S)[1:] if use_workspace else (None, 0)
+    _abi.call("epg_hist_s3", pX, R, N, ldx, S, _arg("hist_s3: counts", counts, torch.int32, N * N * S * S, dev), pws, nws, _stream())
     return counts
 
 
 def normalise(counts, q=None, ws=None):
     """q = float32(counts / sum(counts)) on device (expectedCombination.py:42)."""
+    name = {torch.int64: "epg_normalise_i64", torch.int32: "epg_normalise_i32"}.get(getattr(counts, "dtype", None))
+    if name is None:
+        raise ValueError("engine.normalise: counts must be an int64 or int32 tensor")
+    pcounts, n, dev = _arg("normalise: counts", counts, counts.dtype, 0), counts.numel(), counts.device
     if q is None:
-        q = torch.empty(counts.numel(), dtype=torch.float32, device=counts.device)
-    if ws is None:
-        ws = torch.empty(256, dtype=torch.uint8, device=counts.device)
-    name = {torch.int64: "epg_normalise_i64", torch.int32: "epg_normalise_i32"}[counts.dtype]
-    _abi.call(name, _ptr(counts), counts.numel(), _ptr(q), _ptr(ws), ws.numel(), _stream())
+        q = torch.empty(n, dtype=torch.float32, device=dev)
+    _ws, pws, nws = _scratch("normalise: ws", ws, dev, None)
+    _abi.call(name, pcounts, n, _arg("normalise: q", q, torch.float32, n, dev), pws, nws, _stream())
     return q
 
 
-def _outs(R, S, device, want32, want64, out32=None, out64=None):
-    o32 = out32 if out32 is not None else (torch.empty((R, S), dtype=torch.float32, device=device) if want32 else None)
-    o64 = out64 if out64 is not None else (torch.empty((R, S), dtype=torch.float64, device=device) if want64 else None)
-    return o32, o64
+def _outs(where, R, S, dev, want32, want64, out32=None, out64=None):
+    """The two score outputs of a call, [R, S] each: given, allocated when wanted, or None -> (out32, out64, address of out64, of out32)."""
+    o32 = out32 if out32 is not None else (torch.empty((R, S), dtype=torch.float32, device=dev) if want32 else None)
+    o64 = out64 if out64 is not None else (torch.empty((R, S), dtype=torch.float64, device=dev) if want64 else None)
+    return (o32, o64, _arg(where + ": out64", o64, torch.float64, R * S, dev, null=True),
+            _arg(where + ": out32", o32, torch.float32, R * S, dev, null=True))
 
 
 def workspace(saliency, R, N, S, device="cuda"):
     """Caller-owned scratch for the score calls of one saliency (tables; plus a histogram cache when R > 0)."""
-    return _ws(saliency, R, N, S, device)
-
-
-def _ws(saliency, R, N, S, device):
-    nbytes = _abi.call("epg_ws_bytes", saliency, R, N, S)
-    return torch.empty(max(nbytes, 256), dtype=torch.uint8, device=device)
+    return torch.empty(_scratch_bytes("epg_ws_bytes", saliency, R, N, S), dtype=torch.uint8, device=device)
 
 
 def score_s1(X, N, S, q, want32=True, want64=False, out32=None, out64=None, ws=None):
-    R, ldx = _check_states(X, N)
-    o32, o64 = _outs(R, S, X.device, want32, want64, out32, out64)
-    if ws is None:
-        ws = _ws(1, R, N, S, X.device)
-    _abi.call("epg_score_s1", _ptr(X), R, N, ldx, S, _ptr(q), _ptr(o64), _ptr(o32), _ptr(ws), ws.numel(), _stream())
+    pX, R, ldx = _mat("score_s1: X", X, torch.int8, N)
+    dev = X.device
+    o32, o64, p64, p32 = _outs("score_s1", R, S, dev, want32, want64, out32, out64)
+    _ws, pws, nws = _scratch("score_s1: ws", ws, dev, "epg_ws_bytes", 1, R, N, S)
+    _abi.call("epg_score_s1", pX, R, N, ldx, S, _arg("score_s1: q", q, torch.float32, S, dev), p64, p32, pws, nws, _stream())
     return o32, o64
 
 
 def score_s1_from_binhist(H, N, S, q, want32=True, want64=False, out32=None, out64=None, ws=None):
-    R = H.shape[0]
-    o32, o64 = _outs(R, S, H.device, want32, want64, out32, out64)
-    if ws is None:
-        ws = _ws(1, 0, N, S, H.device)
-    _abi.call("epg_score_s1_from_binhist", _ptr(H), R, N, S, _ptr(q), _ptr(o64), _ptr(o32), _ptr(ws), ws.numel(),
-              _stream())
+    pH, R = _rows("score_s1_from_binhist: H", H, S)
+    dev = H.device
+    o32, o64, p64, p32 = _outs("score_s1_from_binhist", R, S, dev, want32, want64, out32, out64)
+    _ws, pws, nws = _scratch("score_s1_from_binhist: ws", ws, dev, "epg_ws_bytes", 1, 0, N, S)
+    _abi.call("epg_score_s1_from_binhist", pH, R, N, S, _arg("score_s1_from_binhist: q", q, torch.float32, S, dev), p64, p32, pws, nws, _stream())
     return o32, o64
 
 
 def score_s1_from_binhist_table(H, N, S, T64=None, T32=None, out32=None, out64=None):
     """S1 scores of cached histograms from a caller-built table T[c, s], c = 0..N (device tensors [N + 1, S]; T32 -> float32
     scores, T64 -> float64 scores).  scores.s1ScoreTable builds the pair on the host with the reference's arithmetic."""
-    R = H.shape[0]
-    for T, dt in ((T64, torch.float64), (T32, torch.float32)):
-        if T is not None and (T.dtype != dt or T.numel() != (N + 1) * S or not T.is_contiguous()):
-            raise ValueError("S1 table must be a contiguous [N + 1, S] tensor of its output's dtype")
-    o32, o64 = _outs(R, S, H.device, T32 is not None, T64 is not None, out32, out64)
-    _abi.call("epg_score_s1_from_binhist_table", _ptr(H), R, N, S, _ptr(T64), _ptr(T32), _ptr(o64), _ptr(o32), _stream())
+    w = "score_s1_from_binhist_table"
+    pH, R = _rows(w + ": H", H, S)
+    dev = H.device
+    pT64 = _arg(w + ": T64", T64, torch.float64, (N + 1) * S, dev, null=True)
+    pT32 = _arg(w + ": T32", T32, torch.float32, (N + 1) * S, dev, null=True)
+    o32, o64, p64, p32 = _outs(w, R, S, dev, T32 is not None, T64 is not None, out32, out64)
+    _abi.call("epg_score_s1_from_binhist_table", pH, R, N, S, pT64, pT32, p64, p32, _stream())
     return o32, o64
 
 
 def combine_score_s1(counts, H, N, S, q=None, want32=True, want64=False, out32=None, out64=None, ws=None, rezero=False):
     """STEP 2 + STEP 3 of an S1 job in one ABI call: q = normalise(counts) (the all-reduced int64[S] vector), then the
     scores of the cached histograms H.  Returns (q, out32, out64)."""
-    R = H.shape[0]
-    o32, o64 = _outs(R, S, H.device, want32, want64, out32, out64)
+    w = "combine_score_s1"
+    pH, R = _rows(w + ": H", H, S)
+    dev = H.device
+    o32, o64, p64, p32 = _outs(w, R, S, dev, want32, want64, out32, out64)
     if q is None:
-        q = torch.empty(S, dtype=torch.float32, device=H.device)
-    if ws is None:
-        ws = _ws(1, 0, N, S, H.device)
-    _abi.call("epg_combine_score_s1", _ptr(counts), 1 if rezero else 0, _ptr(H), R, N, S, _ptr(q), _ptr(o64), _ptr(o32),
-              _ptr(ws), ws.numel(), _stream())
+        q = torch.empty(S, dtype=torch.float32, device=dev)
+    _ws, pws, nws = _scratch(w + ": ws", ws, dev, "epg_ws_bytes", 1, 0, N, S)
+    _abi.call("epg_combine_score_s1", _arg(w + ": counts", counts, torch.int64, S, dev), 1 if rezero else 0, pH, R, N, S,
+              _arg(w + ": q", q, torch.float32, S, dev), p64, p32, pws, nws, _stream())
     return q, o32, o64
 
 
 def s1_tables(counts, N, S, q=None, ws=None):
     """STEP 2 and the S1 score table of group width N in ONE launch, nothing else (epg_combine_score_s1 with no bins):
     q = normalise(counts) and T[c, s] = kl(c / N, q[s]), c = 0..N.  Returns (q, T64, T32); the tables are views of `ws`."""
-    dev = counts.device
+    pcounts, dev = _arg("s1_tables: counts", counts, torch.int64, S), counts.device
     if q is None:
         q = torch.empty(S, dtype=torch.float32, device=dev)
-    if ws is None:
-        ws = _ws(1, 0, N, S, dev)
-    _abi.call("epg_combine_score_s1", _ptr(counts), 0, None, 0, N, S, _ptr(q), None, None, _ptr(ws), ws.numel(), _stream())
+    ws, pws, nws = _scratch("s1_tables: ws", ws, dev, "epg_ws_bytes", 1, 0, N, S)
+    _abi.call("epg_combine_score_s1", pcounts, 0, None, 0, N, S, _arg("s1_tables: q", q, torch.float32, S, dev), None, None, pws, nws, _stream())
     nent = (N + 1) * S
     off = (nent * 8 + 255) // 256 * 256
     return q, ws[:nent * 8].view(torch.float64), ws[off:off + nent * 4].view(torch.float32)
 
 
 def score_s2(X, N, S, q, perms=None, want32=True, want64=False):
-    R, ldx = _check_states(X, N)
+    pX, R, ldx = _mat("score_s2: X", X, torch.int8, N)
+    dev = X.device
     perms = N * (N - 1) if perms is None else perms
-    o32, o64 = _outs(R, S, X.device, want32, want64)
-    ws = _ws(2, R, N, S, X.device)
-    _abi.call("epg_score_s2", _ptr(X), R, N, ldx, S, perms, _ptr(q), _ptr(o64), _ptr(o32), _ptr(ws), ws.numel(),
-              _stream())
+    o32, o64, p64, p32 = _outs("score_s2", R, S, dev, want32, want64)
+    _ws, pws, nws = _scratch("score_s2: ws", None, dev, "epg_ws_bytes", 2, R, N, S)
+    _abi.call("epg_score_s2", pX, R, N, ldx, S, perms, _arg("score_s2: q", q, torch.float32, S * S, dev), p64, p32, pws, nws, _stream())
     return o32, o64
 
 
 def score_s2_from_binhist(H, N, S, q, perms=None, want32=True, want64=False, out32=None, out64=None, ws=None):
-    R = H.shape[0]
+    w = "score_s2_from_binhist"
+    pH, R = _rows(w + ": H", H, S)
+    dev = H.device
     perms = N * (N - 1) if perms is None else perms
-    o32, o64 = _outs(R, S, H.device, want32, want64, out32, out64)
-    if ws is None:
-        ws = _ws(2, 0, N, S, H.device)
-    _abi.call("epg_score_s2_from_binhist", _ptr(H), R, N, S, perms, _ptr(q), _ptr(o64), _ptr(o32), _ptr(ws),
-              ws.numel(), _stream())
+    o32, o64, p64, p32 = _outs(w, R, S, dev, want32, want64, out32, out64)
+    _ws, pws, nws = _scratch(w + ": ws", ws, dev, "epg_ws_bytes", 2, 0, N, S)
+    _abi.call("epg_score_s2_from_binhist", pH, R, N, S, perms, _arg(w + ": q", q, torch.float32, S * S, dev), p64, p32, pws, nws, _stream())
     return o32, o64
 
 
 def score_s3(X, N, S, q, want32=True, want64=False, ws=None):
     """`ws`: caller-owned workspace of at least epg_ws_bytes(3, R, N, S) bytes (tables + transposed matrix + cells)."""
-    R, ldx = _check_states(X, N)
-    o32, o64 = _outs(R, S, X.device, want32, want64)
-    if ws is None:
-        ws = _ws(3, R, N, S, X.device)
-    _abi.call("epg_score_s3", _ptr(X), R, N, ldx, S, _ptr(q), _ptr(o64), _ptr(o32), _ptr(ws), ws.numel(), _stream())
+    pX, R, ldx = _mat("score_s3: X", X, torch.int8, N)
+    dev = X.device
+    o32, o64, p64, p32 = _outs("score_s3", R, S, dev, want32, want64)
+    _ws, pws, nws = _scratch("score_s3: ws", ws, dev, "epg_ws_bytes", 3, R, N, S)
+    _abi.call("epg_score_s3", pX, R, N, ldx, S, _arg("score_s3: q", q, torch.float32, N * N * S * S, dev), p64, p32, pws, nws, _stream())
     return o32, o64
+
+
+def _pair_tables(w, S, widths, tables, dev):
+    """The four S1 tables of a paired call, float32 [width + 1, S] each -> their addresses."""
+    return [_arg("%s: %s" % (w, name), T, torch.float32, (width + 1) * S, dev) for name, width, T in zip(("TA", "TB", "TnA", "TnB"), widths, tables)]
 
 
 def pair_scores_s1_from_binhist(HA, HB, HnA, HnB, S, NA, NB, ga, gb, TA, TB, TnA, TnB):
     """Paired S1 in one pass over the four histograms (epg_pair_scores_s1_from_binhist): delta [R, S], null distance [R], STEP 4's
     distance [R] and 1-based largest-difference state [R].  T*: float32 [width + 1, S] device tables (scores.s1ScoreTable).
     Raises EpilogosHipError(-2) when the tables do not fit a CU's LDS; the separate calls give the same results."""
-    R = HA.shape[0]
+    w = "pair_scores_s1_from_binhist"
+    pHA, R = _rows(w + ": HA", HA, S)
     dev = HA.device
+    hists = [pHA] + [_arg("%s: %s" % (w, name), H, torch.int16, R * S, dev) for name, H in (("HB", HB), ("HnA", HnA), ("HnB", HnB))]
     delta = torch.empty((R, S), dtype=torch.float32, device=dev)
     null = torch.empty(R, dtype=torch.float32, device=dev)
     dist = torch.empty(R, dtype=torch.float32, device=dev)
     maxdiff = torch.empty(R, dtype=torch.int32, device=dev)
-    _abi.call("epg_pair_scores_s1_from_binhist", _ptr(HA), _ptr(HB), _ptr(HnA), _ptr(HnB), R, S, NA, NB, ga, gb, _ptr(TA), _ptr(TB), _ptr(TnA),
-              _ptr(TnB), _ptr(delta), _ptr(null), _ptr(dist), _ptr(maxdiff), _stream())
+    _abi.call("epg_pair_scores_s1_from_binhist", *hists, R, S, NA, NB, ga, gb, *_pair_tables(w, S, (NA, NB, ga, gb), (TA, TB, TnA, TnB), dev),
+              _ptr(delta), _ptr(null), _ptr(dist), _ptr(maxdiff), _stream())
     return delta, null, dist, maxdiff
 
 
@@ -1102,56 +1186,66 @@ def pair_scores_s1_parts(parts, S, NA, NB, ga, gb, TA, TB, TnA, TnB, qstate=None
     n = len(parts)
     if n == 0:
         return []
+    w = "pair_scores_s1_parts"
     dev = parts[0][0].device
+    rows = [p[0].shape[0] for p in parts]
+    hists = [_parts("%s: parts[.][%d]" % (w, k), [p[k] for p in parts], torch.int16, [r * S for r in rows], dev) for k in range(4)]
     outs = []
-    for HA, _HB, _HnA, _HnB in parts:
-        R = HA.shape[0]
+    for R in rows:
         outs.append({"delta": torch.empty((R, S), dtype=torch.float32, device=dev), "null": torch.empty(R, dtype=torch.float32, device=dev),
                      "rdist": torch.empty(R, dtype=torch.float32, device=dev), "mdiff": torch.empty(R, dtype=torch.int32, device=dev),
                      "quies": torch.empty(R, dtype=torch.uint8, device=dev) if qstate is not None else None})
-    arr = lambda ts: (C.c_void_p * n)(*[t.data_ptr() if t is not None and t.numel() else None for t in ts])
-    rows = (C.c_int64 * n)(*[p[0].shape[0] for p in parts])
-    _abi.call("epg_pair_scores_s1_parts", n, arr([p[0] for p in parts]), arr([p[1] for p in parts]), arr([p[2] for p in parts]),
-              arr([p[3] for p in parts]), rows, S, NA, NB, ga, gb, _ptr(TA), _ptr(TB), _ptr(TnA), _ptr(TnB), arr([o["delta"] for o in outs]),
-              arr([o["null"] for o in outs]), arr([o["rdist"] for o in outs]), arr([o["mdiff"] for o in outs]),
-              arr([o["quies"] for o in outs]) if qstate is not None else None, -1 if qstate is None else int(qstate), _stream())
+    out = lambda key: _ptr_array([o[key] for o in outs])
+    _abi.call("epg_pair_scores_s1_parts", n, *hists, _ints(C.c_int64, rows), S, NA, NB, ga, gb,
+              *_pair_tables(w, S, (NA, NB, ga, gb), (TA, TB, TnA, TnB), dev), out("delta"), out("null"), out("rdist"), out("mdiff"),
+              out("quies") if qstate is not None else None, -1 if qstate is None else int(qstate), _stream())
     return outs
 
 
+def _grid(where, x, dtype=torch.int32):
+    """_arg for a dense [R, S] grid whose shape is the call's -> (address, R, S)."""
+    p = _arg(where, x, dtype, 0)
+    if x.dim() != 2:
+        raise ValueError("engine.%s must be 2-D [R, S]" % where)
+    return p, x.shape[0], x.shape[1]
+
+
 def pair_finish(a, b, want_dist=True):
-    R, S = a.shape
+    pa, R, S = _grid("pair_finish: a", a, torch.float32)
+    pb = _arg("pair_finish: b", b, torch.float32, R * S, a.device)
     delta = torch.empty_like(a)
     dist = torch.empty(R, dtype=torch.float32, device=a.device) if want_dist else None
-    _abi.call("epg_pair_finish", _ptr(a), _ptr(b), R, S, _ptr(delta), _ptr(dist), _stream())
+    _abi.call("epg_pair_finish", pa, pb, R, S, _ptr(delta), _ptr(dist), _stream())
     return delta, dist
 
 
 def pair_metrics(delta, roundtrip=True):
     """Signed squared distance float32[R] and 1-based largest-|delta| state int32[R] (roiAndVisualPairwise.py:347-354)."""
-    R, S = delta.shape
+    pdelta, R, S = _grid("pair_metrics: delta", delta, torch.float32)
     dist = torch.empty(R, dtype=torch.float32, device=delta.device)
     maxdiff = torch.empty(R, dtype=torch.int32, device=delta.device)
-    _abi.call("epg_pair_metrics", _ptr(delta), R, S, 1 if roundtrip else 0, _ptr(dist), _ptr(maxdiff), _stream())
+    _abi.call("epg_pair_metrics", pdelta, R, S, 1 if roundtrip else 0, _ptr(dist), _ptr(maxdiff), _stream())
     return dist, maxdiff
 
 
 def quiescent(XA, NA, XB, NB, qstate):
-    R, ldxa = _check_states(XA, NA)
-    R2, ldxb = _check_states(XB, NB)
+    pXA, R, ldxa = _mat("quiescent: XA", XA, torch.int8, NA)
+    pXB, R2, ldxb = _mat("quiescent: XB", XB, torch.int8, NB, XA.device)
     if R != R2:
         raise ValueError("paired inputs must have the same number of bins")
     mask = torch.empty(R, dtype=torch.uint8, device=XA.device)
-    _abi.call("epg_quiescent", _ptr(XA), NA, ldxa, _ptr(XB), NB, ldxb, R, qstate, _ptr(mask), _stream())
+    _abi.call("epg_quiescent", pXA, NA, ldxa, pXB, NB, ldxb, R, qstate, _ptr(mask), _stream())
     return mask
 
 
 def null_hist(XA, NA, XB, NB, S, ga, gb, seed, row0=0):
-    R, ldxa = _check_states(XA, NA)
-    _, ldxb = _check_states(XB, NB)
+    pXA, R, ldxa = _mat("null_hist: XA", XA, torch.int8, NA)
+    pXB, R2, ldxb = _mat("null_hist: XB", XB, torch.int8, NB, XA.device)
+    if R != R2:
+        raise ValueError("paired inputs must have the same number of bins")
     HA = torch.empty((R, S), dtype=torch.int16, device=XA.device)
     HB = torch.empty((R, S), dtype=torch.int16, device=XA.device)
-    _abi.call("epg_null_hist", _ptr(XA), NA, ldxa, _ptr(XB), NB, ldxb, R, S, ga, gb, seed, row0, _ptr(HA), _ptr(HB),
-              _stream())
+    _abi.call("epg_null_hist", pXA, NA, ldxa, pXB, NB, ldxb, R, S, ga, gb, seed, row0, _ptr(HA), _ptr(HB), _stream())
     return HA, HB
 
 
@@ -1307,9 +1401,10 @@ def upload_states(pinned, R, ldx, copy_stream, device="cuda"):
 
 def quiescent_from_binhist(HA, NA, HB, NB, S, qstate):
     """Quiescence mask from the two groups' histograms (scores.py:294-303)."""
-    R = HA.shape[0]
+    pHA, R = _rows("quiescent_from_binhist: HA", HA, S)
+    pHB = _arg("quiescent_from_binhist: HB", HB, torch.int16, R * S, HA.device)
     mask = torch.empty(R, dtype=torch.uint8, device=HA.device)
-    _abi.call("epg_quiescent_from_binhist", _ptr(HA), _ptr(HB), R, S, NA, NB, qstate, _ptr(mask), _stream())
+    _abi.call("epg_quiescent_from_binhist", pHA, pHB, R, S, NA, NB, qstate, _ptr(mask), _stream())
     return mask
 
 
@@ -1317,14 +1412,109 @@ def null_hist_from_binhist(HA, HB, n_cols, S, ga, gb, seed, row0=0, stream=None)
     """Histograms of the two shuffled null groups from the REAL groups' histograms (multivariate hypergeometric, exact).
     stream: a torch.cuda.Stream to launch on instead of the current one (the outputs are allocated from the CURRENT stream's
     pool all the same; the caller orders the streams with events)."""
+    pHA, R = _rows("null_hist_from_binhist: HA", HA, S)
+    pHB = _arg("null_hist_from_binhist: HB", HB, torch.int16, R * S, HA.device)
     if HA.shape != HB.shape:
         raise ValueError("paired histograms must have the same shape")
     OA, OB = torch.empty_like(HA), torch.empty_like(HB)
-    _abi.call("epg_null_hist_from_binhist", _ptr(HA), _ptr(HB), HA.shape[0], S, n_cols, ga, gb, seed, row0, _ptr(OA), _ptr(OB),
-              _stream() if stream is None else C.c_void_p(stream.cuda_stream))
+    _abi.call("epg_null_hist_from_binhist", pHA, pHB, R, S, n_cols, ga, gb, seed, row0, _ptr(OA), _ptr(OB), _stream(stream))
     return OA, OB
 
 
 def hist_to_numpy(H):
     """int16-stored uint16 histogram tensor -> numpy uint16."""
     return H.cpu().numpy().view(np.uint16)
+
+
+# ---- similarity search (include/epilogos_amd.h, include/epilogos_simsearch_pick.h) and the scores-text parser
+def simsearch_ws_bytes(Pg, S, W, B):
+    return _scratch_bytes("epg_simsearch_ws_bytes", Pg, S, W, B, floor=0)
+
+
+def simsearch(g, W, q, self_start, n, key_bound, ws=None, want_dist=False):
+    """STEP 2's search (epg_simsearch): g int32 [Pg, S], q int32 [B, W, S], self_start int32 [B] -> (idx int32 [B, n], mode int64 [B],
+    dist int64 [B, Pg - W + 1] or None), device tensors."""
+    pg, Pg, S = _grid("simsearch: g", g)
+    dev, B = g.device, int(self_start.numel()) if isinstance(self_start, torch.Tensor) else 0
+    pq = _arg("simsearch: q", q, torch.int32, B * W * S, dev)
+    pss = _arg("simsearch: self_start", self_start, torch.int32, B, dev)
+    _ws, pws, nws = _scratch("simsearch: ws", ws, dev, "epg_simsearch_ws_bytes", Pg, S, W, B)
+    idx = torch.empty((B, n), dtype=torch.int32, device=dev)
+    mode = torch.empty(B, dtype=torch.int64, device=dev)
+    dist = torch.empty((B, Pg - W + 1), dtype=torch.int64, device=dev) if want_dist else None
+    _abi.call("epg_simsearch", pg, Pg, S, W, pq, B, pss, n, C.c_uint64(key_bound), pws, nws, _ptr(idx), _ptr(mode), _ptr(dist), _stream())
+    return idx, mode, dist
+
+
+def simsearch_reduce(x, blockSize):
+    """The block-reduced genome (epg_simsearch_reduce): x int32 [R, S] -> int32 [ceil(R / blockSize), S]."""
+    px, R, S = _grid("simsearch_reduce: x", x)
+    g = torch.empty((-(-R // int(blockSize)), S), dtype=torch.int32, device=x.device)
+    _abi.call("epg_simsearch_reduce", px, R, S, int(blockSize), _ptr(g), None, _stream())
+    return g
+
+
+def simsearch_slices(x, first, nblk, blockSize):
+    """The block-reduced windows of x int32 [R, S] that start at rows `first` (a HOST int64 array, as the ABI wants) -> int32
+    [B, nblk, S] (epg_simsearch_slices)."""
+    px, R, S = _grid("simsearch_slices: x", x)
+    first = np.ascontiguousarray(first, dtype=np.int64)
+    q = torch.empty((len(first), int(nblk), S), dtype=torch.int32, device=x.device)
+    _abi.call("epg_simsearch_slices", px, R, S, int(blockSize), int(nblk), first.ctypes.data_as(C.c_void_p), len(first), _ptr(q), _stream())
+    return q
+
+
+def simsearch_rowscore(x):
+    """x int32 [G, S] -> float64 [G], pandas' row sums of the scores (epg_simsearch_rowscore)."""
+    px, G, S = _grid("simsearch_rowscore: x", x)
+    score = torch.empty(G, dtype=torch.float64, device=x.device)
+    _abi.call("epg_simsearch_rowscore", px, G, S, _ptr(score), _stream())
+    return score
+
+
+def simsearch_rolling_max(v, W):
+    """float64 [n] (contiguous) -> float64 [n], the centred rolling maximum (epg_simsearch_rolling_max)."""
+    pv = _arg("simsearch_rolling_max: v", v, torch.float64, 0)
+    out = torch.empty_like(v)
+    _abi.call("epg_simsearch_rolling_max", pv, v.numel(), int(W), _ptr(out), _stream())
+    return out
+
+
+def simsearch_rank(rmax, rmean, score):
+    """-> int32 [n] (the bits of the library's uint32): each window's position in np.lexsort((-score, -rmean, -rmax)) (epg_simsearch_rank)."""
+    prmax, dev = _arg("simsearch_rank: rmax", rmax, torch.float64, 0), rmax.device
+    n = rmax.numel()
+    prmean, pscore = _arg("simsearch_rank: rmean", rmean, torch.float64, n, dev), _arg("simsearch_rank: score", score, torch.float64, n, dev)
+    rank = torch.empty(n, dtype=torch.int32, device=dev)
+    _ws, pws, nws = _scratch("simsearch_rank: ws", None, dev, "epg_simsearch_rank_ws_bytes", n)
+    _abi.call("epg_simsearch_rank", prmax, prmean, pscore, n, _ptr(rank), pws, nws, _stream())
+    return rank
+
+
+def simsearch_pick(rank, W, maxRegions):
+    """The greedy pick (epg_simsearch_pick): rank int32 [n] -> (picked int64 [ceil(n / W)], count int64 [1], device tensors; the
+    sweeps over the tiles, a host int).  Synchronises as the header says."""
+    prank, dev = _arg("simsearch_pick: rank", rank, torch.int32, 0), rank.device
+    n = rank.numel()
+    picked = torch.empty(max(-(-n // int(W)), 1), dtype=torch.int64, device=dev)
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    launches = C.c_int32(0)
+    _ws, pws, nws = _scratch("simsearch_pick: ws", None, dev, "epg_simsearch_pick_ws_bytes", n, int(W))
+    _abi.call("epg_simsearch_pick", prank, n, int(W), int(maxRegions), _ptr(picked), _ptr(count), C.byref(launches), pws, nws, _stream())
+    return picked, count, int(launches.value)
+
+
+def scores_ws_bytes(nbytes):
+    return _scratch_bytes("epgt_scores_ws_bytes", nbytes, floor=0)
+
+
+def scores_parse(text, nbytes, F, rows, row0, x, start, end, chrom_at, ws, status):
+    """One chunk of a scores file parsed (epgt_scores_parse, include/epilogos_scores_text.h): text uint8 holds the chunk's nbytes
+    bytes; rows row0 .. row0 + rows of x int32 [R, F - 3], start / end int64 [R] and chrom_at int32 [R] are written, status int64 [2]
+    is the word all chunks share.  ws: scores_ws_bytes(nbytes) bytes at least."""
+    w, top = "scores_parse: ", int(row0) + int(rows)
+    ptext, dev = _arg(w + "text", text, torch.uint8, int(nbytes)), text.device
+    _ws, pws, nws = _scratch(w + "ws", ws, dev, "epgt_scores_ws_bytes", int(nbytes))
+    _abi.call("epgt_scores_parse", ptext, int(nbytes), int(F), int(rows), int(row0), _arg(w + "x", x, torch.int32, top * (int(F) - 3), dev),
+              _arg(w + "start", start, torch.int64, top, dev), _arg(w + "end", end, torch.int64, top, dev),
+              _arg(w + "chrom_at", chrom_at, torch.int32, top, dev), pws, nws, _arg(w + "status", status, torch.int64, 2, dev), _stream())

@@ -12,11 +12,9 @@ read_scores_device(path, inflate="gpu") (`simsearch --inflate gpu`) inflates a B
 (csrc/epg_bgzf_inflate.h): bgzfIndex.members gives the member table, the COMPRESSED bytes are uploaded through the two page-locked
 buffers in groups of whole members and inflated into one device text buffer, the newline index of the text (engine.newline_index)
 lets the host cut the chunks and count their rows without the text, and the parser runs on slices of the device text."""
-import ctypes as C
-
 import numpy as np
 
-from . import _abi, _io
+from . import _io
 
 CHUNK_BYTES = 32 << 20
 CLEAN = 2 ** 63 - 1
@@ -130,6 +128,33 @@ def cut_chunks_indexed(n, chunk_bytes, seg_bytes, count, last):
     return chunks, rows
 
 
+def _parse_chunks(dev, chunks, rows, row0, F, texts, timings):
+    """What both readers do with their chunks: the outputs for all row0[-1] rows, the status word the chunks share, and one
+    epgt_scores_parse per chunk -- texts(parse) brings chunk after chunk to the device its own way and calls parse(k, device text)
+    for each, on the current stream.  -> (x int32 [R, S], start, end int64 [R], chrom_at int32 [R]), device tensors; raises NotStrict.
+    Synchronises once, to read the status word; timings receives upload_parse_ms (HIP events around all chunks)."""
+    import torch
+    from . import engine
+    R, S = int(row0[-1]), F - 3
+    x = torch.empty((R, S), dtype=torch.int32, device=dev)
+    start = torch.empty(R, dtype=torch.int64, device=dev)
+    end = torch.empty(R, dtype=torch.int64, device=dev)
+    chrom_at = torch.empty(R, dtype=torch.int32, device=dev)
+    status = torch.tensor([CLEAN, 0], dtype=torch.int64, device=dev)
+    ws = torch.empty(engine.scores_ws_bytes(max(hi - lo for lo, hi in chunks)), dtype=torch.uint8, device=dev)
+    main = torch.cuda.current_stream()
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev0.record(main)
+    texts(lambda k, t: engine.scores_parse(t, chunks[k][1] - chunks[k][0], F, int(rows[k]), int(row0[k]), x, start, end, chrom_at, ws, status))
+    ev1.record(main)
+    word, _found = status.cpu().tolist()
+    if timings is not None:
+        timings["upload_parse_ms"] = ev0.elapsed_time(ev1)
+    if word != CLEAN:
+        raise NotStrict(REASONS.get(word & 15, "reason %d" % (word & 15)), word >> 4, word & 15)
+    return x, start, end, chrom_at
+
+
 GROUP_BYTES = 32 << 20
 INFLATE_CHOICES = ("host", "gpu")
 
@@ -184,8 +209,7 @@ def _read_scores_inflated(path, chunk_bytes, timings):
                     dcomp[b0:b1].copy_(pinned[s][:nb], non_blocking=True)
                     copied[s].record(copy)
                 main.wait_event(copied[s])
-                _abi.call("epgz_bgzf_inflate", engine._ptr(dcomp), comp_bytes, engine._ptr(dtable[m0:m1]), m1 - m0, engine._ptr(text), total,
-                          engine._ptr(mstatus[m0:m1]), engine._ptr(flags[k:k + 1]), engine._stream())
+                engine.bgzf_inflate(dcomp, dtable[m0:m1], out=text, status=mstatus[m0:m1], flags=flags[k:k + 1])
             ev[1].record(main)
             count, last = engine.newline_index(text, seg_bytes, total)
             ev[2].record(main)
@@ -210,27 +234,14 @@ def _read_scores_inflated(path, chunk_bytes, timings):
         raise NotStrict(REASONS[1], 0, 1)
     chunks, rows = cut_chunks_indexed(total, chunk_bytes, seg_bytes, count, last)
     row0 = np.concatenate(([0], np.cumsum(rows))).astype(np.int64)
-    R, S = int(row0[-1]), F - 3
+    R = int(row0[-1])
     if timings is not None:
         timings["count_s"] = perf_counter() - t0
-    x = torch.empty((R, S), dtype=torch.int32, device=dev)
-    start = torch.empty(R, dtype=torch.int64, device=dev)
-    end = torch.empty(R, dtype=torch.int64, device=dev)
-    chrom_at = torch.empty(R, dtype=torch.int32, device=dev)
-    status = torch.tensor([CLEAN, 0], dtype=torch.int64, device=dev)
-    wsb = _abi.call("epgt_scores_ws_bytes", max(hi - lo for lo, hi in chunks))
-    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record(main)
-    for k, (lo, hi) in enumerate(chunks):                                      # slices of the device text: no second upload
-        _abi.call("epgt_scores_parse", engine._ptr(text[lo:hi]), hi - lo, F, int(rows[k]), int(row0[k]), engine._ptr(x), engine._ptr(start),
-                  engine._ptr(end), engine._ptr(chrom_at), engine._ptr(ws), wsb, engine._ptr(status), engine._stream())
-    ev1.record(main)
-    word, _found = status.cpu().tolist()
-    if timings is not None:
-        timings["upload_parse_ms"] = ev0.elapsed_time(ev1)
-    if word != CLEAN:
-        raise NotStrict(REASONS.get(word & 15, "reason %d" % (word & 15)), word >> 4, word & 15)
+
+    def texts(parse):                                                          # slices of the device text: no second upload
+        for k, (lo, hi) in enumerate(chunks):
+            parse(k, text[lo:hi])
+    x, start, end, chrom_at = _parse_chunks(dev, chunks, rows, row0, F, texts, timings)
     t0 = perf_counter()
     runs = _runs_of(_DeviceText(text, total), chrom_at, chunks, row0, R)
     start, end = start.cpu().numpy(), end.cpu().numpy()
@@ -303,60 +314,34 @@ def read_scores_device(path, chunk_bytes=CHUNK_BYTES, timings=None, inflate="hos
         if a[-1] != 10:
             rows[-1] += 1
         row0 = np.concatenate(([0], np.cumsum(rows))).astype(np.int64)
-        R, S = int(row0[-1]), F - 3
+        R = int(row0[-1])
         if timings is not None:
             timings["count_s"] = perf_counter() - t0
         dev = torch.device("cuda", torch.cuda.current_device())
         cap = max(hi - lo for lo, hi in chunks)
-        x = torch.empty((R, S), dtype=torch.int32, device=dev)
-        start = torch.empty(R, dtype=torch.int64, device=dev)
-        end = torch.empty(R, dtype=torch.int64, device=dev)
-        chrom_at = torch.empty(R, dtype=torch.int32, device=dev)
-        status = torch.tensor([CLEAN, 0], dtype=torch.int64, device=dev)
-        wsb = _abi.call("epgt_scores_ws_bytes", cap)
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
         pinned = [torch.empty(cap, dtype=torch.uint8).pin_memory() for _ in range(min(2, len(chunks)))]
         dtext = [torch.empty(cap, dtype=torch.uint8, device=dev) for _ in pinned]
         copied = [torch.cuda.Event() for _ in pinned]
         parsed = [torch.cuda.Event() for _ in pinned]
         main, copy = torch.cuda.current_stream(), torch.cuda.Stream()
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record(main)
-        for k, (lo, hi) in enumerate(chunks):
-            s, n = k % 2, hi - lo
-            if k >= 2:
-                copied[s].synchronize()                          # the pinned buffer's last upload has left it
-            pinned[s].numpy()[:n] = a[lo:hi]
-            with torch.cuda.stream(copy):
+
+        def texts(parse):                                        # chunk k + 1 is staged and uploaded while chunk k parses
+            for k, (lo, hi) in enumerate(chunks):
+                s, n = k % 2, hi - lo
                 if k >= 2:
-                    copy.wait_event(parsed[s])                   # the device buffer's last parse is done
-                dtext[s][:n].copy_(pinned[s][:n], non_blocking=True)
-                copied[s].record(copy)
-            main.wait_event(copied[s])
-            _abi.call("epgt_scores_parse", engine._ptr(dtext[s]), n, F, int(rows[k]), int(row0[k]), engine._ptr(x), engine._ptr(start),
-                      engine._ptr(end), engine._ptr(chrom_at), engine._ptr(ws), wsb, engine._ptr(status), engine._stream())
-            parsed[s].record(main)
-        ev1.record(main)
-        word, _found = status.cpu().tolist()                     # the one synchronisation
-        if timings is not None:
-            timings["upload_parse_ms"] = ev0.elapsed_time(ev1)
-        if word != CLEAN:
-            raise NotStrict(REASONS.get(word & 15, "reason %d" % (word & 15)), word >> 4, word & 15)
+                    copied[s].synchronize()                      # the pinned buffer's last upload has left it
+                pinned[s].numpy()[:n] = a[lo:hi]
+                with torch.cuda.stream(copy):
+                    if k >= 2:
+                        copy.wait_event(parsed[s])               # the device buffer's last parse is done
+                    dtext[s][:n].copy_(pinned[s][:n], non_blocking=True)
+                    copied[s].record(copy)
+                main.wait_event(copied[s])
+                parse(k, dtext[s])
+                parsed[s].record(main)
+        x, start, end, chrom_at = _parse_chunks(dev, chunks, rows, row0, F, texts, timings)      # (ends with the one synchronisation)
         t0 = perf_counter()
-        at = torch.nonzero(chrom_at >= 0).reshape(-1)
-        pos = chrom_at[at].cpu().numpy().astype(np.int64)
-        at = at.cpu().numpy()
-        pos += np.asarray([c[0] for c in chunks], dtype=np.int64)[np.searchsorted(row0, at, side="right") - 1]
-        runs = []
-        for r, p in zip(at.tolist(), pos.tolist()):              # one turn per change of chromosome (and per chunk)
-            name = _name_at(a, p)
-            if runs and runs[-1][0] == name:                     # a chunk's first row carries on the chromosome before it
-                continue
-            if name.lower() in NOT_TEXT:
-                raise NotStrict("a chromosome name pandas does not keep as text (%s)" % name, r)
-            if runs:
-                runs[-1][2] = r
-            runs.append([name, r, R])
+        runs = _runs_of(a, chrom_at, chunks, row0, R)
         start, end = start.cpu().numpy(), end.cpu().numpy()
         if timings is not None:
             timings["coords_s"] = perf_counter() - t0

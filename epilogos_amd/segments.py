@@ -239,7 +239,7 @@ def build_matrices_device(files, chroms, width=BIN_WIDTH, sizes=None, state_name
     with TextBatches(files, batch, threads, dev, lambda k, data: count_lines(data)) as batches:
         info_of, runs_of = pointers(infos), pointers(runs)
         for b in batches:
-            k0, nb, stream = b.k0, b.nb, engine._stream()
+            k0, nb, stream = b.k0, b.nb, engine.stream()
             caps.extend(b.facts)
             loff = offsets_of([max(n, 1) for n in b.facts])       # where every file's lines start in `first` and `state`
             wsb = max(int(_abi.call("epg_seg_ws_bytes", n, nchrom)) for n in b.sizes)
@@ -248,8 +248,8 @@ def build_matrices_device(files, chroms, width=BIN_WIDTH, sizes=None, state_name
             state = torch.empty(int(loff[-1]), dtype=torch.int8, device=dev)
             text_of, first_of, state_of = pointers(b.text, b.offsets[:-1]), pointers(first, loff[:-1]), pointers(state, loff[:-1])
             for j in range(nb):
-                _abi.call("epg_seg_parse", text_of[j], b.sizes[j], engine._ptr(names), nchrom, int(width), first_of[j], state_of[j], caps[k0 + j],
-                          runs_of[k0 + j], info_of[k0 + j], engine._ptr(ws), wsb, stream)
+                _abi.call("epg_seg_parse", text_of[j], b.sizes[j], engine.ptr(names), nchrom, int(width), first_of[j], state_of[j], caps[k0 + j],
+                          runs_of[k0 + j], info_of[k0 + j], engine.ptr(ws), wsb, stream)
             e2 = mark()
             b.release()
             ev["upload"].append(b.upload), ev["parse"].append((b.upload[1], e2))
@@ -275,7 +275,7 @@ def build_matrices_device(files, chroms, width=BIN_WIDTH, sizes=None, state_name
                 for j in range(nb):
                     _abi.call("epg_seg_expand", first_of[j], state_of[j], runs_of[k0 + j], i, col_of[j], R, stream)
                 e4 = mark()
-                _abi.call("epg_sbl_transpose", engine._ptr(cols), nb, col_pitch, R, engine._ptr(X[i]), ldx, k0, stream)
+                _abi.call("epg_sbl_transpose", engine.ptr(cols), nb, col_pitch, R, engine.ptr(X[i]), ldx, k0, stream)
                 e5 = mark()
                 ev["expand"].append((e3, e4)), ev["transpose"].append((e4, e5))
         inflate_s = batches.inflate_s

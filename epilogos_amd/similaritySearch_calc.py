@@ -5,7 +5,6 @@ epilogos/similaritySearch_calc.py (main :14-33, runEuclideanDistance :67-123): s
 For every region of interest (ROI) the distance to every window of the reduced genome, their mode, their stable order and the
 greedy pick of non-overlapping windows closer than half the mode run in epg_simsearch (csrc/epg_simsearch.hip) on exact
 integers, ROI batches sized from a workspace cap."""
-import ctypes as C
 import os
 import sys
 from pathlib import Path
@@ -13,7 +12,6 @@ from time import time
 
 import numpy as np
 
-from . import _abi
 from .helpers import splitRows
 from .similaritySearch_max_mean import to_grid
 
@@ -49,9 +47,9 @@ def check_exact(bound, S, W):
 
 def batch_rows(Pg, S, W, R, ws_cap=WS_CAP_BYTES):
     """ROIs per epg_simsearch call under the workspace cap (at least 1)."""
-    lib = _abi.load()
+    from . import engine
     P = Pg - W + 1
-    fixed = lib.epg_simsearch_ws_bytes(Pg, S, W, 1) - 20 * P
+    fixed = engine.simsearch_ws_bytes(Pg, S, W, 1) - 20 * P
     return int(max(1, min(R, (ws_cap - fixed) // (20 * P))))
 
 
@@ -77,21 +75,13 @@ def search_on_device(g, g_range, R, W, nDesiredMatches, batch_of, ws_cap=WS_CAP_
     mode = np.zeros(R, dtype=np.int64)
     dist = np.zeros((R, P), dtype=np.int64) if want_dist else None
     B = int(batch) if batch else batch_rows(Pg, S, W, R, ws_cap)
-    lib = _abi.load()
-    wsb = lib.epg_simsearch_ws_bytes(Pg, S, W, min(B, R))
-    _abi.check(wsb)
-    ws = torch.empty(int(wsb), dtype=torch.uint8, device=g.device)
+    ws = torch.empty(engine.simsearch_ws_bytes(Pg, S, W, min(B, R)), dtype=torch.uint8, device=g.device)
     for r0 in range(0, R, B):
         r1 = min(R, r0 + B)
-        b = r1 - r0
         q, ss = batch_of(r0, r1)
         bound = bound_from_ranges(g_range, tensor_ranges(q), W)
         check_exact(bound, S, W)
-        o_idx = torch.empty((b, n), dtype=torch.int32, device=g.device)
-        o_mode = torch.empty(b, dtype=torch.int64, device=g.device)
-        o_dist = torch.empty((b, P), dtype=torch.int64, device=g.device) if want_dist else None
-        _abi.call("epg_simsearch", engine._ptr(g), Pg, S, W, engine._ptr(q), b, engine._ptr(ss), n, C.c_uint64(bound),
-                  engine._ptr(ws), int(wsb), engine._ptr(o_idx), engine._ptr(o_mode), engine._ptr(o_dist), engine._stream())
+        o_idx, o_mode, o_dist = engine.simsearch(g, W, q, ss, n, bound, ws=ws, want_dist=want_dist)
         idx[r0:r1] = o_idx.cpu().numpy()
         mode[r0:r1] = o_mode.cpu().numpy()
         if want_dist:

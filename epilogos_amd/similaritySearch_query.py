@@ -15,7 +15,6 @@ The scores file is read by readGrid: on the GPU as text (scoresText.read_scores_
 
 The device steps are module-level functions (readGrid, reduceGenome, slices, search): a host test puts numpy in place of the
 last three."""
-import ctypes as C
 from pathlib import Path
 from time import time
 
@@ -87,22 +86,14 @@ def reduceGenome(genome, blockSize):
     engine.require_gpu()
     dev = torch.device("cuda", torch.cuda.current_device())
     x = torch.from_numpy(np.ascontiguousarray(genome, dtype=np.int32)).to(dev)
-    R, S = x.shape
-    g = torch.empty((-(-R // blockSize), S), dtype=torch.int32, device=dev)
-    _abi.call("epg_simsearch_reduce", engine._ptr(x), R, S, int(blockSize), engine._ptr(g), None, engine._stream())
+    g = engine.simsearch_reduce(x, blockSize)
     return x, g, calc.tensor_ranges(g)
 
 
 def slices(state, first, nblk, blockSize):
     """The block-reduced slices of the windows that start at rows `first` (int64 [B]): int32 [B, nblk, S], a device tensor."""
-    import torch
     from . import engine
-    x = state[0]
-    first = np.ascontiguousarray(first, dtype=np.int64)
-    q = torch.empty((len(first), int(nblk), x.shape[1]), dtype=torch.int32, device=x.device)
-    _abi.call("epg_simsearch_slices", engine._ptr(x), x.shape[0], x.shape[1], int(blockSize), int(nblk),
-              first.ctypes.data_as(C.c_void_p), len(first), engine._ptr(q), engine._stream())
-    return q
+    return engine.simsearch_slices(state[0], first, nblk, blockSize)
 
 
 def search(state, first, nblk, blockSize, nDesiredMatches, ws_cap=None, batch=None):

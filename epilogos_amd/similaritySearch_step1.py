@@ -20,7 +20,6 @@ similaritySearch_max_mean.main.  Without a GPU or the library the module raises,
 The device steps are module-level functions (readDevice, rowScores, rollingMax, rankWindows, pickWindows, slices, reduce, deviceOf): a host
 test puts numpy restatements in their place, on CPU tensors.  `python -m epilogos_amd.similaritySearch_step1 outputDir scoresPath
 windowBins blockSize windowBP filterState filterScore` is the child of a `--gpus N` build: one fresh process on LOCAL_RANK."""
-import ctypes as C
 import os
 import sys
 import threading
@@ -30,7 +29,6 @@ from time import perf_counter, time
 import numpy as np
 import pandas as pd
 
-from . import _abi
 from . import similaritySearch_max_mean as mm
 
 SLICE_BATCH = 256
@@ -48,76 +46,45 @@ def readDevice(scoresPath, timings=None, inflate="host"):
 
 def rowScores(x):
     """x int32 [G, S] -> float64 [G], pandas' row sums of the scores (epg_simsearch_rowscore)."""
-    import torch
     from . import engine
-    G, S = x.shape
-    score = torch.empty(G, dtype=torch.float64, device=x.device)
-    _abi.call("epg_simsearch_rowscore", engine._ptr(x), G, S, engine._ptr(score), engine._stream())
-    return score
+    return engine.simsearch_rowscore(x)
 
 
 def rollingMax(v, W):
     """float64 [n] -> float64 [n], _io.rolling_max(v, W): NaN where the centred window is incomplete."""
-    import torch
     from . import engine
-    v = v.contiguous()
-    out = torch.empty_like(v)
-    _abi.call("epg_simsearch_rolling_max", engine._ptr(v), v.numel(), int(W), engine._ptr(out), engine._stream())
-    return out
+    return engine.simsearch_rolling_max(v.contiguous(), W)
 
 
 def rankWindows(rmax, rmean, score):
     """-> int32 [n] (the bits of the library's uint32): the position of each window in np.lexsort((-score, -rmean, -rmax))."""
-    import torch
     from . import engine
-    rmax, rmean, score = rmax.contiguous(), rmean.contiguous(), score.contiguous()
-    n = rmax.numel()
-    rank = torch.empty(n, dtype=torch.int32, device=rmax.device)
-    ws = torch.empty(max(_abi.call("epg_simsearch_rank_ws_bytes", n), 256), dtype=torch.uint8, device=rmax.device)
-    _abi.call("epg_simsearch_rank", engine._ptr(rmax), engine._ptr(rmean), engine._ptr(score), n, engine._ptr(rank), engine._ptr(ws), ws.numel(), engine._stream())
-    return rank
+    return engine.simsearch_rank(rmax.contiguous(), rmean.contiguous(), score.contiguous())
 
 
 def pickWindows(rank, W, maxRegions):
     """-> (picked positions int64, ascending, host array; sweeps over the tiles)."""
-    import torch
     from . import engine
-    n = rank.numel()
-    picked = torch.empty(max(-(-n // int(W)), 1), dtype=torch.int64, device=rank.device)
-    count = torch.zeros(1, dtype=torch.int64, device=rank.device)
-    launches = C.c_int32(0)
-    ws = torch.empty(max(_abi.call("epg_simsearch_pick_ws_bytes", n, int(W)), 256), dtype=torch.uint8, device=rank.device)
-    _abi.call("epg_simsearch_pick", engine._ptr(rank), n, int(W), int(maxRegions), engine._ptr(picked), engine._ptr(count),
-              C.byref(launches), engine._ptr(ws), ws.numel(), engine._stream())
-    k = int(count.cpu()[0])
-    return picked[:k].cpu().numpy(), int(launches.value)
+    picked, count, launches = engine.simsearch_pick(rank, W, maxRegions)
+    return picked[:int(count.cpu()[0])].cpu().numpy(), launches
 
 
 def slices(x, first, nblk, blockSize):
     """The block-reduced windows that start at rows `first`: int64 [B, nblk, S] host array (epg_simsearch_slices, SLICE_BATCH
     windows a call)."""
-    import torch
     from . import engine
     first = np.ascontiguousarray(first, dtype=np.int64)
-    G, S = x.shape
-    out = np.empty((len(first), int(nblk), S), dtype=np.int64)
+    out = np.empty((len(first), int(nblk), x.shape[1]), dtype=np.int64)
     for b0 in range(0, len(first), SLICE_BATCH):
         f = first[b0:b0 + SLICE_BATCH]
-        q = torch.empty((len(f), int(nblk), S), dtype=torch.int32, device=x.device)
-        _abi.call("epg_simsearch_slices", engine._ptr(x), G, S, int(blockSize), int(nblk), f.ctypes.data_as(C.c_void_p), len(f),
-                  engine._ptr(q), engine._stream())
-        out[b0:b0 + len(f)] = q.cpu().numpy()
+        out[b0:b0 + len(f)] = engine.simsearch_slices(x, f, nblk, blockSize).cpu().numpy()
     return out
 
 
 def reduce(x, blockSize):
     """The block-reduced genome: int64 [ceil(G / blockSize), S] host array (epg_simsearch_reduce)."""
-    import torch
     from . import engine
-    G, S = x.shape
-    g = torch.empty((-(-G // int(blockSize)), S), dtype=torch.int32, device=x.device)
-    _abi.call("epg_simsearch_reduce", engine._ptr(x), G, S, int(blockSize), engine._ptr(g), None, engine._stream())
-    return g.cpu().numpy().astype(np.int64)
+    return engine.simsearch_reduce(x, blockSize).cpu().numpy().astype(np.int64)
 
 
 def deviceOf():

@@ -138,9 +138,9 @@ def build_matrix_device(files, timings=None, threads=None):
             ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
             e1 = mark()                                          # (behind the first batch's fill of X, which is not the parser's time)
             for j, text in enumerate(pointers(b.text, b.offsets[:-1])):
-                _abi.call("epg_sbl_parse", text, b.sizes[j], col_of[j], R, info_of[b.k0 + j], engine._ptr(ws), wsb, engine._stream())
+                _abi.call("epg_sbl_parse", text, b.sizes[j], col_of[j], R, info_of[b.k0 + j], engine.ptr(ws), wsb, engine.stream())
             e2 = mark()
-            _abi.call("epg_sbl_transpose", engine._ptr(cols), b.nb, col_pitch, R, engine._ptr(X), X.shape[1], b.k0, engine._stream())
+            _abi.call("epg_sbl_transpose", engine.ptr(cols), b.nb, col_pitch, R, engine.ptr(X), X.shape[1], b.k0, engine.stream())
             e3 = mark()
             b.release()
             ev["upload"].append(b.upload), ev["parse"].append((e1, e2)), ev["transpose"].append((e2, e3))

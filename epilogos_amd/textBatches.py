@@ -185,4 +185,4 @@ def put_column(X, k, col, pitch):
     R = X.shape[0]
     c = torch.empty(pitch, dtype=torch.int8, device=X.device)
     c[:R].copy_(torch.from_numpy(col))
-    _abi.call("epg_sbl_transpose", engine._ptr(c), 1, pitch, R, engine._ptr(X), X.shape[1], k, engine._stream())
+    _abi.call("epg_sbl_transpose", engine.ptr(c), 1, pitch, R, engine.ptr(X), X.shape[1], k, engine.stream())
