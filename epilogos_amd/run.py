@@ -13,14 +13,18 @@ import os
 import re
 import sys
 import time as _time
+from collections import namedtuple
+from contextlib import closing
 from pathlib import Path, PurePath
+from types import SimpleNamespace
 
 _T_START = _time.time()
 
 import click
 
 from . import __version__
-from .helpers import getNumStates, parseColumns
+from .helpers import getNumStates, parseColumns, parseGroupings
+from .launch import _launch, _launch_command, _strip_gpus, _visible_gpus  # noqa: F401
 
 
 def _natural_key(p):
@@ -68,45 +72,45 @@ def checkArguments(mode, saliency, inputDirPath, inputDirPath2, outputDirPath, n
         sys.exit()
 
 
-def _check_biosamples_exist(files, top):
-    """The command line's pre-check of column groups: biosample top + 1, the largest asked for, is a column of every file."""
+def _check_biosamples_exist(files, top, resident=None):
+    """The command line's pre-check of column groups: biosample top + 1, the largest asked for, is a column of every file -- or of
+    every matrix of `resident`, which [--chromhmm] built under these names."""
     from . import driver
     for f in files:
         try:
-            n = driver._columns_of(f)
+            n = driver._columns_of(f) if resident is None else resident[f][1]
         except Exception:                                        # (an empty or unreadable file: the parse reports it, or it has no rows)
             continue
         if n and top >= n:
-            print("ERROR: biosample {} is not in {}: the file has {} biosample columns".format(top + 1, f, n)); sys.exit()
+            _usage("biosample {} is not in {}: the {} has {} biosample columns".format(top + 1, f, "file" if resident is None else "matrix", n))
 
 
-def _check_chromhmm_flags(mode, chromhmm, metadata, chromsizes, segments, binWidth, stateNames, keepMatrices, inputDirectory,
-                          inputDirectory1, inputDirectory2, columnsA, columnsB, groupingsFile, cacheDir, gpus):
+def _check_chromhmm_flags(o):
     """The usage errors of [--chromhmm] and the options that go with it.  Silent for a command line that has none of them."""
     def refuse(text):
         print("ERROR: [--chromhmm] " + text); sys.exit()
-    if chromhmm is None:
-        for given, opt in ((metadata, "--metadata"), (chromsizes, "--chromsizes"), (segments or None, "--segments"), (binWidth, "--bin-width"),
-                           (stateNames, "--state-names"), (keepMatrices, "--keep-matrices")):
+    if o.chromhmm is None:
+        for given, opt in ((o.metadata, "--metadata"), (o.chromsizes, "--chromsizes"), (o.segments or None, "--segments"), (o.binWidth, "--bin-width"),
+                           (o.stateNames, "--state-names"), (o.keepMatrices, "--keep-matrices")):
             if given is not None:
                 refuse("is required with [{}]: the option describes a ChromHMM output directory".format(opt))
         return
-    for given, opt in ((inputDirectory, "-i"), (inputDirectory1, "-a"), (inputDirectory2, "-b")):
+    for given, opt in ((o.inputDirectory, "-i"), (o.inputDirectory1, "-a"), (o.inputDirectory2, "-b")):
         if given is not None:
             refuse("takes the place of the input directories; it cannot be combined with [{}]".format(opt))
-    for given, opt in ((metadata, "--metadata"), (chromsizes, "--chromsizes")):
+    for given, opt in ((o.metadata, "--metadata"), (o.chromsizes, "--chromsizes")):
         if given is None:
             refuse("requires [{}]".format(opt))
-    for given, opt in ((binWidth, "--bin-width"), (stateNames, "--state-names")):
-        if given is not None and not segments:
+    for given, opt in ((o.binWidth, "--bin-width"), (o.stateNames, "--state-names")):
+        if given is not None and not o.segments:
             refuse("[{}] goes with [--segments]".format(opt))
-    if binWidth is not None and binWidth <= 0:
+    if o.binWidth is not None and o.binWidth <= 0:
         refuse("the bin width must be positive")
-    if mode == "paired" and columnsA is None and columnsB is None and groupingsFile is None:
+    if o.mode == "paired" and o.columnsA is None and o.columnsB is None and o.groupingsFile is None:
         refuse("builds one set of matrices: paired mode needs [--columns-a] and [--columns-b], or [--groupings], to name the two groups")
-    if cacheDir is not None:
+    if o.cacheDir is not None:
         refuse("cannot be combined with [--cache-dir]: the matrices are built on the GPU, there is no parsed text to cache")
-    if gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+    if o.gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
         refuse("runs on one GPU: it builds and holds the matrices, sharing them out over several ranks is not done yet; "
                "use [--gpus 1]")
 
@@ -120,35 +124,231 @@ def _selects_a_file(datadir, metadata, chromsizes, segments):
     return any(files for _chrom, files, _names in stateByLine.iter_calls_named(datadir, metadata, chromsizes))
 
 
-def _build_resident(chromhmm, metadata, chromsizes, segments, binWidth, stateNames, keepMatrices, numStates, checkStates):
+def _usage(text):
+    print("ERROR: " + text); sys.exit()
+
+
+def _refuse(*family):
+    """A family of usage errors as (whether it applies, its message), in the order they are looked for: the first one that applies
+    is the one the user hears of."""
+    for applies, text in family:
+        if applies:
+            _usage(text)
+
+
+def _absolute(path):
+    return Path(path) if PurePath(path).is_absolute() else Path.cwd() / path
+
+
+def _world():
+    return int(os.environ.get("WORLD_SIZE", "1"))
+
+
+def _check_null_draws(o):
+    many = o.nullDraws > 1
+    _refuse((o.nullDraws < 1, "[--null-draws] must be at least 1"),
+            (many and o.mode != "paired", "[--null-draws] greater than 1 is only valid in paired mode"),
+            (many and not o.pvalBool, "[--null-draws] greater than 1 requires [-n, --null-distribution]"),
+            (many and (o.gpus > 1 or _world() > 1), "[--null-draws] greater than 1 runs on one GPU: the exceedance counts of several ranks "
+                                                    "are not added up yet; use [--gpus 1]"))
+
+
+def _check_stage_choices(o):
+    """[--fit gpu], [--pvals gpu], [--metrics gpu]: single mode fits nothing and writes no pairwiseMetrics file.  ([--writer gpu] and
+    [--roi gpu] are valid in both modes.)"""
+    fit, pvals, single = o.fit == "gpu", o.pvals == "gpu", o.mode != "paired"
+    _refuse((fit and single, "[--fit gpu] is only valid in paired mode"),
+            (fit and not o.pvalBool, "[--fit gpu] requires [-n, --null-distribution]: without it nothing is fitted"),
+            (fit and o.nullDraws > 1, "[--fit gpu] cannot be combined with [--null-draws] greater than 1: empirical p-values need no fit"),
+            (pvals and single, "[--pvals gpu] is only valid in paired mode"),
+            (pvals and not o.pvalBool, "[--pvals gpu] requires [-n, --null-distribution]: without it no p-value is computed"),
+            (o.metrics == "gpu" and single, "[--metrics gpu] is only valid in paired mode"))
+
+
+def _check_groupings(o):
+    """-> the parsed groupings of [--groupings], or None without the option.  Nothing is read but that file."""
+    if o.groupingsFile is None:
+        return None
+    _refuse(*((given is not None, "[--groupings] names the biosamples of every grouping itself; it cannot be combined with [{}]".format(opt))
+              for given, opt in ((o.columns, "--columns"), (o.columnsA, "--columns-a"), (o.columnsB, "--columns-b"),
+                                 (o.inputDirectory1, "-a"), (o.inputDirectory2, "-b"))),
+            (o.inputDirectory is None, "[-i, --input-directory] is required with [--groupings]"))
+    try:
+        return parseGroupings(o.groupingsFile, o.mode)
+    except ValueError as e:
+        _usage("[--groupings] {}".format(e))
+
+
+def _parse_spec(opt, text):
+    try:
+        return parseColumns(text)
+    except ValueError as e:
+        _usage("[{}] {}".format(opt, e))
+
+
+def _check_columns(o, groupings):
+    """-> (pairedColumns, cols, colsA, colsB): whether both groups of a paired run come out of the one directory of [-i], and the
+    parsed [--columns] (single mode) or [--columns-a] and [--columns-b] (paired mode, without [--groupings])."""
+    a, b = o.columnsA is not None, o.columnsB is not None
+    pairedColumns = o.mode == "paired" and (a or b or groupings is not None)
+    _refuse((o.mode == "single" and (a or b), "[--columns-a] and [--columns-b] are only valid in paired mode; single mode takes [--columns]"),
+            (o.mode == "paired" and o.columns is not None, "[--columns] is only valid in single mode; paired mode takes [--columns-a] and [--columns-b]"))
+    cols = _parse_spec("--columns", o.columns) if o.columns is not None else None
+    if not pairedColumns or groupings is not None:
+        return pairedColumns, cols, None, None
+    _refuse((not (a and b), "[--columns-a] and [--columns-b] must be given together"),
+            (o.inputDirectory1 is not None or o.inputDirectory2 is not None,
+             "[--columns-a] and [--columns-b] select from [-i, --input-directory]; they cannot be combined with [-a] and [-b]"),
+            (o.inputDirectory is None, "[-i, --input-directory] is required with [--columns-a] and [--columns-b]"))
+    colsA, colsB = _parse_spec("--columns-a", o.columnsA), _parse_spec("--columns-b", o.columnsB)
+    both = sorted(set(colsA.tolist()) & set(colsB.tolist()))
+    if both:
+        _usage("biosample {} is in both [--columns-a] and [--columns-b]".format(both[0] + 1))
+    return pairedColumns, cols, colsA, colsB
+
+
+def _check_flags(o, pairedColumns):
+    """The reference's flag combinations (run.py:328-375)."""
+    single, dirs = o.mode == "single", o.mode == "paired" and not pairedColumns
+    _refuse((single and o.inputDirectory is None, "[-i, --input-directory] is required in single mode"),
+            (single and (o.inputDirectory1 is not None or o.inputDirectory2 is not None), "[-a] and [-b] are only valid in paired mode"),
+            (dirs and (o.inputDirectory1 is None or o.inputDirectory2 is None),
+             "[-a, --directory-one] and [-b, --directory-two] are required in paired mode"),
+            (dirs and o.inputDirectory is not None, "[-i] is only valid in single mode"),
+            (o.outputDirectory is None, "[-o, --output-directory] is required"),
+            (o.stateInfo is None, "[-j, --state-info] is required"))
+
+
+_AS_GIVEN = ("mode stateInfo saliency groupSize roiWidth numProcesses numTrials samplingSize pvalBool nullDraws nullSeed checkStates gpus "
+             "metadata chromsizes segments binWidth stateNames keepMatrices fit pvals writer roi metrics").split()
+
+
+class RunSpec(namedtuple("RunSpec", _AS_GIVEN + "fileTag inputDirPath inputDirPath2 outputDirPath numStates quiescentState cols colsA colsB "
+                                                "groupings pairedColumns chromhmm".split())):
+    """One run of the command line, checked: what `main` and everything after it read.  The options of _AS_GIVEN as they were given
+    (fit, pvals, writer, roi and metrics are the five host|gpu stage choices), and: fileTag, given or the default; the absolute
+    input, second input (paired: [-b], or inputDirPath when both groups are columns of its files) and output paths; numStates; the
+    0-based quiescentState (-1: off); cols, colsA and colsB, 0-based as parseColumns gives them; the parsed groupings, or None;
+    chromhmm, whether inputDirPath is a ChromHMM output directory.  Nothing in it changes; a paired run without [--null-seed]
+    goes on with a copy that has the seed it drew."""
+    __slots__ = ()
+
+    @property
+    def storedExpPath(self):
+        return self.outputDirPath / "exp_freq_{}.npy".format(self.fileTag)
+
+    def topBiosample(self):
+        """The largest biosample asked for by column, 0-based; -1 when the run selects none."""
+        asked = [c for g in self.groupings for c in g[1:]] if self.groupings is not None else [self.cols, self.colsA, self.colsB]
+        return max([int(c.max()) for c in asked if c is not None] + [-1])
+
+    def extra(self, *stages):
+        """The keywords that the choices of these stages add to a call: none for `host`, so that a run without the options calls
+        the drivers and STEP 4 exactly as it did before they existed.  The run's one seed travels with fit="gpu"."""
+        kw = {s: "gpu" for s in stages if getattr(self, s) == "gpu"}
+        return dict(kw, seed=self.nullSeed) if "fit" in kw else kw
+
+
+def _describe_run(o):
+    """The click options `o` -> RunSpec; every usage error of the command line comes out of here.  The order of checks and side
+    effects is what users and tests see; nothing moves across another item:
+     1. [-v].
+     2. [--chromhmm] flag checks; the directory is the run's input directory from then on.
+     3. [--null-draws] checks.
+     4. [--fit], [--pvals] and [--metrics] checks.
+     5. [--groupings] checks: incompatible options, [-i] required, file parse.
+     6. Column checks and SPEC parse.
+     7. The reference's flag combinations ([-i], [-a], [-b], [-o], [-j]).  Up to here nothing but the groupings file is read.
+     8. EPILOGOS_CACHE_DIR / EPILOGOS_NUM_CORES are set.
+     9. getNumStates reads the state file.
+    10. Paths are made absolute.
+    11. [--groupings]: its largest biosample against the headers of the files.
+    12. [--chromhmm] file checks, and the OSError of a directory none of whose files is selected.
+    13. checkArguments, which creates the output directory.
+    14. The default file tag.
+    15. [--gpus] below 0.  The record is complete; main goes on with it.
+    16. The launcher fork, before torch is imported.
+    17. File lists, and the FileNotFoundError of paired directories that do not match (_open_inputs, to 19).
+    18. [--columns*]: the largest biosample against the headers of the files.
+    19. The early readers start.
+    20. Device and process group; on failure the early readers are aborted.
+    21. [--chromhmm]: the matrices are built, with their own biosample check ("the matrix has").
+    22. The "State Model" line.
+    23. The null seed is drawn and broadcast.
+    24. STEP 1-3 and STEP 4 of every route (_routes, _step4).
+    25. flushCacheWrites, the timing and memory lines, destroy_process_group."""
+    if o.version:
+        print("Version:", __version__); sys.exit()
+    _check_chromhmm_flags(o)
+    if o.chromhmm is not None:
+        o.inputDirectory = o.chromhmm                            # required-ness, tag, emptiness: all as for [-i]
+    _check_null_draws(o)
+    _check_stage_choices(o)
+    groupings = _check_groupings(o)
+    pairedColumns, cols, colsA, colsB = _check_columns(o, groupings)
+    _check_flags(o, pairedColumns)
+    if o.cacheDir:
+        os.environ["EPILOGOS_CACHE_DIR"] = str(Path(o.cacheDir).resolve())
+    if o.numProcesses > 0:                                       # the reference's core budget (run.py:36,148): see _io.host_budget
+        os.environ["EPILOGOS_NUM_CORES"] = str(o.numProcesses)
+    numStates = getNumStates(o.stateInfo)
+    paired = o.mode == "paired"
+    inputDirPath = _absolute(o.inputDirectory if not paired or pairedColumns else o.inputDirectory1)
+    inputDirPath2 = (inputDirPath if pairedColumns else _absolute(o.inputDirectory2)) if paired else Path("")
+    spec = RunSpec(**{name: getattr(o, name) for name in _AS_GIVEN}, fileTag=o.fileTag, inputDirPath=inputDirPath,
+                   inputDirPath2=inputDirPath2, outputDirPath=_absolute(o.outputDirectory), numStates=numStates,
+                   quiescentState=numStates - 1 if o.quiescentState == -1 else o.quiescentState - 1,       # 1-based -> 0-based, 0 -> off
+                   cols=cols, colsA=colsA, colsB=colsB, groupings=groupings, pairedColumns=pairedColumns, chromhmm=o.chromhmm is not None)
+    if groupings is not None and inputDirPath.is_dir() and not spec.chromhmm:
+        _check_biosamples_exist(sorted(inputDirPath.glob("*"), key=_natural_key), spec.topBiosample())
+    if spec.chromhmm:
+        for given, opt in ((o.metadata, "--metadata"), (o.chromsizes, "--chromsizes"), (o.stateNames, "--state-names")):
+            if given is not None and not Path(given).is_file():
+                _usage("[{}] is not a file: {}".format(opt, given))
+        if inputDirPath.is_dir() and list(inputDirPath.glob("*")) and not _selects_a_file(inputDirPath, o.metadata, o.chromsizes, o.segments):
+            # no file of the directory is anybody's: epilogos-prep would leave an empty directory, which [-i] refuses like this
+            raise OSError("Ensure that directory is not empty: {}".format(str(inputDirPath)))
+    checkArguments(o.mode, o.saliency, inputDirPath, inputDirPath2, spec.outputDirPath, o.numProcesses, numStates, spec.quiescentState,
+                   o.groupSize, o.numTrials, o.samplingSize, o.roiWidth)
+    if o.fileTag == "null":
+        spec = spec._replace(fileTag="{}_s{}".format(inputDirPath.name, o.saliency) if not paired
+                             else "{0}_A_{0}_B_s{1}".format(inputDirPath.name, o.saliency) if pairedColumns
+                             else "{}_{}_s{}".format(inputDirPath.name, inputDirPath2.name, o.saliency))
+    if o.gpus < 0:
+        _usage("Number of GPUs must be positive or zero (0 means use all visible GPUs)")
+    return spec
+
+
+def _build_resident(spec):
     """[--chromhmm]: the matrices of the ChromHMM output directory, built on the device by epilogos-prep's own generator
-    (preprocess.iter_matrices, which prints its progress lines) and kept there.  -> (files, resident): the virtual paths
+    (preprocess.iter_matrices, which prints its progress lines) and kept there.  -> _Inputs(files, [], resident): the virtual paths
     `matrix_{chr}.epgm` the run sees them under -- in OUTDIR with [--keep-matrices], where they are then also written, as built --
     in the natural-key order in which [-i] would run those files, and {path: (X, N, Locations)} for driver.run_groupings.
     Without [--check-states] a matrix is handed over as stateByLine.read_epgm would have read its file: what is no state of the
     parser's limit is -1.  A state range outside the model raises what the readers of the files raise.  The matrices must fit on
     the device next to a session by the resident store's own rule, applied once to their total; if not, the run ends here."""
+    t_build = _time.time()
     from . import _io, driver, preprocess, segments as segmentFiles, stateByLine
-    _io.set_state_limit(numStates)
-    table = segmentFiles.read_state_names(stateNames) if stateNames else None
+    _io.set_state_limit(spec.numStates)
+    table = segmentFiles.read_state_names(spec.stateNames) if spec.stateNames else None
     outdir = None
-    if keepMatrices is not None:
-        outdir = Path(keepMatrices)
+    if spec.keepMatrices is not None:
+        outdir = Path(spec.keepMatrices)
         outdir.mkdir(parents=True, exist_ok=True)
     resident, ranges = {}, {}
-    for chrom, X, N, name, rng, _names, width in preprocess.iter_matrices(chromhmm, metadata, chromsizes, sys.stdout, segments,
-                                                                          binWidth or stateByLine.BIN_WIDTH, table):
+    for chrom, X, N, name, rng, _names, width in preprocess.iter_matrices(spec.inputDirPath, spec.metadata, spec.chromsizes, sys.stdout,
+                                                                          spec.segments, spec.binWidth or stateByLine.BIN_WIDTH, table):
         path = preprocess.matrix_path(outdir if outdir is not None else "", chrom)
         if outdir is not None:
             stateByLine.write_epgm(path, X[:, :N].contiguous(), name, rng, width)
-        if not checkStates and rng[1] > _io.state_limit():       # (a byte is a state value - 1; the pad columns are -1 as built)
+        if not spec.checkStates and rng[1] > _io.state_limit():       # (a byte is a state value - 1; the pad columns are -1 as built)
             X[(X >= _io.state_limit()) | (X < 0)] = -1
         resident[path] = (X, N, stateByLine.synth_locations(name, 0, X.shape[0], width))
         ranges[path] = rng
         del X
     files = sorted(resident, key=_natural_key)
     for f in files:
-        driver._check_range(f, ranges[f], numStates)
+        driver._check_range(f, ranges[f], spec.numStates)
     if files:
         nbytes = sum(driver._nbytes(resident[f][0]) for f in files)
         free = driver._device_free(resident[files[0]][0])
@@ -158,7 +358,29 @@ def _build_resident(chromhmm, metadata, chromsizes, segments, binWidth, stateNam
                   "epilogos -i MATRICES".format(nbytes, driver._ResidentStore.FREE_FACTOR * nbytes + driver._ResidentStore.FREE_SLACK,
                                                 driver._ResidentStore.FREE_FACTOR, driver._ResidentStore.FREE_SLACK, free))
             sys.exit(1)
-    return files, resident
+    _timing("matrices built on the device", _time.time() - t_build)
+    if not files:                                                # (segment files that hold no chromosome of the sizes file)
+        raise OSError("Ensure that directory is not empty: {}".format(str(spec.inputDirPath)))
+    _check_biosamples_exist(files, spec.topBiosample(), resident)
+    return _Inputs(files, [], resident)
+
+
+def _rank():
+    return int(os.environ.get("RANK", "0"))
+
+
+def _under_launcher():
+    return "WORLD_SIZE" in os.environ and "RANK" in os.environ
+
+
+def _say(*args, **kwargs):
+    if _rank() == 0:
+        print(*args, **kwargs)
+
+
+def _timing(label, seconds):
+    if os.environ.get("EPILOGOS_TIMING") and _rank() == 0:
+        print("    [timing] %-34s %7.2f s" % (label, seconds), flush=True)
 
 
 def _init_device_and_group(world, under_launcher):
@@ -188,6 +410,118 @@ def _init_device_and_group(world, under_launcher):
         else:
             dist.init_process_group(backend=backend, timeout=limit)
     return device
+
+
+_Inputs = namedtuple("_Inputs", "files files2 resident")   # files of [-i] or [-a]; those of [-b]; [--chromhmm]: {path: (X, N, Locations)}
+
+
+def _open_inputs(spec):
+    """-> _Inputs: the files in the order they run in, every biosample asked for by column being a column of each.  In a single
+    process their readers start NOW -- inflating needs neither torch nor the GPU, and importing the one and initialising the other
+    takes about a second, which a whole-genome run spent before its first byte was read.  A reader asks for its (page-locked)
+    destination only after its inflate; the session is attached when it exists."""
+    files = sorted(spec.inputDirPath.glob("*"), key=_natural_key) if not spec.chromhmm else []    # (--chromhmm: named once they are built)
+    files2 = []
+    if spec.mode == "paired" and not spec.pairedColumns:
+        for file in files:
+            if not list(spec.inputDirPath2.glob(file.name)):
+                raise FileNotFoundError("File not found: {}".format(str(spec.inputDirPath2 / file.name))
+                                        + " Please ensure corresponding files within input directories 1 and 2 have the same name")
+            files2.append(next(spec.inputDirPath2.glob(file.name)))
+    from . import _io, driver
+    if spec.groupings is None and spec.topBiosample() >= 0:
+        _check_biosamples_exist(files, spec.topBiosample())
+    if not spec.chromhmm and _world() == 1 and not _under_launcher() and os.environ.get("EPILOGOS_EARLY_READERS", "1") != "0":
+        _io.set_state_limit(spec.numStates)
+        jobs = [(f, 0, None) for pair in (zip(files, files2) if files2 else zip(files)) for f in pair]
+        driver.start_readers_early(jobs, raw=spec.checkStates)   # (--check-states: .epgm bytes reach the device as they are)
+    return _Inputs(files, files2, None)
+
+
+def _draw_null_seed(device):
+    """The seed of a paired run without [--null-seed]: every rank must shuffle with the same one (--groupings: every grouping too)."""
+    import numpy as np
+    seed = np.array([int(np.random.SeedSequence().generate_state(1)[0])], dtype=np.int64)
+    if _world() > 1:
+        import torch
+        import torch.distributed as dist
+        t = torch.from_numpy(seed)
+        t = t.to(device) if device is not None else t
+        dist.broadcast(t, src=0)
+        seed = t.cpu().numpy()
+    return int(seed[0])
+
+
+def _routes(spec, inputs, device):
+    """STEP 1-3 of every route of the command line -> generator of (subdirectory of the output directory, results), each to be followed
+    by its STEP 4.  Flat runs over files go to driver.run_single_group, run_paired_groups ([-a] [-b]) or run_paired_columns, under
+    the banner of their mode; [--groupings] and every run of [--chromhmm] to driver.run_groupings: every file is parsed and uploaded
+    once (--chromhmm: is resident already), and the groupings run one after another from the resident matrices, each with its text
+    complete before the next begins.  [--chromhmm] without [--groupings] is one grouping written to the output directory itself."""
+    from . import driver
+    world, paired = _world(), spec.mode == "paired"
+    model = (spec.numStates, spec.saliency, spec.outputDirPath, spec.fileTag)
+    null = (spec.quiescentState, spec.groupSize, spec.nullSeed)
+    common = dict(verbose=False, device=device, defer_writes=True, checkStates=spec.checkStates, **spec.extra("writer"))
+    shuffled = dict(common, keep_temps=False, nullDraws=spec.nullDraws)
+    flat = spec.groupings is None
+    if not flat:
+        _say("\nSTEP 1-3 of %d grouping(s): background counts -> all-reduce -> scores%s, from one read of the matrices (%d GPU(s))"
+             % (len(spec.groupings), ", null groups, deltas" if paired else "", world))
+    elif paired:
+        _say("\nSTEP 1-3: background counts over [A|B] -> all-reduce -> scores, null groups, deltas (%d GPU(s))" % world)
+    else:
+        _say("\nSTEP 1-3: background counts -> all-reduce -> scores (bin-range partition over %d GPU(s))" % world)
+    if not flat or inputs.resident is not None:
+        groupings = spec.groupings if not flat else [("", spec.colsA, spec.colsB)] if paired else [("", spec.cols)]
+        runs = driver.run_groupings(inputs.files, groupings, *model, *null, **shuffled,
+                                    **({} if inputs.resident is None else {"resident": inputs.resident, "flat": flat}))
+        try:
+            for k, g in enumerate(groupings):
+                if not flat:
+                    _say("\nGrouping %d of %d: %s" % (k + 1, len(groupings), g[0]), flush=True)
+                name, _q, results, _info = next(runs)
+                yield name, results
+        finally:
+            runs.close()
+            driver.abort_early_readers()
+            driver.finish_writes()
+        return
+    try:
+        if not paired:
+            _, results = driver.run_single_group(inputs.files, *model, **common, keep_temp_scores=False, columns=spec.cols)
+        elif spec.pairedColumns:
+            _, results = driver.run_paired_columns(inputs.files, spec.colsA, spec.colsB, *model, *null, **shuffled)
+        else:
+            _, results = driver.run_paired_groups(inputs.files, inputs.files2, *model, *null, **shuffled)
+    finally:
+        driver.abort_early_readers()                             # (nothing to do once the stage driver has taken them over)
+    yield "", results
+
+
+def _step4(spec, results, outDir):
+    """STEP 4 of one grouping, on rank 0; every rank then waits for its writers (the score text is still being written under it)."""
+    from . import driver
+    paired = spec.mode == "paired"
+    if paired and spec.pvalBool and max(spec.numProcesses, 1) > 1 and spec.nullDraws == 1 and spec.fit != "gpu":
+        driver.finish_writes()                                   # -n -c K forks a pool for the fits: not with writer threads running
+    try:
+        if _rank() == 0:
+            t0 = _time.perf_counter()
+            if paired:
+                print("\nSTEP 4: Generating p-values & regions of interest (figures are not produced)", flush=True)
+                from .roiAndVisualPairwise import mainFromArrays as roiPairwise
+                roiPairwise(results, spec.stateInfo, outDir, spec.fileTag, max(spec.numProcesses, 1), spec.pvalBool, spec.numTrials,
+                            spec.samplingSize, outDir / spec.storedExpPath.name, spec.roiWidth or 125, False,
+                            **spec.extra("fit", "pvals", "roi", "metrics"))
+            else:
+                print("\nSTEP 4: Finding regions of interest", flush=True)
+                from .roiSingle import mainFromArrays as roiSingle
+                roiSingle(results, outDir, spec.stateInfo, spec.fileTag, outDir / spec.storedExpPath.name, spec.roiWidth or 50, False,
+                          **spec.extra("roi", "metrics"))
+            _timing("STEP 4", _time.perf_counter() - t0)
+    finally:
+        driver.finish_writes()
 
 
 @click.command(context_settings=dict(help_option_names=["-h", "--help"]))
@@ -279,383 +613,49 @@ def _init_device_and_group(world, under_launcher):
               help="With --chromhmm --segments: a state metadata TSV (one_index, short_name) for labels that are names")
 @click.option("--keep-matrices", "keepMatrices", type=str, default=None,
               help="With --chromhmm: also write the matrix_<chr>.epgm files of epilogos-prep here")
-def main(mode, commandLineBool, inputDirectory, inputDirectory1, inputDirectory2, outputDirectory, stateInfo, saliency,
-         numProcesses, exitBool, diagnosticBool, numTrials, samplingSize, quiescentState, groupSize, version, partition,
-         pvalBool, roiWidth, fileTag, expFreqMem, expCombMem, scoreMem, roiMem, nullSeed, nullDraws, gpus, cacheDir, columns, columnsA, columnsB, checkStates,
-         groupingsFile, chromhmm, metadata, chromsizes, segments, binWidth, stateNames, keepMatrices, fit="host", pvals="host", writer="host",
-         roi="host", metrics="host"):
+def main(**options):
     """Information-theoretic navigation of multi-tissue functional genomic annotations -- MI355X scoring engine."""
-    if version:
-        print("Version:", __version__)
-        sys.exit()
-    # --chromhmm and what goes with it: its own combinations before all others, so that every command line without these options
-    # gets today's messages; nothing is read and no directory is made
-    _check_chromhmm_flags(mode, chromhmm, metadata, chromsizes, segments, binWidth, stateNames, keepMatrices, inputDirectory,
-                          inputDirectory1, inputDirectory2, columnsA, columnsB, groupingsFile, cacheDir, gpus)
-    if chromhmm is not None:
-        inputDirectory = chromhmm                         # from here on the run's input directory: required-ness, tag, emptiness
-    # --null-draws: its own combinations first, so that every command line without it gets today's messages
-    if nullDraws < 1:
-        print("ERROR: [--null-draws] must be at least 1"); sys.exit()
-    if nullDraws > 1 and mode != "paired":
-        print("ERROR: [--null-draws] greater than 1 is only valid in paired mode"); sys.exit()
-    if nullDraws > 1 and not pvalBool:
-        print("ERROR: [--null-draws] greater than 1 requires [-n, --null-distribution]"); sys.exit()
-    if nullDraws > 1 and (gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
-        print("ERROR: [--null-draws] greater than 1 runs on one GPU: the exceedance counts of several ranks are not added up yet; "
-              "use [--gpus 1]"); sys.exit()
-    # --fit gpu: the same, so that every command line without it gets today's messages
-    if fit == "gpu" and mode != "paired":
-        print("ERROR: [--fit gpu] is only valid in paired mode"); sys.exit()
-    if fit == "gpu" and not pvalBool:
-        print("ERROR: [--fit gpu] requires [-n, --null-distribution]: without it nothing is fitted"); sys.exit()
-    if fit == "gpu" and nullDraws > 1:
-        print("ERROR: [--fit gpu] cannot be combined with [--null-draws] greater than 1: empirical p-values need no fit"); sys.exit()
-    # --pvals gpu: the same
-    if pvals == "gpu" and mode != "paired":
-        print("ERROR: [--pvals gpu] is only valid in paired mode"); sys.exit()
-    if pvals == "gpu" and not pvalBool:
-        print("ERROR: [--pvals gpu] requires [-n, --null-distribution]: without it no p-value is computed"); sys.exit()
-    # --metrics gpu: the same; single mode writes no such file (--roi gpu is valid in both modes)
-    if metrics == "gpu" and mode != "paired":
-        print("ERROR: [--metrics gpu] is only valid in paired mode"); sys.exit()
-    # --groupings: as above, its own combinations and its file's errors before everything else -- nothing is read but that file
-    groupings = None
-    if groupingsFile is not None:
-        from .helpers import parseGroupings
-        for given, opt in ((columns, "--columns"), (columnsA, "--columns-a"), (columnsB, "--columns-b"), (inputDirectory1, "-a"),
-                           (inputDirectory2, "-b")):
-            if given is not None:
-                print("ERROR: [--groupings] names the biosamples of every grouping itself; it cannot be combined with [{}]".format(opt))
-                sys.exit()
-        if inputDirectory is None:
-            print("ERROR: [-i, --input-directory] is required with [--groupings]"); sys.exit()
-        try:
-            groupings = parseGroupings(groupingsFile, mode)
-        except ValueError as e:
-            print("ERROR: [--groupings] {}".format(e)); sys.exit()
-    # column groups: the flag combinations that involve the new options come first, so that every combination without them
-    # gets today's message
-    pairedColumns = mode == "paired" and (columnsA is not None or columnsB is not None or groupings is not None)
-    if mode == "single" and (columnsA is not None or columnsB is not None):
-        print("ERROR: [--columns-a] and [--columns-b] are only valid in paired mode; single mode takes [--columns]"); sys.exit()
-    if mode == "paired" and columns is not None:
-        print("ERROR: [--columns] is only valid in single mode; paired mode takes [--columns-a] and [--columns-b]"); sys.exit()
-    if pairedColumns and groupings is None:
-        if columnsA is None or columnsB is None:
-            print("ERROR: [--columns-a] and [--columns-b] must be given together"); sys.exit()
-        if inputDirectory1 is not None or inputDirectory2 is not None:
-            print("ERROR: [--columns-a] and [--columns-b] select from [-i, --input-directory]; they cannot be combined with [-a] and [-b]"); sys.exit()
-        if inputDirectory is None:
-            print("ERROR: [-i, --input-directory] is required with [--columns-a] and [--columns-b]"); sys.exit()
-    cols = colsA = colsB = None
-    try:
-        what = "--columns"
-        cols = parseColumns(columns) if columns is not None else None
-        if pairedColumns and groupings is None:
-            what = "--columns-a"
-            colsA = parseColumns(columnsA)
-            what = "--columns-b"
-            colsB = parseColumns(columnsB)
-    except ValueError as e:
-        print("ERROR: [{}] {}".format(what, e)); sys.exit()
-    if pairedColumns and groupings is None:
-        both = sorted(set(colsA.tolist()) & set(colsB.tolist()))
-        if both:
-            print("ERROR: biosample {} is in both [--columns-a] and [--columns-b]".format(both[0] + 1)); sys.exit()
-    # flag combinations (reference run.py:328-375)
-    if mode == "single" and inputDirectory is None:
-        print("ERROR: [-i, --input-directory] is required in single mode"); sys.exit()
-    if mode == "single" and (inputDirectory1 is not None or inputDirectory2 is not None):
-        print("ERROR: [-a] and [-b] are only valid in paired mode"); sys.exit()
-    if mode == "paired" and not pairedColumns and (inputDirectory1 is None or inputDirectory2 is None):
-        print("ERROR: [-a, --directory-one] and [-b, --directory-two] are required in paired mode"); sys.exit()
-    if mode == "paired" and not pairedColumns and inputDirectory is not None:
-        print("ERROR: [-i] is only valid in single mode"); sys.exit()
-    if outputDirectory is None:
-        print("ERROR: [-o, --output-directory] is required"); sys.exit()
-    if stateInfo is None:
-        print("ERROR: [-j, --state-info] is required"); sys.exit()
-
-    if cacheDir:
-        os.environ["EPILOGOS_CACHE_DIR"] = str(Path(cacheDir).resolve())
-    if numProcesses > 0:                                      # the reference's core budget (run.py:36,148): see _io.host_budget
-        os.environ["EPILOGOS_NUM_CORES"] = str(numProcesses)
-    numStates = getNumStates(stateInfo)
-    quiescentState = numStates - 1 if quiescentState == -1 else quiescentState - 1     # 1-based -> 0-based, 0 -> off
-    inputDirPath = Path(inputDirectory if mode == "single" or pairedColumns else inputDirectory1)
-    inputDirPath2 = (inputDirPath if pairedColumns else Path(inputDirectory2)) if mode == "paired" else Path("")
-    if not PurePath(inputDirPath).is_absolute():
-        inputDirPath = Path.cwd() / inputDirPath
-    if mode == "paired" and not PurePath(inputDirPath2).is_absolute():
-        inputDirPath2 = Path.cwd() / inputDirPath2
-    outputDirPath = Path(outputDirectory)
-    if not PurePath(outputDirPath).is_absolute():
-        outputDirPath = Path.cwd() / outputDirPath
-    if groupings is not None and inputDirPath.is_dir() and chromhmm is None:
-        # the largest biosample number of the file against every matrix's columns, before the first directory is made
-        _check_biosamples_exist(sorted(inputDirPath.glob("*"), key=_natural_key), max(int(c.max()) for g in groupings for c in g[1:]))
-    if chromhmm is not None:
-        for given, opt in ((metadata, "--metadata"), (chromsizes, "--chromsizes"), (stateNames, "--state-names")):
-            if given is not None and not Path(given).is_file():
-                print("ERROR: [{}] is not a file: {}".format(opt, given)); sys.exit()
-        if inputDirPath.is_dir() and list(inputDirPath.glob("*")) and not _selects_a_file(inputDirPath, metadata, chromsizes, segments):
-            # no file of the directory is anybody's: epilogos-prep would leave an empty directory, which [-i] refuses like this
-            raise OSError("Ensure that directory is not empty: {}".format(str(inputDirPath)))
-    checkArguments(mode, saliency, inputDirPath, inputDirPath2, outputDirPath, numProcesses, numStates, quiescentState,
-                   groupSize, numTrials, samplingSize, roiWidth)
-    if fileTag == "null":
-        fileTag = ("{}_s{}".format(inputDirPath.name, saliency) if mode == "single"
-                   else "{0}_A_{0}_B_s{1}".format(inputDirPath.name, saliency) if pairedColumns
-                   else "{}_{}_s{}".format(inputDirPath.name, inputDirPath2.name, saliency))
-    storedExpPath = outputDirPath / "exp_freq_{}.npy".format(fileTag)
-
-    # --gpus N from a plain start: fan out into one process per GPU (the reference submits its own SLURM jobs,
-    # run.py:190-279,454-505) -- as a CHILD process, before this one has imported torch or touched a GPU
-    if gpus < 0:
-        print("ERROR: Number of GPUs must be positive or zero (0 means use all visible GPUs)"); sys.exit()
-    if "WORLD_SIZE" not in os.environ and gpus != 1:
-        if gpus == 0:
-            gpus = 1 if nullDraws > 1 else _visible_gpus()   # (--null-draws K > 1 runs on one GPU)
+    spec = _describe_run(SimpleNamespace(**options))             # items 1-15 of its order contract; the rest follow here
+    if "WORLD_SIZE" not in os.environ and spec.gpus != 1:
+        # --gpus N from a plain start: one process per GPU (the reference submits its own SLURM jobs, run.py:190-279,454-505) -- as
+        # a CHILD process, before this one has imported torch or touched a GPU
+        gpus = spec.gpus or (1 if spec.nullDraws > 1 else _visible_gpus())     # (0: all visible; --null-draws K > 1 runs on one GPU)
         if gpus > 1:
             sys.exit(_launch(gpus, sys.argv[1:] if _ARGV is None else _ARGV))
-
-    # one process per GPU when launched under torch.distributed.run
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    under_launcher = "WORLD_SIZE" in os.environ and "RANK" in os.environ
-    files = sorted(inputDirPath.glob("*"), key=_natural_key) if chromhmm is None else []    # (--chromhmm: named once they are built)
-    files2 = []
-    if mode == "paired" and not pairedColumns:
-        for file in files:
-            if not list(inputDirPath2.glob(file.name)):
-                raise FileNotFoundError("File not found: {}".format(str(inputDirPath2 / file.name))
-                                        + " Please ensure corresponding files within input directories 1 and 2 have the same name")
-            files2.append(next(inputDirPath2.glob(file.name)))
-    from . import driver, _io
-    if groupings is None and (cols is not None or pairedColumns):     # every biosample asked for must exist in every file
-        _check_biosamples_exist(files, max(int(c.max()) for c in ((cols,) if cols is not None else (colsA, colsB))))
-    if chromhmm is None and world == 1 and not under_launcher and os.environ.get("EPILOGOS_EARLY_READERS", "1") != "0":
-        # A single process: the files' readers start NOW -- inflating needs neither torch nor the GPU, and importing the one and
-        # initialising the other takes about a second, which a whole-genome run spent before its first byte was read.  A reader
-        # asks for its (page-locked) destination only after its inflate; the session is attached when it exists.
-        _io.set_state_limit(numStates)
-        jobs = []
-        for k, f in enumerate(files):
-            jobs += [(f, 0, None)] + ([(files2[k], 0, None)] if files2 else [])
-        driver.start_readers_early(jobs, raw=checkStates)     # (--check-states: .epgm bytes reach the device as they are)
+    inputs = _open_inputs(spec)
+    from . import driver
     try:
-        device = _init_device_and_group(world, under_launcher)
+        device = _init_device_and_group(_world(), _under_launcher())
     except BaseException:
         driver.abort_early_readers()
         raise
-    rank = int(os.environ.get("RANK", "0"))
-    say = print if rank == 0 else (lambda *a, **k: None)
-    if os.environ.get("EPILOGOS_TIMING") and rank == 0:
-        import time
-        print("    [timing] %-34s %7.2f s" % ("imports + device init (since process start)", time.time() - _T_START), flush=True)
-
-    resident = None
-    if chromhmm is not None:
-        # epilogos-prep's part of the job, its progress lines included, before the run's own output
-        t_build = _time.time()
-        files, resident = _build_resident(inputDirPath, metadata, chromsizes, segments, binWidth, stateNames, keepMatrices, numStates,
-                                          checkStates)
-        if os.environ.get("EPILOGOS_TIMING"):
-            print("    [timing] %-34s %7.2f s" % ("matrices built on the device", _time.time() - t_build), flush=True)
-        if not files:                                            # (segment files that hold no chromosome of the sizes file)
-            raise OSError("Ensure that directory is not empty: {}".format(str(inputDirPath)))
-        asked = [c for g in groupings for c in g[1:]] if groupings is not None else [c for c in (cols, colsA, colsB) if c is not None]
-        top = max([int(c.max()) for c in asked] + [-1])
-        for f in files:
-            n = resident[f][1]
-            if n and top >= n:
-                print("ERROR: biosample {} is not in {}: the matrix has {} biosample columns".format(top + 1, f, n)); sys.exit()
-
-    say("State Model =", numStates, " Saliency level =", saliency, " GPUs =", world)
-    def step4_single(results, outDir):
-        try:
-            if rank == 0:
-                say("\nSTEP 4: Finding regions of interest", flush=True)
-                import time
-                t0 = time.perf_counter()
-                from .roiSingle import mainFromArrays as roiSingle
-                roiSingle(results, outDir, stateInfo, fileTag, outDir / storedExpPath.name, roiWidth if roiWidth else 50, False, **roiOptions())
-                if os.environ.get("EPILOGOS_TIMING"):
-                    print("    [timing] %-34s %7.2f s" % ("STEP 4", time.perf_counter() - t0), flush=True)
-        finally:
-            driver.finish_writes()                               # one process: the score text was still being written under STEP 4
-
-    def fitOptions():
-        # nothing for --fit host: STEP 4 is called exactly as before.  nullSeed is the run's one seed by now, drawn or given
-        return dict(fit="gpu", seed=nullSeed) if fit == "gpu" else {}
-
-    def pvalOptions():
-        # nothing for --pvals host, as above
-        return dict(pvals="gpu") if pvals == "gpu" else {}
-
-    def roiOptions():
-        # nothing for --roi host and --metrics host, as above
-        return {**(dict(roi="gpu") if roi == "gpu" else {}), **(dict(metrics="gpu") if metrics == "gpu" else {})}
-
-    def writerOptions():
-        # nothing for --writer host, as above: the drivers are called exactly as before
-        return dict(writer="gpu") if writer == "gpu" else {}
-
-    def step4_paired(results, outDir):
-        if pvalBool and max(numProcesses, 1) > 1 and nullDraws == 1 and fit != "gpu":
-            driver.finish_writes()                               # -n -c K forks a pool for the fits: not with writer threads running
-        try:
-            if rank == 0:
-                say("\nSTEP 4: Generating p-values & regions of interest (figures are not produced)", flush=True)
-                import time
-                t0 = time.perf_counter()
-                from .roiAndVisualPairwise import mainFromArrays as roiPairwise
-                roiPairwise(results, stateInfo, outDir, fileTag, max(numProcesses, 1), pvalBool, numTrials, samplingSize,
-                            outDir / storedExpPath.name, roiWidth if roiWidth else 125, False, **fitOptions(), **pvalOptions(), **roiOptions())
-                if os.environ.get("EPILOGOS_TIMING"):
-                    print("    [timing] %-34s %7.2f s" % ("STEP 4", time.perf_counter() - t0), flush=True)
-        finally:
-            driver.finish_writes()
-
-    if mode == "paired" and nullSeed is None:
-        import numpy as np
-        seed = np.array([int(np.random.SeedSequence().generate_state(1)[0])], dtype=np.int64)
-        if world > 1:                                            # every rank must shuffle with the same seed
-            import torch
-            import torch.distributed as dist
-            t = torch.from_numpy(seed)
-            t = t.to(device) if device is not None else t
-            dist.broadcast(t, src=0)
-            seed = t.cpu().numpy()
-        nullSeed = int(seed[0])                                  # (--groupings: the one seed of every grouping)
-    if groupings is not None or resident is not None:
-        # every file is parsed and uploaded once; the groupings then run one after another from the resident matrices, each with
-        # STEP 4 and its text complete before the next begins (driver.run_groupings yields as it goes).  --chromhmm: the matrices
-        # are resident before the first grouping, and a run without --groupings is one grouping written to the output directory itself
-        flat = groupings is None
-        if not flat:
-            say("\nSTEP 1-3 of %d grouping(s): background counts -> all-reduce -> scores%s, from one read of the matrices (%d GPU(s))"
-                % (len(groupings), ", null groups, deltas" if mode == "paired" else "", world))
-        elif mode == "single":
-            groupings = [("", cols)]
-            say("\nSTEP 1-3: background counts -> all-reduce -> scores (bin-range partition over %d GPU(s))" % world)
-        else:
-            groupings = [("", colsA, colsB)]
-            say("\nSTEP 1-3: background counts over [A|B] -> all-reduce -> scores, null groups, deltas (%d GPU(s))" % world)
-        runs = driver.run_groupings(files, groupings, numStates, saliency, outputDirPath, fileTag, quiescentState, groupSize, nullSeed,
-                                    verbose=False, device=device, keep_temps=False, defer_writes=True, nullDraws=nullDraws,
-                                    checkStates=checkStates, **({} if resident is None else {"resident": resident, "flat": flat}),
-                                    **writerOptions())
-        resident = None                                          # (the store's from here on: gone with the run)
-        try:
-            for k, g in enumerate(groupings):
-                if not flat:
-                    say("\nGrouping %d of %d: %s" % (k + 1, len(groupings), g[0]), flush=True)
-                name, _q, results, _info = next(runs)
-                (step4_single if mode == "single" else step4_paired)(results, outputDirPath / name)
-        finally:
-            runs.close()
-            driver.abort_early_readers()
-            driver.finish_writes()
-    elif mode == "single":
-        from .driver import run_single_group
-        say("\nSTEP 1-3: background counts -> all-reduce -> scores (bin-range partition over %d GPU(s))" % world)
-        try:
-            _, results = run_single_group(files, numStates, saliency, outputDirPath, fileTag, verbose=False, device=device,
-                                          keep_temp_scores=False, defer_writes=True, columns=cols, checkStates=checkStates, **writerOptions())
-        finally:
-            driver.abort_early_readers()                         # (nothing to do once the stage driver has taken them over)
-        step4_single(results, outputDirPath)
-    else:
-        from .driver import run_paired_columns, run_paired_groups
-        say("\nSTEP 1-3: background counts over [A|B] -> all-reduce -> scores, null groups, deltas (%d GPU(s))" % world)
-        try:
-            if pairedColumns:
-                _, results = run_paired_columns(files, colsA, colsB, numStates, saliency, outputDirPath, fileTag, quiescentState,
-                                                groupSize, nullSeed, verbose=False, device=device, keep_temps=False, defer_writes=True,
-                                                nullDraws=nullDraws, checkStates=checkStates, **writerOptions())
-            else:
-                _, results = run_paired_groups(files, files2, numStates, saliency, outputDirPath, fileTag, quiescentState, groupSize,
-                                               nullSeed, verbose=False, device=device, keep_temps=False, defer_writes=True,
-                                               nullDraws=nullDraws, checkStates=checkStates, **writerOptions())
-        finally:
-            driver.abort_early_readers()
-        step4_paired(results, outputDirPath)
+    _timing("imports + device init (since process start)", _time.time() - _T_START)
+    if spec.chromhmm:
+        inputs = _build_resident(spec)                           # epilogos-prep's part of the job, its progress lines included
+    _say("State Model =", spec.numStates, " Saliency level =", spec.saliency, " GPUs =", _world())
+    if spec.mode == "paired" and spec.nullSeed is None:
+        spec = spec._replace(nullSeed=_draw_null_seed(device))
+    runs = _routes(spec, inputs, device)
+    del inputs                                                   # (--chromhmm: the matrices are the run's from here on, gone with it)
+    with closing(runs):
+        for name, results in runs:
+            _step4(spec, results, spec.outputDirPath / name)
     from .helpers import flushCacheWrites
     flushCacheWrites()                                           # --cache-dir: files of first-time reads, written in the background
-    if os.environ.get("EPILOGOS_TIMING") and rank == 0:
-        import time
-        print("    [timing] %-34s %7.2f s" % ("end of main (since process start)", time.time() - _T_START), flush=True)
+    _timing("end of main (since process start)", _time.time() - _T_START)
+    if os.environ.get("EPILOGOS_TIMING") and _rank() == 0:
         try:                                                     # what the process holds (and will have to give back at exit)
             st = dict(l.split(":", 1) for l in open("/proc/self/status").read().splitlines() if ":" in l)
             print("    [timing] memory at the end: " + ", ".join("%s %.1f GB" % (k, int(st[k].split()[0]) / 1048576.0)
                                                               for k in ("VmHWM", "VmRSS", "RssAnon", "RssFile", "RssShmem") if k in st), flush=True)
         except (OSError, ValueError):
             pass
-    if world > 1 or under_launcher:
+    if _world() > 1 or _under_launcher():
         import torch.distributed as dist
         dist.destroy_process_group()
 
 
 _ARGV = None            # the argument list cli() was called with, when it is not sys.argv[1:]
-
-
-def _visible_gpus():
-    """GPUs this process could use, counted WITHOUT loading torch or touching HIP (the parent of the ranks must stay
-    GPU-free): the KFD topology lists every compute node (a GPU has simd_count > 0, a CPU node 0), and the usual
-    *_VISIBLE_DEVICES lists narrow it down."""
-    n = 0
-    try:
-        for node in sorted(Path("/sys/class/kfd/kfd/topology/nodes").iterdir()):
-            props = dict(l.split()[:2] for l in (node / "properties").read_text().splitlines() if len(l.split()) >= 2)
-            if int(props.get("simd_count", "0")) > 0:
-                n += 1
-    except (OSError, ValueError):
-        n = 0
-    # a container may see the host's whole KFD topology and only some of its render nodes: a GPU without an accessible
-    # /dev/dri/renderD* cannot be opened (a rank on it would die in torch.cuda.set_device)
-    try:
-        usable = len([d for d in Path("/dev/dri").iterdir() if d.name.startswith("renderD") and os.access(d, os.R_OK | os.W_OK)])
-        if n and usable:
-            n = min(n, usable)
-    except OSError:
-        pass
-    for var in ("ROCR_VISIBLE_DEVICES", "HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES"):
-        v = os.environ.get(var)
-        if v is not None:
-            listed = len([t for t in v.split(",") if t.strip()])
-            n = min(n, listed) if n else listed
-    return max(n, 1)
-
-
-def _strip_gpus(argv):
-    """The argument list without --gpus (the children learn their number from WORLD_SIZE)."""
-    from .helpers import splitGpusOption
-    return splitGpusOption(argv)[1]
-
-
-def _launch_command(gpus, argv, port):
-    return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(gpus),
-            "--master-addr", "127.0.0.1", "--master-port", str(port), "-m", "epilogos_amd.run"] + _strip_gpus(argv)
-
-
-def _launch(gpus, argv):
-    """One process per GPU under torch.distributed.run, as a child of this (GPU-free) process; its exit code is ours."""
-    import socket
-    import subprocess
-    with socket.socket() as sock:
-        sock.bind(("127.0.0.1", 0))
-        port = sock.getsockname()[1]
-    env = dict(os.environ)
-    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")       # dmabuf IPC: what RCCL needs on this driver
-    env.setdefault("OMP_NUM_THREADS", str(max(1, (os.cpu_count() or gpus) // gpus)))
-    root = str(Path(__file__).resolve().parents[1])
-    env["PYTHONPATH"] = root + (os.pathsep + env["PYTHONPATH"] if env.get("PYTHONPATH") else "")
-    cmd = _launch_command(gpus, argv, port)
-    if os.environ.get("EPILOGOS_LAUNCH_DRYRUN"):
-        print(" ".join(cmd))
-        return 0
-    return subprocess.call(cmd, env=env)
 
 
 def cli(argv=None):
