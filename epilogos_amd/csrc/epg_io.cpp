@@ -68,9 +68,43 @@ struct Uncount {
     ~Uncount() { if (was) census_add(1); }
 };
 
-void join_all(std::vector<std::thread>& th) {
+// The one place that starts worker threads: work(i) for i in [0, T) on T threads, the caller waiting -- and out of the census --
+// meanwhile.  Every thread that was started is joined on every path out.  A thread that cannot be started (the threads before it
+// run on and are joined) or an exception in a worker makes the call fail once all are joined: false, with fail() saying what.
+// Nothing leaves a thread function.
+template <class F>
+bool run_workers(int T, F&& work) {
+    Uncount uncount_;
+    std::mutex m;
+    char what[256] = "";                                      // (no allocation on the way out of a failed allocation)
+    auto note = [&](const char* w) {
+        std::lock_guard<std::mutex> g(m);
+        if (!what[0]) snprintf(what, sizeof(what), "%s", w[0] ? w : "exception");
+    };
+    std::vector<std::thread> th;
+    try {
+        th.reserve((size_t)T);
+        for (int i = 0; i < T; ++i)
+            th.emplace_back([&, i] {
+                Census census_;
+                try { work(i); }
+                catch (const std::exception& e) { note(e.what()); }
+                catch (...) { note("unknown exception"); }
+            });
+    }
+    catch (const std::exception& e) { note(e.what()); }
+    catch (...) { note("unknown exception"); }
     for (auto& t : th) t.join();
+    if (what[0]) { fail("worker threads: %s", what); return false; }
+    return true;
 }
+
+// No exception leaves the library.  Every extern "C" entry point that allocates or starts threads is a function-try-block closed
+// by this: what the call owned is released by its owners' destructors on the way here (the table, the text, the open FILE),
+// fail() names the entry point and the exception, and the caller gets the entry point's failure value.
+#define EPGIO_CATCH(entry, failure)                                                     \
+    catch (const std::exception& e) { fail("%s: %s", entry, e.what()); return failure; } \
+    catch (...) { fail("%s: unknown exception", entry); return failure; }
 
 // threads to use when the caller says 0: EPILOGOS_HOST_THREADS when set (the share of the host the driver gives this rank: a
 // node's cores divided by the ranks on it, capped by -c), else the hardware threads, capped by the cgroup CPU quota (a container
@@ -195,6 +229,14 @@ struct Text {
 
 bool is_gzip(const unsigned char* p, size_t n) { return n >= 18 && p[0] == 0x1f && p[1] == 0x8b; }
 
+uint32_t le32(const unsigned char* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+
+double now_s() {
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return ts.tv_sec + 1e-9 * ts.tv_nsec;
+}
+
 // Ask for transparent huge pages under a big fresh buffer (the pool runs THP in "madvise" mode): a whole genome's text is 26 GB
 // of first-touch pages, 6.5 M faults of 4 KiB.  Harmless where it is not honoured.
 void advise_huge(void* p, size_t n) {
@@ -204,83 +246,6 @@ void advise_huge(void* p, size_t n) {
 #else
     (void)p; (void)n;
 #endif
-}
-
-// gzip members of in[0, flen) -> t.heap through epginflate, then ISIZE and CRC-32 of every member (epg_crc32.h: carry-less
-// multiplication, ~20 GB/s where zlib's table-driven crc32 does 1 GB/s; in pieces over the threads).  false = use zlib instead.
-bool inflate_own(const unsigned char* in, size_t flen, size_t cap_hint, Text& t, int32_t threads) {
-    struct Member { size_t out0, out1; uint32_t crc, isize; };
-    std::vector<Member> members;
-    epginflate::Out out{nullptr, 0, cap_hint};
-    t.heap = big_alloc(cap_hint + 320 + 16, &t.heap_cap);
-    if (!t.heap) return false;
-    out.cap = t.heap_cap - 320 - 16;                       // (a reused buffer may be larger than asked for)
-    out.base = (unsigned char*)t.heap;
-    auto grow = [&](size_t min_cap) {
-        size_t ncap = out.cap + out.cap / 2 + (1u << 24);
-        if (ncap < min_cap) ncap = min_cap + (1u << 24);
-        size_t got = 0;
-        char* nh = big_grow(t.heap, t.heap_cap, out.pos, ncap + 320 + 16, &got);
-        if (!nh) return false;
-        t.heap = nh;
-        t.heap_cap = got;
-        out.base = (unsigned char*)nh;
-        out.cap = got - 320 - 16;
-        return true;
-    };
-    size_t pos = 0;
-    while (pos < flen && is_gzip(in + pos, flen - pos)) {
-        const unsigned char* h = in + pos;
-        if (h[2] != 8 || (h[3] & 0xe0)) return false;
-        size_t hp = pos + 10;
-        const int flg = h[3];
-        if (flg & 4) { if (hp + 2 > flen) return false; hp += 2 + ((size_t)in[hp] | ((size_t)in[hp + 1] << 8)); }
-        if (flg & 8) { while (hp < flen && in[hp]) ++hp; ++hp; }
-        if (flg & 16) { while (hp < flen && in[hp]) ++hp; ++hp; }
-        if (flg & 2) hp += 2;
-        if (hp + 8 > flen) return false;
-        const size_t out0 = out.pos;
-        const size_t used = epginflate::inflate_raw(in + hp, flen - hp - 8, out, grow);
-        if (!used) return false;
-        const unsigned char* tr = in + hp + used;
-        Member m;
-        m.out0 = out0; m.out1 = out.pos;
-        m.crc = (uint32_t)tr[0] | (uint32_t)tr[1] << 8 | (uint32_t)tr[2] << 16 | (uint32_t)tr[3] << 24;
-        m.isize = (uint32_t)tr[4] | (uint32_t)tr[5] << 8 | (uint32_t)tr[6] << 16 | (uint32_t)tr[7] << 24;
-        if ((uint32_t)(m.out1 - m.out0) != m.isize) return false;
-        members.push_back(m);
-        pos = hp + used + 8;
-    }
-    if (members.empty()) return false;
-    // CRC-32: pieces of <= 32 MiB over the threads, stitched per member with crc32_combine
-    struct Piece { size_t off, len; uint32_t crc; };
-    std::vector<Piece> pieces;
-    std::vector<size_t> first(members.size() + 1, 0);
-    const size_t PIECE = (size_t)32 << 20;
-    for (size_t k = 0; k < members.size(); ++k) {
-        first[k] = pieces.size();
-        for (size_t o = members[k].out0; o < members[k].out1; o += PIECE) pieces.push_back(Piece{o, std::min(PIECE, members[k].out1 - o), 0});
-    }
-    first[members.size()] = pieces.size();
-    const int T = (int)std::max<size_t>(1, std::min<size_t>((size_t)(threads > 0 ? threads : reader_share()), pieces.size()));
-    Uncount uncount_;
-    std::vector<std::thread> th;
-    for (int w = 0; w < T; ++w)
-        th.emplace_back([&, w] {
-            Census census_;
-            for (size_t i = (size_t)w; i < pieces.size(); i += (size_t)T)
-                pieces[i].crc = epgcrc::crc32_fast(0, (const unsigned char*)t.heap + pieces[i].off, pieces[i].len);
-        });
-    join_all(th);
-    for (size_t k = 0; k < members.size(); ++k) {
-        uLong crc = crc32(0L, Z_NULL, 0);
-        for (size_t i = first[k]; i < first[k + 1]; ++i) crc = crc32_combine(crc, pieces[i].crc, (z_off_t)pieces[i].len);
-        if ((uint32_t)crc != members[k].crc) return false;
-    }
-    memset(t.heap + out.pos, 0, 16);
-    t.data = t.heap;
-    t.size = out.pos;
-    return true;
 }
 
 // BGZF -- the blocked gzip of htslib (bgzip, tabix): every member is at most 64 KiB and carries its own compressed size in an extra
@@ -315,8 +280,8 @@ bool bgzf_index(const unsigned char* in, size_t flen, std::vector<BgzfBlock>& bl
         BgzfBlock b;
         b.in_off = pos + hl;
         b.in_len = (uint32_t)(total - hl - 8);
-        b.crc = (uint32_t)tr[0] | (uint32_t)tr[1] << 8 | (uint32_t)tr[2] << 16 | (uint32_t)tr[3] << 24;
-        b.isize = (uint32_t)tr[4] | (uint32_t)tr[5] << 8 | (uint32_t)tr[6] << 16 | (uint32_t)tr[7] << 24;
+        b.crc = le32(tr);
+        b.isize = le32(tr + 4);
         if (b.isize > 65536) return false;
         b.out_off = out;
         out += b.isize;
@@ -325,6 +290,81 @@ bool bgzf_index(const unsigned char* in, size_t flen, std::vector<BgzfBlock>& bl
     }
     *out_total = out;
     return !blocks.empty();
+}
+
+// Length of the gzip member header at h (RFC 1952: the fixed ten bytes, then FEXTRA, FNAME, FCOMMENT and FHCRC as the flags say),
+// with the 8 bytes of a trailer still behind it; 0 = not deflate, a reserved flag, or cut short.
+size_t gzip_header(const unsigned char* h, size_t avail) {
+    if (h[2] != 8 || (h[3] & 0xe0)) return 0;
+    const int flg = h[3];
+    size_t hp = 10;
+    if (flg & 4) { if (hp + 2 > avail) return 0; hp += 2 + ((size_t)h[hp] | ((size_t)h[hp + 1] << 8)); }
+    if (flg & 8) { while (hp < avail && h[hp]) ++hp; ++hp; }
+    if (flg & 16) { while (hp < avail && h[hp]) ++hp; ++hp; }
+    if (flg & 2) hp += 2;
+    return hp + 8 > avail ? 0 : hp;
+}
+
+// gzip members of in[0, flen) -> t.heap through epginflate, then ISIZE and CRC-32 of every member (epg_crc32.h: carry-less
+// multiplication, ~20 GB/s where zlib's table-driven crc32 does 1 GB/s; in pieces over the threads).  false = use zlib instead.
+bool inflate_own(const unsigned char* in, size_t flen, size_t cap_hint, Text& t, int32_t threads) {
+    struct Member { size_t out0, out1; uint32_t crc, isize; };
+    std::vector<Member> members;
+    epginflate::Out out{nullptr, 0, cap_hint};
+    t.heap = big_alloc(cap_hint + 320 + 16, &t.heap_cap);
+    if (!t.heap) return false;
+    out.cap = t.heap_cap - 320 - 16;                       // (a reused buffer may be larger than asked for)
+    out.base = (unsigned char*)t.heap;
+    auto grow = [&](size_t min_cap) {
+        size_t ncap = out.cap + out.cap / 2 + (1u << 24);
+        if (ncap < min_cap) ncap = min_cap + (1u << 24);
+        size_t got = 0;
+        char* nh = big_grow(t.heap, t.heap_cap, out.pos, ncap + 320 + 16, &got);
+        if (!nh) return false;
+        t.heap = nh;
+        t.heap_cap = got;
+        out.base = (unsigned char*)nh;
+        out.cap = got - 320 - 16;
+        return true;
+    };
+    size_t pos = 0;
+    while (pos < flen && is_gzip(in + pos, flen - pos)) {
+        const size_t hl = gzip_header(in + pos, flen - pos);
+        if (!hl) return false;
+        const size_t hp = pos + hl, out0 = out.pos;
+        const size_t used = epginflate::inflate_raw(in + hp, flen - hp - 8, out, grow);
+        if (!used) return false;
+        const unsigned char* tr = in + hp + used;
+        const Member m{out0, out.pos, le32(tr), le32(tr + 4)};
+        if ((uint32_t)(m.out1 - m.out0) != m.isize) return false;
+        members.push_back(m);
+        pos = hp + used + 8;
+    }
+    if (members.empty()) return false;
+    // CRC-32: pieces of <= 32 MiB over the threads, stitched per member with crc32_combine
+    struct Piece { size_t off, len; uint32_t crc; };
+    std::vector<Piece> pieces;
+    std::vector<size_t> first(members.size() + 1, 0);
+    const size_t PIECE = (size_t)32 << 20;
+    for (size_t k = 0; k < members.size(); ++k) {
+        first[k] = pieces.size();
+        for (size_t o = members[k].out0; o < members[k].out1; o += PIECE) pieces.push_back(Piece{o, std::min(PIECE, members[k].out1 - o), 0});
+    }
+    first[members.size()] = pieces.size();
+    const int T = (int)std::max<size_t>(1, std::min<size_t>((size_t)(threads > 0 ? threads : reader_share()), pieces.size()));
+    if (!run_workers(T, [&](int w) {
+            for (size_t i = (size_t)w; i < pieces.size(); i += (size_t)T)
+                pieces[i].crc = epgcrc::crc32_fast(0, (const unsigned char*)t.heap + pieces[i].off, pieces[i].len);
+        })) { g_err[0] = 0; return false; }                       // (zlib takes the file: its verdict is the call's)
+    for (size_t k = 0; k < members.size(); ++k) {
+        uLong crc = crc32(0L, Z_NULL, 0);
+        for (size_t i = first[k]; i < first[k + 1]; ++i) crc = crc32_combine(crc, pieces[i].crc, (z_off_t)pieces[i].len);
+        if ((uint32_t)crc != members[k].crc) return false;
+    }
+    memset(t.heap + out.pos, 0, 16);
+    t.data = t.heap;
+    t.size = out.pos;
+    return true;
 }
 
 // false = not BGZF, or a member is not what its header and trailer say: the general reader (and then zlib) judges the file.
@@ -360,13 +400,12 @@ bool inflate_bgzf(const unsigned char* in, size_t flen, Text& t, int32_t threads
                 }
             }
         };
-        if (T == 1) work();
-        else {
-            Uncount uncount_;
-            std::vector<std::thread> th;
-            for (int w = 0; w < T; ++w) th.emplace_back([&] { Census census_; work(); });
-            join_all(th);
-        }
+        // a round that cannot have its scratch or its threads declines the file like any other doubt, inline or not, and leaves
+        // no message behind: the general reader's verdict is the call's
+        bool ran = true;
+        if (T == 1) { try { work(); } catch (const std::exception&) { ran = false; } }
+        else ran = run_workers(T, [&](int) { work(); });
+        if (!ran) { g_err[0] = 0; return false; }
         next.store(r1);
     }
     if (bad.load()) return false;
@@ -444,7 +483,7 @@ bool slurp(const char* path, Text& t, int32_t threads = 0) {
         t.data = t.heap; t.size = flen;
         return true;
     }
-    size_t cap = (size_t)((uint32_t)in[flen - 4] | (uint32_t)in[flen - 3] << 8 | (uint32_t)in[flen - 2] << 16 | (uint32_t)in[flen - 1] << 24);
+    size_t cap = le32(in + flen - 4);
     if (cap < flen) cap = flen * 4;                     // ISIZE is the LAST member's size mod 2^32: a hint only
     cap += 64;
     // The library's own inflate first (epg_inflate.h, ~2-3x zlib's rate); every member's ISIZE and CRC-32 are checked, and on
@@ -462,8 +501,6 @@ bool slurp(const char* path, Text& t, int32_t threads = 0) {
     }
     return inflate_zlib(in, flen, cap, t, path);
 }
-
-}  // namespace
 
 #if defined(__x86_64__)
 // One row's states with AVX-512 (VBMI2): 64 bytes of "\t18\t7\t18..." per step.  Every byte position is treated as if a value
@@ -549,6 +586,55 @@ void fold_minmax512(const void* mn, const void* mx, int T, int* vlo, int* vhi) {
 }
 #endif
 
+// One row's states by the scalar code, which also judges every row the vector parser declines: the same q, nl, out, cols and
+// max0, the smallest / largest value as written folded into lo / hi; returns cols, or -1 for a malformed row.
+inline int parse_row_scalar(const char* q, const char* nl, int8_t* out, int cols, int& lo, int& hi, int max0) {
+    int c = 0;
+    // fast path: one- or two-digit values ("\t7", "\t18"), which is every state of a 1..31-state model; the text has 16 readable
+    // bytes after its end, a row ends in '\n' (not a digit), so looking three characters ahead is safe.  Anything else (sign,
+    // three digits, '\r', malformed) leaves the loop for the general one.
+    while (c < cols && *q == '\t') {
+        const unsigned d0 = (unsigned)(unsigned char)q[1] - '0';
+        if (d0 > 9) break;
+        const unsigned d1 = (unsigned)(unsigned char)q[2] - '0';
+        int v;
+        if (d1 > 9) { v = (int)d0; q += 2; }
+        else {
+            if ((unsigned)(unsigned char)q[3] - '0' <= 9) break;       // three or more digits
+            v = (int)(d0 * 10 + d1);
+            q += 3;
+        }
+        lo = v < lo ? v : lo;
+        hi = v > hi ? v : hi;
+        --v;                                                        // file states are 1-based (helpers.py:155)
+        out[c++] = (int8_t)(((unsigned)v > (unsigned)max0) ? -1 : v);  // outside 0..max0: "not a state" (see below)
+    }
+    if (c == cols && q < nl && *q == '\r') ++q;                    // CRLF line ends
+    while (q < nl && c < cols) {
+        // a value is introduced by a TAB and by nothing else: the fast path above can stop on any byte ("1.5", "1x5", "1 5"),
+        // and that byte must not be swallowed as if it were the separator
+        if (*q != '\t') return -1;
+        ++q;                                // the tab before the value
+        int v = 0;
+        bool neg = false, any = false;
+        if (q < nl && *q == '-') { neg = true; ++q; }
+        while (q < nl && *q >= '0' && *q <= '9') { v = v * 10 + (*q - '0'); ++q; any = true; if (v > 100000) break; }
+        if (q < nl && *q == '\r') ++q;
+        if (!any || (q < nl && *q != '\t')) return -1;
+        v = neg ? -v : v;
+        lo = v < lo ? v : lo;
+        hi = v > hi ? v : hi;
+        v -= 1;                             // file states are 1-based (helpers.py:155)
+        // the kernels of models up to 31 states decode five bits and treat 31 as "not a state": anything outside 0..max0 (30,
+        // or 126 for the wide models) is stored as -1 so that it cannot alias a state; the caller sees it in
+        // epgio_table_state_range and in the count check (sum of counts != rows * columns)
+        out[c++] = (int8_t)((v < 0 || v > max0) ? -1 : v);
+    }
+    return c == cols && q == nl ? cols : -1;
+}
+
+}  // namespace
+
 struct epgio_table {
     int64_t rows = 0;
     int32_t cols = 0;
@@ -560,151 +646,165 @@ struct epgio_table {
     int32_t state_lo = 0, state_hi = 0;   // smallest / largest state value as written in the file (1-based); 0, 0 when empty
 };
 
-extern "C" {
-
-const char* epgio_last_error(void) { return g_err; }
-
-int64_t epgio_count_rows(const char* path) {
-    Census census_;
-    gzFile f = gzopen(path, "rb");
-    if (!f) return fail("cannot open %s", path);
-    gzbuffer(f, 1 << 20);
-    std::vector<char> buf(1 << 22);
-    int64_t total = 0;
-    for (;;) {
-        const int got = gzread(f, buf.data(), (unsigned)buf.size());
-        if (got < 0) { gzclose(f); return fail("read error in %s", path); }
-        if (got == 0) break;
-        const char* p = buf.data();
-        const char* e = p + got;
-        while ((p = (const char*)memchr(p, '\n', (size_t)(e - p)))) { ++total; ++p; }
-    }
-    gzclose(f);
-    (void)ends_with_gz;
-    return total;
-}
-
-static double now_s() {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return ts.tv_sec + 1e-9 * ts.tv_nsec;
-}
-
-epgio_table* epgio_open_table(const char* path, int64_t row_lo, int64_t row_hi, int32_t threads) {
-    return epgio_open_table_ex(path, row_lo, row_hi, threads, 31);
-}
-
-void epgio_thread_census(int32_t* live, int32_t* peak, int32_t reset) {
-    if (live) *live = g_live.load();
-    if (peak) *peak = g_peak.load();
-    if (reset) g_peak.store(g_live.load());
-}
-
-int32_t epgio_default_threads(void) { return n_threads(0); }
-void epgio_set_host_threads(int32_t n) { g_host_threads.store(n > 0 ? n : 0, std::memory_order_relaxed); }
-
-
-int64_t epgio_inflate_mem(const void* in, int64_t n, void* out, int64_t cap, int32_t own) {
-    if (!in || n < 0 || cap < 0 || (cap > 0 && !out)) return fail("inflate_mem: bad argument");
-    const unsigned char* p = (const unsigned char*)in;
-    if (!is_gzip(p, (size_t)n)) return fail("inflate_mem: not a gzip stream");
-    Text t;
-    size_t hint = (size_t)((uint32_t)p[n - 4] | (uint32_t)p[n - 3] << 8 | (uint32_t)p[n - 2] << 16 | (uint32_t)p[n - 1] << 24);
-    if (hint < (size_t)n || hint > ((size_t)1 << 28)) hint = (size_t)n * 4;
-    hint += 64;
-    const bool ok = own == 2 ? inflate_bgzf(p, (size_t)n, t, 2) : own ? inflate_own(p, (size_t)n, hint, t, 1) : inflate_zlib(p, (size_t)n, hint, t, "memory");
-    if (!ok) return own ? fail("inflate_mem: the library's inflate declined the stream") : -1;
-    if ((int64_t)t.size > cap) return fail("inflate_mem: output %lld > cap %lld", (long long)t.size, (long long)cap);
-    if (t.size) memcpy(out, t.data, t.size);
-    return (int64_t)t.size;
-}
-
 struct epgio_text {
     Text t;
 };
 
-epgio_text* epgio_open_text(const char* path, int32_t threads) {
-    if (!path) { fail("open_text: NULL path"); return nullptr; }
-    Census census_;
-    epgio_text* h = new (std::nothrow) epgio_text();
-    if (!h) { fail("out of memory reading %s", path); return nullptr; }
-    try {
-        if (!slurp(path, h->t, threads)) { delete h; return nullptr; }
-    } catch (const std::exception& e) {                          // (the readers' vectors and threads: nothing crosses the C ABI)
-        delete h;
-        fail("reading %s: %s", path, e.what());
-        return nullptr;
-    }
-    return h;
-}
+namespace {
 
-const char* epgio_text_data(const epgio_text* h, int64_t* size) {
-    if (size) *size = h ? (int64_t)h->t.size : 0;
-    return h ? h->t.data : nullptr;
-}
-
-void epgio_close_text(epgio_text* h) { delete h; }
-
-int64_t epgio_count_newlines(const char* p, int64_t n, int32_t threads) {
-    if (n < 0 || (n > 0 && !p)) return fail("count_newlines: bad argument");
-    auto count = [](const char* a, const char* e) {
-        int64_t c = 0;
-        while (a < e && (a = (const char*)memchr(a, '\n', (size_t)(e - a)))) { ++c; ++a; }
-        return c;
-    };
-    const int64_t PIECE = (int64_t)8 << 20;
-    const int T = (int)std::max<int64_t>(1, std::min<int64_t>(n_threads(threads), n / PIECE));
-    Census census_;
-    if (T == 1) return count(p, p + n);
-    std::vector<int64_t> part((size_t)T, 0);
-    {
-        Uncount uncount_;
-        std::vector<std::thread> th;
-        for (int w = 0; w < T; ++w)
-            th.emplace_back([&, w] { Census c_; part[(size_t)w] = count(p + n * w / T, p + n * (w + 1) / T); });
-        join_all(th);
-    }
-    int64_t total = 0;
-    for (int64_t c : part) total += c;
-    return total;
-}
-
-static epgio_table* open_table_impl(const char* path, int64_t row_lo, int64_t row_hi, int32_t threads, int32_t max_state,
-                                    epgio_alloc_fn alloc, void* user);
-
-epgio_table* epgio_open_table_ex(const char* path, int64_t row_lo, int64_t row_hi, int32_t threads, int32_t max_state) {
-    return open_table_impl(path, row_lo, row_hi, threads, max_state, nullptr, nullptr);
-}
-
-epgio_table* epgio_open_table_into(const char* path, int64_t row_lo, int64_t row_hi, int32_t threads, int32_t max_state,
-                                   epgio_alloc_fn alloc, void* user) {
-    if (!alloc) { fail("open_table_into: no allocator"); return nullptr; }
-    return open_table_impl(path, row_lo, row_hi, threads, max_state, alloc, user);
-}
-
-extern "C" void epgio_set_reader_plan(int32_t n) { g_reader_plan.store(n > 0 ? n : 0); }
-
-// The kept text buffers (their pages are released after every file already) go back to the kernel -- on a thread of its own
-// when `background`.  For a process that is done reading and goes on living.
-extern "C" void epgio_release_buffers(int32_t background) {
-    std::vector<std::pair<char*, size_t>> bufs;
-    {
-        BigBufs& b = big_bufs();
-        std::lock_guard<std::mutex> g(b.m);
-        bufs.swap(b.free_list);
-    }
-    if (bufs.empty()) return;
-    auto work = [bufs] { for (auto& e : bufs) free(e.first); };
-    if (background) std::thread(work).detach();
-    else work();
-}
 struct ReaderScope {
     ReaderScope() { g_readers.fetch_add(1); }
     ~ReaderScope() { g_readers.fetch_sub(1); }
 };
 
-static epgio_table* open_table_impl(const char* path, int64_t row_lo, int64_t row_hi, int32_t threads, int32_t max_state,
-                                    epgio_alloc_fn alloc, void* user) {
+// The phases of open_table_impl.  Rows: the complete lines of a text cut into T segments on line starts, and the caller's row
+// range -- what every parallel pass walks.
+struct Rows {
+    std::vector<const char*> seg;      // [T + 1]
+    std::vector<int64_t> first;        // [T + 1]: the row a segment starts with; first[T] = all rows
+    int64_t lo = 0, hi = 0;            // the rows asked for, clipped
+    int T() const { return (int)seg.size() - 1; }
+    template <class F>
+    void each(int i, F&& fn) const {   // fn(row - lo, its first byte, its '\n') for the rows of segment i inside [lo, hi)
+        const char* p = seg[i];
+        int64_t r = first[i];
+        while (p < seg[i + 1]) {
+            const char* nl = (const char*)memchr(p, '\n', (size_t)(seg[i + 1] - p));
+            if (r >= hi) break;
+            if (r >= lo) fn(r - lo, p, nl);
+            p = nl + 1;
+            ++r;
+        }
+    }
+};
+
+// complete lines only (the reference counts newlines, helpers.py:94: a dangling last line does not exist): the byte behind the
+// last '\n', nullptr when there is none
+const char* complete_lines_end(const char* base, const char* end) {
+    for (const char* p = end; p > base;)
+        if (*--p == '\n') return p + 1;
+    return nullptr;
+}
+
+std::vector<const char*> segment_borders(const char* base, const char* end, int T) {
+    std::vector<const char*> seg((size_t)T + 1);
+    seg[0] = base;
+    for (int i = 1; i < T; ++i) {
+        const char* p = base + (size_t)((end - base) / T) * i;
+        if (p < seg[i - 1]) p = seg[i - 1];
+        const char* nl = (const char*)memchr(p, '\n', (size_t)(end - p));
+        seg[i] = nl ? nl + 1 : end;
+    }
+    seg[T] = end;
+    return seg;
+}
+
+bool count_lines(Rows& rows) {
+    const int T = rows.T();
+    std::vector<int64_t> n((size_t)T, 0);
+    if (!run_workers(T, [&](int i) {
+            int64_t c = 0;
+            const char* p = rows.seg[i];
+            const char* e = rows.seg[i + 1];
+            while (p < e && (p = (const char*)memchr(p, '\n', (size_t)(e - p)))) { ++c; ++p; }
+            n[i] = c;
+        })) return false;
+    rows.first.assign((size_t)T + 1, 0);
+    for (int i = 0; i < T; ++i) rows.first[i + 1] = rows.first[i] + n[i];
+    return true;
+}
+
+// number of state columns, from the first line: its tabs less the two inside the location
+int32_t state_columns(const char* base, const char* end) {
+    const char* nl = (const char*)memchr(base, '\n', (size_t)(end - base));
+    int tabs = 0;
+    for (const char* p = base; p < nl; ++p) tabs += *p == '\t';
+    return tabs - 2;
+}
+
+// where the states go, and its row pitch: the caller's buffer or the table's own matrix
+int8_t* state_destination(epgio_table& t, epgio_alloc_fn alloc, void* user, const char* path, int64_t* sld) {
+    *sld = t.cols;
+    if (!alloc) {
+        t.states.reset(new int8_t[(size_t)t.rows * t.cols + 1]);
+        advise_huge(t.states.get(), (size_t)t.rows * t.cols);
+        return t.states.get();
+    }
+    // the caller's destination (a pinned, row-padded staging buffer): rows are parsed straight into it -- no 1 GB intermediate
+    // matrix, no copy of it (round 3: both, single-threaded, after the parse)
+    int64_t ld = 0;
+    int8_t* p = alloc(t.rows, t.cols, &ld, user);
+    if (!p || ld < t.cols) { fail("%s: no destination for %lld x %d states", path, (long long)t.rows, t.cols); return nullptr; }
+    *sld = t.ext_ld = ld;
+    t.ext = p;
+    return p;
+}
+
+// pass 1: loc_off[r + 1] = length of row r's location text with the '\n' that ends it; the caller's prefix sum makes offsets of it
+bool location_lengths(const Rows& rows, epgio_table& t) {
+    return run_workers(rows.T(), [&](int i) {
+        rows.each(i, [&](int64_t r, const char* p, const char* nl) {
+            int tabs = 0;
+            const char* q = p;
+            for (; q < nl; ++q)
+                if (*q == '\t' && ++tabs == 3) break;
+            t.loc_off[(size_t)r + 1] = q - p + 1;
+        });
+    });
+}
+
+// the segments' ranges of state values as written, folded into the table's (0, 0 while it has seen none)
+void fold_state_range(epgio_table& t, const std::vector<int>& vlo, const std::vector<int>& vhi) {
+    for (size_t i = 0; i < vlo.size(); ++i)
+        if (vlo[i] <= vhi[i]) {
+            if (t.state_lo == 0 && t.state_hi == 0) { t.state_lo = vlo[i]; t.state_hi = vhi[i]; }
+            t.state_lo = std::min(t.state_lo, vlo[i]);
+            t.state_hi = std::max(t.state_hi, vhi[i]);
+        }
+}
+
+// pass 2: every row's location text and states (pad bytes of a wider pitch: 0xFF, not a state), the range of the values, and in
+// *bad_row the first malformed row of the range (-1: none)
+bool parse_rows(const Rows& rows, epgio_table& t, int8_t* sbase, int64_t sld, int max0, int64_t* bad_row) {
+    const int T = rows.T(), cols = t.cols;
+    std::vector<int64_t> bad((size_t)T, -1);
+    std::vector<int> vlo((size_t)T, 1 << 30), vhi((size_t)T, -(1 << 30));
+#if defined(__x86_64__)
+    struct alignas(64) V512 { __m512i v; };
+    const bool simd = have_avx512_parser();
+    std::vector<V512> vmin512((size_t)T), vmax512((size_t)T);
+    if (simd) init_minmax512(vmin512.data(), vmax512.data(), T);
+#endif
+    if (!run_workers(T, [&](int i) {
+            int lo = vlo[i], hi = vhi[i];
+            rows.each(i, [&](int64_t r, const char* p, const char* nl) {
+                const int64_t len = t.loc_off[(size_t)r + 1] - t.loc_off[(size_t)r] - 1;
+                memcpy(t.loc.data() + t.loc_off[(size_t)r], p, (size_t)len);
+                t.loc[(size_t)(t.loc_off[(size_t)r] + len)] = '\n';
+                const char* q = p + len;                                           // the tab in front of the first value
+                int8_t* out = sbase + (size_t)r * (size_t)sld;
+                if (sld > cols) memset(out + cols, 0xff, (size_t)(sld - cols));
+#if defined(__x86_64__)
+                // anything unusual: the scalar code parses the row again from its first value
+                if (simd && parse_row_avx512(q, nl, out, cols, vmin512[i].v, vmax512[i].v, max0) == cols) return;
+#endif
+                if (parse_row_scalar(q, nl, out, cols, lo, hi, max0) != cols && bad[i] < 0) bad[i] = r;
+            });
+            vlo[i] = lo;
+            vhi[i] = hi;
+        })) return false;
+#if defined(__x86_64__)
+    if (simd) fold_minmax512(vmin512.data(), vmax512.data(), T, vlo.data(), vhi.data());
+#endif
+    fold_state_range(t, vlo, vhi);
+    *bad_row = -1;
+    for (int i = T - 1; i >= 0; --i)
+        if (bad[i] >= 0) *bad_row = bad[i];
+    return true;
+}
+
+epgio_table* open_table_impl(const char* path, int64_t row_lo, int64_t row_hi, int32_t threads, int32_t max_state,
+                             epgio_alloc_fn alloc, void* user) {
     Census census_;                                           // the caller: the inflate of a file is one serial thread
     ReaderScope reader_;
     const int max0 = (max_state > 31 ? 127 : 31) - 1;        // largest 0-based state kept: two classes, like the kernels
@@ -721,205 +821,152 @@ static epgio_table* open_table_impl(const char* path, int64_t row_lo, int64_t ro
     Text buf;
     if (!slurp(path, buf, threads)) return nullptr;
     lap("read / inflate");
+    std::unique_ptr<epgio_table> t(new epgio_table());        // released on success only
     const char* base = buf.data;
-    const char* end = base + buf.size;
-    // complete lines only (the reference counts newlines, helpers.py:94: a dangling last line does not exist)
-    const char* last_nl = nullptr;
-    for (const char* p = end; p > base;) { --p; if (*p == '\n') { last_nl = p; break; } }
-    if (!last_nl) { auto* t = new epgio_table(); t->loc_off.assign(1, 0); return t; }
-    end = last_nl + 1;
+    const char* end = complete_lines_end(base, base + buf.size);
+    if (!end) { t->loc_off.assign(1, 0); return t.release(); }
 
-    const int T = threads > 0 ? threads : reader_share();
-    // segment borders on line starts
-    std::vector<const char*> seg(T + 1);
-    seg[0] = base;
-    for (int i = 1; i < T; ++i) {
-        const char* p = base + (size_t)((end - base) / T) * i;
-        if (p < seg[i - 1]) p = seg[i - 1];
-        const char* nl = (const char*)memchr(p, '\n', (size_t)(end - p));
-        seg[i] = nl ? nl + 1 : end;
-    }
-    seg[T] = end;
-    std::vector<int64_t> seg_rows(T, 0);
-    {
-        Uncount uncount_;
-        std::vector<std::thread> th;
-        for (int i = 0; i < T; ++i)
-            th.emplace_back([&, i] {
-            Census census_;
-                int64_t n = 0;
-                const char* p = seg[i];
-                while (p < seg[i + 1] && (p = (const char*)memchr(p, '\n', (size_t)(seg[i + 1] - p)))) { ++n; ++p; }
-                seg_rows[i] = n;
-            });
-        join_all(th);
-    }
+    Rows rows;
+    rows.seg = segment_borders(base, end, threads > 0 ? threads : reader_share());
+    if (!count_lines(rows)) return nullptr;
     lap("count lines");
-    std::vector<int64_t> seg_first(T + 1, 0);
-    for (int i = 0; i < T; ++i) seg_first[i + 1] = seg_first[i] + seg_rows[i];
-    const int64_t total = seg_first[T];
-    if (row_hi < 0 || row_hi > total) row_hi = total;
-    if (row_lo < 0) row_lo = 0;
-    if (row_lo > row_hi) row_lo = row_hi;
+    const int64_t total = rows.first.back();
+    rows.hi = row_hi < 0 || row_hi > total ? total : row_hi;
+    rows.lo = std::min(std::max<int64_t>(row_lo, 0), rows.hi);
+    t->rows = rows.hi - rows.lo;
+    t->cols = state_columns(base, end);
+    if (t->cols < 1) { fail("%s: expected at least 4 tab-separated columns, found %d", path, t->cols + 3); return nullptr; }
+    int64_t sld = 0;
+    int8_t* sbase = state_destination(*t, alloc, user, path, &sld);
+    if (!sbase) return nullptr;
 
-    // number of state columns from the first line
-    int32_t cols = 0;
-    {
-        const char* nl = (const char*)memchr(base, '\n', (size_t)(end - base));
-        int tabs = 0;
-        for (const char* p = base; p < nl; ++p) tabs += *p == '\t';
-        cols = tabs - 2;
-        if (cols < 1) { fail("%s: expected at least 4 tab-separated columns, found %d", path, tabs + 1); return nullptr; }
-    }
-    auto* t = new epgio_table();
-    t->rows = row_hi - row_lo;
-    t->cols = cols;
-    int8_t* sbase = nullptr;
-    int64_t sld = cols;
-    if (alloc) {
-        // the caller's destination (a pinned, row-padded staging buffer): rows are parsed straight into it -- no 1 GB intermediate
-        // matrix, no copy of it (round 3: both, single-threaded, after the parse)
-        int64_t ld = 0;
-        sbase = alloc(t->rows, cols, &ld, user);
-        if (!sbase || ld < cols) { fail("%s: no destination for %lld x %d states", path, (long long)t->rows, cols); delete t; return nullptr; }
-        sld = ld;
-        t->ext = sbase;
-        t->ext_ld = ld;
-    } else {
-        t->states.reset(new int8_t[(size_t)t->rows * cols + 1]);
-        advise_huge(t->states.get(), (size_t)t->rows * cols);
-        sbase = t->states.get();
-    }
     t->loc_off.assign((size_t)t->rows + 1, 0);
-
-    // pass 1: location text lengths; pass 2 (after prefix sum): states + location text.  Both per segment.
-    std::vector<int> err(T, 0);
-    std::vector<int64_t> bad_row(T, -1);
-    std::vector<int> vlo(T, 1 << 30), vhi(T, -(1 << 30));
-    auto for_rows = [&](int i, auto&& fn) {
-        const char* p = seg[i];
-        int64_t r = seg_first[i];
-        while (p < seg[i + 1]) {
-            const char* nl = (const char*)memchr(p, '\n', (size_t)(seg[i + 1] - p));
-            if (r >= row_hi) break;
-            if (r >= row_lo) fn(r - row_lo, p, nl);
-            p = nl + 1;
-            ++r;
-        }
-    };
-    {
-        Uncount uncount_;
-        std::vector<std::thread> th;
-        for (int i = 0; i < T; ++i)
-            th.emplace_back([&, i] {
-            Census census_;
-                for_rows(i, [&](int64_t r, const char* p, const char* nl) {
-                    int tabs = 0;
-                    const char* q = p;
-                    for (; q < nl; ++q)
-                        if (*q == '\t' && ++tabs == 3) break;
-                    t->loc_off[(size_t)r + 1] = q - p + 1; // length (+ the '\n' that terminates the row's text) for now
-                });
-            });
-        join_all(th);
-    }
+    if (!location_lengths(rows, *t)) return nullptr;
     lap("location lengths");
     for (int64_t r = 0; r < t->rows; ++r) t->loc_off[(size_t)r + 1] += t->loc_off[(size_t)r];
     t->loc.resize((size_t)t->loc_off[(size_t)t->rows]);
-    {
-#if defined(__x86_64__)
-        struct alignas(64) V512 { __m512i v; };
-        const bool simd = have_avx512_parser();
-        std::vector<V512> vmin512((size_t)T), vmax512((size_t)T);
-        if (simd) init_minmax512(vmin512.data(), vmax512.data(), T);
-#endif
-        Uncount uncount_;
-        std::vector<std::thread> th;
-        for (int i = 0; i < T; ++i)
-            th.emplace_back([&, i] {
-            Census census_;
-                for_rows(i, [&](int64_t r, const char* p, const char* nl) {
-                    const int64_t len = t->loc_off[(size_t)r + 1] - t->loc_off[(size_t)r] - 1;
-                    memcpy(t->loc.data() + t->loc_off[(size_t)r], p, (size_t)len);
-                    t->loc[(size_t)(t->loc_off[(size_t)r] + len)] = '\n';
-                    const char* q = p + len;
-                    int8_t* out = sbase + (size_t)r * (size_t)sld;
-                    if (sld > cols) memset(out + cols, 0xff, (size_t)(sld - cols));    // pad bytes: not a state
-                    int c = 0;
-#if defined(__x86_64__)
-                    if (simd) {
-                        if (parse_row_avx512(q, nl, out, cols, vmin512[i].v, vmax512[i].v, max0) == cols) return;
-                        // anything unusual: the scalar code below parses the row again from its first value
-                    }
-#endif
-                    // fast path: one- or two-digit values ("\t7", "\t18"), which is every state of a 1..31-state model; the
-                    // text has 16 readable bytes after its end, a row ends in '\n' (not a digit), so looking three characters
-                    // ahead is safe.  Anything else (sign, three digits, '\r', malformed) leaves the loop for the general one.
-                    {
-                        int lo = vlo[i], hi = vhi[i];
-                        while (c < cols && *q == '\t') {
-                            const unsigned d0 = (unsigned)(unsigned char)q[1] - '0';
-                            if (d0 > 9) break;
-                            const unsigned d1 = (unsigned)(unsigned char)q[2] - '0';
-                            int v;
-                            if (d1 > 9) { v = (int)d0; q += 2; }
-                            else {
-                                if ((unsigned)(unsigned char)q[3] - '0' <= 9) break;       // three or more digits
-                                v = (int)(d0 * 10 + d1);
-                                q += 3;
-                            }
-                            lo = v < lo ? v : lo;
-                            hi = v > hi ? v : hi;
-                            --v;                                                        // file states are 1-based (helpers.py:155)
-                            out[c++] = (int8_t)(((unsigned)v > (unsigned)max0) ? -1 : v);  // outside 0..max0: "not a state" (see below)
-                        }
-                        vlo[i] = lo; vhi[i] = hi;
-                        if (c == cols && q < nl && *q == '\r') ++q;                    // CRLF line ends
-                    }
-                    while (q < nl && c < cols) {
-                        // a value is introduced by a TAB and by nothing else: the fast path above can stop on any byte
-                        // ("1.5", "1x5", "1 5"), and that byte must not be swallowed as if it were the separator
-                        if (*q != '\t') { err[i] = 1; if (bad_row[i] < 0) bad_row[i] = r; return; }
-                        ++q;                                // the tab before the value
-                        int v = 0;
-                        bool neg = false, any = false;
-                        if (q < nl && *q == '-') { neg = true; ++q; }
-                        while (q < nl && *q >= '0' && *q <= '9') { v = v * 10 + (*q - '0'); ++q; any = true; if (v > 100000) break; }
-                        if (q < nl && *q == '\r') ++q;
-                        if (!any || (q < nl && *q != '\t')) { err[i] = 1; if (bad_row[i] < 0) bad_row[i] = r; return; }
-                        v = neg ? -v : v;
-                        if (v < vlo[i]) vlo[i] = v;
-                        if (v > vhi[i]) vhi[i] = v;
-                        v -= 1;                             // file states are 1-based (helpers.py:155)
-                        // the kernels of models up to 31 states decode five bits and treat 31 as "not a state": anything
-                        // outside 0..max0 (30, or 126 for the wide models) is stored as -1 so that it cannot alias a state; the caller sees it in epgio_table_state_range and in the
-                        // count check (sum of counts != rows * columns)
-                        out[c++] = (int8_t)((v < 0 || v > max0) ? -1 : v);
-                    }
-                    if (c != cols || q != nl) { err[i] = 1; if (bad_row[i] < 0) bad_row[i] = r; }
-                });
-            });
-        join_all(th);
-#if defined(__x86_64__)
-        if (simd) fold_minmax512(vmin512.data(), vmax512.data(), T, vlo.data(), vhi.data());
-#endif
-    }
+    int64_t bad_row = -1;
+    if (!parse_rows(rows, *t, sbase, sld, max0, &bad_row)) return nullptr;
     lap("parse states + locations");
-    for (int i = 0; i < T; ++i) {
-        if (vlo[i] <= vhi[i]) {
-            if (t->state_lo == 0 && t->state_hi == 0) { t->state_lo = vlo[i]; t->state_hi = vhi[i]; }
-            t->state_lo = std::min(t->state_lo, vlo[i]);
-            t->state_hi = std::max(t->state_hi, vhi[i]);
-        }
+    if (bad_row >= 0) {
+        fail("%s: malformed line at row %lld (expected %d integer state columns)", path, (long long)(bad_row + rows.lo), t->cols);
+        return nullptr;
     }
-    for (int i = 0; i < T; ++i)
-        if (err[i]) {
-            fail("%s: malformed line at row %lld (expected %d integer state columns)", path, (long long)(bad_row[i] + row_lo), cols);
-            delete t;
-            return nullptr;
-        }
-    return t;
+    return t.release();
 }
+
+}  // namespace
+
+extern "C" {
+
+const char* epgio_last_error(void) { return g_err; }
+
+int64_t epgio_count_rows(const char* path) try {
+    Census census_;
+    std::vector<char> buf(1 << 22);
+    gzFile f = gzopen(path, "rb");
+    if (!f) return fail("cannot open %s", path);
+    gzbuffer(f, 1 << 20);
+    int64_t total = 0;
+    for (;;) {
+        const int got = gzread(f, buf.data(), (unsigned)buf.size());
+        if (got < 0) { gzclose(f); return fail("read error in %s", path); }
+        if (got == 0) break;
+        const char* p = buf.data();
+        const char* e = p + got;
+        while ((p = (const char*)memchr(p, '\n', (size_t)(e - p)))) { ++total; ++p; }
+    }
+    gzclose(f);
+    return total;
+} EPGIO_CATCH("epgio_count_rows", -1)
+
+epgio_table* epgio_open_table_ex(const char* path, int64_t row_lo, int64_t row_hi, int32_t threads, int32_t max_state) try {
+    return open_table_impl(path, row_lo, row_hi, threads, max_state, nullptr, nullptr);
+} EPGIO_CATCH("epgio_open_table_ex", nullptr)
+
+epgio_table* epgio_open_table(const char* path, int64_t row_lo, int64_t row_hi, int32_t threads) {
+    return epgio_open_table_ex(path, row_lo, row_hi, threads, 31);
+}
+
+epgio_table* epgio_open_table_into(const char* path, int64_t row_lo, int64_t row_hi, int32_t threads, int32_t max_state,
+                                   epgio_alloc_fn alloc, void* user) try {
+    if (!alloc) { fail("open_table_into: no allocator"); return nullptr; }
+    return open_table_impl(path, row_lo, row_hi, threads, max_state, alloc, user);
+} EPGIO_CATCH("epgio_open_table_into", nullptr)
+
+void epgio_thread_census(int32_t* live, int32_t* peak, int32_t reset) {
+    if (live) *live = g_live.load();
+    if (peak) *peak = g_peak.load();
+    if (reset) g_peak.store(g_live.load());
+}
+
+int32_t epgio_default_threads(void) { return n_threads(0); }
+void epgio_set_host_threads(int32_t n) { g_host_threads.store(n > 0 ? n : 0, std::memory_order_relaxed); }
+void epgio_set_reader_plan(int32_t n) { g_reader_plan.store(n > 0 ? n : 0); }
+
+// The kept text buffers (their pages are released after every file already) go back to the kernel -- on a thread of its own
+// when `background` (no worker: nobody waits for it).  For a process that is done reading and goes on living.
+void epgio_release_buffers(int32_t background) try {
+    std::vector<std::pair<char*, size_t>> bufs;
+    {
+        BigBufs& b = big_bufs();
+        std::lock_guard<std::mutex> g(b.m);
+        bufs.swap(b.free_list);
+    }
+    if (bufs.empty()) return;
+    auto work = [bufs = std::move(bufs)] { for (auto& e : bufs) free(e.first); };
+    // no thread to be had, or no memory for its copy of the list: freed on this one -- nothing leaks, nothing is thrown
+    if (background) try { std::thread(work).detach(); return; } catch (const std::exception&) {}
+    work();
+} catch (...) {}                                              // (the list could not be reached: nothing was taken from it)
+
+int64_t epgio_inflate_mem(const void* in, int64_t n, void* out, int64_t cap, int32_t own) try {
+    if (!in || n < 0 || cap < 0 || (cap > 0 && !out)) return fail("inflate_mem: bad argument");
+    const unsigned char* p = (const unsigned char*)in;
+    if (!is_gzip(p, (size_t)n)) return fail("inflate_mem: not a gzip stream");
+    Text t;
+    size_t hint = le32(p + n - 4);
+    if (hint < (size_t)n || hint > ((size_t)1 << 28)) hint = (size_t)n * 4;
+    hint += 64;
+    const bool ok = own == 2 ? inflate_bgzf(p, (size_t)n, t, 2) : own ? inflate_own(p, (size_t)n, hint, t, 1) : inflate_zlib(p, (size_t)n, hint, t, "memory");
+    if (!ok) return own ? fail("inflate_mem: the library's inflate declined the stream") : -1;
+    if ((int64_t)t.size > cap) return fail("inflate_mem: output %lld > cap %lld", (long long)t.size, (long long)cap);
+    if (t.size) memcpy(out, t.data, t.size);
+    return (int64_t)t.size;
+} EPGIO_CATCH("epgio_inflate_mem", -1)
+
+epgio_text* epgio_open_text(const char* path, int32_t threads) try {
+    if (!path) { fail("open_text: NULL path"); return nullptr; }
+    Census census_;
+    std::unique_ptr<epgio_text> h(new epgio_text());
+    if (!slurp(path, h->t, threads)) return nullptr;
+    return h.release();
+} EPGIO_CATCH("epgio_open_text", nullptr)
+
+const char* epgio_text_data(const epgio_text* h, int64_t* size) {
+    if (size) *size = h ? (int64_t)h->t.size : 0;
+    return h ? h->t.data : nullptr;
+}
+
+void epgio_close_text(epgio_text* h) { delete h; }
+
+int64_t epgio_count_newlines(const char* p, int64_t n, int32_t threads) try {
+    if (n < 0 || (n > 0 && !p)) return fail("count_newlines: bad argument");
+    auto count = [](const char* a, const char* e) {
+        int64_t c = 0;
+        while (a < e && (a = (const char*)memchr(a, '\n', (size_t)(e - a)))) { ++c; ++a; }
+        return c;
+    };
+    const int64_t PIECE = (int64_t)8 << 20;
+    const int T = (int)std::max<int64_t>(1, std::min<int64_t>(n_threads(threads), n / PIECE));
+    Census census_;
+    if (T == 1) return count(p, p + n);
+    std::vector<int64_t> part((size_t)T, 0);
+    if (!run_workers(T, [&](int w) { part[(size_t)w] = count(p + n * w / T, p + n * (w + 1) / T); })) return -1;
+    int64_t total = 0;
+    for (int64_t c : part) total += c;
+    return total;
+} EPGIO_CATCH("epgio_count_newlines", -1)
 
 int64_t epgio_table_rows(const epgio_table* t) { return t ? t->rows : fail("null table"); }
 int32_t epgio_table_cols(const epgio_table* t) { return t ? t->cols : fail("null table"); }
@@ -1073,23 +1120,63 @@ bool gzip_member(const std::vector<char>& in, int level, std::vector<unsigned ch
     return rc == Z_STREAM_END;
 }
 
+struct CloseFile {
+    void operator()(FILE* f) const { fclose(f); }
+};
+
+// The writers' skeleton.  Rows [0, R) go out in chunks of CH rows, in rounds of T chunks: a worker per chunk has rows(r0, r1,
+// txt) put the chunk's text into the empty txt and, with `compress`, makes one gzip member of it (level outside 0..9: 6;
+// EPILOGOS_BGZF: BGZF blocks); the round's chunks are then written in order.  No row at all: an empty member, like
+// gzip.open(..).close(); BGZF under a name that ends in "gz": the end marker.  Without `compress` the text goes out as it is.
+template <class F>
+int write_chunked(const char* path, int64_t R, int64_t CH, int32_t threads, int32_t level, bool compress, F&& rows) {
+    if (level < 0 || level > 9) level = 6;
+    std::unique_ptr<FILE, CloseFile> f(fopen(path, "wb"));
+    if (!f) return fail("cannot create %s", path);
+    const int T = n_threads(threads);
+    const int64_t nchunks = (R + CH - 1) / CH;
+    if (R == 0 && compress) {
+        std::vector<unsigned char> z;
+        gzip_member(std::vector<char>(), level, z);
+        fwrite(z.data(), 1, z.size(), f.get());
+    }
+    bool ok = true;
+    for (int64_t c0 = 0; c0 < nchunks && ok; c0 += T) {
+        const int nb = (int)std::min<int64_t>(T, nchunks - c0);
+        std::vector<std::vector<unsigned char>> z(nb);
+        std::vector<std::vector<char>> plain(nb);
+        std::vector<int> good(nb, 0);
+        if (!run_workers(nb, [&](int k) {
+                const int64_t r0 = (c0 + k) * CH, r1 = std::min(R, r0 + CH);
+                std::vector<char> txt;
+                rows(r0, r1, txt);
+                if (compress) good[k] = gzip_member(txt, level, z[k]);
+                else { plain[k].swap(txt); good[k] = 1; }
+            })) return -1;
+        for (int k = 0; k < nb && ok; ++k) {
+            const void* p = compress ? (const void*)z[k].data() : (const void*)plain[k].data();
+            const size_t n = compress ? z[k].size() : plain[k].size();
+            if (!good[k] || fwrite(p, 1, n, f.get()) != n) ok = false;
+        }
+    }
+    if (ok && bgzf_on() && ends_with_gz(path) && fwrite(BGZF_EOF, 1, sizeof(BGZF_EOF), f.get()) != sizeof(BGZF_EOF)) ok = false;
+    if (fclose(f.release()) != 0) ok = false;
+    return ok ? 0 : fail("write error on %s", path);
+}
+
 }  // namespace
 
 extern "C" {
 
 int epgio_parse_locations(const char* loc, const int64_t* loc_off, int64_t R, int64_t* start, int64_t* end, int32_t* same_chrom,
-                          int32_t threads) {
+                          int32_t threads) try {
     if (R < 0 || (R > 0 && (!loc || !loc_off || !start || !end))) return fail("parse_locations: bad argument");
     const int T = (int)std::max<int64_t>(1, std::min<int64_t>(n_threads(threads), (R + 65535) / 65536));
     std::vector<int> bad(T, 0), same(T, 1);
     const char* c0 = loc + (R ? loc_off[0] : 0);
     const char* c0e = R ? (const char*)memchr(c0, '\t', (size_t)(loc_off[1] - loc_off[0])) : c0;
     const size_t c0n = c0e ? (size_t)(c0e - c0) : 0;
-    Uncount uncount_;
-    std::vector<std::thread> th;
-    for (int t = 0; t < T; ++t)
-        th.emplace_back([&, t] {
-            Census census_;
+    if (!run_workers(T, [&](int t) {
             for (int64_t r = R * t / T; r < R * (t + 1) / T; ++r) {
                 const char* p = loc + loc_off[r];
                 const char* e = loc + loc_off[r + 1];
@@ -1112,8 +1199,7 @@ int epgio_parse_locations(const char* loc, const int64_t* loc_off, int64_t R, in
                 start[r] = v[0];
                 end[r] = v[1];
             }
-        });
-    join_all(th);
+        })) return -1;
     int all_same = 1;
     for (int t = 0; t < T; ++t) {
         if (bad[t]) return fail("parse_locations: a row is not 'name<TAB>integer<TAB>integer'");
@@ -1121,16 +1207,12 @@ int epgio_parse_locations(const char* loc, const int64_t* loc_off, int64_t R, in
     }
     if (same_chrom) *same_chrom = all_same;
     return 0;
-}
+} EPGIO_CATCH("epgio_parse_locations", -1)
 
-int epgio_row_sums_f32(const float* a, int64_t R, int32_t S, int64_t lda, float* out, int32_t threads) {
+int epgio_row_sums_f32(const float* a, int64_t R, int32_t S, int64_t lda, float* out, int32_t threads) try {
     if (R < 0 || S < 1 || S > 128 || lda < S || (R > 0 && (!a || !out))) return fail("row_sums: bad argument (S must be 1..128)");
     const int T = (int)std::max<int64_t>(1, std::min<int64_t>(n_threads(threads), (R + 65535) / 65536));
-    Uncount uncount_;
-    std::vector<std::thread> th;
-    for (int t = 0; t < T; ++t)
-        th.emplace_back([&, t] {
-            Census census_;
+    return run_workers(T, [&](int t) {
             const int n8 = S - S % 8;
             for (int64_t r = R * t / T; r < R * (t + 1) / T; ++r) {
                 const float* p = a + r * lda;
@@ -1148,21 +1230,15 @@ int epgio_row_sums_f32(const float* a, int64_t R, int32_t S, int64_t lda, float*
                 }
                 out[r] = res;
             }
-        });
-    join_all(th);
-    return 0;
-}
+        }) ? 0 : -1;
+} EPGIO_CATCH("epgio_row_sums_f32", -1)
 
-int epgio_rolling_max_f64(const double* x, int64_t n, int32_t W, double* out, int32_t threads) {
+int epgio_rolling_max_f64(const double* x, int64_t n, int32_t W, double* out, int32_t threads) try {
     if (n < 0 || W < 1 || (n > 0 && (!x || !out))) return fail("rolling_max: bad argument");
     const int64_t back = W / 2, fwd = (W - 1) / 2;
     const double nan = std::nan("");
     const int T = (int)std::max<int64_t>(1, std::min<int64_t>(n_threads(threads), (n + (1 << 20) - 1) >> 20));
-    Uncount uncount_;
-    std::vector<std::thread> th;
-    for (int t = 0; t < T; ++t)
-        th.emplace_back([&, t] {
-            Census census_;
+    return run_workers(T, [&](int t) {
             const int64_t i0 = n * t / T, i1 = n * (t + 1) / T;
             // monotonic deque of candidate indices (values decreasing; a later equal value replaces an earlier one, like
             // pandas) over the window [i - back, i + fwd], in a power-of-two ring
@@ -1185,18 +1261,16 @@ int epgio_rolling_max_f64(const double* x, int64_t n, int32_t W, double* out, in
                 while (dq[head & mask] < lo) ++head;
                 out[i] = x[dq[head & mask]];
             }
-        });
-    join_all(th);
-    return 0;
-}
+        }) ? 0 : -1;
+} EPGIO_CATCH("epgio_rolling_max_f64", -1)
 
-int64_t epgio_gzip_fast(const void* in, int64_t n, void* out, int64_t cap) {
+int64_t epgio_gzip_fast(const void* in, int64_t n, void* out, int64_t cap) try {
     if (n < 0 || (n > 0 && !in) || !out || cap < n + n / 8 + 1100) return fail("gzip_fast: bad argument");
     std::vector<unsigned char> z;
     epgdeflate::gzip_member_fast(static_cast<const unsigned char*>(in), (size_t)n, z);
     memcpy(out, z.data(), z.size());
     return (int64_t)z.size();
-}
+} EPGIO_CATCH("epgio_gzip_fast", -1)
 
 int64_t epgio_format_f5(const float* v, int64_t n, char sep, char* buf, int64_t cap) {
     if (cap < 48 * n) return fail("format_f5: buffer too small");
@@ -1206,177 +1280,81 @@ int64_t epgio_format_f5(const float* v, int64_t n, char sep, char* buf, int64_t 
 }
 
 int epgio_write_scores(const char* path, const char* loc, const int64_t* loc_off, const float* scores, int64_t R, int32_t S,
-                       int32_t threads, int32_t gzip_level) {
+                       int32_t threads, int32_t gzip_level) try {
     Census census_;
     if (!path || (R > 0 && (!loc || !loc_off || !scores)) || S < 1) return fail("write_scores: bad argument");
-    if (gzip_level < 0 || gzip_level > 9) gzip_level = 6;
-    FILE* f = fopen(path, "wb");
-    if (!f) return fail("cannot create %s", path);
-    const int T = n_threads(threads);
-    const int64_t CH = 32768;                                   // rows per gzip member
-    const int64_t nchunks = (R + CH - 1) / CH;
-    if (R == 0) {                                               // an empty gzip stream, like gzip.open(..).close()
-        std::vector<unsigned char> z;
-        gzip_member(std::vector<char>(), gzip_level, z);
-        fwrite(z.data(), 1, z.size(), f);
-    }
-    bool ok = true;
-    for (int64_t c0 = 0; c0 < nchunks && ok; c0 += T) {
-        const int nb = (int)std::min<int64_t>(T, nchunks - c0);
-        std::vector<std::vector<unsigned char>> z(nb);
-        std::vector<int> good(nb, 0);
-        Uncount uncount_;
-        std::vector<std::thread> th;
-        for (int k = 0; k < nb; ++k)
-            th.emplace_back([&, k] {
-            Census census_;
-                const int64_t r0 = (c0 + k) * CH, r1 = std::min(R, r0 + CH);
-                std::vector<char> txt((size_t)((loc_off[r1] - loc_off[r0]) + (r1 - r0) * (2 + 48 * (int64_t)S)));
-                char* o = txt.data();
-                for (int64_t r = r0; r < r1; ++r) {
-                    const int64_t len = loc_off[r + 1] - loc_off[r] - 1;   // without the row's '\n'
-                    memcpy(o, loc + loc_off[r], (size_t)len);
-                    o += len;
-                    const float* row = scores + r * S;
-                    for (int s = 0; s < S; ++s) { *o++ = '\t'; o = fmt_f5(row[s], o); }
-                    *o++ = '\n';
-                }
-                txt.resize((size_t)(o - txt.data()));
-                good[k] = gzip_member(txt, gzip_level, z[k]);
-            });
-        join_all(th);
-        for (int k = 0; k < nb && ok; ++k) {
-            if (!good[k] || fwrite(z[k].data(), 1, z[k].size(), f) != z[k].size()) ok = false;
+    return write_chunked(path, R, 32768, threads, gzip_level, true, [&](int64_t r0, int64_t r1, std::vector<char>& txt) {
+        txt.resize((size_t)((loc_off[r1] - loc_off[r0]) + (r1 - r0) * (2 + 48 * (int64_t)S)));
+        char* o = txt.data();
+        for (int64_t r = r0; r < r1; ++r) {
+            const int64_t len = loc_off[r + 1] - loc_off[r] - 1;   // without the row's '\n'
+            memcpy(o, loc + loc_off[r], (size_t)len);
+            o += len;
+            const float* row = scores + r * S;
+            for (int s = 0; s < S; ++s) { *o++ = '\t'; o = fmt_f5(row[s], o); }
+            *o++ = '\n';
         }
-    }
-    if (ok && bgzf_on() && ends_with_gz(path) && fwrite(BGZF_EOF, 1, sizeof(BGZF_EOF), f) != sizeof(BGZF_EOF)) ok = false;
-    if (fclose(f) != 0) ok = false;
-    return ok ? 0 : fail("write error on %s", path);
-}
+        txt.resize((size_t)(o - txt.data()));
+    });
+} EPGIO_CATCH("epgio_write_scores", -1)
 
 int epgio_write_states(const char* path, const char* chrom, int64_t start0, int64_t step, const int8_t* states, int64_t R, int32_t N,
-                       int64_t ldx, int32_t threads, int32_t gzip_level) {
+                       int64_t ldx, int32_t threads, int32_t gzip_level) try {
     Census census_;
     if (!path || !chrom || (R > 0 && !states) || N < 1 || ldx < N || step < 1) return fail("write_states: bad argument");
-    if (gzip_level < 0 || gzip_level > 9) gzip_level = 6;
-    FILE* f = fopen(path, "wb");
-    if (!f) return fail("cannot create %s", path);
-    const bool gz = ends_with_gz(path);
-    const int T = n_threads(threads);
-    const int64_t CH = 8192;                                    // rows per gzip member (~1.7 KB of text per row at N = 833)
-    const int64_t nchunks = (R + CH - 1) / CH;
     const size_t clen = strlen(chrom);
-    if (R == 0 && gz) {
-        std::vector<unsigned char> z;
-        gzip_member(std::vector<char>(), gzip_level, z);
-        fwrite(z.data(), 1, z.size(), f);
-    }
-    bool ok = true;
-    for (int64_t c0 = 0; c0 < nchunks && ok; c0 += T) {
-        const int nb = (int)std::min<int64_t>(T, nchunks - c0);
-        std::vector<std::vector<unsigned char>> z(nb);
-        std::vector<std::vector<char>> plain(nb);
-        std::vector<int> good(nb, 0);
-        Uncount uncount_;
-        std::vector<std::thread> th;
-        for (int k = 0; k < nb; ++k)
-            th.emplace_back([&, k] {
-            Census census_;
-                const int64_t r0 = (c0 + k) * CH, r1 = std::min(R, r0 + CH);
-                std::vector<char>& txt = plain[k];
-                txt.resize((size_t)(r1 - r0) * (clen + 48 + 5 * (size_t)N));
-                char* o = txt.data();
-                for (int64_t r = r0; r < r1; ++r) {
-                    memcpy(o, chrom, clen);
-                    o += clen;
-                    o += sprintf(o, "\t%lld\t%lld", (long long)(start0 + r * step), (long long)(start0 + (r + 1) * step));
-                    const int8_t* row = states + r * ldx;
-                    for (int c = 0; c < N; ++c) {
-                        int v = (int)row[c] + 1;                // file states are 1-based
-                        *o++ = '\t';
-                        if (v < 0) { *o++ = '-'; v = -v; }
-                        if (v >= 100) { *o++ = (char)('0' + v / 100); v %= 100; *o++ = (char)('0' + v / 10); *o++ = (char)('0' + v % 10); }
-                        else if (v >= 10) { *o++ = (char)('0' + v / 10); *o++ = (char)('0' + v % 10); }
-                        else *o++ = (char)('0' + v);
-                    }
-                    *o++ = '\n';
-                }
-                txt.resize((size_t)(o - txt.data()));
-                good[k] = gz ? gzip_member(txt, gzip_level, z[k]) : 1;
-            });
-        join_all(th);
-        for (int k = 0; k < nb && ok; ++k) {
-            if (!good[k]) { ok = false; break; }
-            const void* p = gz ? (const void*)z[k].data() : (const void*)plain[k].data();
-            const size_t n = gz ? z[k].size() : plain[k].size();
-            if (fwrite(p, 1, n, f) != n) ok = false;
+    // 8192 rows per gzip member: ~1.7 KB of text per row at N = 833
+    return write_chunked(path, R, 8192, threads, gzip_level, ends_with_gz(path), [&](int64_t r0, int64_t r1, std::vector<char>& txt) {
+        txt.resize((size_t)(r1 - r0) * (clen + 48 + 5 * (size_t)N));
+        char* o = txt.data();
+        for (int64_t r = r0; r < r1; ++r) {
+            memcpy(o, chrom, clen);
+            o += clen;
+            o += sprintf(o, "\t%lld\t%lld", (long long)(start0 + r * step), (long long)(start0 + (r + 1) * step));
+            const int8_t* row = states + r * ldx;
+            for (int c = 0; c < N; ++c) {
+                int v = (int)row[c] + 1;                // file states are 1-based
+                *o++ = '\t';
+                if (v < 0) { *o++ = '-'; v = -v; }
+                if (v >= 100) { *o++ = (char)('0' + v / 100); v %= 100; *o++ = (char)('0' + v / 10); *o++ = (char)('0' + v % 10); }
+                else if (v >= 10) { *o++ = (char)('0' + v / 10); *o++ = (char)('0' + v % 10); }
+                else *o++ = (char)('0' + v);
+            }
+            *o++ = '\n';
         }
-    }
-    if (ok && bgzf_on() && ends_with_gz(path) && fwrite(BGZF_EOF, 1, sizeof(BGZF_EOF), f) != sizeof(BGZF_EOF)) ok = false;
-    if (fclose(f) != 0) ok = false;
-    return ok ? 0 : fail("write error on %s", path);
-}
+        txt.resize((size_t)(o - txt.data()));
+    });
+} EPGIO_CATCH("epgio_write_states", -1)
 
 int epgio_write_metrics(const char* path, const char* chrom, const int64_t* chrom_off, const int32_t* chrom_idx, const int64_t* start,
                         const int64_t* end, const char* names, const int64_t* names_off, const int32_t* maxdiff, const float* dist,
-                        const double* pvals, const double* mh, int64_t R, int32_t threads, int32_t gzip_level) {
+                        const double* pvals, const double* mh, int64_t R, int32_t threads, int32_t gzip_level) try {
     Census census_;
     if (!path || (R > 0 && (!chrom || !chrom_off || !chrom_idx || !start || !end || !names || !names_off || !maxdiff || !dist)) ||
         ((pvals == nullptr) != (mh == nullptr)))
         return fail("write_metrics: bad argument");
-    if (gzip_level < 0 || gzip_level > 9) gzip_level = 6;
-    FILE* f = fopen(path, "wb");
-    if (!f) return fail("cannot create %s", path);
-    const int T = n_threads(threads);
-    const int64_t CH = 32768;
-    const int64_t nchunks = (R + CH - 1) / CH;
-    if (R == 0) {
-        std::vector<unsigned char> z;
-        gzip_member(std::vector<char>(), gzip_level, z);
-        fwrite(z.data(), 1, z.size(), f);
-    }
-    bool ok = true;
-    for (int64_t c0 = 0; c0 < nchunks && ok; c0 += T) {
-        const int nb = (int)std::min<int64_t>(T, nchunks - c0);
-        std::vector<std::vector<unsigned char>> z(nb);
-        std::vector<int> good(nb, 0);
-        Uncount uncount_;
-        std::vector<std::thread> th;
-        for (int k = 0; k < nb; ++k)
-            th.emplace_back([&, k] {
-            Census census_;
-                const int64_t r0 = (c0 + k) * CH, r1 = std::min(R, r0 + CH);
-                std::vector<char> txt;
-                txt.reserve((size_t)(r1 - r0) * 96);
-                char num[64];
-                for (int64_t r = r0; r < r1; ++r) {
-                    const int32_t ci = chrom_idx[r], mi = maxdiff[r] - 1;
-                    txt.insert(txt.end(), chrom + chrom_off[ci], chrom + chrom_off[ci + 1]);
-                    int n = snprintf(num, sizeof num, "\t%lld\t%lld\t", (long long)start[r], (long long)end[r]);
-                    txt.insert(txt.end(), num, num + n);
-                    txt.insert(txt.end(), names + names_off[mi], names + names_off[mi + 1]);
-                    txt.push_back('\t');
-                    const float d = dist[r];
-                    char* e = fmt_f5(std::fabs(d), num);                     // "{:.5f}".format(abs(distance)) of the float32
-                    txt.insert(txt.end(), num, e);
-                    txt.push_back('\t');
-                    txt.push_back(d >= 0.0f ? '+' : '-');                   // helpers.findSign: x >= 0
-                    if (pvals) {
-                        n = snprintf(num, sizeof num, "\t%.5e\t%.5e", pvals[r], mh[r]);
-                        txt.insert(txt.end(), num, num + n);
-                    }
-                    txt.push_back('\n');
-                }
-                good[k] = gzip_member(txt, gzip_level, z[k]);
-            });
-        join_all(th);
-        for (int k = 0; k < nb && ok; ++k) {
-            if (!good[k] || fwrite(z[k].data(), 1, z[k].size(), f) != z[k].size()) ok = false;
+    return write_chunked(path, R, 32768, threads, gzip_level, true, [&](int64_t r0, int64_t r1, std::vector<char>& txt) {
+        txt.reserve((size_t)(r1 - r0) * 96);
+        char num[64];
+        for (int64_t r = r0; r < r1; ++r) {
+            const int32_t ci = chrom_idx[r], mi = maxdiff[r] - 1;
+            txt.insert(txt.end(), chrom + chrom_off[ci], chrom + chrom_off[ci + 1]);
+            int n = snprintf(num, sizeof num, "\t%lld\t%lld\t", (long long)start[r], (long long)end[r]);
+            txt.insert(txt.end(), num, num + n);
+            txt.insert(txt.end(), names + names_off[mi], names + names_off[mi + 1]);
+            txt.push_back('\t');
+            const float d = dist[r];
+            char* e = fmt_f5(std::fabs(d), num);                     // "{:.5f}".format(abs(distance)) of the float32
+            txt.insert(txt.end(), num, e);
+            txt.push_back('\t');
+            txt.push_back(d >= 0.0f ? '+' : '-');                   // helpers.findSign: x >= 0
+            if (pvals) {
+                n = snprintf(num, sizeof num, "\t%.5e\t%.5e", pvals[r], mh[r]);
+                txt.insert(txt.end(), num, num + n);
+            }
+            txt.push_back('\n');
         }
-    }
-    if (ok && bgzf_on() && ends_with_gz(path) && fwrite(BGZF_EOF, 1, sizeof(BGZF_EOF), f) != sizeof(BGZF_EOF)) ok = false;
-    if (fclose(f) != 0) ok = false;
-    return ok ? 0 : fail("write error on %s", path);
-}
+    });
+} EPGIO_CATCH("epgio_write_metrics", -1)
 
 }  // extern "C"

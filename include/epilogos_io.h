@@ -14,7 +14,8 @@
  * gzip file); the decompressed bytes are identical to the reference's.
  *
  * All functions are thread-safe with respect to different handles/paths.  Errors: negative return (or NULL) and
- * epgio_last_error() (thread-local).
+ * epgio_last_error() (thread-local).  No C++ exception leaves the library: memory that cannot be had, or a worker thread that
+ * cannot be started, is such an error return ("<entry point>: <what>") where the process used to abort.
  */
 #ifndef EPILOGOS_IO_H
 #define EPILOGOS_IO_H

@@ -19,22 +19,13 @@ from epilogos_amd import similaritySearch_write as ssw
 from tests import bgzf_ref
 from tests import bgzf_streams as bs
 from tests.abi_headers import ctypes_of
+from tests.host_programs import build_program as _build_program
 
 NAMES = ["epgz_bgzf_inflate", "epgz_inflate_lds_bytes", "epgz_newline_index", "epgz_newline_segments"]
 ROOT = build.ROOT
 
 
 # ---- (a) the stand-alone program -----------------------------------------------------------------------------------------------------
-def _build_program(tmp_path, name, sources, libs):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no C++ compiler")
-    exe = tmp_path / name
-    cmd = [cxx, "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-std=c++17", "-pthread", "-I" + str(ROOT / "include"),
-           "-I" + str(build.CSRC)] + [str(s) for s in sources] + libs + ["-o", str(exe)]
-    res = subprocess.run(cmd, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
-    return exe
 
 
 def test_the_inflater_s_phases_agree_with_zlib_on_the_host_under_the_sanitizers(tmp_path):

@@ -18,6 +18,7 @@ from epilogos_amd import _abi, _io, backend, build, driver
 from tests import bgzf_ref
 from tests.abi_headers import ctypes_of
 from tests.groupings_backend import GroupingsBackend
+from tests.host_programs import build_program as _build_program
 
 NAMES = ["epgw_bgzf_bytes_max", "epgw_bgzf_compress", "epgw_bgzf_ws_bytes", "epgw_format_scores", "epgw_format_ws_bytes", "epgw_text_bytes_max"]
 ROOT = build.ROOT
@@ -339,16 +340,6 @@ def test_argument_validation_and_size_queries_without_gpu(lib):
 
 
 # ---- (e) the stand-alone programs ------------------------------------------------------------------------------------------------------
-def _build_program(tmp_path, name, sources, libs):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if cxx is None:
-        pytest.skip("no C++ compiler")
-    exe = tmp_path / name
-    cmd = [cxx, "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-std=c++17", "-pthread", "-I" + str(ROOT / "include"),
-           "-I" + str(build.CSRC)] + [str(s) for s in sources] + libs + ["-o", str(exe)]
-    res = subprocess.run(cmd, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr
-    return exe
 
 
 def test_the_format_arithmetic_is_fmt_f5_s_under_the_sanitizers(tmp_path):
